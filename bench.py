@@ -18,6 +18,8 @@ Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--n-pts N] [--d D] 
         After the K timed steps ONE extra, untimed step records a HIP-event pair around every launch of the MFMA
         kernel (roofline.achieved); roofline.traffic comes from the committed PMC passes under profiles/ when
         their source hash matches the kernels being run.
+        --dump-outputs DIR (one GPU): what the last timed step handed back (alpha and nll; with --batch the
+        per-problem nll and info) as DIR/<name>.npy in float64, so that two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -34,6 +36,19 @@ sys.path.insert(0, ROOT)
 METRIC = "Gram-build GB/s + Cholesky fp64 TFLOP/s at N=65536 d=2; |alpha-alpha_ref|/|alpha_ref|"
 HBM_PEAK_GBS = 8000.0     # MI355X HBM3E spec (MI355X_MICROARCH.md: 8.0 TB/s spec, 6.29 measured copy)
 MFMA_F64_PEAK_TF = 78.6   # MI355X fp64 matrix peak, vendor spec
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all files together
+
+
+def dump_outputs(path, outputs):
+    """--dump-outputs: every array of `outputs` (name -> array) as path/<name>.npy in float64.  An array larger than its share
+    of DUMP_MAX_BYTES is replaced by a fixed, seeded sample of its entries (flattened, in index order)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // len(outputs) // 8
+    for name, a in outputs.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.size > share:
+            a = a.ravel()[np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def synth_pairs(n_pts, d, seed=1234):
@@ -212,10 +227,12 @@ def batch_leg(args):
     for _ in range(max(args.warmup, 1)):
         fit_batch(args.family, x, y, z, hyp, s2, want_alpha=False)
     ts = []
-    for _ in range(max(args.steps, 5)):
+    for _ in range(args.steps):
         t0 = time.perf_counter()
         _, nll, info = fit_batch(args.family, x, y, z, hyp, s2, want_alpha=False)
         ts.append(time.perf_counter() - t0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"nll": nll, "info": info})
     t = float(np.median(ts))
     flop_fit = n**3 / 3.0 + 2.0 * n * n            # factor + the two triangular solves (the Gram build is not flop on the matrix cores)
     out = {"metric": "batched nll_chol bodies per second (one sgpr_fit_batch call per batch)", "value": B / t, "unit": "fits/s",
@@ -297,9 +314,16 @@ def main():
     ap.add_argument("--lower-only", action="store_true",
                     help="build only the lower triangle of K (what the factor reads) instead of the "
                          "full matrix build_K defines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="one GPU: write what the last timed step returned (alpha, nll; with --batch nll, info) to DIR/<name>.npy "
+                         "(float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.dump_outputs and (args.gpus > 1 or world > 1 or args.force_dist):
+        ap.error("--dump-outputs is implemented for the one-GPU legs only")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(args.gpus))     # nothing above has touched the GPU
 
@@ -383,6 +407,8 @@ def main():
     dt = time.perf_counter() - t0
     stage /= max(args.steps, 1)
     ms_per_step = dt / args.steps * 1e3
+    if args.dump_outputs:        # before the untimed passes below run the fit again
+        dump_outputs(args.dump_outputs, {"alpha": fit.alpha(), "nll": fit.nll()})
 
     # roofline pass: ONE more step, outside the timed region, with a HIP-event pair (from a fixed
     # pool) around every launch of the MFMA kernel on the stream it is launched on

@@ -221,6 +221,39 @@ def test_bench_starts_its_own_ranks_before_touching_the_gpu(monkeypatch):
     assert "sympgpr_amd._lib" not in set(sys.modules) - before      # the product library was not even loaded
 
 
+def test_bench_dump_outputs_format_and_cap(tmp_path, monkeypatch):
+    """--dump-outputs: float64 .npy files, 64 MB at most in all (a larger array becomes the same seeded sample every run);
+    --steps below 1 and a dump on the multi-rank legs are refused before anything touches the GPU"""
+    import importlib.util
+    import sys
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    big = np.arange(10**7, dtype=np.float64)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"alpha": big, "nll": 1.5, "info": np.array([0, 3], dtype=np.int32)})
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["alpha.npy", "info.npy", "nll.npy"]
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= bench.DUMP_MAX_BYTES
+    for f in files:
+        a, b = np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f))
+        assert a.dtype == np.float64 and np.array_equal(a, b)
+    sample = np.load(str(tmp_path / "a" / "alpha.npy"))
+    assert 0 < sample.size < big.size and np.all(np.diff(sample) > 0)      # distinct entries, in index order
+    assert np.load(str(tmp_path / "a" / "nll.npy")) == 1.5
+    assert list(np.load(str(tmp_path / "a" / "info.npy"))) == [0.0, 3.0]
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    before = set(sys.modules)
+    for argv in (["--steps", "0"], ["--gpus", "2", "--dump-outputs", str(tmp_path / "c")]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        with pytest.raises(SystemExit) as e:
+            bench.main()
+        assert e.value.code == 2
+    assert not (tmp_path / "c").exists()
+    assert "sympgpr_amd._lib" not in set(sys.modules) - before
+
+
 def test_family_selection_process_default_and_thread_scope():
     """func.set_family selects the mirrored kernels*.f90 PROCESS-wide, as the reference's compiled module does: a selection made in
     the main thread is what a new thread sees (an optimiser's callback pool).  ops.family_scope shadows it for the calling thread

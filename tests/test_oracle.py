@@ -121,21 +121,19 @@ def test_multi_rhs_solve(oracle, fits):
     assert np.abs(Ky @ X - B).max() < 1e-10
 
 
-def test_length_scale_derivative_kernels_vs_reference_fortran(oracle):
+def test_length_scale_derivative_kernels_vs_reference_fortran(oracle, golden_dir):
     """the eight d../dl functions build_dK / build_dKreg use (kernels.f90:135-231,
     kernels_sq.f90:124-217, kernels_sum.f90:120-208), restated in the oracle, against the reference's
-    compiled Fortran."""
-    from oracle.oracle import Ref, DL_NAMES
-    if not Ref.available():
-        pytest.skip("oracle/_ref not built (no /root/reference on this machine)")
-    ref = Ref()
-    rng = np.random.default_rng(3)
+    compiled Fortran (tests/golden/dl_kernels.npz, make_dl_golden.py: 100 random arguments per family)."""
+    from oracle.oracle import DL_NAMES
+    g = np.load(os.path.join(golden_dir, "dl_kernels.npz"))
+    assert list(g["names"]) == list(DL_NAMES.values())
     for fam in "ABC":
-        for _ in range(100):
-            a = rng.uniform(-3, 3, 4)
-            lx, ly = rng.uniform(0.3, 2, 2)
-            for w, name in DL_NAMES.items():
-                v, r = oracle.scalar_dl(fam, w, *a, lx, ly), ref.scalar(fam, name, *a, lx, ly)
+        args, vals = g[fam + "_args"], g[fam + "_values"]
+        assert args.shape == (100, 6) and vals.shape == (100, len(DL_NAMES))
+        for a, rs in zip(args, vals):
+            for w, r in zip(DL_NAMES, rs):
+                v = oracle.scalar_dl(fam, w, *a)
                 assert abs(v - r) <= 1e-12 * max(abs(r), 1e-3)
 
 
