@@ -187,6 +187,15 @@ int sgpr_fit_nll_grad_terms(sgpr_fit_t f, double *terms5);
 int sgpr_fit_eig(sgpr_fit_t f, double *w, double *c);
 /* K* . alpha for m test points with d pairs each: Xt (m x 2d), out (m x 2d), both column-major */
 int sgpr_fit_predict_nd(sgpr_fit_t f, int m, const double *Xt, size_t ldxt, double *out);
+/* Posterior mean and covariance at m test points from the cached factor: mean_t = K*_t alpha,
+ * cov_t = K**_t - K*_t Ky^-1 K*_t^T (latent prior, no noise).  Xt (m x 2d; (q, P) for d = 1 and reg), column-major,
+ * ldxt >= m.  D = 2d outputs per point (1 with SGPR_FIT_REG).  mean (m x D, ld m): the same bits as
+ * sgpr_fit_predict_rows / _nd.  cov: point t's D x D matrix, column-major, at cov + t*D*D, exactly symmetric.
+ * The values are returned as computed: rounding can leave a diagonal entry slightly negative next to a training point.
+ * SGPR_E_STATE before a solve and for SGPR_FIT_BLOCK_QQ / _PP fits; SGPR_E_HIP if a strip solve gave up on a hand-off.
+ * Device scratch: the fit's block-solve scratch plus one n x 256 block of doubles and a 256 x 256 one, kept until
+ * sgpr_fit_trim.  Added in ABI 5 (an additional entry point). */
+int sgpr_fit_predict_cov(sgpr_fit_t f, int m, const double *Xt, size_t ldxt, double *mean, double *cov);
 /* cond_2(Ky) estimated from below with the device's own kernels (needs a valid factor): lambda_max by `iters` power iterations on
  * Ky v -- the rows of K re-evaluated from the training points by the prediction kernel, plus |sig2n| v --, lambda_min by `iters`
  * inverse iterations with the cached factor.  out4 = {lambda_max, lambda_min, cond, relative change of the quotients in the last

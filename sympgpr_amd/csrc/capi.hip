@@ -94,9 +94,9 @@ struct sgpr_fit {
 // scratch for a solve with nrhs right-hand sides: the fit's own block, grown when a call needs more.  (Allocating and freeing
 // ~0.8 GB per call -- n = 98304 -- put milliseconds of idle device, a synchronising hipFree among them, in front of every
 // solve; see sgpr_fit_solve_rhs_dev for what that does to the first launch behind it.)
-static int rhs_scratch(sgpr_fit_t f, int nrhs, double **out)
+static int rhs_scratch(sgpr_fit_t f, int nrhs, double **out, size_t extra = 0)
 {
-    const size_t need = potrs_mat_scratch(f->n, nrhs, f->dA, (size_t)f->n);
+    const size_t need = potrs_mat_scratch(f->n, nrhs, f->dA, (size_t)f->n) + extra;
     if (need > f->rhs_scratch_bytes) {
         if (f->rhs_scratch) { SGPR_HIP(hipStreamSynchronize(f->st)); (void)hipFree(f->rhs_scratch); }
         f->rhs_scratch = nullptr; f->rhs_scratch_bytes = 0;
@@ -874,6 +874,82 @@ int sgpr_fit_predict_nd(sgpr_fit_t f, int m, const double *Xt, size_t ldxt, doub
                          f->dalpha, dO.as<double>(), f->st)))
         return rc;
     SGPR_HIP(hipMemcpyAsync(out, dO.p, (size_t)m * D * sizeof(double), hipMemcpyDeviceToHost, f->st));
+    SGPR_HIP(hipStreamSynchronize(f->st));
+    return 0;
+}
+
+/* Posterior mean and covariance (latent prior, no noise) at m test points, in chunks of mc = 256 / D points:
+ *   mean = K* alpha by the prediction kernels (one launch over all m: the bits of sgpr_fit_predict_rows / _nd);
+ *   per chunk  V = K*^T (n x D mc, the Gram kernels with the training points as rows, noise 0; point t's output a in column
+ *              a mc + t),  V := L^-1 V (potrs_mat_fwd: the strip solves' forward passes, 64 columns each),
+ *              K** = the chunk's test x test Gram block (D mc x D mc, same index map), cov_t = K**_t - V_t^T V_t (postcov.hip).
+ * Scratch: the fit's rhs_scratch, [solve scratch | V | K** | stage-1 partial sums]. */
+int sgpr_fit_predict_cov(sgpr_fit_t f, int m, const double *Xt, size_t ldxt, double *mean, double *cov)
+{
+    if (!f || m < 0 || !Xt || !mean || !cov || ldxt < (size_t)(m > 0 ? m : 1)) { set_error("fit_predict_cov: bad arguments"); return SGPR_E_ARG; }
+    if (!f->solved) { set_error("fit_predict_cov: not solved"); return SGPR_E_STATE; }
+    if (f->flags & (SGPR_FIT_BLOCK_QQ | SGPR_FIT_BLOCK_PP)) { set_error("fit_predict_cov: not defined for a single-block fit"); return SGPR_E_STATE; }
+    if (m == 0) return 0;
+    const bool reg = f->flags & SGPR_FIT_REG;
+    const int D = reg ? 1 : 2 * f->d, nx = 2 * f->d, N = f->npts;
+    const int mc = POSTCOV_COLS / D;
+    const size_t n = (size_t)f->n;
+    DevBuf dT, dM, dC;
+    int rc;
+    if ((rc = dT.alloc((size_t)m * nx * sizeof(double))) || (rc = dM.alloc((size_t)m * D * sizeof(double))) ||
+        (rc = dC.alloc((size_t)m * D * D * sizeof(double))))
+        return rc;
+    double *T = dT.as<double>(), *M = dM.as<double>(), *C = dC.as<double>();
+    SGPR_HIP(hipMemcpy2DAsync(T, (size_t)m * sizeof(double), Xt, ldxt * sizeof(double), (size_t)m * sizeof(double), nx,
+                              hipMemcpyHostToDevice, f->st));
+    if (reg)
+        rc = predict_reg(f->family, m, T, T + m, N, f->dx, f->dy, f->kc, f->dalpha, M, f->st);
+    else if (f->d == 1)
+        rc = predict_rows(f->family, m, T, T + m, N, f->dx, f->dy, f->kc, f->dalpha, M, M + m, f->st);
+    else
+        rc = predict_nd(f->family, f->d, m, T, (size_t)m, N, f->dX, (size_t)N, f->hyp_nd, f->nhyp_nd, f->dalpha, M, f->st);
+    if (rc) return rc;
+    // scratch: the solve's for D mc columns (a chunk of fewer columns takes the same path or, with one column, the transposed
+    // fallback, whose n doubles the strip scratch covers), then V, K** and the partial sums, each on a 256-byte boundary
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t solve_raw = potrs_mat_scratch(f->n, D * mc, f->dA, n), solve_b = up(solve_raw);
+    const size_t v_b = up(n * D * mc * sizeof(double)), k_b = up((size_t)D * mc * D * mc * sizeof(double));
+    const size_t p_b = up(postcov_partial_doubles(f->n, D, mc) * sizeof(double));
+    double *S;
+    if ((rc = rhs_scratch(f, D * mc, &S, solve_b - solve_raw + v_b + k_b + p_b))) return rc;
+    char *base = reinterpret_cast<char *>(S);
+    double *V = reinterpret_cast<double *>(base + solve_b), *Kss = reinterpret_cast<double *>(base + solve_b + v_b);
+    double *part = reinterpret_cast<double *>(base + solve_b + v_b + k_b);
+    for (int c0 = 0; c0 < m; c0 += mc) {
+        const int cnt = m - c0 < mc ? m - c0 : mc, ncols = D * cnt;
+        const double *tq = T + c0, *tp = T + m + c0;
+        const size_t kld = (size_t)ncols;
+        if (reg) {
+            if ((rc = gram_reg(f->family, N, cnt, f->dx, f->dy, tq, tp, f->kc, V, n, 0, 0.0, f->st))) return rc;
+        } else if (f->d == 1) {
+            if ((rc = gram_pairs(f->family, N, cnt, f->dx, f->dy, tq, tp, f->kc, V, V + N, V + n * cnt, V + N + n * cnt, n, 0, 0.0,
+                                 SGPR_G_ALL, f->st))) return rc;
+        } else {
+            if ((rc = gram_nd(f->family, f->d, N, cnt, f->dX, (size_t)N, tq, (size_t)m, f->hyp_nd, f->nhyp_nd, V, n, (size_t)N,
+                              (size_t)cnt, 0, 0.0, f->st))) return rc;
+        }
+        if ((rc = potrs_mat_fwd(f->n, f->dA, n, f->work, V, n, ncols, S, f->st))) return rc;
+        if (reg) {
+            rc = gram_reg(f->family, cnt, cnt, tq, tp, tq, tp, f->kc, Kss, kld, 0, 0.0, f->st);
+        } else if (f->d == 1) {
+            rc = gram_pairs(f->family, cnt, cnt, tq, tp, tq, tp, f->kc, Kss, Kss + cnt, Kss + kld * cnt, Kss + cnt + kld * cnt, kld, 0,
+                            0.0, SGPR_G_ALL, f->st);
+        } else {
+            rc = gram_nd(f->family, f->d, cnt, cnt, tq, (size_t)m, tq, (size_t)m, f->hyp_nd, f->nhyp_nd, Kss, kld, (size_t)cnt,
+                         (size_t)cnt, 0, 0.0, f->st);
+        }
+        if (rc) return rc;
+        if ((rc = postcov(D, f->n, cnt, V, n, Kss, kld, part, C + (size_t)c0 * D * D, f->st))) return rc;
+        // waits for the chunk; the next chunk's solve clears the give-up words, so they are read here
+        if ((rc = solve_status(f->n, f->dA, n, f->work, f->st))) return rc;
+    }
+    SGPR_HIP(hipMemcpyAsync(mean, M, (size_t)m * D * sizeof(double), hipMemcpyDeviceToHost, f->st));
+    SGPR_HIP(hipMemcpyAsync(cov, C, (size_t)m * D * D * sizeof(double), hipMemcpyDeviceToHost, f->st));
     SGPR_HIP(hipStreamSynchronize(f->st));
     return 0;
 }

@@ -1892,6 +1892,21 @@ int potrs_mat(int n, const double *L, size_t ldl, const void *work, double *B, s
     return transpose(nrhs, n, scratch, (size_t)nrhs, B, ldb, st);
 }
 
+// B (n x nrhs) := L^-1 B, the forward half of potrs_mat on the path potrs_mat would take for this block: the strip solves'
+// forward passes, or the right-hand sides transposed into rows (scratch, nrhs x n), X^T = B^T L^-T, transposed back.
+// scratch: potrs_mat_scratch(n, nrhs, L, ldl) bytes; a give-up of a strip pass is read through solve_status.
+int potrs_mat_fwd(int n, const double *L, size_t ldl, const void *work, double *B, size_t ldb, int nrhs,
+                  double *scratch, hipStream_t st)
+{
+    if (n <= 0 || nrhs <= 0) return 0;
+    if (potrs_mat_uses_strips(n, nrhs, L, ldl))
+        return trsm_strips_fwd(n, L, ldl, static_cast<const double *>(work), B, ldb, nrhs, solve_state(n, work), scratch, st);
+    int rc = transpose(n, nrhs, B, ldb, scratch, (size_t)nrhs, st);
+    if (rc) return rc;
+    if ((rc = trsm_rlt(nrhs, n, L, ldl, scratch, (size_t)nrhs, work, st))) return rc;
+    return transpose(nrhs, n, scratch, (size_t)nrhs, B, ldb, st);
+}
+
 // one-sided solve: b := L^-1 b (trans = 0) or L^-T b (trans = 1)
 int trsv(int n, const double *L, size_t ldl, void *work, double *b, int trans, hipStream_t st)
 {

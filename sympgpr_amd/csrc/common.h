@@ -125,6 +125,8 @@ int solve_status(int n, const double *L, size_t ldl, const void *work, hipStream
 int trsm_rl(int m, int n, const double *L, size_t ldl, double *B, size_t ldb, const void *work, hipStream_t st);  // B := B L^-1
 int potrs_mat(int n, const double *L, size_t ldl, const void *work, double *B, size_t ldb, int nrhs, double *scratch,
               hipStream_t st);  // B (n x nrhs) := L^-T L^-1 B; scratch: potrs_mat_scratch(n, nrhs, L, ldl) bytes
+int potrs_mat_fwd(int n, const double *L, size_t ldl, const void *work, double *B, size_t ldb, int nrhs, double *scratch,
+                  hipStream_t st);  // B := L^-1 B (the forward half of potrs_mat, same path, same scratch)
 size_t potrs_mat_scratch(int n, int nrhs, const double *L, size_t ldl);
 bool potrs_mat_uses_strips(int n, int nrhs, const double *L, size_t ldl);   // the one-launch block solves of trsm.hip (hand-off words in `work`: solve_status)
 int trsv(int n, const double *L, size_t ldl, void *work, double *b, int trans, hipStream_t st);
@@ -151,6 +153,14 @@ void trsm_piece_counts(int T, int C, size_t out[2]);
 size_t trsm_strips_scratch(int n);                                // bytes
 int potrs_strips(int n, const double *L, size_t ldl, const double *inv, double *B, size_t ldb, int nrhs, int *state /* TRSM_STATE_INTS ints */,
                  double *scratch, hipStream_t st);
+int trsm_strips_fwd(int n, const double *L, size_t ldl, const double *inv, double *B, size_t ldb, int nrhs, int *state,
+                    double *scratch, hipStream_t st);   // B := L^-1 B: potrs_strips' passes without the backward launch
+
+// ---- postcov.hip : posterior covariance blocks from V = L^-1 K*^T (two-stage deterministic reduction)
+constexpr int POSTCOV_COLS = 256;                                 // right-hand-side columns of one chunk at most
+size_t postcov_partial_doubles(int n, int D, int mc);             // stage-1 scratch of a chunk of mc points
+int postcov(int D, int n, int mc, const double *V, size_t ldv, const double *Kss, size_t ldk, double *part, double *cov,
+            hipStream_t st);
 
 // ---- batch.hip : many small fits (order <= 256 each) in one launch, one workgroup per problem
 int fit_batch_max_order();

@@ -919,13 +919,14 @@ size_t trsm_strips_scratch(int n)
            (size_t)2 * (n / LEAF + 1) * sizeof(int);
 }
 
-// B (n x nrhs, column-major, device) := L^-T L^-1 B, 64 columns per pass through the images; `state`: TRSM_STATE_INTS ints of
-// device scratch; `scratch`: trsm_strips_scratch(n) bytes.
-int potrs_strips(int n, const double *L, size_t ldl, const double *inv, double *B, size_t ldb, int nrhs, int *state,
-                 double *scratch, hipStream_t st)
+// B (n x nrhs, column-major, device) := L^-T L^-1 B (backward) or L^-1 B (forward only), 64 columns per pass through the
+// images; `state`: TRSM_STATE_INTS ints of device scratch; `scratch`: trsm_strips_scratch(n) bytes.  One body for both
+// callers: a forward-only pass is a full pass without the backward launch, unpacked from the forward solution's image.
+static int strips_solve(int n, const double *L, size_t ldl, const double *inv, double *B, size_t ldb, int nrhs, int *state,
+                        double *scratch, bool backward, hipStream_t st)
 {
     if (n <= 0 || nrhs <= 0) return 0;
-    if (!trsm_strips_ok(n, L, ldl)) { set_error("potrs_strips: shape not supported"); return SGPR_E_ARG; }
+    if (!trsm_strips_ok(n, L, ldl)) { set_error(backward ? "potrs_strips: shape not supported" : "trsm_strips_fwd: shape not supported"); return SGPR_E_ARG; }
     const int T = n / LEAF;
     // chain class: four quarters of the strips next to the frontier, each MS_F + 1 products long
     static const int nchain_env = (int)tune("trsm_chain", 0);
@@ -959,19 +960,35 @@ int potrs_strips(int n, const double *L, size_t ldl, const double *inv, double *
         hipLaunchKernelGGL(trsm_strips_kernel<true>, dim3(nchain + nstream), dim3(MS_T), 0, st, a);
         SGPR_CHECK_LAUNCH();
         if (dbg) dbg_report(a, "forward", st);
-        // backward: in = the forward solution, out = the first image
-        SGPR_HIP(hipMemsetAsync(I0, 0xFF, img * sizeof(double), st));
-        SGPR_HIP(hipMemsetAsync(S, 0xFF, img * sizeof(double), st));
-        if (xbytes) SGPR_HIP(hipMemsetAsync(X, 0xFF, xbytes, st));
-        a.Bin = I1; a.P = I0;
-        a.state = state + 4; a.ready = state + 12; a.mflag = mflag + T + 1;
-        hipLaunchKernelGGL(trsm_strips_kernel<false>, dim3(nchain + nstream), dim3(MS_T), 0, st, a);
-        SGPR_CHECK_LAUNCH();
-        if (dbg) { dbg_report(a, "backward", st); (void)hipFree(a.dbg); }
-        hipLaunchKernelGGL(unpack_rhs_kernel, dim3((n + 63) / 64), dim3(256), 0, st, n, nc, I0, B + (size_t)c0 * ldb, ldb);
+        if (backward) {
+            // backward: in = the forward solution, out = the first image
+            SGPR_HIP(hipMemsetAsync(I0, 0xFF, img * sizeof(double), st));
+            SGPR_HIP(hipMemsetAsync(S, 0xFF, img * sizeof(double), st));
+            if (xbytes) SGPR_HIP(hipMemsetAsync(X, 0xFF, xbytes, st));
+            a.Bin = I1; a.P = I0;
+            a.state = state + 4; a.ready = state + 12; a.mflag = mflag + T + 1;
+            hipLaunchKernelGGL(trsm_strips_kernel<false>, dim3(nchain + nstream), dim3(MS_T), 0, st, a);
+            SGPR_CHECK_LAUNCH();
+            if (dbg) dbg_report(a, "backward", st);
+        }
+        if (dbg) (void)hipFree(a.dbg);
+        hipLaunchKernelGGL(unpack_rhs_kernel, dim3((n + 63) / 64), dim3(256), 0, st, n, nc, backward ? I0 : I1, B + (size_t)c0 * ldb, ldb);
         SGPR_CHECK_LAUNCH();
     }
     return 0;
+}
+
+int potrs_strips(int n, const double *L, size_t ldl, const double *inv, double *B, size_t ldb, int nrhs, int *state,
+                 double *scratch, hipStream_t st)
+{
+    return strips_solve(n, L, ldl, inv, B, ldb, nrhs, state, scratch, true, st);
+}
+
+// B := L^-1 B: the forward half of potrs_strips (the same passes, hand-off words and give-up word state[2])
+int trsm_strips_fwd(int n, const double *L, size_t ldl, const double *inv, double *B, size_t ldb, int nrhs, int *state,
+                    double *scratch, hipStream_t st)
+{
+    return strips_solve(n, L, ldl, inv, B, ldb, nrhs, state, scratch, false, st);
 }
 
 }  // namespace sgpr

@@ -21,6 +21,7 @@ class SympFit:
         if x.shape != y.shape or x.ndim != 1:
             raise ValueError("x and y must be 1-D arrays of equal length")
         self.n_pts = len(x)
+        self.d, self.reg = 1, bool(reg)
         if block not in (None, "qq", "PP") or (block and reg):
             raise ValueError("block must be None, 'qq' or 'PP' (and excludes reg)")
         self.n = self.n_pts if (reg or block) else 2 * self.n_pts
@@ -45,7 +46,7 @@ class SympFit:
         if X.ndim != 2 or X.shape[1] % 2:
             raise ValueError("X must be (n_pts, 2d)")
         self.n_pts, D = X.shape
-        self.d = D // 2
+        self.d, self.reg = D // 2, False
         self.n = D * self.n_pts
         hyp = L.f64(hyp)
         z = L.f64(z) if z is not None else np.zeros(self.n)
@@ -63,6 +64,39 @@ class SympFit:
         out = np.empty((m, Xt.shape[1]), order="F")
         L.check(self._lib.sgpr_fit_predict_nd(self._h, m, L.dptr(Xt), max(m, 1), L.dptr(out)), "sgpr_fit_predict_nd")
         return out
+
+    def predict_pairs_cov(self, Xt):
+        """Posterior mean and covariance at test points Xt (m, 2d) of a create_nd / pairs fit, D = 2d outputs per point.
+        -> (mean (m, D), cov (m, D, D)).  Column / index a is dF/dx_a, as in predict_pairs; for d > 1 `mean` has the bits of
+        predict_pairs(Xt) (for d = 1 those of predict_rows, the same numbers to rounding).  cov[t] = K**_t - K*_t Ky^-1 K*_t^T
+        with K**_t the latent prior (no |sig2n| added): the covariance of the noise-free map, not of a new noisy observation.
+        Exactly symmetric; the values are returned as computed, so next to a training point rounding can leave a diagonal
+        entry slightly negative.  Needs a solved fit (run())."""
+        Xt = np.asfortranarray(np.atleast_2d(Xt), dtype=np.float64)
+        if Xt.ndim != 2 or Xt.shape[1] != 2 * self.d:
+            raise ValueError("Xt must be (m, %d)" % (2 * self.d))
+        return self._predict_cov(Xt)
+
+    def predict_cov(self, q, P):
+        """Posterior mean and covariance at the test points (q, P) of a d = 1 pair fit (D = 2) or a reg=True fit (D = 1).
+        -> (mean (m, D), cov (m, D, D)).  Pair fit: index 0 is predict_rows' out_p, index 1 its out_q, and `mean` has their
+        bits; reg fit: mean[:, 0] is predict_rows' out_p.  cov[t] = K**_t - K*_t Ky^-1 K*_t^T with K**_t the latent prior (no
+        |sig2n| added).  Exactly symmetric; the values are returned as computed, so next to a training point rounding can leave
+        a diagonal entry slightly negative.  Needs a solved fit (run()); not defined for block="qq" / "PP" fits."""
+        if self.d != 1:
+            raise ValueError("predict_cov is for d = 1 fits: use predict_pairs_cov")
+        q, P = L.f64(np.atleast_1d(q)), L.f64(np.atleast_1d(P))
+        if q.shape != P.shape or q.ndim != 1:
+            raise ValueError("q and P must be 1-D arrays of equal length")
+        return self._predict_cov(np.asfortranarray(np.column_stack((q, P)).reshape(len(q), 2)))
+
+    def _predict_cov(self, Xt):
+        m, D = Xt.shape[0], 1 if self.reg else 2 * self.d
+        mean = np.empty((m, D), order="F")
+        cov = np.empty((m, D, D))       # C order: point t's D x D block contiguous; symmetric, so its order does not matter
+        L.check(self._lib.sgpr_fit_predict_cov(self._h, m, L.dptr(Xt), max(m, 1), L.dptr(mean), L.dptr(cov)),
+                "sgpr_fit_predict_cov")
+        return mean, cov
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
