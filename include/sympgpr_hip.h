@@ -196,6 +196,17 @@ int sgpr_fit_predict_nd(sgpr_fit_t f, int m, const double *Xt, size_t ldxt, doub
  * Device scratch: the fit's block-solve scratch plus one n x 256 block of doubles and a 256 x 256 one, kept until
  * sgpr_fit_trim.  Added in ABI 5 (an additional entry point). */
 int sgpr_fit_predict_cov(sgpr_fit_t f, int m, const double *Xt, size_t ldxt, double *mean, double *cov);
+/* Gradient of the fit's NLL (1/2 z^T alpha + sum log L_ii) in every hyperparameter, from the cached factor and alpha:
+ * grad_theta = 1/2 sum_ij (Ky^-1 - alpha alpha^T)_ij dKy_ij/dtheta.  ngrad must be nhyp + 1.  grad[0 .. nhyp-1] follow the
+ * fit's hyp order -- d = 1 and SGPR_FIT_REG (lx, ly, [p,] sig), create_nd (lq_1..lq_d, lP_1..lP_d, [p_1..p_d,] sig) --, and
+ * grad[nhyp] is d/dsig2n: Ky holds |sig2n|, so it is sign(sig2n) 1/2 (tr Ky^-1 - alpha^T alpha), sign(0) = +1.
+ * Ky^-1 is formed by panels of 2048 rows (4096 above n = 8192) on the trailing blocks of the factor, 2 n^3 / 3 flop in all,
+ * each panel contracted with the derivatives of K evaluated pair by pair; the sums are deterministic.  The factor, alpha
+ * and the NLL are left as they are.  SGPR_E_ARG for a null handle or grad or a wrong ngrad (before any device call);
+ * SGPR_E_STATE before a solve and for SGPR_FIT_BLOCK_QQ / _PP fits; SGPR_E_HIP if the fit's strip solve gave up on a hand-off.
+ * Device scratch, allocated and freed per call: one panel (min(n, 2048 or 4096) x n doubles, 4.3 GB at n = 131 072) and
+ * the partial sums (a few MB).  Added in ABI 5 (an additional entry point). */
+int sgpr_fit_nll_grad_full(sgpr_fit_t f, double *grad, int ngrad);
 /* cond_2(Ky) estimated from below with the device's own kernels (needs a valid factor): lambda_max by `iters` power iterations on
  * Ky v -- the rows of K re-evaluated from the training points by the prediction kernel, plus |sig2n| v --, lambda_min by `iters`
  * inverse iterations with the cached factor.  out4 = {lambda_max, lambda_min, cond, relative change of the quotients in the last

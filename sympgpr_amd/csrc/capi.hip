@@ -852,6 +852,46 @@ int sgpr_fit_nll_grad_terms(sgpr_fit_t f, double *terms5)
     return 0;
 }
 
+/* The gradient of the NLL in every hyperparameter and sig2n (nllgrad.hip): Ky^-1 by row panels on the trailing blocks of
+ * the cached factor, each panel contracted with dK evaluated pair by pair; the raw sums come back and are scaled here --
+ * the lengths and periods by sig / 2 (the kernels differentiate k without sig), sig by 1/2, sig2n by sign(sig2n) / 2. */
+int sgpr_fit_nll_grad_full(sgpr_fit_t f, double *grad, int ngrad)
+{
+    if (!f || !grad) { set_error("fit_nll_grad_full: null argument"); return SGPR_E_ARG; }
+    const bool reg = f->flags & SGPR_FIT_REG, hasp = family_has_p(f->family);
+    const int nhyp = f->d > 1 ? f->nhyp_nd : (hasp ? 4 : 3);
+    if (ngrad != nhyp + 1) { set_error("fit_nll_grad_full: ngrad must be nhyp + 1 = " + std::to_string(nhyp + 1)); return SGPR_E_ARG; }
+    if (!f->solved) { set_error("fit_nll_grad_full: run the fit first"); return SGPR_E_STATE; }
+    if (f->flags & (SGPR_FIT_BLOCK_QQ | SGPR_FIT_BLOCK_PP)) { set_error("fit_nll_grad_full: not defined for a single-block fit"); return SGPR_E_STATE; }
+    const int d = f->d, nl = reg ? 2 : 2 * d;
+    double l[6], pp[3] = {0.0, 0.0, 0.0}, sig;
+    if (d > 1) {
+        for (int m = 0; m < nl; ++m) l[m] = f->hyp_nd[m];
+        for (int m = 0; m < d && hasp; ++m) pp[m] = f->hyp_nd[nl + m];
+        sig = f->hyp_nd[nhyp - 1];
+    } else {
+        l[0] = f->kc.lx; l[1] = f->kc.ly; pp[0] = f->kc.p; sig = f->kc.sig;
+    }
+    const int nacc = nhyp + 1;
+    DevBuf S, O;
+    int rc;
+    if ((rc = S.alloc(nll_grad_full_scratch(f->n, f->npts, nacc))) || (rc = O.alloc(nacc * sizeof(double)))) return rc;
+    if ((rc = nll_grad_full(f->family, d, reg, f->npts, f->n, f->dA, (size_t)f->n, f->work, f->dX, f->dalpha, l, pp, nacc,
+                            S.as<double>(), O.as<double>(), f->st)))
+        return rc;
+    double raw[12];
+    int h[8] = {};
+    const bool strips = trsv_uses_strips(f->n, f->dA, (size_t)f->n);
+    SGPR_HIP(hipMemcpyAsync(raw, O.p, nacc * sizeof(double), hipMemcpyDeviceToHost, f->st));
+    if (strips) SGPR_HIP(hipMemcpyAsync(h, trsv_state(f->n, f->work), sizeof(h), hipMemcpyDeviceToHost, f->st));
+    SGPR_HIP(hipStreamSynchronize(f->st));
+    if (h[2] || h[6]) { set_error("fit_nll_grad_full: the fit's triangular solve gave up on a hand-off between strips"); return SGPR_E_HIP; }
+    for (int k = 0; k < nhyp - 1; ++k) grad[k] = 0.5 * sig * raw[k];
+    grad[nhyp - 1] = 0.5 * raw[nhyp - 1];
+    grad[nhyp] = (f->sig2n < 0.0 ? -0.5 : 0.5) * raw[nhyp];
+    return 0;
+}
+
 /* K*(2d x 2d N) . alpha for m test points Xt (m x 2d, column-major, leading dimension ldxt):
  * out (m x 2d, column-major, ld m): column a = predicted d F / d x_a */
 int sgpr_fit_predict_nd(sgpr_fit_t f, int m, const double *Xt, size_t ldxt, double *out)

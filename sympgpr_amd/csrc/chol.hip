@@ -1865,6 +1865,23 @@ int trsm_rl(int m, int n, const double *L, size_t ldl, double *B, size_t ldb, co
     return trsm_rl_rec(m, n, L, ldl, B, ldb, 0, c);
 }
 
+// The two panel solves against the trailing block L[off:, off:] of a factor (off a multiple of LEAF; L points at that
+// block, n is its order): the recursion's leaf-aligned offset picks the factor's own leaf inverses from `work`.
+int trsm_rlt_off(int m, int n, const double *L, size_t ldl, double *B, size_t ldb, const void *work, int off, hipStream_t st)
+{
+    if (m <= 0 || n <= 0) return 0;
+    if (off < 0 || off % (int)LEAF) { set_error("trsm_rlt_off: offset not on a leaf boundary"); return SGPR_E_ARG; }
+    Ctx c{const_cast<double *>(static_cast<const double *>(work)), nullptr, st};
+    return trsm_rec(m, n, L, ldl, B, ldb, off, c);
+}
+int trsm_rl_off(int m, int n, const double *L, size_t ldl, double *B, size_t ldb, const void *work, int off, hipStream_t st)
+{
+    if (m <= 0 || n <= 0) return 0;
+    if (off < 0 || off % (int)LEAF) { set_error("trsm_rl_off: offset not on a leaf boundary"); return SGPR_E_ARG; }
+    Ctx c{const_cast<double *>(static_cast<const double *>(work)), nullptr, st};
+    return trsm_rl_rec(m, n, L, ldl, B, ldb, off, c);
+}
+
 // Blocks of 2 .. 256 right-hand sides take the one-launch strip solves of trsm.hip (L streamed once per 64 columns);
 // more than that is compute-bound and stays with the recursion over the grid-wide MFMA kernel.  SGPR_TRSM=rec: always.
 bool potrs_mat_uses_strips(int n, int nrhs, const double *L, size_t ldl)

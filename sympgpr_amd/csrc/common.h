@@ -123,6 +123,9 @@ int trsm_rlt(int m, int n, const double *L, size_t ldl, double *B, size_t ldb, c
 int potrs_vec(int n, const double *L, size_t ldl, void *work, double *b, hipStream_t st);
 int solve_status(int n, const double *L, size_t ldl, const void *work, hipStream_t st);   // syncs st; SGPR_E_HIP if a strip solve gave up
 int trsm_rl(int m, int n, const double *L, size_t ldl, double *B, size_t ldb, const void *work, hipStream_t st);  // B := B L^-1
+// the same two against the trailing block L[off:, off:] (L points at it, n its order, off a multiple of 128)
+int trsm_rlt_off(int m, int n, const double *L, size_t ldl, double *B, size_t ldb, const void *work, int off, hipStream_t st);
+int trsm_rl_off(int m, int n, const double *L, size_t ldl, double *B, size_t ldb, const void *work, int off, hipStream_t st);
 int potrs_mat(int n, const double *L, size_t ldl, const void *work, double *B, size_t ldb, int nrhs, double *scratch,
               hipStream_t st);  // B (n x nrhs) := L^-T L^-1 B; scratch: potrs_mat_scratch(n, nrhs, L, ldl) bytes
 int potrs_mat_fwd(int n, const double *L, size_t ldl, const void *work, double *B, size_t ldb, int nrhs, double *scratch,
@@ -161,6 +164,12 @@ constexpr int POSTCOV_COLS = 256;                                 // right-hand-
 size_t postcov_partial_doubles(int n, int D, int mc);             // stage-1 scratch of a chunk of mc points
 int postcov(int D, int n, int mc, const double *V, size_t ldv, const double *Kss, size_t ldk, double *part, double *cov,
             hipStream_t st);
+
+// ---- nllgrad.hip : the NLL gradient in all hyperparameters from Ky^-1 by row panels (sgpr_fit_nll_grad_full)
+size_t nll_grad_full_scratch(int n, int N, int nacc);             // bytes: one panel of Ky^-1 + the partial sums
+int nll_grad_full(int family, int d, bool reg, int N, int n, const double *L, size_t ldl, const void *work, const double *X,
+                  const double *alpha, const double *l, const double *pp, int nacc, double *scratch, double *out,
+                  hipStream_t st);
 
 // ---- batch.hip : many small fits (order <= 256 each) in one launch, one workgroup per problem
 int fit_batch_max_order();

@@ -25,6 +25,7 @@ class SympFit:
         if block not in (None, "qq", "PP") or (block and reg):
             raise ValueError("block must be None, 'qq' or 'PP' (and excludes reg)")
         self.n = self.n_pts if (reg or block) else 2 * self.n_pts
+        self.nhyp = len(hyp)
         z = L.f64(z) if z is not None else np.zeros(self.n)
         if z.shape != (self.n,):
             raise ValueError("z must have length %d" % self.n)
@@ -49,6 +50,7 @@ class SympFit:
         self.d, self.reg = D // 2, False
         self.n = D * self.n_pts
         hyp = L.f64(hyp)
+        self.nhyp = len(hyp)
         z = L.f64(z) if z is not None else np.zeros(self.n)
         if z.shape != (self.n,):
             raise ValueError("z must have length %d" % self.n)
@@ -148,6 +150,23 @@ class SympFit:
         """d nll / d(lx, ly) (functions/func.py:132-162: nlp_grad) on a solved fit."""
         g = np.empty(2)
         L.check(self._lib.sgpr_fit_nll_grad(self._h, L.dptr(g)), "sgpr_fit_nll_grad")
+        return g
+
+    def nll_grad_full(self):
+        """Gradient of the fit's NLL (1/2 z^T alpha + sum log L_ii) in every hyperparameter, on a solved fit: an ndarray of
+        shape (nhyp + 1,).  Entries 0 .. nhyp-1 follow the fit's hyp order -- (lx, ly, [p,] sig) for SympFit(...) and
+        SympFit(..., reg=True), (lq_1..lq_d, lP_1..lP_d, [p_1..p_d,] sig) for SympFit.pairs --, the last entry is d/dsig2n.
+        Ky holds |sig2n|, so that entry is sign(sig2n) * 1/2 (tr Ky^-1 - alpha^T alpha), with sign(0) = +1.  Exact (no
+        finite differences), deterministic, and the factor, alpha and nll() are left as they are.  Not defined for
+        block="qq" / "PP" fits.  With SciPy's L-BFGS-B over (hyp, sig2n):
+
+            def fun(h):
+                f.set_hyp(h[:-1], h[-1]); f.run()
+                return f.nll(), f.nll_grad_full()
+            res = scipy.optimize.minimize(fun, np.append(hyp, sig2n), jac=True, method="L-BFGS-B")
+        """
+        g = np.empty(self.nhyp + 1)
+        L.check(self._lib.sgpr_fit_nll_grad_full(self._h, L.dptr(g), len(g)), "sgpr_fit_nll_grad_full")
         return g
 
     def nll_grad_terms(self):

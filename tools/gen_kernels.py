@@ -6,7 +6,8 @@ The reference derives every kernel function from ONE symbolic definition and emi
 the device: define k(x_a, y_a, x_b, y_b; lx, ly[, p]), differentiate, common-subexpression-eliminate,
 print C -- one device function per family for the four functions that enter K (k, d2k/dx_a dx_b,
 d2k/dy_a dy_b, d2k/dx_a dy_b) and one each for their lx- and ly-derivatives (the dkdl*, d3k..dl*
-functions build_dK / build_dKreg need, functions/func.py:52-129).
+functions build_dK / build_dKreg need, functions/func.py:52-129), plus their derivatives by the period p (zero for the
+families without one; sgpr_fit_nll_grad_full).
 
     python tools/gen_kernels.py            # rewrites sympgpr_amd/csrc/generated/pair_generated.h
 
@@ -107,13 +108,17 @@ namespace gen {
 template <int FAM> __device__ __forceinline__ void pair(double x_a, double y_a, double x_b, double y_b, double lx, double ly, double p, double *out);
 template <int FAM> __device__ __forceinline__ void pair_dlx(double x_a, double y_a, double x_b, double y_b, double lx, double ly, double p, double *out);
 template <int FAM> __device__ __forceinline__ void pair_dly(double x_a, double y_a, double x_b, double y_b, double lx, double ly, double p, double *out);
+//   gen::pair_dp<FAM>(..., out): the same four differentiated by the period p (all zero for a family without one)
+template <int FAM> __device__ __forceinline__ void pair_dp(double x_a, double y_a, double x_b, double y_b, double lx, double ly, double p, double *out);
 //   gen::extra<FAM>(which, ...): the seven functions no caller of the reference uses, by SGPR_K_* code (16 .. 22): with pair,
 //     pair_dlx and pair_dly all 19 functions of a kernels*.f90
 //   gen::factor<FAM, Q>(dx, l, p, out): one coordinate's factor f of the d > 1 product / sum kernel (Q = 1: a q, Q = 0: a P):
 //     out = { log f, f'/f, -f''/f };  gen::factor_dl<FAM, Q>: the same three differentiated by the length l
+//     gen::factor_dp<FAM, Q>: the same three differentiated by the period p (all zero for a factor without one)
 template <int FAM> __device__ double extra(int which, double x_a, double y_a, double x_b, double y_b, double lx, double ly, double p);
 template <int FAM, int Q> __device__ __forceinline__ void factor(double dx, double l, double p, double *out);
 template <int FAM, int Q> __device__ __forceinline__ void factor_dl(double dx, double l, double p, double *out);
+template <int FAM, int Q> __device__ __forceinline__ void factor_dp(double dx, double l, double p, double *out);
 '''
     body = []
     names = ["k", "d2k/dx_a dx_b", "d2k/dy_a dy_b", "d2k/dx_a dy_b"]
@@ -122,7 +127,7 @@ template <int FAM, int Q> __device__ __forceinline__ void factor_dl(double dx, d
     for fam, (enum, fq, fP, mode) in fams.items():
         k = kernel_of(fq, fP, mode)
         four = [k, sp.diff(k, x_a, x_b), sp.diff(k, y_a, y_b), sp.diff(k, x_a, y_b)]
-        for fn, var in (("pair", None), ("pair_dlx", lx), ("pair_dly", ly)):
+        for fn, var in (("pair", None), ("pair_dlx", lx), ("pair_dly", ly), ("pair_dp", p)):
             ex = four if var is None else [sp.diff(e, var) for e in four]
             nm = names if var is None else ["d/d%s %s" % (var, n) for n in names]
             body.append("// family %s: k = %s\ntemplate <> __device__ __forceinline__ void %s<%s>(double x_a, double y_a, double x_b, "
@@ -139,7 +144,8 @@ template <int FAM, int Q> __device__ __forceinline__ void factor_dl(double dx, d
             fd = f.subs({a: dx, b: 0, lsym: l})
             three = [sp.simplify(sp.log(fd)), sp.simplify(sp.diff(fd, dx) / fd), sp.simplify(-sp.diff(fd, dx, 2) / fd)]
             nm3 = ["log f", "f'/f", "-f''/f"]
-            for fn, ex, nm in (("factor", three, nm3), ("factor_dl", [sp.diff(e, l) for e in three], ["d/dl " + n for n in nm3])):
+            for fn, ex, nm in (("factor", three, nm3), ("factor_dl", [sp.diff(e, l) for e in three], ["d/dl " + n for n in nm3]),
+                               ("factor_dp", [sp.diff(e, p) for e in three], ["d/dp " + n for n in nm3])):
                 body.append("template <> __device__ __forceinline__ void %s<%s, %d>(double dx, double l, double p, double *out)\n"
                             "{\n    (void)p;\n%s\n}\n" % (fn, enum, Q, emit(ex, nm)))
     ufq, ufP, umode = USER_FAMILY
