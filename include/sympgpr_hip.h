@@ -26,6 +26,9 @@
  *     take device pointers (hipMalloc / torch tensors) and a hipStream_t passed as void*.
  *   - There is NO CPU fallback: without a usable gfx950 device every compute call
  *     returns SGPR_E_NODEVICE.
+ *   - Argument errors (bad extents, leading dimensions, null pointers) of the `*_dev` primitives are
+ *     reported as SGPR_E_ARG before any device is looked for, so before SGPR_E_NODEVICE; the message
+ *     names the entry point.
  */
 #ifndef SYMPGPR_HIP_H
 #define SYMPGPR_HIP_H

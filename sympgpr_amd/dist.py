@@ -14,9 +14,10 @@ on grid position (I mod pr, J mod pc).  Per panel step K of the right-looking fa
                          (RCCL broadcasts on row / column sub-communicators over xGMI: a rank
                          receives n/pr + n/pc rows of the panel, not all n)
     everyone:            local trailing update A(I,J) -= L(I,K) L(J,K)^T on the blocks it owns
-                         (sgpr_gemm_nt_bc_dev, fp64 MFMA, tiles above the global diagonal
-                         skipped) -- block column K+1 first, so that panel K+1 can be factored
-                         and broadcast (asynchronously) underneath the bulk of update K
+                         (one sgpr_gemm_nt_dev per local column block J, fp64 MFMA, over the
+                         row blocks I >= J of its packed panel) -- block column K+1 first, so
+                         that panel K+1 can be factored and broadcast (asynchronously)
+                         underneath the bulk of update K
 
 The Gram build needs no communication: every rank evaluates exactly the pairs of the blocks it
 owns (inputs are replicated, 16 N bytes).  The triangular solves keep b replicated and exchange
