@@ -241,9 +241,23 @@ int sgpr_fit_batch_max_order(void);
 int sgpr_fit_batch(int family, int nbatch, int n_pts, const double *x, const double *y, const double *z,
                    const double *hyp, int nhyp, const double *sig2n, unsigned flags, double *alpha,
                    double *nll, int *info);
+/* sgpr_fit_batch plus d nll / d(hyp, sig2n) per problem.  Order per problem n = 2 n_pts (n_pts with SGPR_FIT_REG) <= 256.
+ * grad: nbatch x (nhyp + 1), row-major; row b = (d/dhyp_0 .. d/dhyp_{nhyp-1}, d/dsig2n).  hyp layout and nhyp as
+ * sgpr_fit_batch: (lx, ly, sig), or (lx, ly, p, sig) for families with a period.  Ky holds |sig2n[b]|, so the last entry is
+ * sign(sig2n[b]) * 1/2 (tr Ky^-1 - alpha^T alpha), with sign(0) = +1.  info[b] > 0: nll[b] and the whole row grad[b] are NaN.
+ * nll, alpha and info are bit-identical to sgpr_fit_batch's (the same factor and solves); the gradient of a problem is
+ * deterministic and does not depend on its place in the batch.  One launch, one workgroup per problem: after the fit it
+ * forms L^-1 from the leaf inverses, Ky^-1 = L^-T L^-1 and contracts Ky^-1 - alpha alpha^T with dK pair by pair.  SGPR_E_ARG
+ * (before any device call) for an unknown family, a wrong nhyp, an unknown flag, nbatch < 0, n_pts <= 0, an order above 256
+ * and a null pointer other than alpha; nbatch == 0 returns 0.  Device scratch: the sgpr_fit_batch arena grows to ~1.3 MiB per
+ * workgroup (up to 1024 workgroups: ~1.3 GiB), kept until sgpr_trim.  Added in ABI 5 (an additional entry point). */
+int sgpr_fit_batch_grad(int family, int nbatch, int n_pts, const double *x, const double *y, const double *z,
+                        const double *hyp, int nhyp, const double *sig2n, unsigned flags, double *alpha,
+                        double *nll, double *grad, int *info);
 
 /* Gives back what the CALLING thread's earlier calls keep for re-use: the device arena and page-locked staging block of
- * sgpr_fit_batch (up to ~2 GiB after a large batch of order-2048 problems; they also shrink by themselves when a much smaller batch
+ * sgpr_fit_batch and sgpr_fit_batch_grad (up to ~2 GiB after a large batch of order-2048 problems, ~1.3 GiB after a gradient batch
+ * of 1024 problems or more; they also shrink by themselves when a much smaller batch
  * follows) and the pooled events of its factorisations.  Never needed for correctness; call it between a hyper-parameter search
  * over small problems and a fit that wants the whole HBM.  No call of this thread may be in flight. */
 int sgpr_trim(void);

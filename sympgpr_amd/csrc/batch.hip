@@ -18,6 +18,7 @@
 #include "common.h"
 #include "gemm_tile.h"
 #include "leaf.h"
+#include "nllgrad_pair.h"
 #include "pair_eval.h"
 
 namespace sgpr {
@@ -28,6 +29,7 @@ using namespace leaf;
 using namespace pairf;
 
 constexpr int BMAX = 2 * LEAF;            // largest order per problem
+constexpr size_t PER_WG = (size_t)BMAX * BMAX + 2 * (size_t)LEAF * LEAF + 2 * BMAX;   // scratch doubles per workgroup (fit)
 
 struct BatchArgs {
     int nbatch, npts, n, reg;
@@ -35,18 +37,27 @@ struct BatchArgs {
     const KConst *kc;                     // per problem
     const double *noise;                  // per problem, >= 0
     double *scratch;                      // per workgroup: BMAX*BMAX (Ky / L) + 2*LEAF*LEAF (leaf inverses) + 2*BMAX
-    double *alpha, *nll;                  // outputs (alpha may be null)
+                                          // [+ BMAX*BMAX (U = L^-T) for the gradient]
+    double *alpha, *nll;                  // outputs (alpha may be null); the gradient kernel writes problem b's raw sums at
+                                          // nll + nbatch + b * grad_nacc<FAM>()
     int *info;                            // per problem, zero on entry
 };
 
+template <int FAM> constexpr bool grad_has_p() { return FAM == SGPR_FAM_D || (FAM == SGPR_FAM_USER && gen::user_has_p); }
+template <int FAM> constexpr int grad_nacc() { return grad_has_p<FAM>() ? 5 : 4; }    // lx, ly, [p,] sig, sig2n
+
 template <int FAM>
+__device__ void grad_problem(const BatchArgs &a, int b, double *s, double *A, const double *inv, double *U, const double *al);
+
+// GRAD: after the fit, the gradient of problem b's nll (grad_problem below); scratch then PER_WG_GRAD doubles per workgroup
+template <int FAM, bool GRAD = false>
 __global__ __launch_bounds__(LT) void fit_batch_kernel(const BatchArgs a)
 {
     __shared__ double s[LEAF_LDS];
     __shared__ double red[LT / 64];
     const int tid = threadIdx.x;
     const int n = a.n, N = a.npts;
-    const size_t per_wg = (size_t)BMAX * BMAX + 2 * (size_t)LEAF * LEAF + 2 * BMAX;
+    const size_t per_wg = (size_t)BMAX * BMAX + 2 * (size_t)LEAF * LEAF + 2 * BMAX + (GRAD ? (size_t)BMAX * BMAX : 0);   // PER_WG [+ U]
     double *A = a.scratch + (size_t)blockIdx.x * per_wg;     // column-major, ld = BMAX
     double *inv = A + (size_t)BMAX * BMAX;
     double *v = inv + 2 * (size_t)LEAF * LEAF;                // y, then alpha
@@ -169,7 +180,125 @@ __global__ __launch_bounds__(LT) void fit_batch_kernel(const BatchArgs a)
             for (int i = tid; i < n; i += LT) a.alpha[(size_t)b * n + i] = al[i];
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
+        if constexpr (GRAD) grad_problem<FAM>(a, b, s, A, inv, v + 2 * BMAX, al);
     }
+}
+
+// The gradient of problem b's nll in (lx, ly, [p,] sig, sig2n), by the workgroup that has just fitted it: A holds L, inv the
+// leaf inverses X11 = L11^-1 and X22 = L22^-1, al alpha; U is BMAX^2 doubles of the workgroup's scratch.
+//   (1) U = L^-T, column-major, zero below the diagonal:  L^-1 = [[X11, 0], [-X22 L21 X11, X22]];  T = L21 X11 goes through LDS.
+//   (2) Ky^-1 = L^-T L^-1 = U U^T, lower triangle, into A (over L: the nll has read its diagonal):  n^3 / 3 flop.
+//   (3) thread i owns row i of W = Ky^-1 - alpha alpha^T and walks the column points j, each pair evaluated once with dK from
+//       the generated forms (nllgrad_pair.h), entries on and below the diagonal weighted W_ii and 2 W_ij.  The per-thread
+//       sums fold wave by wave in a fixed order: a problem's bits do not depend on its place in the batch or on the grid.
+// The sums leave unscaled, as nll_grad_full's (nllgrad.hip): the host applies sig / 2, 1/2 and sign(sig2n) / 2.
+template <int FAM>
+__device__ void grad_problem(const BatchArgs &a, int b, double *s, double *A, const double *inv, double *U, const double *al)
+{
+    constexpr bool HASP = grad_has_p<FAM>();
+    constexpr int NACC = grad_nacc<FAM>();
+    constexpr size_t ld = BMAX;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = a.n, N = a.npts, n1 = min(n, (int)LEAF), n2 = n - n1;
+    double *out = a.nll + a.nbatch + (size_t)b * NACC;
+    // not positive definite (leaf_body's flag, read from L2: the same value for every thread): NaN, nothing computed
+    if (__hip_atomic_load(a.info + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
+        if (tid < NACC) out[tid] = __builtin_nan("");
+        return;
+    }
+    // ---- (1) U = L^-T.  The diagonal blocks (transposed leaf inverses) and the zeros; U[i + k ld] = (L^-1)[k, i]
+    for (int e = tid; e < n * n; e += LT) {
+        const int i = e % n, k = e / n;
+        if (i < n1 && k >= n1) continue;                  // the block right of X11^T: below
+        double u = 0.0;
+        if (k >= i) u = k < n1 ? inv[k + i * LEAF] : inv[LEAF * LEAF + (k - n1) + (i - n1) * LEAF];
+        U[i + k * ld] = u;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (n2 > 0) {                                         // then n1 = LEAF
+        // T = L21 X11 (n2 x LEAF) into LDS, T[m, c] at s[c + m LEAF]; X11[q, c] = U[c + q ld], zero for q < c, so a wave
+        // (64 consecutive c) may start at its first c
+        for (int e = tid; e < n2 * (int)LEAF; e += LT) {
+            const int c = e % LEAF, m = e / LEAF;
+            double acc = 0.0;
+            for (int q = c & ~63; q < (int)LEAF; ++q) acc = __builtin_fma(A[(n1 + m) + q * ld], U[c + q * ld], acc);
+            s[e] = acc;
+        }
+        __syncthreads();
+        // (L^-1)_21 = -X22 T:  its row k is column n1 + k of U
+        const double *X22 = inv + LEAF * LEAF;
+        for (int e = tid; e < n2 * (int)LEAF; e += LT) {
+            const int c = e % LEAF, k = e / LEAF;
+            double acc = 0.0;
+            for (int m = 0; m <= k; ++m) acc = __builtin_fma(-X22[k + m * LEAF], s[c + m * LEAF], acc);
+            U[c + (n1 + k) * ld] = acc;
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+    // ---- (2) Ky^-1[i, j] = sum_{k >= i} U[i, k] U[j, k], i >= j: thread i (n <= LT); k starts at the wave's first row
+    const int i = tid;
+    for (int j = 0; j < n; ++j) {
+        if (i < n && i >= j) {
+            double acc = 0.0;
+            for (int k = max(j, i & ~63); k < n; ++k) acc = __builtin_fma(U[i + k * ld], U[j + k * ld], acc);
+            A[i + j * ld] = acc;
+        }
+    }
+    // ---- (3) the points and alpha into LDS (T is dead), then the contraction
+    double *sx = s, *sy = s + BMAX, *sal = s + 2 * BMAX, *red = s + 3 * BMAX;
+    for (int e = tid; e < N; e += LT) { sx[e] = a.x[(size_t)b * N + e]; sy[e] = a.y[(size_t)b * N + e]; }
+    for (int e = tid; e < n; e += LT) sal[e] = al[e];
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    const KConst kc = a.kc[b];
+    const double l[2] = {kc.lx, kc.ly}, pp[1] = {kc.p};
+    double acc[NACC];
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
+    if (i < n) {
+        const double ai = sal[i];
+        if (a.reg) {
+            const double xi = sx[i], yi = sy[i];
+            for (int j = 0; j <= i; ++j) {
+                const double W = A[i + j * ld] - ai * sal[j];
+                if (j == i) acc[NACC - 1] += W;
+                nllg::reg_grad<FAM, HASP>(sx[j], sy[j], xi, yi, j == i ? W : 2.0 * W, l, kc.p, acc);
+            }
+        } else {
+            const int r = i < N ? 0 : 1, pi = i - r * N;
+            const double xi[2] = {sx[pi], sy[pi]};
+            for (int pj = 0; pj < N; ++pj) {
+                double w[2];
+                bool any = false;
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {                 // columns pj (q part) and N + pj (P part)
+                    const int col = c * N + pj;
+                    w[c] = 0.0;
+                    if (col <= i) {
+                        const double W = A[i + col * ld] - ai * sal[col];
+                        if (col == i) { w[c] = W; acc[NACC - 1] += W; }
+                        else w[c] = 2.0 * W;
+                        any = true;
+                    }
+                }
+                if (!any) break;                              // column pj > i: so are all after it
+                const double xj[2] = {sx[pj], sy[pj]};
+                nllg::pair_grad<FAM, 2, HASP>(xi, xj, w, r, l, pp, acc);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) {
+        double v = acc[k];
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+        if (lane == 0) red[wave * NACC + k] = v;
+    }
+    __syncthreads();
+    if (tid < NACC) out[tid] = red[tid] + red[NACC + tid] + red[2 * NACC + tid] + red[3 * NACC + tid];
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();                                      // A, U and s are the next problem's
 }
 
 // ---- mid-size problems: 256 < n <= 2048 (a CMA-ES generation at N = 512 ... 1024 points) --------------------------
@@ -461,27 +590,22 @@ int fit_batch_mid(int family, int nbatch, int npts, int n, int reg, const double
 
 }  // namespace
 
-// host buffers in, host buffers out; see include/sympgpr_hip.h (sgpr_fit_batch)
-int fit_batch(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
-              int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, int *info)
+namespace {
+
+// problems of order n <= BMAX: one launch of fit_batch_kernel, one workgroup per problem.  grad (nbatch x (nhyp + 1)) non-null:
+// the gradient kernel, whose raw sums come back behind nll in the same device-to-host copy and are scaled here.
+int fit_batch_small(int family, int nbatch, int npts, int n, int reg, const double *x, const double *y, const double *z,
+                    const double *hyp, int nhyp, const double *sig2n, double *alpha, double *nll, int *info, double *grad)
 {
-    const int reg = (flags & SGPR_FIT_REG) ? 1 : 0;
-    const int n = reg ? npts : 2 * npts;
-    if (nbatch < 0 || npts <= 0 || n > potrf_batch_max_order() || !x || !y || !z || !hyp || !sig2n || !nll || !info ||
-        (flags & ~(unsigned)SGPR_FIT_REG)) {
-        set_error("fit_batch: bad arguments (order per problem at most 2048)");
-        return SGPR_E_ARG;
-    }
-    if (nbatch == 0) return 0;
-    if (family < SGPR_FAM_A || family > SGPR_FAM_USER) { set_error("fit_batch: unknown kernel family"); return SGPR_E_ARG; }
-    if (n > BMAX) return fit_batch_mid(family, nbatch, npts, n, reg, x, y, z, hyp, nhyp, sig2n, alpha, nll, info);
     const size_t B = (size_t)nbatch;
     const int grid = nbatch < 1024 ? nbatch : 1024;
-    const size_t per_wg = (size_t)BMAX * BMAX + 2 * (size_t)LEAF * LEAF + 2 * BMAX;
-    // input block (one H2D): x | y | z | KConst | noise ; output block (one D2H): alpha | nll | info
+    const size_t per_wg = PER_WG + (grad ? (size_t)BMAX * BMAX : 0);
+    const size_t nacc = grad ? (size_t)nhyp + 1 : 0;
+    // input block (one H2D): x | y | z | KConst | noise ; output block (one D2H): alpha | nll [| raw gradient sums] | info
     const size_t o_x = 0, o_y = o_x + up256(B * npts * 8), o_z = o_y + up256(B * npts * 8), o_kc = o_z + up256(B * n * 8),
                  o_no = o_kc + up256(B * sizeof(KConst)), in_bytes = o_no + up256(B * 8);
-    const size_t o_al = 0, o_nll = o_al + up256(B * n * 8), o_info = o_nll + up256(B * 8), out_bytes = o_info + up256(B * sizeof(int));
+    const size_t o_al = 0, o_nll = o_al + up256(B * n * 8), o_info = o_nll + up256(B * (1 + nacc) * 8),
+                 out_bytes = o_info + up256(B * sizeof(int));
     const size_t scr_bytes = (size_t)grid * per_wg * 8;
     Arena &ar = t_arena;
     int rc = ar.reserve(in_bytes + out_bytes + scr_bytes, in_bytes + out_bytes);
@@ -505,12 +629,23 @@ int fit_batch(int family, int nbatch, int npts, const double *x, const double *y
                 reinterpret_cast<double *>(din + o_no), reinterpret_cast<double *>(dscr),
                 reinterpret_cast<double *>(dout + o_al), reinterpret_cast<double *>(dout + o_nll),
                 reinterpret_cast<int *>(dout + o_info)};
-    switch (family) {
-    case SGPR_FAM_A: hipLaunchKernelGGL(fit_batch_kernel<SGPR_FAM_A>, dim3(grid), dim3(LT), 0, st, a); break;
-    case SGPR_FAM_B: hipLaunchKernelGGL(fit_batch_kernel<SGPR_FAM_B>, dim3(grid), dim3(LT), 0, st, a); break;
-    case SGPR_FAM_C: hipLaunchKernelGGL(fit_batch_kernel<SGPR_FAM_C>, dim3(grid), dim3(LT), 0, st, a); break;
-    case SGPR_FAM_USER: hipLaunchKernelGGL(fit_batch_kernel<SGPR_FAM_USER>, dim3(grid), dim3(LT), 0, st, a); break;
-    default:         hipLaunchKernelGGL(fit_batch_kernel<SGPR_FAM_D>, dim3(grid), dim3(LT), 0, st, a); break;
+    const dim3 g(grid), t(LT);
+    if (grad) {
+        switch (family) {
+        case SGPR_FAM_A: hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_A, true>), g, t, 0, st, a); break;
+        case SGPR_FAM_B: hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_B, true>), g, t, 0, st, a); break;
+        case SGPR_FAM_C: hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_C, true>), g, t, 0, st, a); break;
+        case SGPR_FAM_USER: hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_USER, true>), g, t, 0, st, a); break;
+        default:         hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_D, true>), g, t, 0, st, a); break;
+        }
+    } else {
+        switch (family) {
+        case SGPR_FAM_A: hipLaunchKernelGGL(fit_batch_kernel<SGPR_FAM_A>, g, t, 0, st, a); break;
+        case SGPR_FAM_B: hipLaunchKernelGGL(fit_batch_kernel<SGPR_FAM_B>, g, t, 0, st, a); break;
+        case SGPR_FAM_C: hipLaunchKernelGGL(fit_batch_kernel<SGPR_FAM_C>, g, t, 0, st, a); break;
+        case SGPR_FAM_USER: hipLaunchKernelGGL(fit_batch_kernel<SGPR_FAM_USER>, g, t, 0, st, a); break;
+        default:         hipLaunchKernelGGL(fit_batch_kernel<SGPR_FAM_D>, g, t, 0, st, a); break;
+        }
     }
     SGPR_CHECK_LAUNCH();
     // without alpha only the tail of the output block comes back
@@ -520,7 +655,52 @@ int fit_batch(int family, int nbatch, int npts, const double *x, const double *y
     if (alpha) memcpy(alpha, hout + o_al, B * n * 8);
     memcpy(nll, hout + o_nll, B * 8);
     memcpy(info, hout + o_info, B * sizeof(int));
+    if (grad) {
+        const double *raw = reinterpret_cast<const double *>(hout + o_nll) + B;
+        for (size_t b = 0; b < B; ++b) {
+            const double *r = raw + b * nacc;
+            double *g = grad + b * nacc;
+            if (info[b] != 0) {
+                nll[b] = std::nan("");
+                for (size_t k = 0; k < nacc; ++k) g[k] = std::nan("");
+                continue;
+            }
+            const double sig = kcs[b].sig;
+            for (int k = 0; k < nhyp - 1; ++k) g[k] = 0.5 * sig * r[k];
+            g[nhyp - 1] = 0.5 * r[nhyp - 1];
+            g[nhyp] = (sig2n[b] < 0.0 ? -0.5 : 0.5) * r[nhyp];
+        }
+    }
     return 0;
+}
+
+}  // namespace
+
+// host buffers in, host buffers out; see include/sympgpr_hip.h (sgpr_fit_batch)
+int fit_batch(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
+              int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, int *info)
+{
+    const int reg = (flags & SGPR_FIT_REG) ? 1 : 0;
+    const int n = reg ? npts : 2 * npts;
+    if (nbatch < 0 || npts <= 0 || n > potrf_batch_max_order() || !x || !y || !z || !hyp || !sig2n || !nll || !info ||
+        (flags & ~(unsigned)SGPR_FIT_REG)) {
+        set_error("fit_batch: bad arguments (order per problem at most 2048)");
+        return SGPR_E_ARG;
+    }
+    if (nbatch == 0) return 0;
+    if (family < SGPR_FAM_A || family > SGPR_FAM_USER) { set_error("fit_batch: unknown kernel family"); return SGPR_E_ARG; }
+    if (n > BMAX) return fit_batch_mid(family, nbatch, npts, n, reg, x, y, z, hyp, nhyp, sig2n, alpha, nll, info);
+    return fit_batch_small(family, nbatch, npts, n, reg, x, y, z, hyp, nhyp, sig2n, alpha, nll, info, nullptr);
+}
+
+int fit_batch_grad_max_order() { return BMAX; }
+
+// sgpr_fit_batch_grad: the arguments have been checked (capi.hip), nbatch > 0, n <= BMAX
+int fit_batch_grad(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
+                   int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, double *grad, int *info)
+{
+    const int reg = (flags & SGPR_FIT_REG) ? 1 : 0;
+    return fit_batch_small(family, nbatch, npts, reg ? npts : 2 * npts, reg, x, y, z, hyp, nhyp, sig2n, alpha, nll, info, grad);
 }
 
 }  // namespace sgpr

@@ -1131,6 +1131,30 @@ int sgpr_fit_batch(int family, int nbatch, int n_pts, const double *x, const dou
     return fit_batch(family, nbatch, n_pts, x, y, z, hyp, nhyp, sig2n, flags, alpha, nll, info);
 }
 
+/* sgpr_fit_batch plus the gradient of every problem's nll (batch.hip: fit_batch_kernel<FAM, true>).  The arguments are checked
+ * before any device call: an argument error is SGPR_E_ARG on any machine, the message names the entry. */
+int sgpr_fit_batch_grad(int family, int nbatch, int n_pts, const double *x, const double *y, const double *z,
+                        const double *hyp, int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll,
+                        double *grad, int *info)
+{
+    auto E = [](const std::string &what) { set_error("fit_batch_grad: " + what); return SGPR_E_ARG; };
+    if (family < SGPR_FAM_A || family > SGPR_FAM_USER) return E("unknown kernel family");
+    const int need = family_has_p(family) ? 4 : 3;
+    if (nhyp != need) return E("nhyp must be " + std::to_string(need) + " for this family");
+    if (flags & ~(unsigned)SGPR_FIT_REG) return E("unknown flag (only SGPR_FIT_REG)");
+    if (nbatch < 0) return E("nbatch < 0");
+    if (n_pts <= 0) return E("n_pts <= 0");
+    const long n = (flags & SGPR_FIT_REG) ? (long)n_pts : 2L * n_pts;
+    const int nmax = fit_batch_grad_max_order();
+    if (n > nmax) return E("order per problem " + std::to_string(n) + " exceeds " + std::to_string(nmax));
+    if (!nll || !grad || !info) return E("null nll, grad or info");
+    if (!x || !y || !z || !hyp || !sig2n) return E("null input");
+    if (nbatch == 0) return 0;
+    int rc = need_device();
+    if (rc) return rc;
+    return fit_batch_grad(family, nbatch, n_pts, x, y, z, hyp, nhyp, sig2n, flags, alpha, nll, grad, info);
+}
+
 /* ---- device-pointer primitives ---------------------------------------------------------- */
 
 // Shape / pointer checks of the *_dev entries, answered before need_device(): an argument error is SGPR_E_ARG on any

@@ -177,6 +177,9 @@ int fit_batch_trim();                            // release the calling thread's
 int potrf_trim();                                // ... and its pooled events
 int fit_batch(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
               int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, int *info);
+int fit_batch_grad_max_order();                  // 256: one workgroup holds the whole problem
+int fit_batch_grad(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
+                   int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, double *grad, int *info);
 
 // ---- blas_small.hip
 int zero_strict_upper(int n, double *A, size_t lda, hipStream_t st);

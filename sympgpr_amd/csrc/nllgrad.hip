@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "generated/pair_generated.h"
+#include "nllgrad_pair.h"
 
 namespace sgpr {
 
@@ -63,7 +64,8 @@ __device__ __forceinline__ void store_partials(const GradArgs &a, double (&acc)[
     }
 }
 
-// pair fits, D = 2d parts; accumulators: l_0 .. l_{D-1}, [p_0 .. p_{d-1},] sig, noise (sig factor applied by the caller)
+// pair fits, D = 2d parts; accumulators: l_0 .. l_{D-1}, [p_0 .. p_{d-1},] sig, noise (sig factor applied by the caller).
+// nllgrad_pair.h's pair_grad is this loop body for the batched gradient; it stays inline here (see that header)
 template <int FAM, int D, bool HASP>
 __global__ __launch_bounds__(NG_T) void nllgrad_pairs_kernel(const GradArgs a)
 {
@@ -201,17 +203,7 @@ __global__ __launch_bounds__(NG_T) void nllgrad_reg_kernel(const GradArgs a)
             const double W = Rrow[(size_t)(col - a.J) * a.ldr] - ai * sal[jj];
             const double w = col == i ? W : 2.0 * W;
             if (col == i) acc[NACC - 1] += W;
-            double o[4];
-            gen::pair<FAM>(sx[jj], sy[jj], xi, yi, a.l[0], a.l[1], a.pp[0], o);
-            acc[NACC - 2] += w * o[0];
-            gen::pair_dlx<FAM>(sx[jj], sy[jj], xi, yi, a.l[0], a.l[1], a.pp[0], o);
-            acc[0] += w * o[0];
-            gen::pair_dly<FAM>(sx[jj], sy[jj], xi, yi, a.l[0], a.l[1], a.pp[0], o);
-            acc[1] += w * o[0];
-            if constexpr (HASP) {
-                gen::pair_dp<FAM>(sx[jj], sy[jj], xi, yi, a.l[0], a.l[1], a.pp[0], o);
-                acc[2] += w * o[0];
-            }
+            nllg::reg_grad<FAM, HASP>(sx[jj], sy[jj], xi, yi, w, a.l, a.pp[0], acc);      // nllgrad_pair.h
         }
     }
     store_partials<NACC>(a, acc);

@@ -290,3 +290,42 @@ def fit_batch(family, x, y, z, hyp, sig2n, reg=False, want_alpha=True):
                                             info.ctypes.data_as(C.POINTER(C.c_int))), "sgpr_fit_batch")
     nll[info != 0] = np.nan
     return alpha, nll, info
+
+
+def batch_grad_max_order():
+    """largest matrix order per problem sgpr_fit_batch_grad takes on the device (256)"""
+    return 256
+
+
+def fit_batch_grad(family, x, y, z, hyp, sig2n, reg=False, want_alpha=False):
+    """fit_batch plus the exact gradient of every problem's nll in (hyp, sig2n).  Shapes as fit_batch:
+        x, y (B, n_pts);  z (B, n), n = 2 n_pts (n_pts with reg);  hyp (B, nhyp);  sig2n (B,) or scalar.
+    -> (alpha (B, n) or None, nll (B,), grad (B, nhyp + 1), info (B,)).  Row b of grad is (d/dhyp_0 .. d/dhyp_{nhyp-1},
+    d/dsig2n); Ky holds |sig2n[b]|, so the last entry carries sign(sig2n[b]) (sign(0) = +1).  Rows with info > 0 are NaN
+    (nll and the whole gradient row).  nll, alpha and info are the same bits fit_batch returns.
+    n <= 256: ONE launch (sgpr_fit_batch_grad), one workgroup per problem.
+    256 < n <= 2048 (the slow path): nll, alpha and info from one fit_batch call, and the gradient of every positive-definite
+    row from SympFit(...).run().nll_grad_full(), one device-resident fit per row."""
+    x, y, z, hyp = (np.ascontiguousarray(np.atleast_2d(np.asarray(v, dtype=np.float64))) for v in (x, y, z, hyp))
+    B, n_pts = x.shape
+    n = n_pts if reg else 2 * n_pts
+    if y.shape != (B, n_pts) or z.shape != (B, n) or hyp.shape[0] != B:
+        raise ValueError("fit_batch_grad: x, y (B, n_pts), z (B, n), hyp (B, nhyp)")
+    s2 = np.ascontiguousarray(np.broadcast_to(np.asarray(sig2n, dtype=np.float64), (B,)))
+    nhyp = hyp.shape[1]
+    if n > batch_grad_max_order():
+        alpha, nll, info = fit_batch(family, x, y, z, hyp, s2, reg=reg, want_alpha=want_alpha)
+        grad = np.full((B, nhyp + 1), np.nan)
+        for b in np.flatnonzero(info == 0):
+            with SympFit(family, x[b], y[b], z[b], hyp[b], s2[b], reg=reg) as f:
+                grad[b] = f.run().nll_grad_full()
+        return alpha, nll, grad, info
+    alpha = np.empty((B, n)) if want_alpha else None
+    nll = np.empty(B)
+    grad = np.empty((B, nhyp + 1))
+    info = np.zeros(B, dtype=np.int32)
+    L.check(L.load_library().sgpr_fit_batch_grad(L.family_id(family), B, n_pts, L.dptr(x), L.dptr(y), L.dptr(z), L.dptr(hyp),
+                                                 nhyp, L.dptr(s2), L.FIT_REG if reg else 0,
+                                                 L.dptr(alpha) if want_alpha else None, L.dptr(nll), L.dptr(grad),
+                                                 info.ctypes.data_as(C.POINTER(C.c_int))), "sgpr_fit_batch_grad")
+    return alpha, nll, grad, info

@@ -155,6 +155,57 @@ def nll_chol_batch(hyps, x, y, N, reg=False):
     return nll
 
 
+def _batch_data(x, y, N, reg):
+    npts = N if reg else N // 2
+    return x[0:npts], x[npts:2 * npts], y[:N if reg else 2 * npts]
+
+
+def nll_chol_grad(hyp, x, y, N, reg=False):
+    """nll_chol (reg=True: nll_chol_reg) and its exact gradient -> (nll, grad), grad[k] = d nll / d hyp[k] for every entry
+    of hyp, the last being sig2_n (Ky holds |hyp[-1]|, so that entry carries its sign).  Sliced exactly like nll_chol /
+    nll_chol_reg; raises LinAlgError where they do.  The objective for scipy.optimize.minimize(..., jac=True).  Up to order
+    256 one launch (sgpr_fit_batch_grad with a batch of one); above, a device-resident fit and SympFit.nll_grad_full."""
+    from .fit import batch_grad_max_order, fit_batch_grad
+    hyp = np.asarray(hyp, dtype=np.float64)
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    if N <= 0:
+        raise ValueError("nll_chol_grad: N must be positive")
+    X, Y, Z = _batch_data(x, y, N, reg)
+    if len(X) != (N if reg else N // 2) or len(Y) != len(X) or len(Z) != (N if reg else 2 * len(X)):
+        raise ValueError("nll_chol_grad: x holds 2 * n_pts coordinates and y the n targets of order N")
+    if N <= batch_grad_max_order():
+        _, nll, grad, info = fit_batch_grad(get_family(), X[None], Y[None], Z[None], hyp[None, :-1], hyp[-1:], reg=reg)
+        if info[0]:
+            raise np.linalg.LinAlgError("%d-th leading minor of the array is not positive definite" % int(info[0]))
+        return float(nll[0]), grad[0]
+    with SympFit(get_family(), X, Y, Z, hyp[:-1], hyp[-1], reg=reg) as f:
+        f.run()
+        return f.nll(), f.nll_grad_full()
+
+
+def nll_chol_grad_batch(hyps, x, y, N, reg=False):
+    """nll_chol_batch with gradients: hyps (B, nhyp + 1) rows like nll_chol's hyp -> (nll (B,), grad (B, nhyp + 1)).  Rows
+    whose Ky is not positive definite give nll = +inf and a NaN gradient row.  Up to order 256 one launch; above it, the
+    nll of every row from one fit_batch call and the gradients row by row (fit.fit_batch_grad's slow path)."""
+    from .fit import fit_batch_grad
+    hyps = np.atleast_2d(np.asarray(hyps, dtype=np.float64))
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    if hyps.ndim != 2 or hyps.shape[1] < 2:
+        raise ValueError("nll_chol_grad_batch: hyps (B, nhyp + 1)")
+    if N <= 0:
+        raise ValueError("nll_chol_grad_batch: N must be positive")
+    X, Y, Z = _batch_data(x, y, N, reg)
+    if len(X) != (N if reg else N // 2) or len(Y) != len(X) or len(Z) != (N if reg else 2 * len(X)):
+        raise ValueError("nll_chol_grad_batch: x holds 2 * n_pts coordinates and y the n targets of order N")
+    B = len(hyps)
+    _, nll, grad, info = fit_batch_grad(get_family(), np.broadcast_to(X, (B, len(X))), np.broadcast_to(Y, (B, len(Y))),
+                                        np.broadcast_to(Z, (B, len(Z))), hyps[:, :-1], hyps[:, -1], reg=reg)
+    nll[info != 0] = np.inf
+    return nll, grad
+
+
 def guessP(x, y, hypp, xtrainp, ztrainp, Kyinvp):
     """functions/func.py:198-201."""
     Ntrain = len(xtrainp) // 2
