@@ -77,6 +77,24 @@ int sgpr_probe_queue_force_giveup(int on);
  * Block solves: trsm_chain (workgroups of the chain class, 0 = built-in), trsm_piece (tiles per stream ticket, 0 = built-in: 16 up
  * to 128 strips, 128 above; read per call). */
 int sgpr_probe_tune(const char *name, double value);
+/* The Strassen front end of the fp64 NT product (csrc/gemm_f64.hip).  Host only: the list of operations one call
+ * C -= A B^T (m x n x k; lower: the lower triangle of a square C) turns into, for a threshold `smin` (smallest half-size of m and n
+ * that qualifies; k: half of it), a k slab `kslab` (< 0: the built-in values / tunables gemm_strassen_min, gemm_strassen_kslab)
+ * and `scratch_doubles` of scratch.  16 words per record, word 0 = kind:
+ *   1 sum:      [1] side (0: A, 1: B) [2] rows [3] cols [4] xr [5] xc [6] yr [7] yc [8] sign    scratch[side] = X + sign Y
+ *   2 product:  [1] a_src (0: block of A at row [2], k column [3]; 1: the A scratch) [4] b_src [5] [6] likewise [7] m [8] n [9] k
+ *               [10] [11] row, column of the first destination block of C [12] its sign [13] [14] [15] the second (sign 0: none)
+ *   3 classical launch: [1] lower [2] ar [3] ac [4] br [5] bc [6] m [7] n [8] k [9] cr [10] cc
+ * tests/test_strassen_plan_cpu.py replays the list in numpy.  *count = records of the plan; `out` is filled up to max_records. */
+int sgpr_probe_strassen_plan(int m, int n, int k, int lower, long smin, long kslab, long scratch_doubles, long long *out,
+                             int max_records, int *count);
+/* the front end itself and the two-destination product (C = beta C + alpha A B^T, C2 += alpha2 A B^T) on device pointers.
+ * Tunables: gemm_strassen_min (8192), gemm_strassen_kslab (16384), gemm_strassen_noscratch (1: the scratch allocation is
+ * treated as failed, every product runs classically), la_max (orders above it take the recursive Cholesky driver). */
+int sgpr_probe_gemm_strassen_dev(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb,
+                                 double beta, double *C, size_t ldc, int lower, void *stream);
+int sgpr_probe_gemm_nt2_dev(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb,
+                            double beta, double *C, size_t ldc, double alpha2, double *C2, size_t ldc2, void *stream);
 /* the last sgpr_applymap_host of this process: K*-row evaluations (residuals of the implicit equation + q updates) summed over
  * its orbits, and the number of workgroups that share one orbit for ntest orbits on n0 training points */
 unsigned sgpr_probe_map_calls(void);

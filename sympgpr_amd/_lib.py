@@ -149,6 +149,12 @@ PROBE_SIGNATURES = {
     "sgpr_probe_trsm_piece": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "sgpr_probe_trsm_counts": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]),
     "sgpr_probe_queue_trace_clear": (C.c_int, []),
+    "sgpr_probe_strassen_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long,
+                                           C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_int)]),
+    "sgpr_probe_gemm_strassen_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                               C.c_double, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
+    "sgpr_probe_gemm_nt2_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                          C.c_double, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p]),
     "sgpr_probe_census": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint), C.c_int,
                                     C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint), C.c_int,
                                     C.POINTER(C.c_ulonglong)]),

@@ -958,6 +958,7 @@ struct Ctx {
     int la_max = 0;   // potrf_rec hands blocks of order <= la_max to the look-ahead driver (0: never)
     int *flags = nullptr;   // hand-off flags of the panel kernel: PFLAG_STRIDE ints per leaf column, zeroed by potrf()
     void *qws = nullptr;    // the task-queue driver's part of the workspace (cholq.h), or null
+    bool strassen = false;  // the deep products of the recursion go through gemm_nt_strassen (potrf() only: the solves' do not)
 };
 
 int potrf_lookahead(int n, double *A, size_t lda, const Ctx &c, int nb, int off0);
@@ -976,7 +977,8 @@ int trsm_rec(int m, int n, const double *L, size_t ldl, double *B, size_t ldb, i
     int rc = trsm_rec(m, n1, L, ldl, B, ldb, off, c);
     if (rc) return rc;
     // B2 -= B1 L21^T
-    rc = gemm_nt(m, n2, n1, -1.0, B, ldb, L + n1, ldl, 1.0, B + (size_t)n1 * ldb, ldb, 0, 0, c.st);
+    if (c.strassen) rc = gemm_nt_strassen(m, n2, n1, -1.0, B, ldb, L + n1, ldl, 1.0, B + (size_t)n1 * ldb, ldb, 0, c.st);
+    else            rc = gemm_nt(m, n2, n1, -1.0, B, ldb, L + n1, ldl, 1.0, B + (size_t)n1 * ldb, ldb, 0, 0, c.st);
     if (rc) return rc;
     return trsm_rec(m, n2, L + n1 + (size_t)n1 * ldl, ldl, B + (size_t)n1 * ldb, ldb, off + n1, c);
 }
@@ -1014,7 +1016,9 @@ int potrf_rec(int n, double *A, size_t lda, int off, const Ctx &c)
     if (rc) return rc;
     rc = trsm_rec(n2, n1, A, lda, A21, lda, off, c);
     if (rc) return rc;
-    rc = gemm_nt(n2, n2, n1, -1.0, A21, lda, A21, lda, 1.0, A22, lda, 1, 0, c.st);  // SYRK, lower
+    // SYRK, lower (large ones: split around their square off-diagonal part, which takes the Strassen front end)
+    if (c.strassen) rc = gemm_nt_strassen(n2, n2, n1, -1.0, A21, lda, A21, lda, 1.0, A22, lda, 1, c.st);
+    else            rc = gemm_nt(n2, n2, n1, -1.0, A21, lda, A21, lda, 1.0, A22, lda, 1, 0, c.st);
     if (rc) return rc;
     return potrf_rec(n2, A22, lda, off + n1, c);
 }
@@ -1724,7 +1728,7 @@ int potrf_trim()
         p.ev.clear();
     }
     (void)hipGetLastError();
-    return 0;
+    return strassen_trim();   // ... and the scratch of the Strassen front end's operand sums
 }
 
 int release_device_streams(int dev)
@@ -1748,10 +1752,17 @@ int potrf(int n, double *A, size_t lda, void *work, size_t lwork, int *dinfo, hi
     static const int nb_env = [] { const char *e = getenv("SGPR_POTRF_NB"); return e ? atoi(e) : 0; }();
     // blocks of order <= la_max go to the blocked look-ahead driver, larger ones split recursively
     // (SGPR_LA_MAX overrides; measured crossover of round 1)
-    static const int la_max_env = [] { const char *e = getenv("SGPR_LA_MAX"); return e ? atoi(e) : 57344; }();
+    // tunable "la_max": the same through sgpr_probe_tune (tests that need the recursive driver at a small order)
+    static const int la_max_env = [] { const char *e = getenv("SGPR_LA_MAX"); return (int)tune("la_max", e ? atoi(e) : 57344); }();
     t_last_potrf_used_queue = false;
     Ctx c{static_cast<double *>(work), dinfo, st, mode == 1 ? 0 : la_max_env, flags};
     if (cholq::ws_bytes(n) > 0) c.qws = static_cast<char *>(work) + inv_bytes(n) + flag_bytes(n) + pub_bytes(n);
+    c.strassen = true;
+    if (n > c.la_max && n > LEAF) {
+        // the two largest products of the recursion (every later one is smaller): size the operand-sum scratch once
+        const int n1 = split(n), n2 = n - n1, n11 = split(n1);
+        strassen_reserve(std::max(strassen_scratch_doubles(n2, n2, n1, 1), strassen_scratch_doubles(n2, n1 - n11, n11, 0)), st);
+    }
     const bool dbg = PANEL_DBG && getenv("SGPR_PANEL_DBG") != nullptr;
     const int T = (n + LEAF - 1) / LEAF;
     if (dbg) {

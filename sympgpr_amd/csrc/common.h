@@ -4,6 +4,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #include "../../include/sympgpr_hip.h"
 
@@ -83,6 +84,18 @@ int gemm_nt_bc(int m, int n, int k, double alpha, const double *A, size_t lda, c
                hipStream_t st);
 int gemm_nn(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb,
             double beta, double *C, size_t ldc, hipStream_t st);
+// two destinations from one product: C = beta C + alpha A B^T, C2 += alpha2 A B^T
+int gemm_nt_two(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb, double beta,
+             double *C, size_t ldc, double alpha2, double *C2, size_t ldc2, hipStream_t st);
+// one level of Strassen's algorithm in front of gemm_nt (gemm_f64.hip); lower: the SYRK decomposition around it
+constexpr int STRASSEN_REC = 16;                 // words per plan record
+enum { PLAN_SUM = 1, PLAN_PROD = 2, PLAN_CLASSIC = 3 };
+int gemm_nt_strassen(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb, double beta,
+                     double *C, size_t ldc, int lower, hipStream_t st);
+int strassen_plan(int m, int n, int k, int lower, long smin, long kslab, size_t scratch_doubles, std::vector<long long> &out);
+size_t strassen_scratch_doubles(int m, int n, int k, int lower);
+void strassen_reserve(size_t doubles, hipStream_t st);
+int strassen_trim();                             // release the scratch of the operand sums (every device)
 int gemm_profile_begin();
 int gemm_profile_end(double *out12);
 int gemm_profile_launches(double *buf, int max_records);

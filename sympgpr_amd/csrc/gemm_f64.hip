@@ -81,6 +81,48 @@ __global__ __launch_bounds__(64 * (BM / 64) * (BN / 64), (BM >= 128 ? 2 : 1)) vo
     else      gemm_body<BM, BN, false>(g, smem, tile_r, tile_c);
 }
 
+// The same product with TWO destinations (the Strassen front end below): C = beta C + alpha P and C2 += alpha2 P from one
+// set of accumulators.  A kernel of its own, so that gemm_nt_kernel is compiled exactly as without it.
+__global__ __launch_bounds__(512, 2) void gemm_nt2_kernel(const GemmArgs g)
+{
+    constexpr int BM = 256, BN = 128, LDA_S = BM + PAD, LDB_S = BN + PAD;
+    __shared__ double smem[SGPR_GEMM_STAGES * BK * (LDA_S + LDB_S)];
+    int tile_r, tile_c;
+    if (!tile_of<(SR * BM) / (4 * BN)>(g, tile_r, tile_c)) return;
+    const int row0 = tile_r * BM, col0 = tile_c * BN;
+    const bool aligned = ((((uintptr_t)g.A | (uintptr_t)g.B) & 15) == 0) && (((g.lda | g.ldb) & 1) == 0);
+    const bool fast = aligned && (row0 + BM <= g.m) && (col0 + BN <= g.n) && (g.k % BK == 0);
+    if (fast) gemm_body_dma<BM, BN, SGPR_GEMM_STAGES, true>(g, smem, tile_r, tile_c);
+    else      gemm_body<BM, BN, false, false, true>(g, smem, tile_r, tile_c);
+}
+
+// T (rows x cols, leading dimension rows) = X + sign Y on column-major blocks: the operand sums of the Strassen front end.
+// HBM-bound (two reads, one write per element): 16-byte accesses, 4 columns per thread in flight, grid-stride over
+// pieces of 512 rows x 4 columns.  rows even, all three bases 16-byte aligned, ldx / ldy even (checked by the caller).
+__global__ __launch_bounds__(256) void block_sum_kernel(int rows, int cols, const double *X, size_t ldx, const double *Y, size_t ldy,
+                                                        double sign, double *T)
+{
+    const int nrc = (rows + 511) / 512, ncg = (cols + 3) / 4;
+    const long pieces = (long)nrc * ncg;
+    for (long p = blockIdx.x; p < pieces; p += gridDim.x) {
+        const int cg = (int)(p / nrc), rc = (int)(p - (long)cg * nrc);
+        const int r = rc * 512 + 2 * (int)threadIdx.x;
+        if (r >= rows) continue;
+        double2_t x[4], y[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int c = min(cg * 4 + u, cols - 1);
+            x[u] = *reinterpret_cast<const double2_t *>(X + (size_t)r + (size_t)c * ldx);
+            y[u] = *reinterpret_cast<const double2_t *>(Y + (size_t)r + (size_t)c * ldy);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int c = cg * 4 + u;
+            if (c < cols) *reinterpret_cast<double2_t *>(T + (size_t)r + (size_t)c * (size_t)rows) = x[u] + sign * y[u];
+        }
+    }
+}
+
 }  // namespace
 
 int gemm_nt(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B,
@@ -93,12 +135,13 @@ int gemm_nt(int m, int n, int k, double alpha, const double *A, size_t lda, cons
 
 static int gemm_launch(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B,
                        size_t ldb, double beta, double *C, size_t ldc, int lower, const int *bc, int transb,
-                       hipStream_t st, unsigned long long *stamps = nullptr, int dbg = 0);
+                       hipStream_t st, unsigned long long *stamps = nullptr, int dbg = 0, double *C2 = nullptr,
+                       size_t ldc2 = 0, double alpha2 = 0.0);
 
 // `bc` = {blk, pr, pi, pc, pj}: the block-cyclic form of the lower-mode skip test (GemmArgs)
-int gemm_nt_bc(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B,
-               size_t ldb, double beta, double *C, size_t ldc, int lower, const int *bc,
-               hipStream_t st)
+static int gemm_chunked(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B,
+                        size_t ldb, double beta, double *C, size_t ldc, int lower, const int *bc,
+                        hipStream_t st, double *C2, size_t ldc2, double alpha2)
 {
     // Products deeper than 8192 run as back-to-back launches of <= 8192 columns each (C re-read per launch, negligible
     // beside the flop), so that the 32 workgroups sharing a super-tile's operand panels restart in step instead of drifting
@@ -110,17 +153,33 @@ int gemm_nt_bc(int m, int n, int k, double alpha, const double *A, size_t lda, c
         const int step = ((k + nchunk - 1) / nchunk + 127) / 128 * 128;
         for (int k0 = 0; k0 < k; k0 += step) {
             const int rc = gemm_launch(m, n, std::min(step, k - k0), alpha, A + (size_t)k0 * lda, lda, B + (size_t)k0 * ldb, ldb,
-                                       k0 == 0 ? beta : 1.0, C, ldc, lower, bc, 0, st);
+                                       k0 == 0 ? beta : 1.0, C, ldc, lower, bc, 0, st, nullptr, 0, C2, ldc2, alpha2);
             if (rc) return rc;
         }
         return 0;
     }
-    return gemm_launch(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, lower, bc, 0, st);
+    return gemm_launch(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, lower, bc, 0, st, nullptr, 0, C2, ldc2, alpha2);
+}
+
+int gemm_nt_bc(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B,
+               size_t ldb, double beta, double *C, size_t ldc, int lower, const int *bc,
+               hipStream_t st)
+{
+    return gemm_chunked(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, lower, bc, st, nullptr, 0, 0.0);
+}
+
+// C = beta C + alpha A B^T and C2 += alpha2 A B^T in one pass over the operands (every k chunk adds to both)
+int gemm_nt_two(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb, double beta,
+             double *C, size_t ldc, double alpha2, double *C2, size_t ldc2, hipStream_t st)
+{
+    const int bc[5] = {1, 1, 0, 1, 0};
+    if (!C2) { set_error("gemm_nt_two: null second destination"); return SGPR_E_ARG; }
+    return gemm_chunked(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, 0, bc, st, C2, ldc2, alpha2);
 }
 
 static int gemm_launch(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B,
                        size_t ldb, double beta, double *C, size_t ldc, int lower, const int *bc, int transb,
-                       hipStream_t st, unsigned long long *stamps, int dbg)
+                       hipStream_t st, unsigned long long *stamps, int dbg, double *C2, size_t ldc2, double alpha2)
 {
     const bool plain = bc[0] == 1 && bc[1] == 1 && bc[3] == 1 && bc[4] == 0;
     const long diag_off = plain ? bc[2] : 1;  // != 0 disables the triangular tile enumeration
@@ -131,8 +190,9 @@ static int gemm_launch(int m, int n, int k, double alpha, const double *A, size_
         set_error("gemm: leading dimension too small");
         return SGPR_E_ARG;
     }
+    if (C2 && (lower || transb || ldc2 < (size_t)m)) { set_error("gemm: bad second destination"); return SGPR_E_ARG; }
     GemmArgs g{m, n, k, alpha, beta, A, lda, B, ldb, C, ldc, lower, diag_off, transb, stamps, 0, 0, 0, 0, 0, 0,
-               0, 0, bc[0], bc[1], bc[2], bc[3], bc[4], dbg};
+               0, 0, bc[0], bc[1], bc[2], bc[3], bc[4], dbg, nullptr, C2, ldc2, alpha2};
     auto set_map = [&](int bm, int bn) {
         g.tiles_m = (m + bm - 1) / bm;
         g.tiles_n = (n + bn - 1) / bn;
@@ -210,7 +270,12 @@ static int gemm_launch(int m, int n, int k, double alpha, const double *A, size_
     static const double small_mb = tune("gemm_small_mb", 0.0);
     const double op_bytes = 8.0 * (double)k * ((A == B && lda == ldb) ? (double)std::max(m, n) : (double)m + n);
     const bool small_k = op_bytes <= small_mb * 1e6 && m > 128 && n > 128;
-    if (n <= 128 && m <= 32768 && !(dbg & 8)) {
+    if (C2) {
+        // two destinations: always the 256x128 shape (the front end only sends products that fill the chip)
+        const dim3 grid(set_map(256, 128));
+        hipLaunchKernelGGL(gemm_nt2_kernel, grid, dim3(512), 0, st, g);
+        rec.big = 1;
+    } else if (n <= 128 && m <= 32768 && !(dbg & 8)) {
         // one column tile (the in-place panel solve against an inverted leaf, k = n <= 128): a
         // latency problem, not a throughput one -- 64-row tiles quadruple the workgroup count and
         // halve the per-workgroup critical path (two waves, register-staged operands)
@@ -310,6 +375,275 @@ int gemm_profile_end(double *out)
     }
     g_prof.recs.clear();
     return 0;
+}
+
+// ---- one level of Strassen's algorithm in front of the NT product ------------------------------------------------
+// P = A B^T with A = [A11 A12; A21 A22] (m halves x k halves), B likewise (n halves x k halves) needs 7 half-size
+// products instead of 8:
+//   M1 = (A11 + A22)(B11 + B22)^T -> C11, C22     M2 = (A21 + A22) B11^T -> C21, -C22    M3 = A11 (B21 - B22)^T -> C12, C22
+//   M4 = A22 (B12 - B11)^T -> C11, C21            M5 = (A11 + A12) B22^T -> -C11, C12    M6 = (A21 - A11)(B11 + B21)^T -> C22
+//   M7 = (A12 - A22)(B12 + B22)^T -> C11
+// Every M is accumulated straight into its destination blocks by the two-destination kernel: no M temporaries, no
+// block-accumulate passes; the ten operand sums go through two scratch blocks (one per side) reused product after product
+// in stream order.  The whole decision -- which sums, which products, which destinations and signs, what stays classical --
+// is host code that emits a list of records (strassen_plan); the device path below executes exactly that list, and
+// tests/test_strassen_plan_cpu.py replays it in numpy.
+// Record = 16 words.  [0] = kind:
+//   PLAN_SUM   [1] side (0: rows of A -> the A scratch, 1: rows of B -> the B scratch) [2] rows [3] cols
+//              [4] xr [5] xc [6] yr [7] yc [8] sign         T = X + sign Y, X / Y the blocks at (row, k column) of that operand
+//   PLAN_PROD  [1] a_src (0: block of A at ([2], [3]), 1: the A scratch) [4] b_src, ([5], [6]) likewise [7] m [8] n [9] k
+//              [10] [11] first destination (row, column of C) [12] its sign [13] [14] [15] the second one (sign 0: none)
+//   PLAN_CLASSIC  [1] lower [2] ar [3] ac [4] br [5] bc [6] m [7] n [8] k [9] cr [10] cc      the classical launch on a block
+namespace {
+struct PlanCfg {
+    long smin;      // smallest half-size of m and n that qualifies (half of k: smin / 2)
+    long kslab;     // k is processed in slabs of at most this many columns (bounds the scratch)
+    size_t scratch; // doubles of scratch available
+};
+void put(std::vector<long long> &out, std::initializer_list<long long> v)
+{
+    size_t i = 0;
+    for (long long x : v) { out.push_back(x); ++i; }
+    for (; i < STRASSEN_REC; ++i) out.push_back(0);
+}
+// slab length of a k extent (0: the extent does not qualify): near-equal slabs of at most kslab columns, multiples of 32
+long slab_of(long k, const PlanCfg &c)
+{
+    if (k <= 0 || k % 32 != 0 || c.kslab < 32) return 0;
+    const long nslab = (k + c.kslab - 1) / c.kslab;
+    const long step = ((k + nslab - 1) / nslab + 31) / 32 * 32;
+    const long kmin = std::max(c.smin / 2, 16L);
+    const long last = k - (nslab - 1) * step;
+    if (last <= 0 || step / 2 < kmin || last / 2 < kmin) return 0;
+    return step;
+}
+bool qualifies(long m, long n, long k, const PlanCfg &c)
+{
+    // halves stay multiples of the 256 x 128 tile, so every workgroup takes the LDS-DMA body
+    if (m <= 0 || n <= 0 || m % 512 != 0 || n % 256 != 0) return false;
+    if (m / 2 < c.smin || n / 2 < c.smin) return false;
+    const long step = slab_of(k, c);
+    if (!step) return false;
+    return (size_t)(m / 2 + n / 2) * (size_t)(step / 2) <= c.scratch;
+}
+void plan_gemm(long m, long n, long k, long ar, long br, long cr, long cc, const PlanCfg &c, std::vector<long long> &out)
+{
+    if (!qualifies(m, n, k, c)) {
+        put(out, {PLAN_CLASSIC, 0, ar, 0, br, 0, m, n, k, cr, cc});
+        return;
+    }
+    const long m2 = m / 2, n2 = n / 2, step = slab_of(k, c);
+    for (long k0 = 0; k0 < k; k0 += step) {
+        const long k2 = std::min(step, k - k0) / 2;
+        // block (i, j) of an operand: row offset, k-column offset
+        const long a1 = ar, a2 = ar + m2, b1 = br, b2 = br + n2, j1 = k0, j2 = k0 + k2;
+        const long c1r = cr, c2r = cr + m2, c1c = cc, c2c = cc + n2;
+        auto sum = [&](int side, long xr, long xc, long yr, long yc, int sign) {
+            put(out, {PLAN_SUM, side, side ? n2 : m2, k2, xr, xc, yr, yc, sign});
+        };
+        auto prod = [&](int as, long pr, long pc, int bs, long qr, long qc, long d1r, long d1c, int s1, long d2r, long d2c, int s2) {
+            put(out, {PLAN_PROD, as, pr, pc, bs, qr, qc, m2, n2, k2, d1r, d1c, s1, d2r, d2c, s2});
+        };
+        sum(0, a1, j1, a2, j2, +1); sum(1, b1, j1, b2, j2, +1);                      // M1
+        prod(1, 0, 0, 1, 0, 0, c1r, c1c, +1, c2r, c2c, +1);
+        sum(0, a2, j1, a2, j2, +1);                                                    // M2
+        prod(1, 0, 0, 0, b1, j1, c2r, c1c, +1, c2r, c2c, -1);
+        sum(1, b2, j1, b2, j2, -1);                                                    // M3
+        prod(0, a1, j1, 1, 0, 0, c1r, c2c, +1, c2r, c2c, +1);
+        sum(1, b1, j2, b1, j1, -1);                                                    // M4
+        prod(0, a2, j2, 1, 0, 0, c1r, c1c, +1, c2r, c1c, +1);
+        sum(0, a1, j1, a1, j2, +1);                                                    // M5
+        prod(1, 0, 0, 0, b2, j2, c1r, c1c, -1, c1r, c2c, +1);
+        sum(0, a2, j1, a1, j1, -1); sum(1, b1, j1, b2, j1, +1);                      // M6
+        prod(1, 0, 0, 1, 0, 0, c2r, c2c, +1, 0, 0, 0);
+        sum(0, a1, j2, a2, j2, -1); sum(1, b1, j2, b2, j2, +1);                      // M7
+        prod(1, 0, 0, 1, 0, 0, c1r, c1c, +1, 0, 0, 0);
+    }
+}
+// lower update of the square block at row / column r0: while its off-diagonal square qualifies, the two diagonal halves
+// recurse and the square goes through plan_gemm; then the triangular launch as before
+void plan_syrk(long n, long k, long r0, const PlanCfg &c, std::vector<long long> &out)
+{
+    const long h = n / 2;
+    if (n % 2 != 0 || !qualifies(h, h, k, c)) {
+        put(out, {PLAN_CLASSIC, 1, r0, 0, r0, 0, n, n, k, r0, r0});
+        return;
+    }
+    plan_syrk(h, k, r0, c, out);
+    plan_gemm(h, h, k, r0 + h, r0, r0 + h, r0, c, out);
+    plan_syrk(h, k, r0 + h, c, out);
+}
+size_t plan_need(const std::vector<long long> &plan)
+{
+    size_t need[2] = {0, 0};
+    for (size_t i = 0; i + STRASSEN_REC <= plan.size(); i += STRASSEN_REC)
+        if (plan[i] == PLAN_SUM) need[plan[i + 1]] = std::max(need[plan[i + 1]], (size_t)plan[i + 2] * (size_t)plan[i + 3]);
+    return need[0] + need[1];
+}
+
+bool strassen_on()
+{
+    static const bool on = [] { const char *e = getenv("SGPR_GEMM_STRASSEN"); return !(e && e[0] == '0'); }();
+    return on;
+}
+// Default threshold: profiles/strassen/sweep.txt.  Tunables "gemm_strassen_min" (half-size of m and n; k: half of it),
+// "gemm_strassen_kslab", "gemm_strassen_noscratch" (tests: the scratch allocation is reported as failed).
+PlanCfg default_cfg()
+{
+    static const long smin = std::max(128L, (long)tune("gemm_strassen_min", 8192));
+    static const long kslab = std::max(32L, (long)tune("gemm_strassen_kslab", 16384));
+    return PlanCfg{smin, kslab, ~(size_t)0};
+}
+
+// Scratch of the operand sums: one buffer per device, owned by the library, grown to the largest qualifying call and
+// released by strassen_trim().  Calls are serialised by the mutex while they ENQUEUE; on the device a call on another
+// stream first waits for the event the previous user recorded behind its last product.
+struct Scratch {
+    std::mutex mu;
+    double *p = nullptr;
+    size_t cap = 0, failed = 0;     // doubles; smallest request that could not be allocated (0: none)
+    hipEvent_t ev = nullptr;
+    hipStream_t last = nullptr;
+    bool used = false;
+};
+Scratch g_scratch[64];
+
+bool scratch_ensure(Scratch &s, size_t need)
+{
+    static const bool forced_fail = tune("gemm_strassen_noscratch", 0) != 0;
+    if (forced_fail) return false;
+    if (s.cap >= need) return true;
+    if (s.failed && need >= s.failed) return false;
+    if (s.p) { (void)hipFree(s.p); s.p = nullptr; s.cap = 0; s.used = false; }   // hipFree waits for the device
+    if (hipMalloc((void **)&s.p, need * sizeof(double)) != hipSuccess) {
+        (void)hipGetLastError();
+        s.p = nullptr;
+        s.failed = need;
+        return false;
+    }
+    s.cap = need;
+    return true;
+}
+int device_of(hipStream_t st)
+{
+    int dev = -1;
+    if ((st ? hipStreamGetDevice(st, &dev) : hipGetDevice(&dev)) != hipSuccess) { (void)hipGetLastError(); return -1; }
+    return (dev >= 0 && dev < 64) ? dev : -1;
+}
+
+int block_sum(int rows, int cols, const double *X, size_t ldx, const double *Y, size_t ldy, double sign, double *T, hipStream_t st)
+{
+    const long pieces = (long)((rows + 511) / 512) * ((cols + 3) / 4);
+    hipLaunchKernelGGL(block_sum_kernel, dim3((unsigned)std::min(pieces, 2048L)), dim3(256), 0, st, rows, cols, X, ldx, Y, ldy, sign, T);
+    SGPR_CHECK_LAUNCH();
+    return 0;
+}
+
+int run_plan(const std::vector<long long> &plan, double alpha, const double *A, size_t lda, const double *B, size_t ldb,
+             double beta, double *C, size_t ldc, double *SA, double *SB, hipStream_t st)
+{
+    for (size_t i = 0; i + STRASSEN_REC <= plan.size(); i += STRASSEN_REC) {
+        const long long *r = &plan[i];
+        int rc = 0;
+        if (r[0] == PLAN_SUM) {
+            const double *P = r[1] ? B : A;
+            const size_t ld = r[1] ? ldb : lda;
+            rc = block_sum((int)r[2], (int)r[3], P + r[4] + (size_t)r[5] * ld, ld, P + r[6] + (size_t)r[7] * ld, ld, (double)r[8],
+                           r[1] ? SB : SA, st);
+        } else if (r[0] == PLAN_PROD) {
+            const int m = (int)r[7], n = (int)r[8], k = (int)r[9];
+            const double *Ap = r[1] ? SA : A + r[2] + (size_t)r[3] * lda;
+            const double *Bp = r[4] ? SB : B + r[5] + (size_t)r[6] * ldb;
+            double *C1 = C + r[10] + (size_t)r[11] * ldc;
+            if (r[15]) rc = gemm_nt_two(m, n, k, alpha * (double)r[12], Ap, r[1] ? (size_t)m : lda, Bp, r[4] ? (size_t)n : ldb, 1.0, C1, ldc,
+                                     alpha * (double)r[15], C + r[13] + (size_t)r[14] * ldc, ldc, st);
+            else       rc = gemm_nt(m, n, k, alpha * (double)r[12], Ap, r[1] ? (size_t)m : lda, Bp, r[4] ? (size_t)n : ldb, 1.0, C1, ldc, 0, 0, st);
+        } else {
+            rc = gemm_nt((int)r[6], (int)r[7], (int)r[8], alpha, A + r[2] + (size_t)r[3] * lda, lda, B + r[4] + (size_t)r[5] * ldb, ldb,
+                         beta, C + r[9] + (size_t)r[10] * ldc, ldc, (int)r[1], 0, st);
+        }
+        if (rc) return rc;
+    }
+    return 0;
+}
+}  // namespace
+
+// the plan of one call as the host decides it (no device): smin / kslab < 0 = the built-in values or tunables
+int strassen_plan(int m, int n, int k, int lower, long smin, long kslab, size_t scratch_doubles, std::vector<long long> &out)
+{
+    if (m < 0 || n < 0 || k < 0 || (lower && m != n)) { set_error("strassen_plan: bad extents"); return SGPR_E_ARG; }
+    PlanCfg c = default_cfg();
+    if (smin >= 0) c.smin = std::max(128L, smin);
+    if (kslab >= 0) c.kslab = std::max(32L, kslab);
+    c.scratch = scratch_doubles;
+    out.clear();
+    if (lower) plan_syrk(n, k, 0, c, out);
+    else       plan_gemm(m, n, k, 0, 0, 0, 0, c, out);
+    return 0;
+}
+
+size_t strassen_scratch_doubles(int m, int n, int k, int lower)
+{
+    std::vector<long long> plan;
+    if (!strassen_on() || strassen_plan(m, n, k, lower, -1, -1, ~(size_t)0, plan)) return 0;
+    return plan_need(plan);
+}
+
+// make room for calls that need up to `doubles` of scratch on st's device (potrf: once, before the first product)
+void strassen_reserve(size_t doubles, hipStream_t st)
+{
+    const int dev = device_of(st);
+    if (!doubles || dev < 0 || !strassen_on()) return;
+    Scratch &s = g_scratch[dev];
+    std::lock_guard<std::mutex> lock(s.mu);
+    (void)scratch_ensure(s, doubles);
+}
+
+int strassen_trim()
+{
+    for (Scratch &s : g_scratch) {
+        std::lock_guard<std::mutex> lock(s.mu);
+        if (s.p) (void)hipFree(s.p);          // waits for whatever still uses it
+        if (s.ev) (void)hipEventDestroy(s.ev);
+        s.p = nullptr; s.ev = nullptr; s.cap = 0; s.failed = 0; s.used = false; s.last = nullptr;
+    }
+    (void)hipGetLastError();
+    return 0;
+}
+
+// C = beta C + alpha A B^T (lower: on and below the diagonal of a square C only) through the plan above.  Whatever does
+// not qualify -- sizes, alignment, beta != 1, no scratch, SGPR_GEMM_STRASSEN=0 -- is the classical launch, bit for bit.
+int gemm_nt_strassen(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb, double beta,
+                     double *C, size_t ldc, int lower, hipStream_t st)
+{
+    const bool aligned = ((((uintptr_t)A | (uintptr_t)B) & 15) == 0) && (((lda | ldb) & 1) == 0);
+    // (the size test first: the short products of the panel solves come through here by the thousand)
+    if (std::min(m, n) / 2 < default_cfg().smin || !strassen_on() || !aligned || beta != 1.0 || (lower && m != n))
+        return gemm_nt(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, lower, 0, st);
+    std::vector<long long> plan;
+    int rc = strassen_plan(m, n, k, lower, -1, -1, ~(size_t)0, plan);
+    if (rc) return rc;
+    const size_t need = plan_need(plan);
+    if (!need) return run_plan(plan, alpha, A, lda, B, ldb, beta, C, ldc, nullptr, nullptr, st);
+    const int dev = device_of(st);
+    if (dev < 0) return gemm_nt(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, lower, 0, st);
+    Scratch &s = g_scratch[dev];
+    std::lock_guard<std::mutex> lock(s.mu);
+    if (!scratch_ensure(s, need)) {
+        // plan again with what there is (possibly nothing): smaller products of a SYRK may still fit
+        if ((rc = strassen_plan(m, n, k, lower, -1, -1, s.cap, plan))) return rc;
+        if (!plan_need(plan)) return run_plan(plan, alpha, A, lda, B, ldb, beta, C, ldc, nullptr, nullptr, st);
+    }
+    if (!s.ev) SGPR_HIP(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+    if (s.used && s.last != st) SGPR_HIP(hipStreamWaitEvent(st, s.ev, 0));
+    size_t na = 0;
+    for (size_t i = 0; i + STRASSEN_REC <= plan.size(); i += STRASSEN_REC)
+        if (plan[i] == PLAN_SUM && plan[i + 1] == 0) na = std::max(na, (size_t)plan[i + 2] * (size_t)plan[i + 3]);
+    rc = run_plan(plan, alpha, A, lda, B, ldb, beta, C, ldc, s.p, s.p + na, st);
+    SGPR_HIP(hipEventRecord(s.ev, st));
+    s.last = st;
+    s.used = true;
+    return rc;
 }
 
 }  // namespace sgpr

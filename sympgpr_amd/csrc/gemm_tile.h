@@ -44,6 +44,10 @@ struct GemmArgs {
     int lblk, lpr, lpi, lpc, lpj;
     int dbg;  // probe switches: 8 = force the 128x128 tile shape, 16 = force the register-staged body
     unsigned long long *kdone;  // diagnostic (task-queue trace): 100 MHz time at which wave 0 left the k-loop, or null
+    // second destination of the same product (gemm_nt2_kernel only, the Strassen front end): C2 += alpha2 * A B^T
+    double *C2;
+    size_t ldc2;
+    double alpha2;
 };
 
 // Workgroup -> tile map.  The dispatcher deals consecutive workgroup ids round-robin over the 8
@@ -198,7 +202,7 @@ __device__ __forceinline__ void store_pass(double *S, int tid, const double2_t &
     *reinterpret_cast<double2_t *>(S + kc * (BR + PAD) + r) = v;
 }
 
-template <int BM, int BN, bool FAST, bool TRANSB = false>
+template <int BM, int BN, bool FAST, bool TRANSB = false, bool TWO = false>
 __device__ __forceinline__ void gemm_body(const GemmArgs &g, double *smem, int tile_r, int tile_c)
 {
     constexpr int WGM = BM / 64, WGN = BN / 64;
@@ -356,6 +360,36 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, double *smem, int t
         }
         __builtin_amdgcn_sched_barrier(0);
     }
+    // second destination: C2 += alpha2 * (the same accumulators).  Written out beside the loop above, not shared with it,
+    // so that the one-destination instantiations compile exactly as they did without it.
+    if constexpr (TWO) {
+        const double alpha2 = g.alpha2;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            double old[4][4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int n = col0 + wn * 64 + i * 16 + 4 * r + l4;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int m = row0 + wm * 64 + j * 16 + l15;
+                    old[r][j] = (interior || (m < g.m && n < g.n)) ? g.C2[(size_t)m + (size_t)n * g.ldc2] : 0.0;
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int n = col0 + wn * 64 + i * 16 + 4 * r + l4;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int m = row0 + wm * 64 + j * 16 + l15;
+                    if (interior || (m < g.m && n < g.n))
+                        g.C2[(size_t)m + (size_t)n * g.ldc2] = __builtin_fma(alpha2, acc[i][j][r], old[r][j]);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
 }
 
 // ---- fast path: LDS-DMA staging + counted LDS waits -------------------------------------------
@@ -392,7 +426,7 @@ __device__ __forceinline__ void read_frags(unsigned aA, unsigned aB, double (&fa
 }
 #define SGPR_LGKM_WAIT(n) do { asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 
-template <int BM, int BN, int STAGES>
+template <int BM, int BN, int STAGES, bool TWO = false>
 __device__ __forceinline__ void gemm_body_dma(const GemmArgs &g, double *smem, int tile_r, int tile_c)
 {
     constexpr int WGM = BM / 64, WGN = BN / 64;
@@ -589,6 +623,33 @@ __device__ __forceinline__ void gemm_body_dma(const GemmArgs &g, double *smem, i
                 cbase[(size_t)(j * 16) + (size_t)(i * 16 + 4 * r) * g.ldc] = (beta == 0.0) ? v : __builtin_fma(beta, old[i & 1][r][j], v);
             }
         __builtin_amdgcn_sched_barrier(0);
+    }
+    // second destination (Strassen front end): C2 += alpha2 * (the same accumulators), the same pipelined fetch.  Written out
+    // beside the loop above, not shared with it, so that the one-destination instantiations compile exactly as they did.
+    if constexpr (TWO) {
+        const double alpha2 = g.alpha2;
+        double *const cbase2 = g.C2 + (size_t)(row0 + wm * 64 + l15) + (size_t)(col0 + wn * 64 + l4) * g.ldc2;
+        auto fetch2 = [&](int i, double (&o)[4][4]) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) o[r][j] = cbase2[(size_t)(j * 16) + (size_t)(i * 16 + 4 * r) * g.ldc2];
+        };
+        fetch2(0, old[0]);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            if (i + 1 < 4) fetch2(i + 1, old[(i + 1) & 1]);
+            __builtin_amdgcn_sched_barrier(0);
+            if (i + 1 < 4) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+            else           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    cbase2[(size_t)(j * 16) + (size_t)(i * 16 + 4 * r) * g.ldc2] = __builtin_fma(alpha2, acc[i][j][r], old[i & 1][r][j]);
+            __builtin_amdgcn_sched_barrier(0);
+        }
     }
 }
 
