@@ -483,7 +483,7 @@ constexpr int QT = 512;
 constexpr unsigned long long Q_WAIT_LIMIT = 3ull * 100000000ull;      // 3 s of the 100 MHz real-time counter (round 3: 20 s).  Every earlier
                                                                        // instance has drained after 3 ms without progress; the last one waits this long for a
                                                                        // panel side that is kept off its CUs, then gives up -- and the caller factors again
-                                                                       // with the look-ahead driver (capi.hip)
+                                                                       // with the look-ahead driver (capi_util.h)
 constexpr unsigned long long Q_GIVEUP_TICKS = 300000ull;               // 3 ms without any publish anywhere: drain this instance
 
 // is the task behind a ticket already done?  (after a rewind the head passes over tasks that were finished out of order)
