@@ -388,6 +388,35 @@ int sgpr_applymap_host(int family, int mode, int nm, int ntest, const double *hy
                        const double *hypp, int nhypp, int n0p, const double *xtrainp,
                        const double *ytrainp, const double *alphap, const double *Q0,
                        const double *P0, double *qmap, double *pmap, double *pdiff);
+/* The symplectic map of a fit with d canonical pairs (d = 1, 2, 3), nm - 1 steps for ntest orbits with every step on the
+ * device: one workgroup per orbit, no workgroup waits on another.  With x = (q_1..q_d, P_1..P_d) and G(x) = K*(x) alpha (what
+ * sgpr_fit_predict_nd returns: G_q = dF/dq = p - P, G_P = dF/dP = Q - q) a step solves
+ *     f(P) = G_q(q, P) - p + P = 0   for P in R^d,   then   Q = q + G_P(q, P),
+ * by Newton from P = p with the ANALYTIC Jacobian I + dG_q/dP (one pass over the training points sums G and the Jacobian
+ * together; the d x d system in closed form).  It stops when max|dP| <= 1e-13 max(1, max|P|) or after 60 iterations (the
+ * d = 1 map's tol and maxiter); one more pass at the final P gives G_P and the residual, and the step is accepted when
+ * max|f| <= 1e-8 max(1, max|p|) (the d = 1 rule).  Otherwise -- also on a non-finite value or a singular Jacobian -- the orbit
+ * is lost: NaN from that step on; an orbit that starts NaN stays NaN.
+ * mode: SGPR_MAP_WRAP_Q (every q_i mod 2 pi after the update) | SGPR_MAP_EXPLICIT (P = p - G_q(q, p), no solve; the sum
+ * kernels' maps); any other bit is SGPR_E_ARG.
+ * Q0, P0: ntest x d column-major host arrays (ldq, ldp >= ntest).  qmap, pmap: [nm][ntest][d] doubles, C order, row 0 = the
+ * start points.  iters (may be NULL): [nm-1][ntest], the Newton iterations of each solve, 0 in explicit mode, -1 for a lost
+ * orbit.  An orbit's bits depend on nothing but its own start point: not on ntest, its index, or a repeated call.
+ * 256 threads per orbit with the training points and alpha staged in LDS up to n0 = 1024, 512 threads reading them from
+ * memory beyond.  One workgroup per orbit at every n0: the d = 1 kernel's teams of workgroups per orbit do not exist here.
+ * Checked before any device call (SGPR_E_ARG): null handle or pointers (iters excepted), nm < 1, ntest < 0, ldq / ldp < ntest,
+ * unknown mode bits -- and for the host form an unknown family, d outside 1..3, nhyp != 2d + 1 (3d + 1 with periods), n0 < 0,
+ * ldx < n0.  ntest == 0 returns 0; nm == 1 writes the start row only.
+ * sgpr_fit_applymap_nd: the training points and alpha of a solved sgpr_fit_create_nd / sgpr_fit_create fit (d = 1 fits run
+ * the same kernel with D = 2); SGPR_E_STATE for an unsolved fit, a SGPR_FIT_REG fit and a SGPR_FIT_BLOCK_* fit.
+ * sgpr_applymap_nd_host: the same from caller-supplied training points X (n0 x 2d column-major, ldx >= n0), alpha (2 d n0,
+ * block by block like the rows of K) and hyp as sgpr_fit_create_nd takes it -- the counterpart of sgpr_applymap_host.
+ * Added in ABI 5 (additional entry points). */
+int sgpr_fit_applymap_nd(sgpr_fit_t f, int mode, int nm, int ntest, const double *Q0, size_t ldq,
+                         const double *P0, size_t ldp, double *qmap, double *pmap, int *iters);
+int sgpr_applymap_nd_host(int family, int d, int mode, int nm, int ntest, const double *hyp, int nhyp, int n0,
+                          const double *X, size_t ldx, const double *alpha, const double *Q0, size_t ldq,
+                          const double *P0, size_t ldp, double *qmap, double *pmap, int *iters);
 /* alpha-solve on device with the factor and its leaf inverses: b (n) := L^-T L^-1 b */
 int sgpr_potrs_vec_dev(int n, const double *L, size_t ldl, void *work, double *b,
                        void *stream);

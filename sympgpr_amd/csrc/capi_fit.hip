@@ -31,7 +31,7 @@ struct sgpr_fit {
 
 // What an entry needs of its handle.  guard() answers a null handle or !args_ok with SGPR_E_ARG, then the state the entry
 // needs with SGPR_E_STATE, in this order; every message begins with the entry's name.
-enum : unsigned { NEED_BUILT = 1, NEED_FACTOR = 2, NEED_SOLVED = 4, NEED_D1 = 8, NEED_ALL_BLOCKS = 16 };
+enum : unsigned { NEED_BUILT = 1, NEED_FACTOR = 2, NEED_SOLVED = 4, NEED_D1 = 8, NEED_ALL_BLOCKS = 16, NEED_PAIR_KERNEL = 32 };
 constexpr unsigned ONE_BLOCK = SGPR_FIT_BLOCK_QQ | SGPR_FIT_BLOCK_PP;
 static int guard(const char *entry, const sgpr_fit *f, bool args_ok, unsigned need = 0)
 {
@@ -42,6 +42,7 @@ static int guard(const char *entry, const sgpr_fit *f, bool args_ok, unsigned ne
     if ((need & NEED_SOLVED) && !f->solved) return fail(SGPR_E_STATE, "not solved");
     if ((need & NEED_D1) && f->d > 1) return fail(SGPR_E_STATE, "defined for d = 1 only");
     if ((need & NEED_ALL_BLOCKS) && (f->flags & ONE_BLOCK)) return fail(SGPR_E_STATE, "not defined for a single-block fit");
+    if ((need & NEED_PAIR_KERNEL) && (f->flags & SGPR_FIT_REG)) return fail(SGPR_E_STATE, "not defined for a scalar-kernel fit");
     return 0;
 }
 
@@ -628,6 +629,25 @@ int sgpr_fit_predict_cov(sgpr_fit_t f, int m, const double *Xt, size_t ldxt, dou
     SGPR_HIP(hipMemcpyAsync(cov, C, (size_t)m * D * D * sizeof(double), hipMemcpyDeviceToHost, f->st));
     SGPR_HIP(hipStreamSynchronize(f->st));
     return 0;
+}
+
+/* nm steps of the fit's symplectic map (gram_nd.hip: applymap_nd_kernel) for ntest orbits, with the fit's own device-resident
+ * training points and alpha; d = 1 fits run the D = 2 instance of the d-pair kernel. */
+int sgpr_fit_applymap_nd(sgpr_fit_t f, int mode, int nm, int ntest, const double *Q0, size_t ldq, const double *P0, size_t ldp,
+                         double *qmap, double *pmap, int *iters)
+{
+    int rc = guard("fit_applymap_nd", f, true);
+    if (rc) return rc;
+    if ((rc = applymap_nd_call_check("fit_applymap_nd", mode, nm, ntest, Q0, ldq, P0, ldp, qmap, pmap))) return rc;
+    if ((rc = guard("fit_applymap_nd", f, true, NEED_SOLVED | NEED_ALL_BLOCKS | NEED_PAIR_KERNEL))) return rc;
+    if (ntest == 0) return 0;
+    double hyp1[4];
+    int nhyp;
+    const double *hyp = fit_hyp_nd(f, hyp1, &nhyp);
+    if ((rc = applymap_nd_io(f->family, f->d, mode, nm, ntest, f->npts, f->dX, (size_t)f->npts, hyp, nhyp, f->dalpha, Q0, ldq, P0,
+                             ldp, qmap, pmap, iters, f->st)))
+        return rc;
+    return check_solve("fit_applymap_nd", f);   // alpha is the strip solves' result: a give-up there is reported by the first call that waits (as sgpr_fit_alpha)
 }
 
 // cond_2(Ky) from below: lambda_max by power iteration on Ky v (the rows of K are re-evaluated from the training points by the

@@ -79,4 +79,50 @@ inline int potrs_dispatch(int n, const double *L, size_t ldl, void *work, double
     return 0;
 }
 
+// What sgpr_fit_applymap_nd and sgpr_applymap_nd_host share.  The checks need no device: an argument error is SGPR_E_ARG on any
+// machine.  The shape of the call (both entries) ...
+inline int applymap_nd_call_check(const char *entry, int mode, int nm, int ntest, const double *Q0, size_t ldq, const double *P0,
+                                  size_t ldp, const double *qmap, const double *pmap)
+{
+    auto E = [&](const char *what) { set_error(std::string(entry) + ": " + what); return SGPR_E_ARG; };
+    if (mode & ~(SGPR_MAP_WRAP_Q | SGPR_MAP_EXPLICIT)) return E("unknown mode bit (only SGPR_MAP_WRAP_Q and SGPR_MAP_EXPLICIT)");
+    if (nm < 1) return E("nm < 1");
+    if (ntest < 0) return E("ntest < 0");
+    if (!Q0 || !P0 || !qmap || !pmap) return E("null Q0, P0, qmap or pmap");
+    if (ldq < (size_t)ntest || ldp < (size_t)ntest) return E("leading dimension of Q0 or P0 smaller than ntest");
+    return 0;
+}
+// ... and the description of the kernel, which a fit handle has checked when it was created
+inline int applymap_nd_kernel_check(const char *entry, int family, int d, const double *hyp, int nhyp)
+{
+    auto E = [&](const char *what) { set_error(std::string(entry) + ": " + what); return SGPR_E_ARG; };
+    if (family < SGPR_FAM_A || family > SGPR_FAM_USER) return E("unknown kernel family");
+    if (d < 1 || d > 3) return E("d must be 1, 2 or 3");
+    if (!hyp || nhyp != (family_has_p(family) ? 3 * d + 1 : 2 * d + 1))
+        return E("hyp must hold (lq_1..lq_d, lP_1..lP_d, sig) -- (lq.., lP.., p_1..p_d, sig) for family D");
+    return 0;
+}
+
+// uploads the start points, runs applymap_nd on device-resident training points and alpha, brings the orbits back and waits
+inline int applymap_nd_io(int family, int d, int mode, int nm, int ntest, int n0, const double *dXtr, size_t ldxtr,
+                          const double *hyp, int nhyp, const double *dalpha, const double *Q0, size_t ldq, const double *P0,
+                          size_t ldp, double *qmap, double *pmap, int *iters, hipStream_t st)
+{
+    int rc;
+    DevBuf q0, p0, qm, pm, it;
+    const size_t nt = (size_t)ntest, out_bytes = (size_t)nm * nt * d * sizeof(double), it_bytes = (size_t)(nm - 1) * nt * sizeof(int);
+    if ((rc = q0.alloc(nt * d * sizeof(double))) || (rc = p0.alloc(nt * d * sizeof(double))) || (rc = qm.alloc(out_bytes)) ||
+        (rc = pm.alloc(out_bytes)) || (iters && (rc = it.alloc(it_bytes))))
+        return rc;
+    if ((rc = copy_in(q0.p, nt, Q0, ldq, nt, d, st)) || (rc = copy_in(p0.p, nt, P0, ldp, nt, d, st))) return rc;
+    if ((rc = applymap_nd(family, d, mode, nm, ntest, n0, dXtr, ldxtr, hyp, nhyp, dalpha, q0.as<double>(), p0.as<double>(),
+                          qm.as<double>(), pm.as<double>(), iters ? it.as<int>() : nullptr, st)))
+        return rc;
+    SGPR_HIP(hipMemcpyAsync(qmap, qm.p, out_bytes, hipMemcpyDeviceToHost, st));
+    SGPR_HIP(hipMemcpyAsync(pmap, pm.p, out_bytes, hipMemcpyDeviceToHost, st));
+    if (iters && it_bytes) SGPR_HIP(hipMemcpyAsync(iters, it.p, it_bytes, hipMemcpyDeviceToHost, st));
+    SGPR_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
 }  // namespace sgpr

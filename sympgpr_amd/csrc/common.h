@@ -74,6 +74,11 @@ int gram_nd_sel(int family, int d, int mi, int mj, const double *Xb, size_t ldxb
                 const double *hyp, int nhyp, double *K, size_t ld, const long *roff, const long *coff, hipStream_t st);
 int predict_nd(int family, int d, int m, const double *Xt, size_t ldxt, int n0, const double *Xtr, size_t ldxtr,
                const double *hyp, int nhyp, const double *alpha, double *out, hipStream_t st);
+// nm steps of the d-pair symplectic map for ntest orbits, one workgroup per orbit (device buffers: Xtr n0 x 2d, alpha 2 d n0,
+// Q0 / P0 ntest x d with leading dimension ntest, qmap / pmap [nm][ntest][d], iters [nm - 1][ntest] or null)
+int applymap_nd(int family, int d, int mode, int nm, int ntest, int n0, const double *Xtr, size_t ldxtr, const double *hyp,
+                int nhyp, const double *alpha, const double *Q0, const double *P0, double *qmap, double *pmap, int *iters,
+                hipStream_t st);
 
 // ---- gemm_f64.hip : C = beta C + alpha A B^T on fp64 MFMA tiles
 int gemm_nt(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B,

@@ -100,6 +100,23 @@ class SympFit:
                 "sgpr_fit_predict_cov")
         return mean, cov
 
+    def applymap_pairs(self, nm, Q0, P0, wrap_q=False, explicit=False, return_iters=False):
+        """nm - 1 steps of the fit's symplectic map for the start points Q0, P0 (Ntest, d) -- for d = 1 also (Ntest,) --, every
+        step on the device: per step the implicit equation G_q(q, P) - p + P = 0 is solved for P by Newton with the analytic
+        Jacobian (G = predict_pairs), then Q = q + G_P(q, P).  wrap_q: every q_i mod 2 pi; explicit: P = p - G_q(q, p), no
+        solve.  -> qmap, pmap (nm, Ntest, d), row 0 the start points, NaN from the step at which an orbit is lost; with
+        return_iters also iters (nm - 1, Ntest): Newton iterations per solve, 0 in explicit mode, -1 for a lost orbit.
+        Needs a solved fit (run()); not defined for reg=True and block="qq" / "PP" fits."""
+        from . import maps
+        Q0, P0 = maps.start_points_nd(Q0, P0, self.d)
+        Ntest = Q0.shape[0]
+        nm, qmap, pmap, iters = maps.map_outputs_nd(nm, Ntest, self.d)
+        mode = (maps.WRAP_Q if wrap_q else 0) | (maps.EXPLICIT if explicit else 0)
+        L.check(self._lib.sgpr_fit_applymap_nd(self._h, mode, nm, Ntest, L.dptr(Q0), max(Ntest, 1), L.dptr(P0), max(Ntest, 1),
+                                               L.dptr(qmap), L.dptr(pmap), iters.ctypes.data_as(C.POINTER(C.c_int))),
+                "sgpr_fit_applymap_nd")
+        return (qmap, pmap, iters) if return_iters else (qmap, pmap)
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             self._lib.sgpr_fit_destroy(self._h)

@@ -9,9 +9,14 @@ One recurrence, the variants the reference's drivers carry in their own func.py 
     applymap          01_pendulum/explicit/func_expl.py:113-128   explicit, q mod 2 pi
     applymap_tok      05_tokamak/SympGPR/func.py:182-211  implicit, q mod 2 pi, an orbit with P < 0 is lost (LOSS_NEGP)
 
+For fits with d canonical pairs (d = 1, 2, 3) the map is run_map_nd / SympFit.applymap_pairs: Newton with the analytic
+Jacobian on the d unknowns P, one workgroup per orbit (include/sympgpr_hip.h: sgpr_applymap_nd_host).
+
 alpha = Kyinv ztrain is formed once (the reference re-multiplies Kyinv inside every calcP / calcQ
 call); a residual of the implicit equation is one block-wide reduction over the training points.
 """
+import ctypes as C
+
 import numpy as np
 
 from . import _lib as L
@@ -68,3 +73,59 @@ def run_map(mode, nm, Ntest, l, Q0map, P0map, xtrain, ztrain, Kyinv, hypp=None, 
                                    L.dptr(yp), L.dptr(alphap), L.dptr(Q0), L.dptr(P0), L.dptr(qmap), L.dptr(pmap),
                                    L.dptr(pdiff) if want_pdiff else None), "sgpr_applymap_host")
     return (qmap, pmap, pdiff) if want_pdiff else (qmap, pmap)
+
+
+def start_points_nd(Q0, P0, d):
+    """Q0, P0 as (Ntest, d) F-ordered float64 arrays; for d = 1 a vector (Ntest,) is accepted too."""
+    out = []
+    for name, v in (("Q0", Q0), ("P0", P0)):
+        v = np.asarray(v, dtype=np.float64)
+        if d == 1 and v.ndim == 1:
+            v = v.reshape(-1, 1)
+        if v.ndim != 2 or v.shape[1] != d:
+            raise ValueError("%s must be (Ntest, %d)%s" % (name, d, " or (Ntest,)" if d == 1 else ""))
+        out.append(np.asfortranarray(v))
+    if out[0].shape != out[1].shape:
+        raise ValueError("Q0 and P0 must have the same shape")
+    return out
+
+
+def map_mode_nd(mode):
+    mode = int(mode)
+    if mode & ~(WRAP_Q | EXPLICIT):
+        raise ValueError("the d-pair map knows WRAP_Q and EXPLICIT only")
+    return mode
+
+
+def map_outputs_nd(nm, Ntest, d):
+    nm = int(nm)
+    if nm < 1:
+        raise ValueError("nm must be at least 1")
+    return nm, np.zeros((nm, Ntest, d)), np.zeros((nm, Ntest, d)), np.zeros((nm - 1, Ntest), dtype=np.int32)
+
+
+def run_map_nd(family, d, mode, nm, hyp, X, alpha, Q0, P0, return_iters=False):
+    """The d-pair symplectic map from the posterior weights themselves: X (N0, 2d) training points with columns
+    (q_1..q_d, P_1..P_d), alpha = Ky^-1 z (2 d N0, block by block like the rows of K), hyp = (lq.., lP.., [p..,] sig),
+    Q0, P0 (Ntest, d) start points; mode = WRAP_Q | EXPLICIT bits.  -> qmap, pmap of shape (nm, Ntest, d), row 0 the start
+    points, NaN from the step at which an orbit is lost; with return_iters also iters (nm - 1, Ntest): Newton iterations of
+    each solve, 0 in explicit mode, -1 for a lost orbit.  Every step runs on the device, one workgroup per orbit."""
+    lib = L.load_library()
+    d = int(d)
+    if d not in (1, 2, 3):
+        raise ValueError("d must be 1, 2 or 3")
+    X = np.asfortranarray(X, dtype=np.float64)
+    if X.ndim != 2 or X.shape[1] != 2 * d:
+        raise ValueError("X must be (N0, %d)" % (2 * d))
+    N0 = X.shape[0]
+    alpha, hyp = L.f64(alpha), L.f64(hyp)
+    if alpha.shape != (2 * d * N0,):
+        raise ValueError("alpha must have length 2 d N0 = %d" % (2 * d * N0))
+    mode = map_mode_nd(mode)
+    Q0, P0 = start_points_nd(Q0, P0, d)
+    Ntest = Q0.shape[0]
+    nm, qmap, pmap, iters = map_outputs_nd(nm, Ntest, d)
+    L.check(lib.sgpr_applymap_nd_host(L.family_id(family), d, mode, nm, Ntest, L.dptr(hyp), len(hyp), N0, L.dptr(X), max(N0, 1),
+                                      L.dptr(alpha), L.dptr(Q0), max(Ntest, 1), L.dptr(P0), max(Ntest, 1), L.dptr(qmap),
+                                      L.dptr(pmap), iters.ctypes.data_as(C.POINTER(C.c_int))), "sgpr_applymap_nd_host")
+    return (qmap, pmap, iters) if return_iters else (qmap, pmap)
