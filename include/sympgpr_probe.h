@@ -95,6 +95,22 @@ int sgpr_probe_gemm_strassen_dev(int m, int n, int k, double alpha, const double
                                  double beta, double *C, size_t ldc, int lower, void *stream);
 int sgpr_probe_gemm_nt2_dev(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb,
                             double beta, double *C, size_t ldc, double alpha2, double *C2, size_t ldc2, void *stream);
+/* The outer Strassen level (csrc/gemm_f64.hip).  Host only: the list of one call with both levels.  Records of the inner level
+ * (kinds 1 - 3 above, unchanged: a call the outer level does not apply to gives exactly sgpr_probe_strassen_plan's list) and
+ *   4 outer sum:     layout of kind 1; the result goes to the OUTER scratch of that side
+ *   5 outer product: layout of kind 2; operands are raw blocks or the outer scratch, [7] [8] [9] the half-size extents.  Not a
+ *                    launch: the inner plan of an m x n x k product (sgpr_probe_strassen_plan) runs on these operands, each of its
+ *                    products going to BOTH destination blocks (offsets inside them as the inner plan says, signs multiplied)
+ * `smin2`: smallest half-size of m and n that takes the outer level; `kslab2`: its k slab -- whole slabs of exactly that many
+ * columns take it, a shorter remainder of k goes through the inner level alone (< 0: the tunables gemm_strassen2_min (16384),
+ * gemm_strassen2_kslab (32768)).  `scratch_doubles` covers the inner and the outer pair together.  Tunable
+ * gemm_strassen2_noscratch: the outer pair's allocation is treated as failed (one level).  tools/strassen2_plan.py replays it. */
+int sgpr_probe_strassen2_plan(int m, int n, int k, int lower, long smin, long kslab, long smin2, long kslab2, long scratch_doubles,
+                              long long *out, int max_records, int *count);
+/* count = 2 .. 4 destinations from one product (disjoint blocks, device pointers; the arrays themselves are host memory):
+ * C[0] = beta C[0] + alpha[0] A B^T, C[d] += alpha[d] A B^T */
+int sgpr_probe_gemm_nt4_dev(int m, int n, int k, const double *A, size_t lda, const double *B, size_t ldb, double beta, int count,
+                            double *const *C, const size_t *ldc, const double *alpha, void *stream);
 /* the last sgpr_applymap_host of this process: K*-row evaluations (residuals of the implicit equation + q updates) summed over
  * its orbits, and the number of workgroups that share one orbit for ntest orbits on n0 training points */
 unsigned sgpr_probe_map_calls(void);

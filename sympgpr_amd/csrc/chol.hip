@@ -1761,7 +1761,10 @@ int potrf(int n, double *A, size_t lda, void *work, size_t lwork, int *dinfo, hi
     if (n > c.la_max && n > LEAF) {
         // the two largest products of the recursion (every later one is smaller): size the operand-sum scratch once
         const int n1 = split(n), n2 = n - n1, n11 = split(n1);
-        strassen_reserve(std::max(strassen_scratch_doubles(n2, n2, n1, 1), strassen_scratch_doubles(n2, n1 - n11, n11, 0)), st);
+        auto need = [&](int levels) {
+            return std::max(strassen_scratch_doubles(n2, n2, n1, 1, levels), strassen_scratch_doubles(n2, n1 - n11, n11, 0, levels));
+        };
+        strassen_reserve(need(2), need(1), st);   // both levels' operand sums, or the inner level's alone if that does not fit
     }
     const bool dbg = PANEL_DBG && getenv("SGPR_PANEL_DBG") != nullptr;
     const int T = (n + LEAF - 1) / LEAF;

@@ -98,8 +98,15 @@ enum { PLAN_SUM = 1, PLAN_PROD = 2, PLAN_CLASSIC = 3 };
 int gemm_nt_strassen(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb, double beta,
                      double *C, size_t ldc, int lower, hipStream_t st);
 int strassen_plan(int m, int n, int k, int lower, long smin, long kslab, size_t scratch_doubles, std::vector<long long> &out);
-size_t strassen_scratch_doubles(int m, int n, int k, int lower);
-void strassen_reserve(size_t doubles, hipStream_t st);
+// a second level around it for the largest products: the outer list (records of the inner level + PLAN2_*, same layouts)
+enum { PLAN2_SUM = 4, PLAN2_PROD = 5 };
+int strassen_outer_plan(int m, int n, int k, int lower, long smin, long kslab, long smin2, long kslab2, size_t scratch_doubles,
+                   std::vector<long long> &out);
+// up to four destinations from one product (disjoint blocks): C[0] = beta C[0] + alpha[0] A B^T, C[d] += alpha[d] A B^T
+int gemm_nt_multi(int m, int n, int k, const double *A, size_t lda, const double *B, size_t ldb, double beta, int count,
+                  double *const *C, const size_t *ldc, const double *alpha, hipStream_t st);
+size_t strassen_scratch_doubles(int m, int n, int k, int lower, int levels);
+void strassen_reserve(size_t both, size_t one, hipStream_t st);
 int strassen_trim();                             // release the scratch of the operand sums (every device)
 int gemm_profile_begin();
 int gemm_profile_end(double *out12);

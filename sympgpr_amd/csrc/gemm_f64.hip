@@ -96,6 +96,24 @@ __global__ __launch_bounds__(512, 2) void gemm_nt2_kernel(const GemmArgs g)
     else      gemm_body<BM, BN, false, false, true>(g, smem, tile_r, tile_c);
 }
 
+// ... and with up to FOUR (two Strassen levels: an inner product of an outer product): C = beta C + alpha P, then C_d += alpha_d P
+// for g.ndst - 1 further destinations.  Again a kernel of its own: the two above are compiled exactly as without it.
+__global__ __launch_bounds__(512, 2) void gemm_nt4_kernel(const GemmArgs g)
+{
+    constexpr int BM = 256, BN = 128, LDA_S = BM + PAD, LDB_S = BN + PAD;
+    __shared__ double smem[SGPR_GEMM_STAGES * BK * (LDA_S + LDB_S)];
+    int tile_r, tile_c;
+    if (!tile_of<(SR * BM) / (4 * BN)>(g, tile_r, tile_c)) return;
+    const int row0 = tile_r * BM, col0 = tile_c * BN;
+    const bool aligned = ((((uintptr_t)g.A | (uintptr_t)g.B) & 15) == 0) && (((g.lda | g.ldb) & 1) == 0);
+    const bool fast = aligned && (row0 + BM <= g.m) && (col0 + BN <= g.n) && (g.k % BK == 0);
+    if (fast) gemm_body_dma<BM, BN, SGPR_GEMM_STAGES, false, true>(g, smem, tile_r, tile_c);
+    else      gemm_body<BM, BN, false, false, false, true>(g, smem, tile_r, tile_c);
+}
+
+// a further destination of a product: C += alpha A B^T
+struct Dst { double *C; size_t ld; double alpha; };
+
 // T (rows x cols, leading dimension rows) = X + sign Y on column-major blocks: the operand sums of the Strassen front end.
 // HBM-bound (two reads, one write per element): 16-byte accesses, 4 columns per thread in flight, grid-stride over
 // pieces of 512 rows x 4 columns.  rows even, all three bases 16-byte aligned, ldx / ldy even (checked by the caller).
@@ -135,13 +153,13 @@ int gemm_nt(int m, int n, int k, double alpha, const double *A, size_t lda, cons
 
 static int gemm_launch(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B,
                        size_t ldb, double beta, double *C, size_t ldc, int lower, const int *bc, int transb,
-                       hipStream_t st, unsigned long long *stamps = nullptr, int dbg = 0, double *C2 = nullptr,
-                       size_t ldc2 = 0, double alpha2 = 0.0);
+                       hipStream_t st, unsigned long long *stamps = nullptr, int dbg = 0, const Dst *x = nullptr, int nx = 0,
+                       bool k4 = false);
 
 // `bc` = {blk, pr, pi, pc, pj}: the block-cyclic form of the lower-mode skip test (GemmArgs)
 static int gemm_chunked(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B,
                         size_t ldb, double beta, double *C, size_t ldc, int lower, const int *bc,
-                        hipStream_t st, double *C2, size_t ldc2, double alpha2)
+                        hipStream_t st, const Dst *x, int nx, bool k4)
 {
     // Products deeper than 8192 run as back-to-back launches of <= 8192 columns each (C re-read per launch, negligible
     // beside the flop), so that the 32 workgroups sharing a super-tile's operand panels restart in step instead of drifting
@@ -153,19 +171,19 @@ static int gemm_chunked(int m, int n, int k, double alpha, const double *A, size
         const int step = ((k + nchunk - 1) / nchunk + 127) / 128 * 128;
         for (int k0 = 0; k0 < k; k0 += step) {
             const int rc = gemm_launch(m, n, std::min(step, k - k0), alpha, A + (size_t)k0 * lda, lda, B + (size_t)k0 * ldb, ldb,
-                                       k0 == 0 ? beta : 1.0, C, ldc, lower, bc, 0, st, nullptr, 0, C2, ldc2, alpha2);
+                                       k0 == 0 ? beta : 1.0, C, ldc, lower, bc, 0, st, nullptr, 0, x, nx, k4);
             if (rc) return rc;
         }
         return 0;
     }
-    return gemm_launch(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, lower, bc, 0, st, nullptr, 0, C2, ldc2, alpha2);
+    return gemm_launch(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, lower, bc, 0, st, nullptr, 0, x, nx, k4);
 }
 
 int gemm_nt_bc(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B,
                size_t ldb, double beta, double *C, size_t ldc, int lower, const int *bc,
                hipStream_t st)
 {
-    return gemm_chunked(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, lower, bc, st, nullptr, 0, 0.0);
+    return gemm_chunked(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, lower, bc, st, nullptr, 0, false);
 }
 
 // C = beta C + alpha A B^T and C2 += alpha2 A B^T in one pass over the operands (every k chunk adds to both)
@@ -174,12 +192,28 @@ int gemm_nt_two(int m, int n, int k, double alpha, const double *A, size_t lda, 
 {
     const int bc[5] = {1, 1, 0, 1, 0};
     if (!C2) { set_error("gemm_nt_two: null second destination"); return SGPR_E_ARG; }
-    return gemm_chunked(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, 0, bc, st, C2, ldc2, alpha2);
+    const Dst x{C2, ldc2, alpha2};
+    return gemm_chunked(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, 0, bc, st, &x, 1, false);
+}
+
+// count (2 .. 4) destinations from one product, disjoint blocks: C[0] = beta C[0] + alpha[0] A B^T, C[d] += alpha[d] A B^T
+// (gemm_nt4_kernel; every k chunk adds to all of them)
+int gemm_nt_multi(int m, int n, int k, const double *A, size_t lda, const double *B, size_t ldb, double beta, int count,
+                  double *const *C, const size_t *ldc, const double *alpha, hipStream_t st)
+{
+    const int bc[5] = {1, 1, 0, 1, 0};
+    if (count < 2 || count > 4 || !C || !ldc || !alpha) { set_error("gemm_nt_multi: 2 to 4 destinations"); return SGPR_E_ARG; }
+    Dst x[3];
+    for (int d = 0; d < count; ++d) {
+        if (!C[d]) { set_error("gemm_nt_multi: null destination"); return SGPR_E_ARG; }
+        if (d) x[d - 1] = Dst{C[d], ldc[d], alpha[d]};
+    }
+    return gemm_chunked(m, n, k, alpha[0], A, lda, B, ldb, beta, C[0], ldc[0], 0, bc, st, x, count - 1, true);
 }
 
 static int gemm_launch(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B,
                        size_t ldb, double beta, double *C, size_t ldc, int lower, const int *bc, int transb,
-                       hipStream_t st, unsigned long long *stamps, int dbg, double *C2, size_t ldc2, double alpha2)
+                       hipStream_t st, unsigned long long *stamps, int dbg, const Dst *x, int nx, bool k4)
 {
     const bool plain = bc[0] == 1 && bc[1] == 1 && bc[3] == 1 && bc[4] == 0;
     const long diag_off = plain ? bc[2] : 1;  // != 0 disables the triangular tile enumeration
@@ -190,9 +224,15 @@ static int gemm_launch(int m, int n, int k, double alpha, const double *A, size_
         set_error("gemm: leading dimension too small");
         return SGPR_E_ARG;
     }
-    if (C2 && (lower || transb || ldc2 < (size_t)m)) { set_error("gemm: bad second destination"); return SGPR_E_ARG; }
+    if (nx < 0 || nx > 3 || (nx && !x)) { set_error("gemm: bad destination count"); return SGPR_E_ARG; }
+    Dst d[3] = {};
+    for (int i = 0; i < nx; ++i) {
+        d[i] = x[i];
+        if (!d[i].C || lower || transb || d[i].ld < (size_t)m) { set_error("gemm: bad second destination"); return SGPR_E_ARG; }
+    }
     GemmArgs g{m, n, k, alpha, beta, A, lda, B, ldb, C, ldc, lower, diag_off, transb, stamps, 0, 0, 0, 0, 0, 0,
-               0, 0, bc[0], bc[1], bc[2], bc[3], bc[4], dbg, nullptr, C2, ldc2, alpha2};
+               0, 0, bc[0], bc[1], bc[2], bc[3], bc[4], dbg, nullptr, d[0].C, d[0].ld, d[0].alpha,
+               d[1].C, d[1].ld, d[1].alpha, d[2].C, d[2].ld, d[2].alpha, nx + 1};
     auto set_map = [&](int bm, int bn) {
         g.tiles_m = (m + bm - 1) / bm;
         g.tiles_n = (n + bn - 1) / bn;
@@ -270,10 +310,11 @@ static int gemm_launch(int m, int n, int k, double alpha, const double *A, size_
     static const double small_mb = tune("gemm_small_mb", 0.0);
     const double op_bytes = 8.0 * (double)k * ((A == B && lda == ldb) ? (double)std::max(m, n) : (double)m + n);
     const bool small_k = op_bytes <= small_mb * 1e6 && m > 128 && n > 128;
-    if (C2) {
-        // two destinations: always the 256x128 shape (the front end only sends products that fill the chip)
+    if (nx) {
+        // several destinations: always the 256x128 shape (the front end only sends products that fill the chip)
         const dim3 grid(set_map(256, 128));
-        hipLaunchKernelGGL(gemm_nt2_kernel, grid, dim3(512), 0, st, g);
+        if (k4 || nx > 1) hipLaunchKernelGGL(gemm_nt4_kernel, grid, dim3(512), 0, st, g);
+        else              hipLaunchKernelGGL(gemm_nt2_kernel, grid, dim3(512), 0, st, g);
         rec.big = 1;
     } else if (n <= 128 && m <= 32768 && !(dbg & 8)) {
         // one column tile (the in-place panel solve against an inverted leaf, k = n <= 128): a
@@ -426,39 +467,42 @@ bool qualifies(long m, long n, long k, const PlanCfg &c)
     if (!step) return false;
     return (size_t)(m / 2 + n / 2) * (size_t)(step / 2) <= c.scratch;
 }
+// the ten sums and seven products of one k slab [k0, k0 + 2 k2) of the m2-, n2-halved product at rows ar / br, destination
+// (cr, cc); `kind_sum` / `kind_prod`: the inner level's records or the outer level's (PLAN2_*, same layout)
+void seven(int kind_sum, int kind_prod, long m2, long n2, long k2, long k0, long ar, long br, long cr, long cc, std::vector<long long> &out)
+{
+    // block (i, j) of an operand: row offset, k-column offset
+    const long a1 = ar, a2 = ar + m2, b1 = br, b2 = br + n2, j1 = k0, j2 = k0 + k2;
+    const long c1r = cr, c2r = cr + m2, c1c = cc, c2c = cc + n2;
+    auto sum = [&](int side, long xr, long xc, long yr, long yc, int sign) {
+        put(out, {kind_sum, side, side ? n2 : m2, k2, xr, xc, yr, yc, sign});
+    };
+    auto prod = [&](int as, long pr, long pc, int bs, long qr, long qc, long d1r, long d1c, int s1, long d2r, long d2c, int s2) {
+        put(out, {kind_prod, as, pr, pc, bs, qr, qc, m2, n2, k2, d1r, d1c, s1, d2r, d2c, s2});
+    };
+    sum(0, a1, j1, a2, j2, +1); sum(1, b1, j1, b2, j2, +1);                      // M1
+    prod(1, 0, 0, 1, 0, 0, c1r, c1c, +1, c2r, c2c, +1);
+    sum(0, a2, j1, a2, j2, +1);                                                    // M2
+    prod(1, 0, 0, 0, b1, j1, c2r, c1c, +1, c2r, c2c, -1);
+    sum(1, b2, j1, b2, j2, -1);                                                    // M3
+    prod(0, a1, j1, 1, 0, 0, c1r, c2c, +1, c2r, c2c, +1);
+    sum(1, b1, j2, b1, j1, -1);                                                    // M4
+    prod(0, a2, j2, 1, 0, 0, c1r, c1c, +1, c2r, c1c, +1);
+    sum(0, a1, j1, a1, j2, +1);                                                    // M5
+    prod(1, 0, 0, 0, b2, j2, c1r, c1c, -1, c1r, c2c, +1);
+    sum(0, a2, j1, a1, j1, -1); sum(1, b1, j1, b2, j1, +1);                      // M6
+    prod(1, 0, 0, 1, 0, 0, c2r, c2c, +1, 0, 0, 0);
+    sum(0, a1, j2, a2, j2, -1); sum(1, b1, j2, b2, j2, +1);                      // M7
+    prod(1, 0, 0, 1, 0, 0, c1r, c1c, +1, 0, 0, 0);
+}
 void plan_gemm(long m, long n, long k, long ar, long br, long cr, long cc, const PlanCfg &c, std::vector<long long> &out)
 {
     if (!qualifies(m, n, k, c)) {
         put(out, {PLAN_CLASSIC, 0, ar, 0, br, 0, m, n, k, cr, cc});
         return;
     }
-    const long m2 = m / 2, n2 = n / 2, step = slab_of(k, c);
-    for (long k0 = 0; k0 < k; k0 += step) {
-        const long k2 = std::min(step, k - k0) / 2;
-        // block (i, j) of an operand: row offset, k-column offset
-        const long a1 = ar, a2 = ar + m2, b1 = br, b2 = br + n2, j1 = k0, j2 = k0 + k2;
-        const long c1r = cr, c2r = cr + m2, c1c = cc, c2c = cc + n2;
-        auto sum = [&](int side, long xr, long xc, long yr, long yc, int sign) {
-            put(out, {PLAN_SUM, side, side ? n2 : m2, k2, xr, xc, yr, yc, sign});
-        };
-        auto prod = [&](int as, long pr, long pc, int bs, long qr, long qc, long d1r, long d1c, int s1, long d2r, long d2c, int s2) {
-            put(out, {PLAN_PROD, as, pr, pc, bs, qr, qc, m2, n2, k2, d1r, d1c, s1, d2r, d2c, s2});
-        };
-        sum(0, a1, j1, a2, j2, +1); sum(1, b1, j1, b2, j2, +1);                      // M1
-        prod(1, 0, 0, 1, 0, 0, c1r, c1c, +1, c2r, c2c, +1);
-        sum(0, a2, j1, a2, j2, +1);                                                    // M2
-        prod(1, 0, 0, 0, b1, j1, c2r, c1c, +1, c2r, c2c, -1);
-        sum(1, b2, j1, b2, j2, -1);                                                    // M3
-        prod(0, a1, j1, 1, 0, 0, c1r, c2c, +1, c2r, c2c, +1);
-        sum(1, b1, j2, b1, j1, -1);                                                    // M4
-        prod(0, a2, j2, 1, 0, 0, c1r, c1c, +1, c2r, c1c, +1);
-        sum(0, a1, j1, a1, j2, +1);                                                    // M5
-        prod(1, 0, 0, 0, b2, j2, c1r, c1c, -1, c1r, c2c, +1);
-        sum(0, a2, j1, a1, j1, -1); sum(1, b1, j1, b2, j1, +1);                      // M6
-        prod(1, 0, 0, 1, 0, 0, c2r, c2c, +1, 0, 0, 0);
-        sum(0, a1, j2, a2, j2, -1); sum(1, b1, j2, b2, j2, +1);                      // M7
-        prod(1, 0, 0, 1, 0, 0, c1r, c1c, +1, 0, 0, 0);
-    }
+    const long step = slab_of(k, c);
+    for (long k0 = 0; k0 < k; k0 += step) seven(PLAN_SUM, PLAN_PROD, m / 2, n / 2, std::min(step, k - k0) / 2, k0, ar, br, cr, cc, out);
 }
 // lower update of the square block at row / column r0: while its off-diagonal square qualifies, the two diagonal halves
 // recurse and the square goes through plan_gemm; then the triangular launch as before
@@ -481,11 +525,13 @@ size_t plan_need(const std::vector<long long> &plan)
     return need[0] + need[1];
 }
 
-bool strassen_on()
+// 0: classical only, 1: one level (bit for bit what the tree did before the outer level existed), 2: both (unset)
+int strassen_levels()
 {
-    static const bool on = [] { const char *e = getenv("SGPR_GEMM_STRASSEN"); return !(e && e[0] == '0'); }();
-    return on;
+    static const int lv = [] { const char *e = getenv("SGPR_GEMM_STRASSEN"); return !e ? 2 : (e[0] == '0' ? 0 : (e[0] == '1' ? 1 : 2)); }();
+    return lv;
 }
+bool strassen_on() { return strassen_levels() > 0; }
 // Default threshold: profiles/strassen/sweep.txt.  Tunables "gemm_strassen_min" (half-size of m and n; k: half of it),
 // "gemm_strassen_kslab", "gemm_strassen_noscratch" (tests: the scratch allocation is reported as failed).
 PlanCfg default_cfg()
@@ -493,6 +539,110 @@ PlanCfg default_cfg()
     static const long smin = std::max(128L, (long)tune("gemm_strassen_min", 8192));
     static const long kslab = std::max(32L, (long)tune("gemm_strassen_kslab", 16384));
     return PlanCfg{smin, kslab, ~(size_t)0};
+}
+
+// ---- the outer level: one more Strassen level AROUND the plan above -----------------------------------
+// The same seven formulas on the halves of the largest products; each outer product M_i = X Y^T (X, Y a raw block or an outer
+// operand sum) is not a launch but a call of the inner level with a PAIR of destinations: the blocks of C that M_i goes to, each
+// with its sign.  The inner plan of M_i is strassen_plan(m / 2, n / 2, kslab2 / 2) as it stands; run_plan turns its records into
+// launches with twice the destinations (a product for two quadrants of M_i accumulates into four blocks of C).
+// The outer list holds the inner level's records unchanged wherever the outer level does not apply (a call that does not
+// qualify at all gives exactly strassen_plan's list), plus two kinds of its own with the layouts of PLAN_SUM / PLAN_PROD:
+//   PLAN2_SUM   outer scratch of that side = X + sign Y
+//   PLAN2_PROD  operands: raw block or the OUTER scratch; [7] [8] [9] the half-size extents; destinations as in PLAN_PROD
+// k: whole slabs of exactly kslab2 columns take the outer level; a remainder shorter than that goes through plan_gemm.
+struct Plan2Cfg {
+    PlanCfg in;     // the inner level (its scratch member is not used here)
+    long smin2;     // smallest half-size of m and n that takes the outer level
+    long kslab2;    // its k slab: exactly this many columns, a multiple of 64 (quarters stay multiples of the k-step)
+    size_t scratch; // doubles available for the inner and the outer pair together
+};
+// Default thresholds: profiles/strassen2/sweep.txt.  Tunables "gemm_strassen2_min", "gemm_strassen2_kslab",
+// "gemm_strassen2_noscratch" (tests: the allocation of the outer part is reported as failed -> one level).
+Plan2Cfg default_cfg2()
+{
+    static const long smin2 = std::max(256L, (long)tune("gemm_strassen2_min", 16384));
+    static const long kslab2 = std::max(64L, (long)tune("gemm_strassen2_kslab", 32768));
+    return Plan2Cfg{default_cfg(), smin2, kslab2, ~(size_t)0};
+}
+bool outer_noscratch()
+{
+    static const bool forced_fail = tune("gemm_strassen2_noscratch", 0) != 0;
+    return forced_fail;
+}
+bool qualifies2(long m, long n, long k, const Plan2Cfg &c)
+{
+    // halves multiples of 512 x 256: the quarters stay multiples of the tile
+    if (m <= 0 || n <= 0 || m % 1024 != 0 || n % 512 != 0) return false;
+    if (m / 2 < c.smin2 || n / 2 < c.smin2) return false;
+    if (c.kslab2 < 64 || c.kslab2 % 64 != 0 || k < c.kslab2) return false;
+    const size_t pair = (size_t)(m / 2 + n / 2) * (size_t)(c.kslab2 / 2);
+    if (pair > c.scratch) return false;
+    // ... and everything the inner level asks of an outer product, with the scratch that is left
+    PlanCfg ci = c.in;
+    ci.scratch = c.scratch - pair;
+    return qualifies(m / 2, n / 2, c.kslab2 / 2, ci);
+}
+PlanCfg inner_of(const Plan2Cfg &c)
+{
+    PlanCfg ci = c.in;
+    ci.scratch = c.scratch;
+    return ci;
+}
+void plan2_gemm(long m, long n, long k, long ar, long br, long cr, long cc, const Plan2Cfg &c, std::vector<long long> &out)
+{
+    if (!qualifies2(m, n, k, c)) { plan_gemm(m, n, k, ar, br, cr, cc, inner_of(c), out); return; }
+    long k0 = 0;
+    for (; k0 + c.kslab2 <= k; k0 += c.kslab2) seven(PLAN2_SUM, PLAN2_PROD, m / 2, n / 2, c.kslab2 / 2, k0, ar, br, cr, cc, out);
+    if (k0 == k) return;
+    // the remainder of k through the inner level alone; plan_gemm counts k columns from 0: move its records to k0
+    size_t i = out.size();
+    plan_gemm(m, n, k - k0, ar, br, cr, cc, inner_of(c), out);
+    for (; i + STRASSEN_REC <= out.size(); i += STRASSEN_REC) {
+        long long *r = &out[i];
+        if (r[0] == PLAN_SUM) { r[5] += k0; r[7] += k0; }
+        else if (r[0] == PLAN_PROD) { if (!r[1]) r[3] += k0; if (!r[4]) r[6] += k0; }
+        else { r[3] += k0; r[5] += k0; }
+    }
+}
+// lower update: the split around the off-diagonal square happens at the outer level first
+void plan2_syrk(long n, long k, long r0, const Plan2Cfg &c, std::vector<long long> &out)
+{
+    const long h = n / 2;
+    if (n % 2 != 0 || !qualifies2(h, h, k, c)) { plan_syrk(n, k, r0, inner_of(c), out); return; }
+    plan2_syrk(h, k, r0, c, out);
+    plan2_gemm(h, h, k, r0 + h, r0, r0 + h, r0, c, out);
+    plan2_syrk(h, k, r0 + h, c, out);
+}
+// the inner plan of one outer product (no offsets: its operands and destinations are passed as pointers)
+void inner_plan(const long long *r, const PlanCfg &ci, std::vector<long long> &out)
+{
+    out.clear();
+    plan_gemm(r[7], r[8], r[9], 0, 0, 0, 0, ci, out);
+}
+// doubles of scratch per region: inner A side, inner B side, outer A side, outer B side
+struct Need2 { size_t v[4] = {0, 0, 0, 0}; size_t inner() const { return v[0] + v[1]; } size_t total() const { return v[0] + v[1] + v[2] + v[3]; } };
+Need2 plan2_need(const std::vector<long long> &plan, const Plan2Cfg &c)
+{
+    Need2 nd;
+    std::vector<long long> in;
+    auto sums = [&](const long long *r, int base) {
+        size_t &v = nd.v[base + r[1]];
+        v = std::max(v, (size_t)r[2] * (size_t)r[3]);
+    };
+    PlanCfg ci = c.in;
+    ci.scratch = ~(size_t)0;
+    for (size_t i = 0; i + STRASSEN_REC <= plan.size(); i += STRASSEN_REC) {
+        const long long *r = &plan[i];
+        if (r[0] == PLAN_SUM) sums(r, 0);
+        else if (r[0] == PLAN2_SUM) sums(r, 2);
+        else if (r[0] == PLAN2_PROD) {
+            inner_plan(r, ci, in);
+            for (size_t j = 0; j + STRASSEN_REC <= in.size(); j += STRASSEN_REC)
+                if (in[j] == PLAN_SUM) sums(&in[j], 0);
+        }
+    }
+    return nd;
 }
 
 // Scratch of the operand sums: one buffer per device, owned by the library, grown to the largest qualifying call and
@@ -539,11 +689,15 @@ int block_sum(int rows, int cols, const double *X, size_t ldx, const double *Y, 
     return 0;
 }
 
-int run_plan(const std::vector<long long> &plan, double alpha, const double *A, size_t lda, const double *B, size_t ldb,
-             double beta, double *C, size_t ldc, double *SA, double *SB, hipStream_t st)
+// Execute nrec inner-level records.  C2 == nullptr: C = beta C + alpha A B^T, one launch per record as the list says.
+// C2 != nullptr (the records are the inner plan of an outer product): the same product also goes to C2 with factor alpha2 --
+// a PLAN_PROD record with two destinations becomes a four-destination launch, one with one destination and a PLAN_CLASSIC
+// record a two-destination launch.
+int run_plan(const long long *recs, size_t nrec, double alpha, const double *A, size_t lda, const double *B, size_t ldb,
+             double beta, double *C, size_t ldc, double alpha2, double *C2, size_t ldc2, double *SA, double *SB, hipStream_t st)
 {
-    for (size_t i = 0; i + STRASSEN_REC <= plan.size(); i += STRASSEN_REC) {
-        const long long *r = &plan[i];
+    for (size_t i = 0; i < nrec; ++i) {
+        const long long *r = recs + i * STRASSEN_REC;
         int rc = 0;
         if (r[0] == PLAN_SUM) {
             const double *P = r[1] ? B : A;
@@ -554,13 +708,68 @@ int run_plan(const std::vector<long long> &plan, double alpha, const double *A, 
             const int m = (int)r[7], n = (int)r[8], k = (int)r[9];
             const double *Ap = r[1] ? SA : A + r[2] + (size_t)r[3] * lda;
             const double *Bp = r[4] ? SB : B + r[5] + (size_t)r[6] * ldb;
+            const size_t la = r[1] ? (size_t)m : lda, lb = r[4] ? (size_t)n : ldb;
             double *C1 = C + r[10] + (size_t)r[11] * ldc;
-            if (r[15]) rc = gemm_nt_two(m, n, k, alpha * (double)r[12], Ap, r[1] ? (size_t)m : lda, Bp, r[4] ? (size_t)n : ldb, 1.0, C1, ldc,
-                                     alpha * (double)r[15], C + r[13] + (size_t)r[14] * ldc, ldc, st);
-            else       rc = gemm_nt(m, n, k, alpha * (double)r[12], Ap, r[1] ? (size_t)m : lda, Bp, r[4] ? (size_t)n : ldb, 1.0, C1, ldc, 0, 0, st);
+            if (C2) {
+                double *cs[4] = {C1, nullptr, nullptr, nullptr};
+                size_t ls[4] = {ldc, 0, 0, 0};
+                double as[4] = {alpha * (double)r[12], 0.0, 0.0, 0.0};
+                int cnt = 1;
+                auto add = [&](double *p, size_t l, double a) { cs[cnt] = p; ls[cnt] = l; as[cnt] = a; ++cnt; };
+                if (r[15]) add(C + r[13] + (size_t)r[14] * ldc, ldc, alpha * (double)r[15]);
+                add(C2 + r[10] + (size_t)r[11] * ldc2, ldc2, alpha2 * (double)r[12]);
+                if (r[15]) add(C2 + r[13] + (size_t)r[14] * ldc2, ldc2, alpha2 * (double)r[15]);
+                if (cnt == 2) rc = gemm_nt_two(m, n, k, as[0], Ap, la, Bp, lb, 1.0, cs[0], ls[0], as[1], cs[1], ls[1], st);
+                else          rc = gemm_nt_multi(m, n, k, Ap, la, Bp, lb, 1.0, cnt, cs, ls, as, st);
+            } else if (r[15]) {
+                rc = gemm_nt_two(m, n, k, alpha * (double)r[12], Ap, la, Bp, lb, 1.0, C1, ldc,
+                                 alpha * (double)r[15], C + r[13] + (size_t)r[14] * ldc, ldc, st);
+            } else {
+                rc = gemm_nt(m, n, k, alpha * (double)r[12], Ap, la, Bp, lb, 1.0, C1, ldc, 0, 0, st);
+            }
+        } else if (r[0] == PLAN_CLASSIC) {
+            const double *Ap = A + r[2] + (size_t)r[3] * lda, *Bp = B + r[4] + (size_t)r[5] * ldb;
+            if (C2) rc = gemm_nt_two((int)r[6], (int)r[7], (int)r[8], alpha, Ap, lda, Bp, ldb, beta, C + r[9] + (size_t)r[10] * ldc, ldc,
+                                     alpha2, C2 + r[9] + (size_t)r[10] * ldc2, ldc2, st);
+            else    rc = gemm_nt((int)r[6], (int)r[7], (int)r[8], alpha, Ap, lda, Bp, ldb, beta, C + r[9] + (size_t)r[10] * ldc, ldc, (int)r[1], 0, st);
         } else {
-            rc = gemm_nt((int)r[6], (int)r[7], (int)r[8], alpha, A + r[2] + (size_t)r[3] * lda, lda, B + r[4] + (size_t)r[5] * ldb, ldb,
-                         beta, C + r[9] + (size_t)r[10] * ldc, ldc, (int)r[1], 0, st);
+            set_error("run_plan: unknown record");
+            rc = SGPR_E_ARG;
+        }
+        if (rc) return rc;
+    }
+    return 0;
+}
+int run_plan(const std::vector<long long> &plan, double alpha, const double *A, size_t lda, const double *B, size_t ldb,
+             double beta, double *C, size_t ldc, double *SA, double *SB, hipStream_t st)
+{
+    return run_plan(plan.data(), plan.size() / STRASSEN_REC, alpha, A, lda, B, ldb, beta, C, ldc, 0.0, nullptr, 0, SA, SB, st);
+}
+// Execute an outer list: S = the scratch buffer, laid out as [inner A | inner B | outer A | outer B] with the sizes of nd
+int run_plan2(const std::vector<long long> &plan, const Plan2Cfg &c, const Need2 &nd, double alpha, const double *A, size_t lda,
+              const double *B, size_t ldb, double beta, double *C, size_t ldc, double *S, hipStream_t st)
+{
+    double *const SA = S, *const SB = S + nd.v[0], *const OA = SB + nd.v[1], *const OB = OA + nd.v[2];
+    PlanCfg ci = c.in;
+    ci.scratch = nd.inner();
+    std::vector<long long> in;
+    for (size_t i = 0; i + STRASSEN_REC <= plan.size(); i += STRASSEN_REC) {
+        const long long *r = &plan[i];
+        int rc = 0;
+        if (r[0] == PLAN2_SUM) {
+            const double *P = r[1] ? B : A;
+            const size_t ld = r[1] ? ldb : lda;
+            rc = block_sum((int)r[2], (int)r[3], P + r[4] + (size_t)r[5] * ld, ld, P + r[6] + (size_t)r[7] * ld, ld, (double)r[8],
+                           r[1] ? OB : OA, st);
+        } else if (r[0] == PLAN2_PROD) {
+            const double *X = r[1] ? OA : A + r[2] + (size_t)r[3] * lda;
+            const double *Y = r[4] ? OB : B + r[5] + (size_t)r[6] * ldb;
+            inner_plan(r, ci, in);
+            rc = run_plan(in.data(), in.size() / STRASSEN_REC, alpha * (double)r[12], X, r[1] ? (size_t)r[7] : lda, Y, r[4] ? (size_t)r[8] : ldb,
+                          1.0, C + r[10] + (size_t)r[11] * ldc, ldc, alpha * (double)r[15], r[15] ? C + r[13] + (size_t)r[14] * ldc : nullptr, ldc,
+                          SA, SB, st);
+        } else {
+            rc = run_plan(r, 1, alpha, A, lda, B, ldb, beta, C, ldc, 0.0, nullptr, 0, SA, SB, st);
         }
         if (rc) return rc;
     }
@@ -582,21 +791,54 @@ int strassen_plan(int m, int n, int k, int lower, long smin, long kslab, size_t 
     return 0;
 }
 
-size_t strassen_scratch_doubles(int m, int n, int k, int lower)
+namespace {
+Plan2Cfg cfg2_of(long smin, long kslab, long smin2, long kslab2, size_t scratch_doubles)
+{
+    Plan2Cfg c = default_cfg2();
+    if (smin >= 0) c.in.smin = std::max(128L, smin);
+    if (kslab >= 0) c.in.kslab = std::max(32L, kslab);
+    if (smin2 >= 0) c.smin2 = std::max(256L, smin2);
+    if (kslab2 >= 0) c.kslab2 = std::max(64L, kslab2);
+    c.scratch = scratch_doubles;
+    return c;
+}
+}  // namespace
+
+// ... and the list with the outer level around it (smin2 / kslab2 < 0 = the built-in values or tunables)
+int strassen_outer_plan(int m, int n, int k, int lower, long smin, long kslab, long smin2, long kslab2, size_t scratch_doubles,
+                   std::vector<long long> &out)
+{
+    if (m < 0 || n < 0 || k < 0 || (lower && m != n)) { set_error("strassen_outer_plan: bad extents"); return SGPR_E_ARG; }
+    const Plan2Cfg c = cfg2_of(smin, kslab, smin2, kslab2, scratch_doubles);
+    out.clear();
+    if (lower) plan2_syrk(n, k, 0, c, out);
+    else       plan2_gemm(m, n, k, 0, 0, 0, 0, c, out);
+    return 0;
+}
+
+// scratch of one call: levels = 1 the inner pair alone, 2 both pairs (as far as SGPR_GEMM_STRASSEN allows)
+size_t strassen_scratch_doubles(int m, int n, int k, int lower, int levels)
 {
     std::vector<long long> plan;
-    if (!strassen_on() || strassen_plan(m, n, k, lower, -1, -1, ~(size_t)0, plan)) return 0;
+    if (!strassen_on()) return 0;
+    if (levels >= 2 && strassen_levels() >= 2) {
+        if (strassen_outer_plan(m, n, k, lower, -1, -1, -1, -1, ~(size_t)0, plan)) return 0;
+        return plan2_need(plan, default_cfg2()).total();
+    }
+    if (strassen_plan(m, n, k, lower, -1, -1, ~(size_t)0, plan)) return 0;
     return plan_need(plan);
 }
 
-// make room for calls that need up to `doubles` of scratch on st's device (potrf: once, before the first product)
-void strassen_reserve(size_t doubles, hipStream_t st)
+// make room for calls that need up to `both` doubles of scratch on st's device (potrf: once, before the first product);
+// if that much cannot be had, `one` (what one level needs): the outer level is then skipped call by call
+void strassen_reserve(size_t both, size_t one, hipStream_t st)
 {
     const int dev = device_of(st);
-    if (!doubles || dev < 0 || !strassen_on()) return;
+    if (dev < 0 || !strassen_on()) return;
     Scratch &s = g_scratch[dev];
     std::lock_guard<std::mutex> lock(s.mu);
-    (void)scratch_ensure(s, doubles);
+    if (both > one && !outer_noscratch() && scratch_ensure(s, both)) return;
+    if (one) (void)scratch_ensure(s, one);
 }
 
 int strassen_trim()
@@ -611,8 +853,9 @@ int strassen_trim()
     return 0;
 }
 
-// C = beta C + alpha A B^T (lower: on and below the diagonal of a square C only) through the plan above.  Whatever does
-// not qualify -- sizes, alignment, beta != 1, no scratch, SGPR_GEMM_STRASSEN=0 -- is the classical launch, bit for bit.
+// C = beta C + alpha A B^T (lower: on and below the diagonal of a square C only) through the plans above.  Whatever does
+// not qualify -- sizes, alignment, beta != 1, no scratch, SGPR_GEMM_STRASSEN=0 -- is the classical launch, bit for bit;
+// without room for the outer pair (or with SGPR_GEMM_STRASSEN=1) the call is the one-level call, bit for bit.
 int gemm_nt_strassen(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb, double beta,
                      double *C, size_t ldc, int lower, hipStream_t st)
 {
@@ -621,11 +864,33 @@ int gemm_nt_strassen(int m, int n, int k, double alpha, const double *A, size_t 
     if (std::min(m, n) / 2 < default_cfg().smin || !strassen_on() || !aligned || beta != 1.0 || (lower && m != n))
         return gemm_nt(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, lower, 0, st);
     std::vector<long long> plan;
-    int rc = strassen_plan(m, n, k, lower, -1, -1, ~(size_t)0, plan);
+    int rc = 0;
+    const int dev = device_of(st);
+    auto enqueue = [&](Scratch &s, auto &&run) {
+        if (!s.ev) SGPR_HIP(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+        if (s.used && s.last != st) SGPR_HIP(hipStreamWaitEvent(st, s.ev, 0));
+        const int r = run();
+        SGPR_HIP(hipEventRecord(s.ev, st));
+        s.last = st;
+        s.used = true;
+        return r;
+    };
+    // both levels, where a product is large enough for the outer one and its scratch can be had
+    const Plan2Cfg c2 = default_cfg2();
+    if (strassen_levels() >= 2 && dev >= 0 && !outer_noscratch() && std::min(lower ? m / 2 : m, lower ? n / 2 : n) / 2 >= c2.smin2) {
+        if ((rc = strassen_outer_plan(m, n, k, lower, -1, -1, -1, -1, ~(size_t)0, plan))) return rc;
+        const Need2 nd = plan2_need(plan, c2);
+        if (nd.v[2] + nd.v[3]) {
+            Scratch &s = g_scratch[dev];
+            std::lock_guard<std::mutex> lock(s.mu);
+            if (scratch_ensure(s, nd.total()))
+                return enqueue(s, [&] { return run_plan2(plan, c2, nd, alpha, A, lda, B, ldb, beta, C, ldc, s.p, st); });
+        }
+    }
+    rc = strassen_plan(m, n, k, lower, -1, -1, ~(size_t)0, plan);
     if (rc) return rc;
     const size_t need = plan_need(plan);
     if (!need) return run_plan(plan, alpha, A, lda, B, ldb, beta, C, ldc, nullptr, nullptr, st);
-    const int dev = device_of(st);
     if (dev < 0) return gemm_nt(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, lower, 0, st);
     Scratch &s = g_scratch[dev];
     std::lock_guard<std::mutex> lock(s.mu);
@@ -634,16 +899,10 @@ int gemm_nt_strassen(int m, int n, int k, double alpha, const double *A, size_t 
         if ((rc = strassen_plan(m, n, k, lower, -1, -1, s.cap, plan))) return rc;
         if (!plan_need(plan)) return run_plan(plan, alpha, A, lda, B, ldb, beta, C, ldc, nullptr, nullptr, st);
     }
-    if (!s.ev) SGPR_HIP(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-    if (s.used && s.last != st) SGPR_HIP(hipStreamWaitEvent(st, s.ev, 0));
     size_t na = 0;
     for (size_t i = 0; i + STRASSEN_REC <= plan.size(); i += STRASSEN_REC)
         if (plan[i] == PLAN_SUM && plan[i + 1] == 0) na = std::max(na, (size_t)plan[i + 2] * (size_t)plan[i + 3]);
-    rc = run_plan(plan, alpha, A, lda, B, ldb, beta, C, ldc, s.p, s.p + na, st);
-    SGPR_HIP(hipEventRecord(s.ev, st));
-    s.last = st;
-    s.used = true;
-    return rc;
+    return enqueue(s, [&] { return run_plan(plan, alpha, A, lda, B, ldb, beta, C, ldc, s.p, s.p + na, st); });
 }
 
 }  // namespace sgpr

@@ -48,6 +48,15 @@ struct GemmArgs {
     double *C2;
     size_t ldc2;
     double alpha2;
+    // further destinations (gemm_nt4_kernel only, two Strassen levels): ndst destinations in all (2 .. 4), C3 += alpha3 * A B^T,
+    // C4 += alpha4 * A B^T.  Appended, so that the fields above keep their kernarg offsets.
+    double *C3;
+    size_t ldc3;
+    double alpha3;
+    double *C4;
+    size_t ldc4;
+    double alpha4;
+    int ndst;
 };
 
 // Workgroup -> tile map.  The dispatcher deals consecutive workgroup ids round-robin over the 8
@@ -202,7 +211,7 @@ __device__ __forceinline__ void store_pass(double *S, int tid, const double2_t &
     *reinterpret_cast<double2_t *>(S + kc * (BR + PAD) + r) = v;
 }
 
-template <int BM, int BN, bool FAST, bool TRANSB = false, bool TWO = false>
+template <int BM, int BN, bool FAST, bool TRANSB = false, bool TWO = false, bool FOUR = false>
 __device__ __forceinline__ void gemm_body(const GemmArgs &g, double *smem, int tile_r, int tile_c)
 {
     constexpr int WGM = BM / 64, WGN = BN / 64;
@@ -390,6 +399,38 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, double *smem, int t
             __builtin_amdgcn_sched_barrier(0);
         }
     }
+    // up to three further destinations (gemm_nt4_kernel): C_d += alpha_d * (the same accumulators), one after the other
+    if constexpr (FOUR) {
+        auto extra = [&](double *Cd, size_t ldd, double ad) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                double old[4][4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int n = col0 + wn * 64 + i * 16 + 4 * r + l4;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int m = row0 + wm * 64 + j * 16 + l15;
+                        old[r][j] = (interior || (m < g.m && n < g.n)) ? Cd[(size_t)m + (size_t)n * ldd] : 0.0;
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int n = col0 + wn * 64 + i * 16 + 4 * r + l4;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int m = row0 + wm * 64 + j * 16 + l15;
+                        if (interior || (m < g.m && n < g.n)) Cd[(size_t)m + (size_t)n * ldd] = __builtin_fma(ad, acc[i][j][r], old[r][j]);
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        };
+        extra(g.C2, g.ldc2, g.alpha2);
+        if (g.ndst > 2) extra(g.C3, g.ldc3, g.alpha3);
+        if (g.ndst > 3) extra(g.C4, g.ldc4, g.alpha4);
+    }
 }
 
 // ---- fast path: LDS-DMA staging + counted LDS waits -------------------------------------------
@@ -426,7 +467,7 @@ __device__ __forceinline__ void read_frags(unsigned aA, unsigned aB, double (&fa
 }
 #define SGPR_LGKM_WAIT(n) do { asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory"); __builtin_amdgcn_sched_barrier(0); } while (0)
 
-template <int BM, int BN, int STAGES, bool TWO = false>
+template <int BM, int BN, int STAGES, bool TWO = false, bool FOUR = false>
 __device__ __forceinline__ void gemm_body_dma(const GemmArgs &g, double *smem, int tile_r, int tile_c)
 {
     constexpr int WGM = BM / 64, WGN = BN / 64;
@@ -650,6 +691,37 @@ __device__ __forceinline__ void gemm_body_dma(const GemmArgs &g, double *smem, i
                     cbase2[(size_t)(j * 16) + (size_t)(i * 16 + 4 * r) * g.ldc2] = __builtin_fma(alpha2, acc[i][j][r], old[i & 1][r][j]);
             __builtin_amdgcn_sched_barrier(0);
         }
+    }
+    // up to three further destinations (gemm_nt4_kernel, two Strassen levels): C_d += alpha_d * (the same accumulators), one
+    // destination after the other, each with the pipelined fetch of the second epilogue above
+    if constexpr (FOUR) {
+        auto extra = [&](double *Cd, size_t ldd, double ad) {
+            double *const cb = Cd + (size_t)(row0 + wm * 64 + l15) + (size_t)(col0 + wn * 64 + l4) * ldd;
+            auto fetchd = [&](int i, double (&o)[4][4]) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) o[r][j] = cb[(size_t)(j * 16) + (size_t)(i * 16 + 4 * r) * ldd];
+            };
+            fetchd(0, old[0]);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if (i + 1 < 4) fetchd(i + 1, old[(i + 1) & 1]);
+                __builtin_amdgcn_sched_barrier(0);
+                if (i + 1 < 4) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+                else           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        cb[(size_t)(j * 16) + (size_t)(i * 16 + 4 * r) * ldd] = __builtin_fma(ad, acc[i][j][r], old[i & 1][r][j]);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        };
+        extra(g.C2, g.ldc2, g.alpha2);
+        if (g.ndst > 2) extra(g.C3, g.ldc3, g.alpha3);
+        if (g.ndst > 3) extra(g.C4, g.ldc4, g.alpha4);
     }
 }
 

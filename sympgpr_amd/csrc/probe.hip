@@ -549,6 +549,23 @@ extern "C" int sgpr_probe_gemm_nt2_dev(int m, int n, int k, double alpha, const 
 {
     return gemm_nt_two(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, alpha2, C2, ldc2, static_cast<hipStream_t>(stream));
 }
+// ---- the outer Strassen level: its list, and the product with up to four destinations
+extern "C" int sgpr_probe_strassen2_plan(int m, int n, int k, int lower, long smin, long kslab, long smin2, long kslab2,
+                                         long scratch_doubles, long long *out, int max_records, int *count)
+{
+    if (!count || scratch_doubles < 0) { set_error("probe_strassen2_plan: bad arguments"); return SGPR_E_ARG; }
+    std::vector<long long> plan;
+    const int rc = strassen_outer_plan(m, n, k, lower, smin, kslab, smin2, kslab2, (size_t)scratch_doubles, plan);
+    if (rc) return rc;
+    *count = (int)(plan.size() / STRASSEN_REC);
+    for (size_t i = 0; out && i < plan.size() && (int)(i / STRASSEN_REC) < max_records; ++i) out[i] = plan[i];
+    return 0;
+}
+extern "C" int sgpr_probe_gemm_nt4_dev(int m, int n, int k, const double *A, size_t lda, const double *B, size_t ldb, double beta,
+                                       int count, double *const *C, const size_t *ldc, const double *alpha, void *stream)
+{
+    return gemm_nt_multi(m, n, k, A, lda, B, ldb, beta, count, C, ldc, alpha, static_cast<hipStream_t>(stream));
+}
 extern "C" unsigned sgpr_probe_map_calls(void) { return applymap_last_calls(); }
 extern "C" int sgpr_probe_map_team(int ntest, int n0) { return applymap_team(ntest, n0); }
 extern "C" int sgpr_probe_trsm_piece(int ticket, int cap, int strips, int out[5]) { if (ticket < 0 || cap < 1 || strips < 0 || !out) return SGPR_E_ARG; trsm_piece_of(ticket, cap, strips, out); return 0; }
