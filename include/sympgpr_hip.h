@@ -417,6 +417,32 @@ int sgpr_fit_applymap_nd(sgpr_fit_t f, int mode, int nm, int ntest, const double
 int sgpr_applymap_nd_host(int family, int d, int mode, int nm, int ntest, const double *hyp, int nhyp, int n0,
                           const double *X, size_t ldx, const double *alpha, const double *Q0, size_t ldq,
                           const double *P0, size_t ldp, double *qmap, double *pmap, int *iters);
+/* The d-pair map WITH ITS TANGENT MAP: the same orbits -- qmap, pmap and iters are bit-identical to sgpr_fit_applymap_nd /
+ * sgpr_applymap_nd_host, whose arguments and checks these entries share -- and the derivative of every step.  After each
+ * accepted step one more pass over the training points sums the Hessian H = dG/dx of the generating function at (q, P), one sum
+ * per unordered pair of coordinates (H is symmetric by construction); with A = H_qq, B = H_qP, C = H_PP and T = (I + B)^-1 (d x d,
+ * closed form) the Jacobian of the step (q, p) -> (Q, P) is
+ *     M = [ I + B^T - C T A    C T ]      rows (Q_1..Q_d, P_1..P_d), columns (q_1..q_d, p_1..p_d),
+ *         [      - T A          T  ]
+ * symplectic (M^T J M = J) for any symmetric A and C; wrapping q does not change it.
+ * jac  (may be NULL): [nm-1][ntest][2d][2d] doubles, C order: M of every step.
+ * mono (may be NULL): [ntest][2d][2d] = M_{nm-1} ... M_1, the identity for nm = 1 (linear stability of a periodic orbit: Greene's
+ *      residue (2 - tr mono) / 4 at d = 1).
+ * lyap (may be NULL): [ntest][2d] finite-time Lyapunov exponents by Benettin's method: Z = M Qmat, modified Gram-Schmidt on the
+ *      columns of Z in column order, log |r_cc| summed per column, divided by nm - 1 (per step of the map, Gram-Schmidt order).
+ * From the step at which an orbit is lost its jac rows are NaN, and so are its mono and lyap; so is the jac row of a step whose
+ * I + B is singular, with mono and lyap (the orbit itself goes on).  An orbit's outputs depend on nothing but its own start point.
+ * SGPR_MAP_EXPLICIT is accepted for the sum kernels only (family B, or a USER sum kernel: B = 0, A depends on q and C on P
+ * only); with a product family it is SGPR_E_ARG here, as is lyap != NULL with nm < 2.  Everything else as for the plain
+ * entries: the same SGPR_E_ARG checks before any device call, SGPR_E_STATE in the same cases, ntest == 0 returns 0.
+ * Added in ABI 5 (additional entry points). */
+int sgpr_fit_applymap_nd_tangent(sgpr_fit_t f, int mode, int nm, int ntest, const double *Q0, size_t ldq,
+                                 const double *P0, size_t ldp, double *qmap, double *pmap, int *iters,
+                                 double *jac, double *mono, double *lyap);
+int sgpr_applymap_nd_tangent_host(int family, int d, int mode, int nm, int ntest, const double *hyp, int nhyp, int n0,
+                                  const double *X, size_t ldx, const double *alpha, const double *Q0, size_t ldq,
+                                  const double *P0, size_t ldp, double *qmap, double *pmap, int *iters,
+                                  double *jac, double *mono, double *lyap);
 /* alpha-solve on device with the factor and its leaf inverses: b (n) := L^-T L^-1 b */
 int sgpr_potrs_vec_dev(int n, const double *L, size_t ldl, void *work, double *b,
                        void *stream);

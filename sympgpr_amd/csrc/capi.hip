@@ -366,6 +366,32 @@ int sgpr_applymap_nd_host(int family, int d, int mode, int nm, int ntest, const 
                           qmap, pmap, iters, st);
 }
 
+/* The same with the tangent map (maptan.h): the orbit outputs have the bits of sgpr_applymap_nd_host. */
+int sgpr_applymap_nd_tangent_host(int family, int d, int mode, int nm, int ntest, const double *hyp, int nhyp, int n0,
+                                  const double *X, size_t ldx, const double *alpha, const double *Q0, size_t ldq, const double *P0,
+                                  size_t ldp, double *qmap, double *pmap, int *iters, double *jac, double *mono, double *lyap)
+{
+    const char *me = "applymap_nd_tangent_host";
+    int rc = applymap_nd_kernel_check(me, family, d, hyp, nhyp);
+    if (rc || (rc = applymap_nd_call_check(me, mode, nm, ntest, Q0, ldq, P0, ldp, qmap, pmap)) ||
+        (rc = applymap_nd_tangent_check(me, family, mode, nm, lyap)))
+        return rc;
+    if (n0 < 0 || (n0 > 0 && (!X || !alpha || ldx < (size_t)n0))) {
+        set_error("applymap_nd_tangent_host: n0 < 0, null X or alpha, or ldx < n0");
+        return SGPR_E_ARG;
+    }
+    if ((rc = need_device())) return rc;
+    if (ntest == 0) return 0;
+    DevBuf dX, dal;
+    hipStream_t st = nullptr;
+    const int D = 2 * d;
+    if ((rc = dX.alloc((size_t)n0 * D * sizeof(double))) || (rc = upload(dal, alpha, (size_t)D * n0, st))) return rc;
+    if (n0 > 0 && (rc = copy_in(dX.p, (size_t)n0, X, ldx, (size_t)n0, D, st))) return rc;
+    const MapTangentOut tan = {jac, mono, lyap};
+    return applymap_nd_io(family, d, mode, nm, ntest, n0, dX.as<double>(), (size_t)n0, hyp, nhyp, dal.as<double>(), Q0, ldq, P0, ldp,
+                          qmap, pmap, iters, st, &tan);
+}
+
 int sgpr_release_device_streams(int device)
 {
     return release_device_streams(device);      // (touches the device only if this library has streams on it)

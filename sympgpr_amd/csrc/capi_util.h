@@ -103,24 +103,55 @@ inline int applymap_nd_kernel_check(const char *entry, int family, int d, const 
     return 0;
 }
 
-// uploads the start points, runs applymap_nd on device-resident training points and alpha, brings the orbits back and waits
+// ... and what the two tangent entries (sgpr_fit_applymap_nd_tangent, sgpr_applymap_nd_tangent_host) ask on top of it
+inline int applymap_nd_tangent_check(const char *entry, int family, int mode, int nm, const double *lyap)
+{
+    auto E = [&](const char *what) { set_error(std::string(entry) + ": " + what); return SGPR_E_ARG; };
+    if ((mode & SGPR_MAP_EXPLICIT) && !family_is_sum(family))
+        return E("SGPR_MAP_EXPLICIT has a tangent map for the sum kernels only (family B, or a USER sum kernel)");
+    if (lyap && nm < 2) return E("lyap needs nm >= 2");
+    return 0;
+}
+
+// the host arrays a tangent entry fills, each or null: jac [nm - 1][ntest][2d][2d], mono [ntest][2d][2d], lyap [ntest][2d]
+struct MapTangentOut {
+    double *jac, *mono, *lyap;
+};
+
+// uploads the start points, runs applymap_nd on device-resident training points and alpha, brings the orbits back and waits;
+// with `tan` the launch is applymap_nd_tangent and its outputs come back too
 inline int applymap_nd_io(int family, int d, int mode, int nm, int ntest, int n0, const double *dXtr, size_t ldxtr,
                           const double *hyp, int nhyp, const double *dalpha, const double *Q0, size_t ldq, const double *P0,
-                          size_t ldp, double *qmap, double *pmap, int *iters, hipStream_t st)
+                          size_t ldp, double *qmap, double *pmap, int *iters, hipStream_t st, const MapTangentOut *tan = nullptr)
 {
     int rc;
-    DevBuf q0, p0, qm, pm, it;
+    DevBuf q0, p0, qm, pm, it, dj, dm, dl;
     const size_t nt = (size_t)ntest, out_bytes = (size_t)nm * nt * d * sizeof(double), it_bytes = (size_t)(nm - 1) * nt * sizeof(int);
+    const size_t DD = (size_t)4 * d * d, mono_bytes = nt * DD * sizeof(double), jac_bytes = (size_t)(nm - 1) * mono_bytes;
+    const size_t lyap_bytes = nt * 2 * d * sizeof(double);
     if ((rc = q0.alloc(nt * d * sizeof(double))) || (rc = p0.alloc(nt * d * sizeof(double))) || (rc = qm.alloc(out_bytes)) ||
         (rc = pm.alloc(out_bytes)) || (iters && (rc = it.alloc(it_bytes))))
         return rc;
-    if ((rc = copy_in(q0.p, nt, Q0, ldq, nt, d, st)) || (rc = copy_in(p0.p, nt, P0, ldp, nt, d, st))) return rc;
-    if ((rc = applymap_nd(family, d, mode, nm, ntest, n0, dXtr, ldxtr, hyp, nhyp, dalpha, q0.as<double>(), p0.as<double>(),
-                          qm.as<double>(), pm.as<double>(), iters ? it.as<int>() : nullptr, st)))
+    if (tan && ((tan->jac && (rc = dj.alloc(jac_bytes))) || (tan->mono && (rc = dm.alloc(mono_bytes))) ||
+                (tan->lyap && (rc = dl.alloc(lyap_bytes)))))
         return rc;
+    if ((rc = copy_in(q0.p, nt, Q0, ldq, nt, d, st)) || (rc = copy_in(p0.p, nt, P0, ldp, nt, d, st))) return rc;
+    if (!tan)
+        rc = applymap_nd(family, d, mode, nm, ntest, n0, dXtr, ldxtr, hyp, nhyp, dalpha, q0.as<double>(), p0.as<double>(),
+                         qm.as<double>(), pm.as<double>(), iters ? it.as<int>() : nullptr, st);
+    else
+        rc = applymap_nd_tangent(family, d, mode, nm, ntest, n0, dXtr, ldxtr, hyp, nhyp, dalpha, q0.as<double>(), p0.as<double>(),
+                                 qm.as<double>(), pm.as<double>(), iters ? it.as<int>() : nullptr, dj.as<double>(),
+                                 dm.as<double>(), dl.as<double>(), st);
+    if (rc) return rc;
     SGPR_HIP(hipMemcpyAsync(qmap, qm.p, out_bytes, hipMemcpyDeviceToHost, st));
     SGPR_HIP(hipMemcpyAsync(pmap, pm.p, out_bytes, hipMemcpyDeviceToHost, st));
     if (iters && it_bytes) SGPR_HIP(hipMemcpyAsync(iters, it.p, it_bytes, hipMemcpyDeviceToHost, st));
+    if (tan) {
+        if (tan->jac && jac_bytes) SGPR_HIP(hipMemcpyAsync(tan->jac, dj.p, jac_bytes, hipMemcpyDeviceToHost, st));
+        if (tan->mono) SGPR_HIP(hipMemcpyAsync(tan->mono, dm.p, mono_bytes, hipMemcpyDeviceToHost, st));
+        if (tan->lyap) SGPR_HIP(hipMemcpyAsync(tan->lyap, dl.p, lyap_bytes, hipMemcpyDeviceToHost, st));
+    }
     SGPR_HIP(hipStreamSynchronize(st));
     return 0;
 }

@@ -79,6 +79,11 @@ int predict_nd(int family, int d, int m, const double *Xt, size_t ldxt, int n0, 
 int applymap_nd(int family, int d, int mode, int nm, int ntest, int n0, const double *Xtr, size_t ldxtr, const double *hyp,
                 int nhyp, const double *alpha, const double *Q0, const double *P0, double *qmap, double *pmap, int *iters,
                 hipStream_t st);
+// the same with the tangent map (maptan.h): jac [nm - 1][ntest][2d][2d], mono [ntest][2d][2d], lyap [ntest][2d], each or null
+int applymap_nd_tangent(int family, int d, int mode, int nm, int ntest, int n0, const double *Xtr, size_t ldxtr, const double *hyp,
+                        int nhyp, const double *alpha, const double *Q0, const double *P0, double *qmap, double *pmap, int *iters,
+                        double *jac, double *mono, double *lyap, hipStream_t st);
+bool family_is_sum(int family);   // k = sum of the factors (family B, or a USER sum kernel): the explicit maps
 
 // ---- gemm_f64.hip : C = beta C + alpha A B^T on fp64 MFMA tiles
 int gemm_nt(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B,

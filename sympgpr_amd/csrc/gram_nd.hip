@@ -10,6 +10,7 @@
 // stored as (2d)^2 blocks of N x N0, block (a, b) at rows a*N, columns b*N0.  d = 1 is build_K
 // (sympgpr.f90:12-38) entry for entry.  One exp and d sincos per PAIR feed all (2d)^2 entries:
 // 32 d^2 bytes written per pair, so the kernel is even more firmly HBM-write bound than d = 1.
+#include <type_traits>
 #include "common.h"
 #include "devmath.h"
 #include "generated/pair_generated.h"
@@ -365,15 +366,20 @@ __device__ __forceinline__ bool newton_step(const double (&J)[d * d], const doub
     return ok;
 }
 
+#include "maptan.h"   // the tangent map: what TAN = true adds to the kernel below
+
 // One workgroup per orbit runs all nm steps; nothing waits on another workgroup, and an orbit's bits depend on nothing but its
 // own start point (TT is chosen from n0 alone).  TT = 256: the training points and alpha are staged in LDS once when they fit
 // (every thread reads back what it wrote itself: no barrier); TT = 512 reads them from memory (L2) on every pass.  512, not 1024:
 // the D = 6 passes hold 150 - 196 VGPRs, and a 1024-thread workgroup leaves 128 per thread -- the compiler spilled up to 86 of
 // them to scratch there; at 512 threads (256 VGPRs each) no instance spills.
-template <int FAM, int D, int TT>
-__global__ __launch_bounds__(TT) void applymap_nd_kernel(const MapNdArgs a)
+// TAN: after every accepted step one more pass (maptan.h) sums the Hessian of the generating function at (q, P); the step's
+// Jacobian M, the product of the M's and the Benettin sums follow from it.  The orbit itself takes the same passes in the same
+// order as without TAN and has the same bits.  A lost orbit's M is NaN from that step on, and with it mono and the exponents.
+template <int FAM, int D, int TT, bool TAN = false>
+__global__ __launch_bounds__(TT) void applymap_nd_kernel(const std::conditional_t<TAN, MapNdTanArgs, MapNdArgs> a)
 {
-    constexpr int d = D / 2, W = TT / 64, NSMAX = D + d * d;
+    constexpr int d = D / 2, W = TT / 64, NSMAX = TAN ? maptan_max_sums<FAM, D, TT>() : D + d * d;
     constexpr bool HAS_STAGE = TT == MAPND_T_SMALL;
     __shared__ double part[2][W * NSMAX];
     __shared__ double res[2][NSMAX];
@@ -403,6 +409,7 @@ __global__ __launch_bounds__(TT) void applymap_nd_kernel(const MapNdArgs a)
     }
     const double nan = __builtin_nan("");
     const double twopi = 6.283185307179586477;
+    if constexpr (TAN) maptan_init<D>();
     for (int i = 0; i + 1 < a.nm; ++i) {
         bool good = true;                                   // block-uniform, like everything below
 #pragma unroll
@@ -469,7 +476,23 @@ __global__ __launch_bounds__(TT) void applymap_nd_kernel(const MapNdArgs a)
             for (int c = 0; c < d; ++c) { a.qmap[o + c] = q[c]; a.pmap[o + c] = p[c]; }
             if (a.iters) a.iters[(size_t)i * a.ntest + k] = good ? its : -1;
         }
+        if constexpr (TAN) {                                // x is still (q, P) of the accepted step
+            double M[D * D];
+            bool tan_ok = false;
+            if (good) {
+                double H[D * (D + 1) / 2];
+                maptan_hessian<FAM, D, TT>(a, x, stg, H, &part[0][0], &res[0][0], W * NSMAX, NSMAX, seq);
+                tan_ok = maptan_matrix<D>(H, M);
+            }
+            if (!tan_ok) {
+#pragma unroll
+                for (int s = 0; s < D * D; ++s) M[s] = nan;
+            }
+            maptan_publish<D>(M, a.jac ? a.jac + ((size_t)i * a.ntest + k) * (D * D) : nullptr);
+            maptan_advance<D>();
+        }
     }
+    if constexpr (TAN) maptan_finish<D>(a, k);
 }
 
 }  // namespace
@@ -562,5 +585,31 @@ int applymap_nd(int family, int d, int mode, int nm, int ntest, int n0, const do
         return 0;
     });
 }
+
+// the same launch with the tangent map: jac ([nm - 1][ntest][D][D]), mono ([ntest][D][D]), lyap ([ntest][D]), each device-resident
+// or null.  The orbit outputs have the bits of applymap_nd.
+int applymap_nd_tangent(int family, int d, int mode, int nm, int ntest, int n0, const double *Xtr, size_t ldxtr, const double *hyp,
+                        int nhyp, const double *alpha, const double *Q0, const double *P0, double *qmap, double *pmap, int *iters,
+                        double *jac, double *mono, double *lyap, hipStream_t st)
+{
+    MapNdTanArgs a{};
+    int rc = fill_args(family, d, hyp, nhyp, a.k);
+    if (rc) return rc;
+    if (nm <= 0 || ntest <= 0) return 0;
+    a.k.mj = n0; a.k.Xa = Xtr; a.k.ldxa = ldxtr;
+    a.nm = nm; a.ntest = ntest; a.mode = mode; a.maxiter = 60; a.tol = 1e-13;   // as applymap_nd
+    a.alpha = alpha; a.Q0 = Q0; a.P0 = P0; a.qmap = qmap; a.pmap = pmap; a.iters = iters;
+    a.jac = jac; a.mono = mono; a.lyap = lyap;
+    const bool small = applymap_nd_threads(n0) == MAPND_T_SMALL;
+    return dispatch_nd(family, d, [&](auto fam, auto dd) {
+        constexpr int F = decltype(fam)::value, D = decltype(dd)::value;
+        if (small) hipLaunchKernelGGL((applymap_nd_kernel<F, D, MAPND_T_SMALL, true>), dim3(ntest), dim3(MAPND_T_SMALL), 0, st, a);
+        else       hipLaunchKernelGGL((applymap_nd_kernel<F, D, MAPND_T_LARGE, true>), dim3(ntest), dim3(MAPND_T_LARGE), 0, st, a);
+        SGPR_CHECK_LAUNCH();
+        return 0;
+    });
+}
+
+bool family_is_sum(int family) { return family == SGPR_FAM_B || (family == SGPR_FAM_USER && gen::user_is_sum); }
 
 }  // namespace sgpr

@@ -117,6 +117,23 @@ class SympFit:
                 "sgpr_fit_applymap_nd")
         return (qmap, pmap, iters) if return_iters else (qmap, pmap)
 
+    def applymap_pairs_tangent(self, nm, Q0, P0, wrap_q=False, explicit=False, jac=True, mono=True, lyap=True):
+        """applymap_pairs with the tangent map -> (qmap, pmap, iters, out): the same orbits bit for bit, and in the dict `out`
+        the requested arrays jac (nm - 1, Ntest, D, D), mono (Ntest, D, D), lyap (Ntest, D) with D = 2 d -- see
+        maps.run_map_nd_tangent; maps.symplectic_defect and maps.greene_residue (d = 1) read them.  explicit: sum kernels only."""
+        from . import maps
+        Q0, P0 = maps.start_points_nd(Q0, P0, self.d)
+        Ntest = Q0.shape[0]
+        nm, qmap, pmap, iters = maps.map_outputs_nd(nm, Ntest, self.d)
+        out = maps.tangent_outputs_nd(nm, Ntest, self.d, jac, mono, lyap)
+        mode = (maps.WRAP_Q if wrap_q else 0) | (maps.EXPLICIT if explicit else 0)
+        opt = lambda name: L.dptr(out[name]) if name in out else None
+        L.check(self._lib.sgpr_fit_applymap_nd_tangent(self._h, mode, nm, Ntest, L.dptr(Q0), max(Ntest, 1), L.dptr(P0),
+                                                       max(Ntest, 1), L.dptr(qmap), L.dptr(pmap),
+                                                       iters.ctypes.data_as(C.POINTER(C.c_int)), opt("jac"), opt("mono"),
+                                                       opt("lyap")), "sgpr_fit_applymap_nd_tangent")
+        return qmap, pmap, iters, out
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             self._lib.sgpr_fit_destroy(self._h)

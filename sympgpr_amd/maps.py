@@ -11,6 +11,8 @@ One recurrence, the variants the reference's drivers carry in their own func.py 
 
 For fits with d canonical pairs (d = 1, 2, 3) the map is run_map_nd / SympFit.applymap_pairs: Newton with the analytic
 Jacobian on the d unknowns P, one workgroup per orbit (include/sympgpr_hip.h: sgpr_applymap_nd_host).
+run_map_nd_tangent / SympFit.applymap_pairs_tangent return the same orbits with the Jacobian of every step, their product and
+finite-time Lyapunov exponents (sgpr_applymap_nd_tangent_host); symplectic_defect and greene_residue read them.
 
 alpha = Kyinv ztrain is formed once (the reference re-multiplies Kyinv inside every calcP / calcQ
 call); a residual of the implicit equation is one block-wide reduction over the training points.
@@ -129,3 +131,76 @@ def run_map_nd(family, d, mode, nm, hyp, X, alpha, Q0, P0, return_iters=False):
                                       L.dptr(alpha), L.dptr(Q0), max(Ntest, 1), L.dptr(P0), max(Ntest, 1), L.dptr(qmap),
                                       L.dptr(pmap), iters.ctypes.data_as(C.POINTER(C.c_int))), "sgpr_applymap_nd_host")
     return (qmap, pmap, iters) if return_iters else (qmap, pmap)
+
+
+def _nd_inputs(d, X, alpha, hyp):
+    d = int(d)
+    if d not in (1, 2, 3):
+        raise ValueError("d must be 1, 2 or 3")
+    X = np.asfortranarray(X, dtype=np.float64)
+    if X.ndim != 2 or X.shape[1] != 2 * d:
+        raise ValueError("X must be (N0, %d)" % (2 * d))
+    alpha, hyp = L.f64(alpha), L.f64(hyp)
+    if alpha.shape != (2 * d * X.shape[0],):
+        raise ValueError("alpha must have length 2 d N0 = %d" % (2 * d * X.shape[0]))
+    return d, X, alpha, hyp
+
+
+def tangent_outputs_nd(nm, Ntest, d, jac=True, mono=True, lyap=True):
+    """the arrays a tangent entry fills, by name, for those that are wanted"""
+    D = 2 * d
+    out = {}
+    if jac:
+        out["jac"] = np.zeros((nm - 1, Ntest, D, D))
+    if mono:
+        out["mono"] = np.zeros((Ntest, D, D))
+    if lyap:
+        if nm < 2:
+            raise ValueError("lyap needs nm >= 2")
+        out["lyap"] = np.zeros((Ntest, D))
+    return out
+
+
+def _optr(out, name):
+    return L.dptr(out[name]) if name in out else None
+
+
+def run_map_nd_tangent(family, d, mode, nm, hyp, X, alpha, Q0, P0, jac=True, mono=True, lyap=True):
+    """run_map_nd with the tangent map: -> (qmap, pmap, iters, out).  qmap, pmap, iters have the bits of run_map_nd; `out` is a
+    dict of the requested arrays: jac (nm - 1, Ntest, D, D), the Jacobian M of every step with rows (Q_1..Q_d, P_1..P_d) and
+    columns (q_1..q_d, p_1..p_d), D = 2 d; mono (Ntest, D, D) = M_{nm-1} ... M_1; lyap (Ntest, D), finite-time Lyapunov exponents
+    per step of the map by Benettin's method, in Gram-Schmidt column order.  All NaN from the step at which an orbit is lost.
+    EXPLICIT is accepted for the sum kernels only (family B)."""
+    lib = L.load_library()
+    d, X, alpha, hyp = _nd_inputs(d, X, alpha, hyp)
+    N0 = X.shape[0]
+    mode = map_mode_nd(mode)
+    Q0, P0 = start_points_nd(Q0, P0, d)
+    Ntest = Q0.shape[0]
+    nm, qmap, pmap, iters = map_outputs_nd(nm, Ntest, d)
+    out = tangent_outputs_nd(nm, Ntest, d, jac, mono, lyap)
+    L.check(lib.sgpr_applymap_nd_tangent_host(L.family_id(family), d, mode, nm, Ntest, L.dptr(hyp), len(hyp), N0, L.dptr(X),
+                                              max(N0, 1), L.dptr(alpha), L.dptr(Q0), max(Ntest, 1), L.dptr(P0), max(Ntest, 1),
+                                              L.dptr(qmap), L.dptr(pmap), iters.ctypes.data_as(C.POINTER(C.c_int)),
+                                              _optr(out, "jac"), _optr(out, "mono"), _optr(out, "lyap")),
+            "sgpr_applymap_nd_tangent_host")
+    return qmap, pmap, iters, out
+
+
+def symplectic_defect(M):
+    """max |M^T J M - J| over the last two axes of M (..., D, D), J = [[0, I], [-I, 0]] in the order (q_1..q_d, p_1..p_d)"""
+    M = np.asarray(M, dtype=np.float64)
+    if M.ndim < 2 or M.shape[-1] != M.shape[-2] or M.shape[-1] % 2:
+        raise ValueError("M must be (..., D, D) with D even")
+    d = M.shape[-1] // 2
+    J = np.zeros((2 * d, 2 * d))
+    J[:d, d:], J[d:, :d] = np.eye(d), -np.eye(d)
+    return np.abs(np.swapaxes(M, -1, -2) @ J @ M - J).max(axis=(-2, -1))
+
+
+def greene_residue(mono):
+    """Greene's residue (2 - tr M) / 4 of the monodromy matrices mono (..., 2, 2) of a one-pair map"""
+    mono = np.asarray(mono, dtype=np.float64)
+    if mono.ndim < 2 or mono.shape[-2:] != (2, 2):
+        raise ValueError("greene_residue is defined for D = 2: mono must be (..., 2, 2)")
+    return (2.0 - np.trace(mono, axis1=-2, axis2=-1)) / 4.0

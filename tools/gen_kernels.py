@@ -89,6 +89,15 @@ def emit(exprs, names):
     return "\n".join(lines)
 
 
+def emit_ret(expr, name):
+    """C statements returning expr through common sub-expressions"""
+    pr = Printer()
+    repl, red = sp.cse([expr], symbols=sp.numbered_symbols("t"), optimizations="basic")
+    lines = ["    const double %s = %s;" % (pr.doprint(s), pr.doprint(e)) for s, e in repl]
+    lines.append("    return %s;   // %s" % (pr.doprint(red[0]), name))
+    return "\n".join(lines)
+
+
 def main():
     fams = families()
     head = '''// pair_generated.h -- GENERATED by tools/gen_kernels.py from the sympy kernel definitions; do not edit.
@@ -119,6 +128,10 @@ template <int FAM> __device__ double extra(int which, double x_a, double y_a, do
 template <int FAM, int Q> __device__ __forceinline__ void factor(double dx, double l, double p, double *out);
 template <int FAM, int Q> __device__ __forceinline__ void factor_dl(double dx, double l, double p, double *out);
 template <int FAM, int Q> __device__ __forceinline__ void factor_dp(double dx, double l, double p, double *out);
+//   gen::factor3<FAM, Q>(dx, l, p): f(3)/f, the third derivative of the same factor over f -- with f'/f and -f''/f all that the
+//     Hessian of K*(x) alpha needs
+//     (the tangent map of the d-pair symplectic map, maptan.h)
+template <int FAM, int Q> __device__ __forceinline__ double factor3(double dx, double l, double p);
 '''
     body = []
     names = ["k", "d2k/dx_a dx_b", "d2k/dy_a dy_b", "d2k/dx_a dy_b"]
@@ -148,6 +161,12 @@ template <int FAM, int Q> __device__ __forceinline__ void factor_dp(double dx, d
                                ("factor_dp", [sp.diff(e, p) for e in three], ["d/dp " + n for n in nm3])):
                 body.append("template <> __device__ __forceinline__ void %s<%s, %d>(double dx, double l, double p, double *out)\n"
                             "{\n    (void)p;\n%s\n}\n" % (fn, enum, Q, emit(ex, nm)))
+    # the third logarithmic derivative of every factor, after everything else: what was printed before it keeps its text
+    for fam, (enum, fq, fP, mode) in fams.items():
+        for Q, f, lsym, a, b in ((1, fq, lx, x_a, x_b), (0, fP, ly, y_a, y_b)):
+            fd = f.subs({a: dx, b: 0, lsym: l})
+            body.append("template <> __device__ __forceinline__ double factor3<%s, %d>(double dx, double l, double p)\n"
+                        "{\n    (void)p;\n%s\n}\n" % (enum, Q, emit_ret(sp.simplify(sp.diff(fd, dx, 3) / fd), "f(3)/f")))
     ufq, ufP, umode = USER_FAMILY
     body.append("// the user slot's shape: sum or product of its two factors; does its q-factor take the extra parameter p\n"
                 "// (then hyp = (lx, ly, p, sig) like family D, and (lq.., lP.., p_1..p_d, sig) for d > 1)\n"
