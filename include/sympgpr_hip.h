@@ -254,6 +254,22 @@ int sgpr_fit_batch(int family, int nbatch, int n_pts, const double *x, const dou
 int sgpr_fit_batch_grad(int family, int nbatch, int n_pts, const double *x, const double *y, const double *z,
                         const double *hyp, int nhyp, const double *sig2n, unsigned flags, double *alpha,
                         double *nll, double *grad, int *info);
+/* The same for 256 < n <= sgpr_fit_batch_max_order() (2048): arguments, hyp layout, the SGPR_FIT_REG flag and the layout of grad
+ * exactly as sgpr_fit_batch_grad -- grad: nbatch x (nhyp + 1), row-major, the last entry sign(sig2n[b]) * 1/2 (tr Ky^-1 -
+ * alpha^T alpha), sign(0) = +1; info[b] > 0: nll[b] and the whole row grad[b] are NaN, the other problems are untouched.  nll,
+ * alpha and info are bit-identical to sgpr_fit_batch's (the same build, factor and solves); a problem's gradient bits do not
+ * depend on its place in the batch, the batch size, the chunk it falls into or a repetition of the call (no atomics, no waiting
+ * between workgroups in the gradient phase).  Per chunk of problems, behind the solves: U = L^-T in a second npad x npad image
+ * (npad = n rounded up to 128) from the leaf inverses by doubling the block size, at most 2 ceil(log2(npad / 128)) launches of
+ * 128 x 128 fp64 MFMA tiles; Ky^-1 = U U^T (lower tiles) over L; one contraction launch with dK pair by pair and a fold per
+ * problem.  SGPR_E_ARG (before any device call) for an order <= 256 (sgpr_fit_batch_grad's range) or above the maximum, an
+ * unknown family, a wrong nhyp, an unknown flag, nbatch < 0, n_pts <= 0 and a null pointer other than alpha; nbatch == 0
+ * returns 0.  Device scratch per chunk: two images of 8 npad^2 bytes per problem, chunks sized to ~2 GiB of images (32
+ * problems of order 2048; sgpr_fit_batch: one image, 64), plus the leaf inverses (8 * 128 npad bytes per problem) and the solve
+ * vectors; it lives in the sgpr_fit_batch arena and sgpr_trim gives it back.  ABI 5 (an additional entry point). */
+int sgpr_fit_batch_grad_mid(int family, int nbatch, int n_pts, const double *x, const double *y, const double *z,
+                            const double *hyp, int nhyp, const double *sig2n, unsigned flags, double *alpha,
+                            double *nll, double *grad, int *info);
 
 /* Gives back what the CALLING thread's earlier calls keep for re-use: the device arena and page-locked staging block of
  * sgpr_fit_batch and sgpr_fit_batch_grad (up to ~2 GiB after a large batch of order-2048 problems, ~1.3 GiB after a gradient batch

@@ -437,6 +437,184 @@ __global__ __launch_bounds__(ST) void mid_finish_kernel(const MidArgs a, const d
         for (int i = t; i < n; i += ST) a.alpha[(size_t)b * n + i] = al[i];
 }
 
+// ---- the gradient of the mid-size problems (sgpr_fit_batch_grad_mid) -------------------------------------------------
+// After the solves a problem's image holds L, `inv` its 128 x 128 leaf inverses and r its alpha.  Three steps, every one a
+// grid over all problems of the chunk, ordered by the stream alone (no workgroup waits for another one):
+//   (a) U = L^-T into a second image, U[i + k ld] = (L^-1)[k, i] as grad_problem's: the diagonal tiles are the transposed
+//       leaf inverses (mid_udiag_kernel); then the block size doubles, 128, 256, ... : for adjacent diagonal blocks 1, 2
+//           T = U11 L21^T   (STEP 0, NT, into the block (1, 2) of the L image: its strict upper triangle is free),
+//           U12 = -T U22    (STEP 1, the TRANSB form),
+//       one 128 x 128 tile per workgroup; the last block 2 is ragged when W is no power of two.  The k range of a tile stops
+//       at the zeros of the triangular operand: U11's tile row ti starts at k = 128 ti, U22's tile column tj ends at
+//       128 (tj + 1).
+//   (b) Ky^-1 = U U^T, lower tiles, over L (mid_kinv_kernel): tile (I, J) sums k >= 128 I.
+//   (c) the contraction of W = Ky^-1 - alpha alpha^T with dK (mid_grad_kernel) in per-workgroup partials, folded per problem in
+//       a fixed order (mid_grad_fold_kernel).
+// A problem that is not positive definite has an arbitrary image: every loop bound here comes from the shape alone.
+constexpr int GT = 256;                   // contraction: rows per workgroup (one per thread)
+constexpr int GCJ = 64;                   // contraction: column points per workgroup
+constexpr int GPART = 8;                  // doubles per workgroup partial (>= grad_nacc)
+
+struct MidInv {
+    double *L, *U;        // problem b at L / U + b * stride (column-major, ld)
+    const double *inv;    // its leaf inverses at inv + b * stride_inv
+    size_t stride, ld, stride_inv;
+    int W, S;             // 128-tiles per side; tiles per side of a (full) diagonal block of this level
+};
+
+__global__ __launch_bounds__(256) void mid_udiag_kernel(const MidInv a)
+{
+    const double *X = a.inv + (size_t)blockIdx.y * a.stride_inv + (size_t)blockIdx.x * LEAF * LEAF;
+    double *U = a.U + (size_t)blockIdx.y * a.stride + (size_t)blockIdx.x * LEAF * (a.ld + 1);
+    for (int e = threadIdx.x; e < (int)(LEAF * LEAF); e += 256) {
+        const int i = e % (int)LEAF, k = e / (int)LEAF;
+        U[i + k * a.ld] = k >= i ? X[k + i * LEAF] : 0.0;         // the tile's lower part: zeros that (b) reads
+    }
+}
+
+template <int STEP>
+__global__ __launch_bounds__(256, 2) void mid_inv_level_kernel(const MidInv a)
+{
+    __shared__ double smem[2 * tile::BK * (2 * (128 + tile::PAD))];
+    const int S = a.S, per = S * S;
+    const int p = (int)blockIdx.x / per, rem = (int)blockIdx.x - p * per, ti = rem % S, tj = rem / S;
+    const int t1 = 2 * S * p, t2 = t1 + S;            // first tile of block 1 (S tiles, full) and of block 2
+    if (t2 + tj >= a.W) return;                       // past the ragged last block (the whole workgroup)
+    double *L = a.L + (size_t)blockIdx.y * a.stride, *U = a.U + (size_t)blockIdx.y * a.stride;
+    const size_t ld = a.ld, r1 = (size_t)t1 * LEAF, r2 = (size_t)t2 * LEAF, ri = r1 + (size_t)ti * LEAF, cj = r2 + (size_t)tj * LEAF;
+    tile::GemmArgs g{};
+    g.m = 128; g.n = 128; g.beta = 0.0;
+    g.lda = ld; g.ldb = ld; g.ldc = ld;
+    if constexpr (STEP == 0) {
+        // T(ti, tj) = sum_{k >= 128 ti} U11[ti, k] L21[tj, k]
+        g.k = (S - ti) * (int)LEAF; g.alpha = 1.0;
+        g.A = U + ri + ri * ld;
+        g.B = L + cj + ri * ld;
+        g.C = L + ri + cj * ld;
+        tile::gemm_body_dma<128, 128, 2>(g, smem, 0, 0);
+    } else {
+        // U12(ti, tj) = -sum_{k < 128 (tj + 1)} T[ti, k] U22[k, tj]
+        g.k = (tj + 1) * (int)LEAF; g.alpha = -1.0; g.transb = 1;
+        g.A = L + ri + r2 * ld;
+        g.B = U + r2 + cj * ld;
+        g.C = U + ri + cj * ld;
+        tile::gemm_body<128, 128, true, true>(g, smem, 0, 0);
+    }
+}
+
+__global__ __launch_bounds__(256, 2) void mid_kinv_kernel(const MidInv a)
+{
+    __shared__ double smem[2 * tile::BK * (2 * (128 + tile::PAD))];
+    int t = (int)blockIdx.x, r = 0;            // lower tiles row by row, as mid_syrk_kernel
+    while (t > r) { t -= r + 1; ++r; }
+    const double *U = a.U + (size_t)blockIdx.y * a.stride;
+    const size_t ld = a.ld, ri = (size_t)r * LEAF, cj = (size_t)t * LEAF;
+    tile::GemmArgs g{};
+    g.m = 128; g.n = 128; g.k = (a.W - r) * (int)LEAF;
+    g.alpha = 1.0; g.beta = 0.0;
+    g.A = U + ri + ri * ld; g.lda = ld;        // U[I, k] = 0 for k < 128 I
+    g.B = U + cj + ri * ld; g.ldb = ld;
+    g.C = a.L + (size_t)blockIdx.y * a.stride + ri + cj * ld; g.ldc = ld;
+    tile::gemm_body_dma<128, 128, 2>(g, smem, 0, 0);
+}
+
+struct MidGrad {
+    int npts, n, reg, nwg, nacc;
+    size_t ld;                            // npad: Ky^-1 (lower) of problem b at K + b ld^2, its alpha at alpha + b ld
+    const double *x, *y;
+    const KConst *kc;
+    const double *K, *alpha;
+    double *part;                         // sum k of workgroup w of problem b at part[(b nwg + w) GPART + k]
+    const int *info;
+    double *out;                          // problem b's raw sums at out + b nacc
+};
+
+// rows i0 .. i0 + GT (one per thread) x column points p0 .. p0 + GCJ of problem blockIdx.z: entries on and below the diagonal,
+// weighted W_ii and 2 W_ij, as grad_problem's step (3); rows and columns below n only
+template <int FAM>
+__global__ __launch_bounds__(GT) void mid_grad_kernel(const MidGrad a)
+{
+    constexpr bool HASP = grad_has_p<FAM>();
+    constexpr int NACC = grad_nacc<FAM>();
+    __shared__ double sx[GCJ], sy[GCJ], sal[2][GCJ];
+    __shared__ double red[GT / 64][NACC];
+    const int b = blockIdx.z, N = a.npts, n = a.n, tid = threadIdx.x;
+    const int p0 = blockIdx.y * GCJ, np = min(GCJ, N - p0);
+    const int i = blockIdx.x * GT + tid;
+    const double *K = a.K + (size_t)b * a.ld * a.ld, *al = a.alpha + (size_t)b * a.ld;
+    if (tid < np) {
+        sx[tid] = a.x[(size_t)b * N + p0 + tid];
+        sy[tid] = a.y[(size_t)b * N + p0 + tid];
+        sal[0][tid] = al[p0 + tid];
+        sal[1][tid] = a.reg ? 0.0 : al[N + p0 + tid];
+    }
+    __syncthreads();
+    const KConst kc = a.kc[b];
+    const double l[2] = {kc.lx, kc.ly}, pp[1] = {kc.p};
+    double acc[NACC];
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
+    if (i < n && p0 <= i) {
+        const double ai = al[i];
+        const double *Krow = K + i;
+        if (a.reg) {
+            const double xi = a.x[(size_t)b * N + i], yi = a.y[(size_t)b * N + i];
+            for (int jj = 0; jj < np; ++jj) {
+                const int j = p0 + jj;
+                if (j > i) break;
+                const double W = Krow[(size_t)j * a.ld] - ai * sal[0][jj];
+                if (j == i) acc[NACC - 1] += W;
+                nllg::reg_grad<FAM, HASP>(sx[jj], sy[jj], xi, yi, j == i ? W : 2.0 * W, l, kc.p, acc);
+            }
+        } else {
+            const int r = i < N ? 0 : 1, pi = i - r * N;
+            const double xi[2] = {a.x[(size_t)b * N + pi], a.y[(size_t)b * N + pi]};
+            for (int jj = 0; jj < np; ++jj) {
+                const int pj = p0 + jj;
+                double w[2];
+                bool any = false;
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {                 // columns pj (q part) and N + pj (P part)
+                    const int col = c * N + pj;
+                    w[c] = 0.0;
+                    if (col <= i) {
+                        const double W = Krow[(size_t)col * a.ld] - ai * sal[c][jj];
+                        if (col == i) { w[c] = W; acc[NACC - 1] += W; }
+                        else w[c] = 2.0 * W;
+                        any = true;
+                    }
+                }
+                if (!any) break;                              // column pj > i: so are all after it
+                const double xj[2] = {sx[jj], sy[jj]};
+                nllg::pair_grad<FAM, 2, HASP>(xi, xj, w, r, l, pp, acc);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) {
+        const double v = wave_sum(acc[k]);
+        if ((tid & 63) == 0) red[tid >> 6][k] = v;
+    }
+    __syncthreads();
+    if (tid < NACC) {
+        double v = red[0][tid];
+#pragma unroll
+        for (int w = 1; w < GT / 64; ++w) v += red[w][tid];
+        a.part[((size_t)b * a.nwg + (size_t)blockIdx.y * gridDim.x + blockIdx.x) * GPART + tid] = v;
+    }
+}
+
+// problem blockIdx.x: its workgroups' partials in their fixed order; NaN where the factorisation failed
+__global__ __launch_bounds__(64) void mid_grad_fold_kernel(const MidGrad a)
+{
+    const int b = blockIdx.x, k = threadIdx.x;
+    if (k >= a.nacc) return;
+    const double *p = a.part + (size_t)b * a.nwg * GPART + k;
+    double v = 0.0;
+    for (int w = 0; w < a.nwg; ++w) v += p[(size_t)w * GPART];
+    a.out[(size_t)b * a.nacc + k] = a.info[b] != 0 ? __builtin_nan("") : v;
+}
+
 // Device + pinned-host staging of one calling thread, grown on demand and kept: a call is then one H2D copy,
 // one launch and one D2H copy (nine hipMalloc / hipFree pairs and eight small pageable copies per call were
 // most of a single small fit's 230 us through a handle).
@@ -486,23 +664,40 @@ int fit_batch_trim() { t_arena.release(); return 0; }     // the calling thread'
 
 namespace {
 
+// the contraction launch of a chunk (step (c) of the gradient phase)
+template <int FAM>
+void launch_mid_grad(const MidGrad &g, dim3 grid, hipStream_t st) { hipLaunchKernelGGL(mid_grad_kernel<FAM>, grid, dim3(GT), 0, st, g); }
+
 // problems of order 256 < n <= 2048: see the kernels above.  Chunks of problems share the scratch images.
+// grad (nbatch x (nhyp + 1)) non-null: sgpr_fit_batch_grad_mid -- a second image per problem (U = L^-T), both images cleared
+// on entry, and the gradient phase behind the solves of every chunk; its raw sums come back behind nll in the chunk's one
+// device-to-host copy and are scaled here as fit_batch_small scales the one-launch gradient's.
 int fit_batch_mid(int family, int nbatch, int npts, int n, int reg, const double *x, const double *y, const double *z,
-                  const double *hyp, int nhyp, const double *sig2n, double *alpha, double *nll, int *info)
+                  const double *hyp, int nhyp, const double *sig2n, double *alpha, double *nll, int *info, double *grad = nullptr)
 {
     const int npad = (n + (int)LEAF - 1) / (int)LEAF * (int)LEAF, W = npad / (int)LEAF;
     const size_t img = (size_t)npad * npad * 8, invb = (size_t)W * LEAF * LEAF * 8;
-    // at most ~2 GiB of images per chunk (64 problems of order 2048; round 3: 6 GiB), at least one chip-full of strips (256 workgroups)
-    int chunk = (int)std::min<size_t>((size_t)nbatch, std::max<size_t>((256 + W - 1) / W, (2ull << 30) / img));
+    const size_t nimg = grad ? 2 : 1, nacc = grad ? (size_t)nhyp + 1 : 0;
+    // at most ~2 GiB of images per chunk (64 problems of order 2048, 32 with the gradient's second image: 2 x 32 MiB each; round 3:
+    // 6 GiB), at least one chip-full of strips (256 workgroups)
+    int chunk = (int)std::min<size_t>((size_t)nbatch, std::max<size_t>((256 + W - 1) / W, (2ull << 30) / (nimg * img)));
     if (chunk > 16384) chunk = 16384;      // grid.z of the build launch
+    if (grad) {                            // tunable "batch_gradmid_chunk" > 0 caps it (tests: several chunks of few problems)
+        const int cap = (int)tune("batch_gradmid_chunk", 0);
+        if (cap > 0 && chunk > cap) chunk = cap;
+    }
     const size_t C = (size_t)chunk;
+    const int ggx = (n + GT - 1) / GT, ggy = (npts + GCJ - 1) / GCJ, gnwg = ggx * ggy;      // contraction workgroups per problem
     const size_t o_x = 0, o_y = o_x + up256(C * npts * 8), o_z = o_y + up256(C * npts * 8), o_kc = o_z + up256(C * n * 8),
                  o_no = o_kc + up256(C * sizeof(KConst)), in_bytes = o_no + up256(C * 8);
-    const size_t o_al = 0, o_nll = o_al + up256(C * n * 8), o_info = o_nll + up256(C * 8), out_bytes = o_info + up256(C * sizeof(int));
+    // (with the gradient: problem b's raw sums at nll + chunk + b * nacc)
+    const size_t o_al = 0, o_nll = o_al + up256(C * n * 8), o_info = o_nll + up256(C * (1 + nacc) * 8),
+                 out_bytes = o_info + up256(C * sizeof(int));
     // (+ the solves: right-hand sides / solution padded to npad, the two publication buffers, 8 state words per problem)
-    const size_t o_A = 0, o_inv = o_A + up256(C * img), o_fl = o_inv + up256(C * invb), o_fl2 = o_fl + up256(potrf_batch_flag_bytes(chunk)),
+    // (with the gradient: the U images directly behind the L images, and the contraction's partials at the end)
+    const size_t o_A = 0, o_inv = o_A + nimg * up256(C * img), o_fl = o_inv + up256(C * invb), o_fl2 = o_fl + up256(potrf_batch_flag_bytes(chunk)),
                  o_r = o_fl2 + up256(potrf_batch_flag_bytes(chunk)), o_pub = o_r + up256(C * npad * 8), o_st = o_pub + up256(2 * C * npad * 8),
-                 scr_bytes = o_st + up256(C * 8 * sizeof(int));
+                 o_part = o_st + up256(C * 8 * sizeof(int)), scr_bytes = o_part + (grad ? up256(C * gnwg * GPART * 8) : 0);
     Arena &ar = t_arena;
     int rc = ar.reserve(in_bytes + out_bytes + scr_bytes, in_bytes + out_bytes);
     if (rc) return rc;
@@ -524,7 +719,13 @@ int fit_batch_mid(int family, int nbatch, int npts, int n, int reg, const double
         SGPR_HIP(hipMemcpyAsync(din, hin, in_bytes, hipMemcpyHostToDevice, st));
         double *dA = reinterpret_cast<double *>(dscr + o_A), *dinv = reinterpret_cast<double *>(dscr + o_inv);
         int *dinfo = reinterpret_cast<int *>(dout + o_info);
-        if (npad != n) SGPR_HIP(hipMemsetAsync(dA, 0, B * img, st));
+        double *dU = dA + C * (img / 8);
+        if (grad) {
+            // both images, unconditionally: the zeros the gradient phase reads above L's diagonal, below U's and in the images of
+            // a problem whose factorisation stops early come from here (and the leaf inverses of such a problem are defined)
+            SGPR_HIP(hipMemsetAsync(dA, 0, (C + B) * img, st));
+            SGPR_HIP(hipMemsetAsync(dinv, 0, B * invb, st));
+        } else if (npad != n) SGPR_HIP(hipMemsetAsync(dA, 0, B * img, st));
         MidArgs a{nb, npts, n, npad, reg, reinterpret_cast<double *>(din + o_x), reinterpret_cast<double *>(din + o_y),
                   reinterpret_cast<double *>(din + o_z), reinterpret_cast<KConst *>(din + o_kc),
                   reinterpret_cast<double *>(din + o_no), dA, dinv, alpha ? reinterpret_cast<double *>(dout + o_al) : nullptr,
@@ -576,6 +777,37 @@ int fit_batch_mid(int family, int nbatch, int npts, int n, int reg, const double
             return rc;
         hipLaunchKernelGGL(mid_finish_kernel, dim3(nb), dim3(ST), 0, st, a, (const double *)dr, (const int *)dst, dinfo);
         SGPR_CHECK_LAUNCH();
+        if (grad) {
+            // (a) U = L^-T: the diagonal tiles, then two launches per doubling of the block size
+            MidInv mi{dA, dU, dinv, (size_t)npad * npad, (size_t)npad, (size_t)W * LEAF * LEAF, W, 1};
+            hipLaunchKernelGGL(mid_udiag_kernel, dim3((unsigned)W, (unsigned)nb), dim3(256), 0, st, mi);
+            SGPR_CHECK_LAUNCH();
+            for (int S = 1; S < W; S *= 2) {
+                mi.S = S;
+                const dim3 gl((unsigned)((W - S + 2 * S - 1) / (2 * S) * S * S), (unsigned)nb);
+                hipLaunchKernelGGL(mid_inv_level_kernel<0>, gl, dim3(256), 0, st, mi);
+                SGPR_CHECK_LAUNCH();
+                hipLaunchKernelGGL(mid_inv_level_kernel<1>, gl, dim3(256), 0, st, mi);
+                SGPR_CHECK_LAUNCH();
+            }
+            // (b) Ky^-1 = U U^T over L
+            hipLaunchKernelGGL(mid_kinv_kernel, dim3((unsigned)(W * (W + 1) / 2), (unsigned)nb), dim3(256), 0, st, mi);
+            SGPR_CHECK_LAUNCH();
+            // (c) the contraction and its fold
+            MidGrad mg{npts, n, reg, gnwg, (int)nacc, (size_t)npad, a.x, a.y, a.kc, dA, dr,
+                       reinterpret_cast<double *>(dscr + o_part), dinfo, reinterpret_cast<double *>(dout + o_nll) + C};
+            const dim3 gg((unsigned)ggx, (unsigned)ggy, (unsigned)nb);
+            switch (family) {
+            case SGPR_FAM_A: launch_mid_grad<SGPR_FAM_A>(mg, gg, st); break;
+            case SGPR_FAM_B: launch_mid_grad<SGPR_FAM_B>(mg, gg, st); break;
+            case SGPR_FAM_C: launch_mid_grad<SGPR_FAM_C>(mg, gg, st); break;
+            case SGPR_FAM_USER: launch_mid_grad<SGPR_FAM_USER>(mg, gg, st); break;
+            default:         launch_mid_grad<SGPR_FAM_D>(mg, gg, st); break;
+            }
+            SGPR_CHECK_LAUNCH();
+            hipLaunchKernelGGL(mid_grad_fold_kernel, dim3(nb), dim3(64), 0, st, mg);
+            SGPR_CHECK_LAUNCH();
+        }
         const size_t from = alpha ? 0 : o_nll;
         SGPR_HIP(hipMemcpyAsync(hout + from, dout + from, out_bytes - from, hipMemcpyDeviceToHost, st));
         SGPR_HIP(hipStreamSynchronize(st));
@@ -584,6 +816,22 @@ int fit_batch_mid(int family, int nbatch, int npts, int n, int reg, const double
         memcpy(info + b0, hout + o_info, B * sizeof(int));
         for (int b = 0; b < nb; ++b)
             if (info[b0 + b] < 0) return info_status(info[b0 + b]);     // a hand-off timed out: an error of the call
+        if (grad) {
+            const double *raw = reinterpret_cast<const double *>(hout + o_nll) + C;
+            for (size_t b = 0; b < B; ++b) {
+                const double *r = raw + b * nacc;
+                double *g = grad + ((size_t)b0 + b) * nacc;
+                if (info[b0 + b] != 0) {
+                    nll[b0 + b] = std::nan("");
+                    for (size_t k = 0; k < nacc; ++k) g[k] = std::nan("");
+                    continue;
+                }
+                const double sig = kcs[b].sig;
+                for (int k = 0; k < nhyp - 1; ++k) g[k] = 0.5 * sig * r[k];
+                g[nhyp - 1] = 0.5 * r[nhyp - 1];
+                g[nhyp] = (sig2n[b0 + b] < 0.0 ? -0.5 : 0.5) * r[nhyp];
+            }
+        }
     }
     return 0;
 }
@@ -694,6 +942,14 @@ int fit_batch(int family, int nbatch, int npts, const double *x, const double *y
 }
 
 int fit_batch_grad_max_order() { return BMAX; }
+
+// sgpr_fit_batch_grad_mid: the arguments have been checked (capi.hip), nbatch > 0, BMAX < n <= fit_batch_max_order()
+int fit_batch_grad_mid(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
+                       int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, double *grad, int *info)
+{
+    const int reg = (flags & SGPR_FIT_REG) ? 1 : 0;
+    return fit_batch_mid(family, nbatch, npts, reg ? npts : 2 * npts, reg, x, y, z, hyp, nhyp, sig2n, alpha, nll, info, grad);
+}
 
 // sgpr_fit_batch_grad: the arguments have been checked (capi.hip), nbatch > 0, n <= BMAX
 int fit_batch_grad(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,

@@ -210,6 +210,9 @@ int fit_batch(int family, int nbatch, int npts, const double *x, const double *y
 int fit_batch_grad_max_order();                  // 256: one workgroup holds the whole problem
 int fit_batch_grad(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
                    int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, double *grad, int *info);
+// the same for 256 < order <= fit_batch_max_order(): the mid path's factor and solves, then Ky^-1 per problem on the matrix cores
+int fit_batch_grad_mid(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
+                       int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, double *grad, int *info);
 
 // ---- blas_small.hip
 int zero_strict_upper(int n, double *A, size_t lda, hipStream_t st);

@@ -363,3 +363,33 @@ def fit_batch_grad(family, x, y, z, hyp, sig2n, reg=False, want_alpha=False):
                                                  L.dptr(alpha) if want_alpha else None, L.dptr(nll), L.dptr(grad),
                                                  info.ctypes.data_as(C.POINTER(C.c_int))), "sgpr_fit_batch_grad")
     return alpha, nll, grad, info
+
+
+def batch_grad_mid_max_order():
+    """largest matrix order per problem sgpr_fit_batch_grad_mid takes (sgpr_fit_batch_max_order(): 2048)"""
+    return L.load_library().sgpr_fit_batch_max_order()
+
+
+def fit_batch_grad_mid(family, x, y, z, hyp, sig2n, reg=False, want_alpha=False):
+    """fit_batch_grad for 256 < n <= batch_grad_mid_max_order(), every gradient on the device (sgpr_fit_batch_grad_mid): shapes,
+    the returned (alpha or None, nll, grad, info) and the NaN rows for info > 0 as fit_batch_grad; nll, alpha and info are the
+    bits fit_batch returns.  Per chunk of problems: L^-T from the leaf inverses by block doubling, Ky^-1 = L^-T L^-1 on the
+    matrix cores, one contraction launch.  ValueError for n <= 256: fit_batch_grad serves that range in one launch."""
+    x, y, z, hyp = (np.ascontiguousarray(np.atleast_2d(np.asarray(v, dtype=np.float64))) for v in (x, y, z, hyp))
+    B, n_pts = x.shape
+    n = n_pts if reg else 2 * n_pts
+    if y.shape != (B, n_pts) or z.shape != (B, n) or hyp.shape[0] != B:
+        raise ValueError("fit_batch_grad_mid: x, y (B, n_pts), z (B, n), hyp (B, nhyp)")
+    if n <= batch_grad_max_order():
+        raise ValueError("fit_batch_grad_mid: order %d <= %d is fit_batch_grad's range" % (n, batch_grad_max_order()))
+    s2 = np.ascontiguousarray(np.broadcast_to(np.asarray(sig2n, dtype=np.float64), (B,)))
+    nhyp = hyp.shape[1]
+    alpha = np.empty((B, n)) if want_alpha else None
+    nll = np.empty(B)
+    grad = np.empty((B, nhyp + 1))
+    info = np.zeros(B, dtype=np.int32)
+    L.check(L.load_library().sgpr_fit_batch_grad_mid(L.family_id(family), B, n_pts, L.dptr(x), L.dptr(y), L.dptr(z), L.dptr(hyp),
+                                                     nhyp, L.dptr(s2), L.FIT_REG if reg else 0,
+                                                     L.dptr(alpha) if want_alpha else None, L.dptr(nll), L.dptr(grad),
+                                                     info.ctypes.data_as(C.POINTER(C.c_int))), "sgpr_fit_batch_grad_mid")
+    return alpha, nll, grad, info

@@ -184,11 +184,17 @@ def nll_chol_grad(hyp, x, y, N, reg=False):
         return f.nll(), f.nll_grad_full()
 
 
-def nll_chol_grad_batch(hyps, x, y, N, reg=False):
+def nll_chol_grad_batch(hyps, x, y, N, reg=False, mid=None):
     """nll_chol_batch with gradients: hyps (B, nhyp + 1) rows like nll_chol's hyp -> (nll (B,), grad (B, nhyp + 1)).  Rows
     whose Ky is not positive definite give nll = +inf and a NaN gradient row.  Up to order 256 one launch; above it, the
-    nll of every row from one fit_batch call and the gradients row by row (fit.fit_batch_grad's slow path)."""
-    from .fit import fit_batch_grad
+    nll of every row from one fit_batch call and the gradients row by row (fit.fit_batch_grad's slow path).
+    mid="device": orders 256 < N <= 2048 go through fit.fit_batch_grad_mid instead, every gradient on the device in a few
+    launches per chunk, with the same conventions (the values agree with the slow path to rounding, not bit for bit).
+    mid=None (the default) is the behaviour described first; making "device" the default is a later one-line change, once
+    that path has a measured record."""
+    from .fit import batch_grad_max_order, batch_grad_mid_max_order, fit_batch_grad, fit_batch_grad_mid
+    if mid not in (None, "device"):
+        raise ValueError('nll_chol_grad_batch: mid is None or "device"')
     hyps = np.atleast_2d(np.asarray(hyps, dtype=np.float64))
     x = np.asarray(x, dtype=np.float64)
     y = np.asarray(y, dtype=np.float64)
@@ -200,8 +206,11 @@ def nll_chol_grad_batch(hyps, x, y, N, reg=False):
     if len(X) != (N if reg else N // 2) or len(Y) != len(X) or len(Z) != (N if reg else 2 * len(X)):
         raise ValueError("nll_chol_grad_batch: x holds 2 * n_pts coordinates and y the n targets of order N")
     B = len(hyps)
-    _, nll, grad, info = fit_batch_grad(get_family(), np.broadcast_to(X, (B, len(X))), np.broadcast_to(Y, (B, len(Y))),
-                                        np.broadcast_to(Z, (B, len(Z))), hyps[:, :-1], hyps[:, -1], reg=reg)
+    fn = fit_batch_grad
+    if mid == "device" and batch_grad_max_order() < N <= batch_grad_mid_max_order():
+        fn = fit_batch_grad_mid
+    _, nll, grad, info = fn(get_family(), np.broadcast_to(X, (B, len(X))), np.broadcast_to(Y, (B, len(Y))),
+                            np.broadcast_to(Z, (B, len(Z))), hyps[:, :-1], hyps[:, -1], reg=reg)
     nll[info != 0] = np.inf
     return nll, grad
 
