@@ -210,6 +210,20 @@ int sgpr_fit_predict_cov(sgpr_fit_t f, int m, const double *Xt, size_t ldxt, dou
  * Device scratch, allocated and freed per call: one panel (min(n, 2048 or 4096) x n doubles, 4.3 GB at n = 131 072) and
  * the partial sums (a few MB).  Added in ABI 5 (an additional entry point). */
 int sgpr_fit_nll_grad_full(sgpr_fit_t f, double *grad, int ngrad);
+/* Leave-one-point-out cross-validation of a solved fit (Rasmussen & Williams 5.4.2, for points): point i owns the D rows
+ * B_i = {c N + i, c = 0 .. D-1} of Ky (D = 2d; 1 with SGPR_FIT_REG), and with C_i = (Ky^-1)[B_i, B_i], a_i = alpha[B_i]:
+ *   residual r_i = C_i^-1 a_i (the observed rows minus their prediction from the fit without point i), covariance
+ *   S_i = C_i^-1 (of that prediction, noise included), lpd_i = -1/2 a_i^T C_i^-1 a_i + 1/2 log det C_i - D/2 log 2 pi.
+ * loo2 (required) = {loo = -sum_i lpd_i, press = sum_i |r_i|^2}.  resid (n doubles, the layout of z: entry c N + i is point i,
+ * part c), cov (point i's D x D matrix at cov + i*D*D, ordered as sgpr_fit_predict_cov's, exactly symmetric) and lpd (N) may
+ * each be NULL.  A point whose block has a pivot that is not positive and finite gives NaN in its r, S and lpd and in loo and
+ * press; the call still returns 0.  Ky^-1 is formed by the row panels of sgpr_fit_nll_grad_full (2 n^3 / 3 flop), the
+ * blocks are copied out of the panels, one thread per point does the D x D algebra; the sums are deterministic.  The factor,
+ * alpha, the NLL and the workspace are left as they are.  SGPR_E_ARG for a null handle or loo2; SGPR_E_STATE before a solve
+ * and for SGPR_FIT_BLOCK_QQ / _PP fits; SGPR_E_HIP if the fit's strip solve gave up on a hand-off.  Device scratch: one
+ * panel (min(n, 2048 or 4096) x n doubles), 8 N D (D + 1) / 2 bytes of blocks, the outputs and the partial sums, in the
+ * fit's own scratch block, kept until sgpr_fit_trim.  ABI 5 (an additional entry point). */
+int sgpr_fit_loo(sgpr_fit_t f, double *loo2, double *resid, double *cov, double *lpd);
 /* cond_2(Ky) estimated from below with the device's own kernels (needs a valid factor): lambda_max by `iters` power iterations on
  * Ky v -- the rows of K re-evaluated from the training points by the prediction kernel, plus |sig2n| v --, lambda_min by `iters`
  * inverse iterations with the cached factor.  out4 = {lambda_max, lambda_min, cond, relative change of the quotients in the last
@@ -270,6 +284,20 @@ int sgpr_fit_batch_grad(int family, int nbatch, int n_pts, const double *x, cons
 int sgpr_fit_batch_grad_mid(int family, int nbatch, int n_pts, const double *x, const double *y, const double *z,
                             const double *hyp, int nhyp, const double *sig2n, unsigned flags, double *alpha,
                             double *nll, double *grad, int *info);
+/* sgpr_fit_batch plus leave-one-point-out cross-validation of every problem (see sgpr_fit_loo; D = 2, 1 with SGPR_FIT_REG), for
+ * every order n = 2 n_pts (n_pts with SGPR_FIT_REG) <= sgpr_fit_batch_max_order().  loo: nbatch x 2, row-major; row b = {loo,
+ * press}.  hyp layout and nhyp as sgpr_fit_batch; the noise enters as |sig2n[b]|.  nll, alpha (may be NULL) and info are
+ * bit-identical to sgpr_fit_batch's; info[b] > 0: nll[b] and the row loo[b] are NaN, the other problems are untouched.  A
+ * problem's loo bits do not depend on its place in the batch, the batch size, the chunk or a repetition (no atomics).  n <= 256:
+ * one launch, one workgroup per problem, which after the fit forms Ky^-1 = L^-T L^-1 as sgpr_fit_batch_grad does and then
+ * takes one thread per point.  Above: the chunks, images and Ky^-1 of sgpr_fit_batch_grad_mid, then one thread per point and a
+ * fold per problem in place of the contraction.  SGPR_E_ARG (before any device call) for an unknown family, a wrong nhyp, an
+ * unknown flag, nbatch < 0, n_pts <= 0, an order above the maximum and a null pointer other than alpha; nbatch == 0 returns 0.
+ * Device scratch: that of sgpr_fit_batch_grad (n <= 256) or sgpr_fit_batch_grad_mid, in the sgpr_fit_batch arena, kept until
+ * sgpr_trim.  ABI 5 (an additional entry point). */
+int sgpr_fit_batch_loo(int family, int nbatch, int n_pts, const double *x, const double *y, const double *z,
+                       const double *hyp, int nhyp, const double *sig2n, unsigned flags, double *alpha,
+                       double *nll, double *loo, int *info);
 
 /* Gives back what the CALLING thread's earlier calls keep for re-use: the device arena and page-locked staging block of
  * sgpr_fit_batch and sgpr_fit_batch_grad (up to ~2 GiB after a large batch of order-2048 problems, ~1.3 GiB after a gradient batch

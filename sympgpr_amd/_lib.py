@@ -72,6 +72,7 @@ SIGNATURES = {
     "sgpr_fit_predict_nd": (C.c_int, [_vp, C.c_int, _dp, C.c_size_t, _dp]),
     "sgpr_fit_predict_cov": (C.c_int, [_vp, C.c_int, _dp, C.c_size_t, _dp, _dp]),
     "sgpr_fit_nll_grad_full": (C.c_int, [_vp, _dp, C.c_int]),
+    "sgpr_fit_loo": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     "sgpr_fit_stage_ms": (C.c_int, [_vp, _dp, _dp, _dp]),
     "sgpr_fit_cond_estimate": (C.c_int, [_vp, C.c_int, _dp]),
     "sgpr_fit_trim": (C.c_int, [_vp]),
@@ -132,6 +133,8 @@ SIGNATURES = {
                                       C.POINTER(C.c_int)]),
     "sgpr_fit_batch_grad_mid": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_uint, _dp, _dp, _dp,
                                           C.POINTER(C.c_int)]),
+    "sgpr_fit_batch_loo": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_uint, _dp, _dp, _dp,
+                                     C.POINTER(C.c_int)]),
 }
 
 # include/sympgpr_probe.h: measurement aids in their own library (never loaded by a product path)

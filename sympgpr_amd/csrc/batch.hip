@@ -18,6 +18,7 @@
 #include "common.h"
 #include "gemm_tile.h"
 #include "leaf.h"
+#include "loo_block.h"
 #include "nllgrad_pair.h"
 #include "pair_eval.h"
 
@@ -39,25 +40,28 @@ struct BatchArgs {
     double *scratch;                      // per workgroup: BMAX*BMAX (Ky / L) + 2*LEAF*LEAF (leaf inverses) + 2*BMAX
                                           // [+ BMAX*BMAX (U = L^-T) for the gradient]
     double *alpha, *nll;                  // outputs (alpha may be null); the gradient kernel writes problem b's raw sums at
-                                          // nll + nbatch + b * grad_nacc<FAM>()
+                                          // nll + nbatch + b * grad_nacc<FAM>(), the loo kernel {loo, press} at nll + nbatch + 2 b
     int *info;                            // per problem, zero on entry
 };
 
 template <int FAM> constexpr bool grad_has_p() { return FAM == SGPR_FAM_D || (FAM == SGPR_FAM_USER && gen::user_has_p); }
 template <int FAM> constexpr int grad_nacc() { return grad_has_p<FAM>() ? 5 : 4; }    // lx, ly, [p,] sig, sig2n
 
-template <int FAM>
+template <int FAM, bool LOO = false>
 __device__ void grad_problem(const BatchArgs &a, int b, double *s, double *A, const double *inv, double *U, const double *al);
 
-// GRAD: after the fit, the gradient of problem b's nll (grad_problem below); scratch then PER_WG_GRAD doubles per workgroup
-template <int FAM, bool GRAD = false>
+enum { MODE_FIT = 0, MODE_GRAD = 1, MODE_LOO = 2 };
+
+// MODE_GRAD: after the fit, the gradient of problem b's nll (grad_problem below); MODE_LOO: its leave-one-point-out sums
+// (grad_problem's Ky^-1, then one thread per point).  Scratch then PER_WG + BMAX^2 doubles per workgroup
+template <int FAM, int MODE = MODE_FIT>
 __global__ __launch_bounds__(LT) void fit_batch_kernel(const BatchArgs a)
 {
     __shared__ double s[LEAF_LDS];
     __shared__ double red[LT / 64];
     const int tid = threadIdx.x;
     const int n = a.n, N = a.npts;
-    const size_t per_wg = (size_t)BMAX * BMAX + 2 * (size_t)LEAF * LEAF + 2 * BMAX + (GRAD ? (size_t)BMAX * BMAX : 0);   // PER_WG [+ U]
+    const size_t per_wg = (size_t)BMAX * BMAX + 2 * (size_t)LEAF * LEAF + 2 * BMAX + (MODE != MODE_FIT ? (size_t)BMAX * BMAX : 0);   // PER_WG [+ U]
     double *A = a.scratch + (size_t)blockIdx.x * per_wg;     // column-major, ld = BMAX
     double *inv = A + (size_t)BMAX * BMAX;
     double *v = inv + 2 * (size_t)LEAF * LEAF;                // y, then alpha
@@ -180,7 +184,8 @@ __global__ __launch_bounds__(LT) void fit_batch_kernel(const BatchArgs a)
             for (int i = tid; i < n; i += LT) a.alpha[(size_t)b * n + i] = al[i];
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if constexpr (GRAD) grad_problem<FAM>(a, b, s, A, inv, v + 2 * BMAX, al);
+        if constexpr (MODE == MODE_GRAD) grad_problem<FAM>(a, b, s, A, inv, v + 2 * BMAX, al);
+        if constexpr (MODE == MODE_LOO) grad_problem<FAM, true>(a, b, s, A, inv, v + 2 * BMAX, al);
     }
 }
 
@@ -192,18 +197,20 @@ __global__ __launch_bounds__(LT) void fit_batch_kernel(const BatchArgs a)
 //       the generated forms (nllgrad_pair.h), entries on and below the diagonal weighted W_ii and 2 W_ij.  The per-thread
 //       sums fold wave by wave in a fixed order: a problem's bits do not depend on its place in the batch or on the grid.
 // The sums leave unscaled, as nll_grad_full's (nllgrad.hip): the host applies sig / 2, 1/2 and sign(sig2n) / 2.
-template <int FAM>
+// LOO: steps (1) and (2), then in place of (3) thread i < N takes point i's block {A[i,i], A[N+i,i], A[N+i,N+i]} of Ky^-1 (one
+// entry for reg) through loo_block.h; lpd and |r|^2 fold wave by wave in the same fixed order into {loo, press}.
+template <int FAM, bool LOO>
 __device__ void grad_problem(const BatchArgs &a, int b, double *s, double *A, const double *inv, double *U, const double *al)
 {
     constexpr bool HASP = grad_has_p<FAM>();
-    constexpr int NACC = grad_nacc<FAM>();
+    constexpr int NACC = grad_nacc<FAM>(), NOUT = LOO ? 2 : NACC;     // LOO returns before step (3)
     constexpr size_t ld = BMAX;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = a.n, N = a.npts, n1 = min(n, (int)LEAF), n2 = n - n1;
-    double *out = a.nll + a.nbatch + (size_t)b * NACC;
+    double *out = a.nll + a.nbatch + (size_t)b * NOUT;
     // not positive definite (leaf_body's flag, read from L2: the same value for every thread): NaN, nothing computed
     if (__hip_atomic_load(a.info + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-        if (tid < NACC) out[tid] = __builtin_nan("");
+        if (tid < NOUT) out[tid] = __builtin_nan("");
         return;
     }
     // ---- (1) U = L^-T.  The diagonal blocks (transposed leaf inverses) and the zeros; U[i + k ld] = (L^-1)[k, i]
@@ -245,6 +252,40 @@ __device__ void grad_problem(const BatchArgs &a, int b, double *s, double *A, co
             for (int k = max(j, i & ~63); k < n; ++k) acc = __builtin_fma(U[i + k * ld], U[j + k * ld], acc);
             A[i + j * ld] = acc;
         }
+    }
+    if constexpr (LOO) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();                                  // point i's block has entries written by thread N + i; T is dead
+        double lv[2] = {0.0, 0.0};
+        if (i < N) {
+            double lpd, rr;
+            if (a.reg) {
+                const double C[1] = {A[i + i * ld]}, ai[1] = {al[i]};
+                double r[1], S[1];
+                loo::block<1>(C, ai, r, S, lpd);
+                rr = r[0] * r[0];
+            } else {
+                const double C[3] = {A[i + i * ld], A[(N + i) + i * ld], A[(N + i) + (N + i) * ld]}, ai[2] = {al[i], al[N + i]};
+                double r[2], S[3];
+                loo::block<2>(C, ai, r, S, lpd);
+                rr = __builtin_fma(r[1], r[1], r[0] * r[0]);
+            }
+            lv[0] = lpd; lv[1] = rr;
+        }
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            double v = lv[k];
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+            if (lane == 0) s[wave * 2 + k] = v;
+        }
+        __syncthreads();
+        if (tid < 2) {
+            const double v = s[tid] + s[2 + tid] + s[4 + tid] + s[6 + tid];
+            out[tid] = tid == 0 ? -v : v;
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();                                  // A, U and s are the next problem's
+        return;
     }
     // ---- (3) the points and alpha into LDS (T is dead), then the contraction
     double *sx = s, *sy = s + BMAX, *sal = s + 2 * BMAX, *red = s + 3 * BMAX;
@@ -615,6 +656,63 @@ __global__ __launch_bounds__(64) void mid_grad_fold_kernel(const MidGrad a)
     a.out[(size_t)b * a.nacc + k] = a.info[b] != 0 ? __builtin_nan("") : v;
 }
 
+// ---- leave-one-point-out sums of the mid-size problems (sgpr_fit_batch_loo): behind step (b) above, in place of (c) ----------
+struct MidLoo {
+    int npts, reg, nwg;
+    size_t ld;                            // npad: Ky^-1 (lower) of problem b at K + b ld^2, its alpha at alpha + b ld
+    const double *K, *alpha;
+    double *part;                         // sum k of workgroup w of problem b at part[(b nwg + w) 2 + k]: k = 0 lpd, 1 |r|^2
+    const int *info;
+    double *out;                          // problem b's {loo, press} at out + 2 b
+};
+
+// points blockIdx.x GT .. + GT (one per thread) of problem blockIdx.z: the point's block from the lower triangle of Ky^-1
+__global__ __launch_bounds__(GT) void mid_loo_kernel(const MidLoo a)
+{
+    __shared__ double red[GT / 64][2];
+    const int b = blockIdx.z, N = a.npts, tid = threadIdx.x, i = blockIdx.x * GT + tid;
+    const double *K = a.K + (size_t)b * a.ld * a.ld, *al = a.alpha + (size_t)b * a.ld;
+    double lv[2] = {0.0, 0.0};
+    if (i < N) {
+        double lpd, rr;
+        if (a.reg) {
+            const double C[1] = {K[i + i * a.ld]}, ai[1] = {al[i]};
+            double r[1], S[1];
+            loo::block<1>(C, ai, r, S, lpd);
+            rr = r[0] * r[0];
+        } else {
+            const double C[3] = {K[i + i * a.ld], K[(N + i) + i * a.ld], K[(N + i) + (N + i) * a.ld]}, ai[2] = {al[i], al[N + i]};
+            double r[2], S[3];
+            loo::block<2>(C, ai, r, S, lpd);
+            rr = __builtin_fma(r[1], r[1], r[0] * r[0]);
+        }
+        lv[0] = lpd; lv[1] = rr;
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const double v = wave_sum(lv[k]);
+        if ((tid & 63) == 0) red[tid >> 6][k] = v;
+    }
+    __syncthreads();
+    if (tid < 2) {
+        double v = red[0][tid];
+#pragma unroll
+        for (int w = 1; w < GT / 64; ++w) v += red[w][tid];
+        a.part[((size_t)b * a.nwg + blockIdx.x) * 2 + tid] = v;
+    }
+}
+
+// problem blockIdx.x: its workgroups' partials in their fixed order; NaN where the factorisation failed
+__global__ __launch_bounds__(64) void mid_loo_fold_kernel(const MidLoo a)
+{
+    const int b = blockIdx.x, k = threadIdx.x;
+    if (k >= 2) return;
+    const double *p = a.part + (size_t)b * a.nwg * 2 + k;
+    double v = 0.0;
+    for (int w = 0; w < a.nwg; ++w) v += p[(size_t)w * 2];
+    a.out[(size_t)b * 2 + k] = a.info[b] != 0 ? __builtin_nan("") : (k == 0 ? -v : v);
+}
+
 // Device + pinned-host staging of one calling thread, grown on demand and kept: a call is then one H2D copy,
 // one launch and one D2H copy (nine hipMalloc / hipFree pairs and eight small pageable copies per call were
 // most of a single small fit's 230 us through a handle).
@@ -672,22 +770,27 @@ void launch_mid_grad(const MidGrad &g, dim3 grid, hipStream_t st) { hipLaunchKer
 // grad (nbatch x (nhyp + 1)) non-null: sgpr_fit_batch_grad_mid -- a second image per problem (U = L^-T), both images cleared
 // on entry, and the gradient phase behind the solves of every chunk; its raw sums come back behind nll in the chunk's one
 // device-to-host copy and are scaled here as fit_batch_small scales the one-launch gradient's.
+// loo (nbatch x 2) non-null: sgpr_fit_batch_loo -- the same images, clear, chunks and steps (a), (b); then mid_loo_kernel and its
+// fold in place of the contraction, {loo, press} behind nll in the same copy.
 int fit_batch_mid(int family, int nbatch, int npts, int n, int reg, const double *x, const double *y, const double *z,
-                  const double *hyp, int nhyp, const double *sig2n, double *alpha, double *nll, int *info, double *grad = nullptr)
+                  const double *hyp, int nhyp, const double *sig2n, double *alpha, double *nll, int *info, double *grad = nullptr,
+                  double *loo = nullptr)
 {
+    const bool kinv = grad || loo;         // the phase behind the solves that forms Ky^-1
     const int npad = (n + (int)LEAF - 1) / (int)LEAF * (int)LEAF, W = npad / (int)LEAF;
     const size_t img = (size_t)npad * npad * 8, invb = (size_t)W * LEAF * LEAF * 8;
-    const size_t nimg = grad ? 2 : 1, nacc = grad ? (size_t)nhyp + 1 : 0;
+    const size_t nimg = kinv ? 2 : 1, nacc = grad ? (size_t)nhyp + 1 : loo ? 2 : 0;
     // at most ~2 GiB of images per chunk (64 problems of order 2048, 32 with the gradient's second image: 2 x 32 MiB each; round 3:
     // 6 GiB), at least one chip-full of strips (256 workgroups)
     int chunk = (int)std::min<size_t>((size_t)nbatch, std::max<size_t>((256 + W - 1) / W, (2ull << 30) / (nimg * img)));
     if (chunk > 16384) chunk = 16384;      // grid.z of the build launch
-    if (grad) {                            // tunable "batch_gradmid_chunk" > 0 caps it (tests: several chunks of few problems)
+    if (kinv) {                            // tunable "batch_gradmid_chunk" > 0 caps it (tests: several chunks of few problems)
         const int cap = (int)tune("batch_gradmid_chunk", 0);
         if (cap > 0 && chunk > cap) chunk = cap;
     }
     const size_t C = (size_t)chunk;
     const int ggx = (n + GT - 1) / GT, ggy = (npts + GCJ - 1) / GCJ, gnwg = ggx * ggy;      // contraction workgroups per problem
+    const int lnwg = (npts + GT - 1) / GT;                                                   // loo workgroups per problem
     const size_t o_x = 0, o_y = o_x + up256(C * npts * 8), o_z = o_y + up256(C * npts * 8), o_kc = o_z + up256(C * n * 8),
                  o_no = o_kc + up256(C * sizeof(KConst)), in_bytes = o_no + up256(C * 8);
     // (with the gradient: problem b's raw sums at nll + chunk + b * nacc)
@@ -697,7 +800,7 @@ int fit_batch_mid(int family, int nbatch, int npts, int n, int reg, const double
     // (with the gradient: the U images directly behind the L images, and the contraction's partials at the end)
     const size_t o_A = 0, o_inv = o_A + nimg * up256(C * img), o_fl = o_inv + up256(C * invb), o_fl2 = o_fl + up256(potrf_batch_flag_bytes(chunk)),
                  o_r = o_fl2 + up256(potrf_batch_flag_bytes(chunk)), o_pub = o_r + up256(C * npad * 8), o_st = o_pub + up256(2 * C * npad * 8),
-                 o_part = o_st + up256(C * 8 * sizeof(int)), scr_bytes = o_part + (grad ? up256(C * gnwg * GPART * 8) : 0);
+                 o_part = o_st + up256(C * 8 * sizeof(int)), scr_bytes = o_part + (grad ? up256(C * gnwg * GPART * 8) : loo ? up256(C * lnwg * 2 * 8) : 0);
     Arena &ar = t_arena;
     int rc = ar.reserve(in_bytes + out_bytes + scr_bytes, in_bytes + out_bytes);
     if (rc) return rc;
@@ -720,7 +823,7 @@ int fit_batch_mid(int family, int nbatch, int npts, int n, int reg, const double
         double *dA = reinterpret_cast<double *>(dscr + o_A), *dinv = reinterpret_cast<double *>(dscr + o_inv);
         int *dinfo = reinterpret_cast<int *>(dout + o_info);
         double *dU = dA + C * (img / 8);
-        if (grad) {
+        if (kinv) {
             // both images, unconditionally: the zeros the gradient phase reads above L's diagonal, below U's and in the images of
             // a problem whose factorisation stops early come from here (and the leaf inverses of such a problem are defined)
             SGPR_HIP(hipMemsetAsync(dA, 0, (C + B) * img, st));
@@ -777,7 +880,7 @@ int fit_batch_mid(int family, int nbatch, int npts, int n, int reg, const double
             return rc;
         hipLaunchKernelGGL(mid_finish_kernel, dim3(nb), dim3(ST), 0, st, a, (const double *)dr, (const int *)dst, dinfo);
         SGPR_CHECK_LAUNCH();
-        if (grad) {
+        if (kinv) {
             // (a) U = L^-T: the diagonal tiles, then two launches per doubling of the block size
             MidInv mi{dA, dU, dinv, (size_t)npad * npad, (size_t)npad, (size_t)W * LEAF * LEAF, W, 1};
             hipLaunchKernelGGL(mid_udiag_kernel, dim3((unsigned)W, (unsigned)nb), dim3(256), 0, st, mi);
@@ -793,6 +896,16 @@ int fit_batch_mid(int family, int nbatch, int npts, int n, int reg, const double
             // (b) Ky^-1 = U U^T over L
             hipLaunchKernelGGL(mid_kinv_kernel, dim3((unsigned)(W * (W + 1) / 2), (unsigned)nb), dim3(256), 0, st, mi);
             SGPR_CHECK_LAUNCH();
+        }
+        if (loo) {
+            MidLoo ml{npts, reg, lnwg, (size_t)npad, dA, dr, reinterpret_cast<double *>(dscr + o_part), dinfo,
+                      reinterpret_cast<double *>(dout + o_nll) + C};
+            hipLaunchKernelGGL(mid_loo_kernel, dim3((unsigned)lnwg, 1, (unsigned)nb), dim3(GT), 0, st, ml);
+            SGPR_CHECK_LAUNCH();
+            hipLaunchKernelGGL(mid_loo_fold_kernel, dim3(nb), dim3(64), 0, st, ml);
+            SGPR_CHECK_LAUNCH();
+        }
+        if (grad) {
             // (c) the contraction and its fold
             MidGrad mg{npts, n, reg, gnwg, (int)nacc, (size_t)npad, a.x, a.y, a.kc, dA, dr,
                        reinterpret_cast<double *>(dscr + o_part), dinfo, reinterpret_cast<double *>(dout + o_nll) + C};
@@ -832,6 +945,14 @@ int fit_batch_mid(int family, int nbatch, int npts, int n, int reg, const double
                 g[nhyp] = (sig2n[b0 + b] < 0.0 ? -0.5 : 0.5) * r[nhyp];
             }
         }
+        if (loo) {
+            const double *raw = reinterpret_cast<const double *>(hout + o_nll) + C;
+            for (size_t b = 0; b < B; ++b) {
+                const bool bad = info[b0 + b] != 0;
+                if (bad) nll[b0 + b] = std::nan("");
+                for (int k = 0; k < 2; ++k) loo[((size_t)b0 + b) * 2 + k] = bad ? std::nan("") : raw[b * 2 + k];
+            }
+        }
     }
     return 0;
 }
@@ -841,14 +962,16 @@ int fit_batch_mid(int family, int nbatch, int npts, int n, int reg, const double
 namespace {
 
 // problems of order n <= BMAX: one launch of fit_batch_kernel, one workgroup per problem.  grad (nbatch x (nhyp + 1)) non-null:
-// the gradient kernel, whose raw sums come back behind nll in the same device-to-host copy and are scaled here.
+// the gradient kernel, whose raw sums come back behind nll in the same device-to-host copy and are scaled here.  loo (nbatch x 2)
+// non-null: the loo kernel, whose {loo, press} come back the same way.
 int fit_batch_small(int family, int nbatch, int npts, int n, int reg, const double *x, const double *y, const double *z,
-                    const double *hyp, int nhyp, const double *sig2n, double *alpha, double *nll, int *info, double *grad)
+                    const double *hyp, int nhyp, const double *sig2n, double *alpha, double *nll, int *info, double *grad,
+                    double *loo = nullptr)
 {
     const size_t B = (size_t)nbatch;
     const int grid = nbatch < 1024 ? nbatch : 1024;
-    const size_t per_wg = PER_WG + (grad ? (size_t)BMAX * BMAX : 0);
-    const size_t nacc = grad ? (size_t)nhyp + 1 : 0;
+    const size_t per_wg = PER_WG + (grad || loo ? (size_t)BMAX * BMAX : 0);
+    const size_t nacc = grad ? (size_t)nhyp + 1 : loo ? 2 : 0;
     // input block (one H2D): x | y | z | KConst | noise ; output block (one D2H): alpha | nll [| raw gradient sums] | info
     const size_t o_x = 0, o_y = o_x + up256(B * npts * 8), o_z = o_y + up256(B * npts * 8), o_kc = o_z + up256(B * n * 8),
                  o_no = o_kc + up256(B * sizeof(KConst)), in_bytes = o_no + up256(B * 8);
@@ -880,11 +1003,19 @@ int fit_batch_small(int family, int nbatch, int npts, int n, int reg, const doub
     const dim3 g(grid), t(LT);
     if (grad) {
         switch (family) {
-        case SGPR_FAM_A: hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_A, true>), g, t, 0, st, a); break;
-        case SGPR_FAM_B: hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_B, true>), g, t, 0, st, a); break;
-        case SGPR_FAM_C: hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_C, true>), g, t, 0, st, a); break;
-        case SGPR_FAM_USER: hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_USER, true>), g, t, 0, st, a); break;
-        default:         hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_D, true>), g, t, 0, st, a); break;
+        case SGPR_FAM_A: hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_A, MODE_GRAD>), g, t, 0, st, a); break;
+        case SGPR_FAM_B: hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_B, MODE_GRAD>), g, t, 0, st, a); break;
+        case SGPR_FAM_C: hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_C, MODE_GRAD>), g, t, 0, st, a); break;
+        case SGPR_FAM_USER: hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_USER, MODE_GRAD>), g, t, 0, st, a); break;
+        default:         hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_D, MODE_GRAD>), g, t, 0, st, a); break;
+        }
+    } else if (loo) {
+        switch (family) {
+        case SGPR_FAM_A: hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_A, MODE_LOO>), g, t, 0, st, a); break;
+        case SGPR_FAM_B: hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_B, MODE_LOO>), g, t, 0, st, a); break;
+        case SGPR_FAM_C: hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_C, MODE_LOO>), g, t, 0, st, a); break;
+        case SGPR_FAM_USER: hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_USER, MODE_LOO>), g, t, 0, st, a); break;
+        default:         hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_D, MODE_LOO>), g, t, 0, st, a); break;
         }
     } else {
         switch (family) {
@@ -917,6 +1048,14 @@ int fit_batch_small(int family, int nbatch, int npts, int n, int reg, const doub
             for (int k = 0; k < nhyp - 1; ++k) g[k] = 0.5 * sig * r[k];
             g[nhyp - 1] = 0.5 * r[nhyp - 1];
             g[nhyp] = (sig2n[b] < 0.0 ? -0.5 : 0.5) * r[nhyp];
+        }
+    }
+    if (loo) {
+        const double *raw = reinterpret_cast<const double *>(hout + o_nll) + B;
+        for (size_t b = 0; b < B; ++b) {
+            const bool bad = info[b] != 0;
+            if (bad) nll[b] = std::nan("");
+            for (int k = 0; k < 2; ++k) loo[b * 2 + k] = bad ? std::nan("") : raw[b * 2 + k];
         }
     }
     return 0;
@@ -957,6 +1096,15 @@ int fit_batch_grad(int family, int nbatch, int npts, const double *x, const doub
 {
     const int reg = (flags & SGPR_FIT_REG) ? 1 : 0;
     return fit_batch_small(family, nbatch, npts, reg ? npts : 2 * npts, reg, x, y, z, hyp, nhyp, sig2n, alpha, nll, info, grad);
+}
+
+// sgpr_fit_batch_loo: the arguments have been checked (capi.hip), nbatch > 0, n <= fit_batch_max_order()
+int fit_batch_loo(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
+                  int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, double *loo, int *info)
+{
+    const int reg = (flags & SGPR_FIT_REG) ? 1 : 0, n = reg ? npts : 2 * npts;
+    if (n > BMAX) return fit_batch_mid(family, nbatch, npts, n, reg, x, y, z, hyp, nhyp, sig2n, alpha, nll, info, nullptr, loo);
+    return fit_batch_small(family, nbatch, npts, n, reg, x, y, z, hyp, nhyp, sig2n, alpha, nll, info, nullptr, loo);
 }
 
 }  // namespace sgpr

@@ -95,9 +95,8 @@ static const double *fit_hyp_nd(const sgpr_fit *f, double buf[4], int *nhyp)
 // scratch for a solve with nrhs right-hand sides: the fit's own block, grown when a call needs more.  (Allocating and freeing
 // ~0.8 GB per call -- n = 98304 -- put milliseconds of idle device, a synchronising hipFree among them, in front of every
 // solve; see sgpr_fit_solve_rhs_dev for what that does to the first launch behind it.)
-static int rhs_scratch(sgpr_fit_t f, int nrhs, double **out, size_t extra = 0)
+static int fit_scratch(sgpr_fit_t f, size_t need, double **out)
 {
-    const size_t need = potrs_mat_scratch(f->n, nrhs, f->dA, (size_t)f->n) + extra;
     if (need > f->rhs_scratch_bytes) {
         if (f->rhs_scratch) { SGPR_HIP(hipStreamSynchronize(f->st)); (void)hipFree(f->rhs_scratch); }
         f->rhs_scratch = nullptr; f->rhs_scratch_bytes = 0;
@@ -106,6 +105,10 @@ static int rhs_scratch(sgpr_fit_t f, int nrhs, double **out, size_t extra = 0)
     }
     *out = static_cast<double *>(f->rhs_scratch);
     return 0;
+}
+static int rhs_scratch(sgpr_fit_t f, int nrhs, double **out, size_t extra = 0)
+{
+    return fit_scratch(f, potrs_mat_scratch(f->n, nrhs, f->dA, (size_t)f->n) + extra, out);
 }
 
 // X = L^-T L^-1 B for a device-resident B on the fit's stream, between the events of the solve_rhs stage
@@ -559,6 +562,29 @@ int sgpr_fit_nll_grad_full(sgpr_fit_t f, double *grad, int ngrad)
     grad[nhyp - 1] = 0.5 * raw[nhyp - 1];
     grad[nhyp] = (f->sig2n < 0.0 ? -0.5 : 0.5) * raw[nhyp];
     return 0;
+}
+
+/* Leave-one-point-out cross-validation of a solved fit (loo.hip): Ky^-1 by the row panels of the gradient, the D x D diagonal
+ * block of every point copied out of the panel that holds it, then one thread per point.  The factor, alpha, nll and the
+ * workspace are only read; the scratch is the fit's own block (sgpr_fit_trim gives it back). */
+int sgpr_fit_loo(sgpr_fit_t f, double *loo2, double *resid, double *cov, double *lpd)
+{
+    int rc = guard("fit_loo", f, loo2, NEED_SOLVED | NEED_ALL_BLOCKS);
+    if (rc) return rc;
+    const int D = (f->flags & SGPR_FIT_REG) ? 1 : 2 * f->d, N = f->npts;
+    const LooLayout o = loo_layout(f->n, N, D);
+    double *S;
+    if ((rc = fit_scratch(f, o.total * sizeof(double), &S))) return rc;
+    if ((rc = fit_loo(D, N, f->n, f->dA, (size_t)f->n, f->work, f->dalpha, S, f->st))) return rc;
+    int h[8] = {};   // the strip solves' state words, fetched in the results' synchronisation
+    SGPR_HIP(hipMemcpyAsync(loo2, S + o.sums, 2 * sizeof(double), hipMemcpyDeviceToHost, f->st));
+    if (resid) SGPR_HIP(hipMemcpyAsync(resid, S + o.resid, (size_t)f->n * sizeof(double), hipMemcpyDeviceToHost, f->st));
+    if (cov) SGPR_HIP(hipMemcpyAsync(cov, S + o.cov, (size_t)N * D * D * sizeof(double), hipMemcpyDeviceToHost, f->st));
+    if (lpd) SGPR_HIP(hipMemcpyAsync(lpd, S + o.lpd, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, f->st));
+    if (trsv_uses_strips(f->n, f->dA, (size_t)f->n))
+        SGPR_HIP(hipMemcpyAsync(h, trsv_state(f->n, f->work), sizeof(h), hipMemcpyDeviceToHost, f->st));
+    SGPR_HIP(hipStreamSynchronize(f->st));
+    return strip_give_up("fit_loo", h);
 }
 
 /* K*(2d x 2d N) . alpha for m test points Xt (m x 2d, column-major, leading dimension ldxt):

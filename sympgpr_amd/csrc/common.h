@@ -201,6 +201,18 @@ int nll_grad_full(int family, int d, bool reg, int N, int n, const double *L, si
                   const double *alpha, const double *l, const double *pp, int nacc, double *scratch, double *out,
                   hipStream_t st);
 
+// a row panel of Ky^-1 from the cached factor: memset, identity, the two recursive panel solves on L[J:, J:]
+int kyinv_panel_width(int n, const char *knob);                   // 2048 rows up to n = 8192, 4096 above; tunable `knob` overrides
+int kyinv_row_panel(int n, int J, int rows, const double *L, size_t ldl, const void *work, double *R, size_t ldr, hipStream_t st);
+
+// ---- loo.hip : leave-one-point-out cross-validation of a solved fit from the same row panels (sgpr_fit_loo)
+struct LooLayout { size_t panel, blocks, part, resid, cov, lpd, sums, total; };   // offsets in doubles into the scratch
+LooLayout loo_layout(int n, int N, int D);
+// D = 2d (pair fits, d = 1 .. 3) or 1 (reg); scratch: loo_layout(n, N, D).total doubles.  Leaves {loo, press} at
+// scratch + sums, the residuals (n, the layout of z) at + resid, the covariances (N x D x D) at + cov, lpd (N) at + lpd.
+int fit_loo(int D, int N, int n, const double *L, size_t ldl, const void *work, const double *alpha, double *scratch,
+            hipStream_t st);
+
 // ---- batch.hip : many small fits (order <= 256 each) in one launch, one workgroup per problem
 int fit_batch_max_order();
 int fit_batch_trim();                            // release the calling thread's batch arena (device + pinned host)
@@ -213,6 +225,10 @@ int fit_batch_grad(int family, int nbatch, int npts, const double *x, const doub
 // the same for 256 < order <= fit_batch_max_order(): the mid path's factor and solves, then Ky^-1 per problem on the matrix cores
 int fit_batch_grad_mid(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
                        int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, double *grad, int *info);
+// the batched fits with leave-one-point-out cross-validation, every order up to fit_batch_max_order(): loo is nbatch x 2,
+// row b = {loo, press}; the arguments have been checked (capi.hip), nbatch > 0
+int fit_batch_loo(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
+                  int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, double *loo, int *info);
 
 // ---- blas_small.hip
 int zero_strict_upper(int n, double *A, size_t lda, hipStream_t st);

@@ -239,8 +239,7 @@ struct Shape { int nb, ldr, npanels, gx, gy; size_t nwg; };
 Shape shape_of(int n, int N)
 {
     Shape s;
-    const int t = (int)tune("nllgrad_nb", 0);
-    s.nb = t > 0 && t % LEAF == 0 ? t : (n <= 8192 ? 2048 : 4096);
+    s.nb = kyinv_panel_width(n, "nllgrad_nb");
     s.ldr = n < s.nb ? n : s.nb;
     s.npanels = (n + s.nb - 1) / s.nb;
     s.gx = (s.ldr + NG_T - 1) / NG_T;
@@ -250,6 +249,27 @@ Shape shape_of(int n, int N)
 }
 
 }  // namespace
+
+// the rows of a panel of Ky^-1 (shape_of's rule, shared with loo.hip); `knob`: the caller's tunable
+int kyinv_panel_width(int n, const char *knob)
+{
+    const int t = (int)tune(knob, 0);
+    return t > 0 && t % LEAF == 0 ? t : (n <= 8192 ? 2048 : 4096);
+}
+
+// R (rows x (n - J), leading dimension ldr) = Ky^-1[J:J+rows, J:] from the factor L (order n) and its workspace
+int kyinv_row_panel(int n, int J, int rows, const double *L, size_t ldl, const void *work, double *R, size_t ldr, hipStream_t st)
+{
+    const int w = n - J;
+    int rc;
+    SGPR_HIP(hipMemsetAsync(R, 0, ldr * w * sizeof(double), st));
+    hipLaunchKernelGGL(panel_identity_kernel, dim3((rows + 255) / 256), dim3(256), 0, st, rows, R, ldr);
+    SGPR_CHECK_LAUNCH();
+    const double *Ltt = L + J + (size_t)J * ldl;
+    if ((rc = trsm_rlt_off(rows, w, Ltt, ldl, R, ldr, work, J, st))) return rc;   // R := R L_tt^-T
+    if ((rc = trsm_rl_off(rows, w, Ltt, ldl, R, ldr, work, J, st))) return rc;    // R := R L_tt^-1
+    return 0;
+}
 
 size_t nll_grad_full_scratch(int n, int N, int nacc)
 {
@@ -278,13 +298,8 @@ int nll_grad_full(int family, int d, bool reg, int N, int n, const double *L, si
     double *R = scratch;
     int rc;
     for (int p = 0; p < s.npanels; ++p) {
-        const int J = p * s.nb, rows = n - J < s.nb ? n - J : s.nb, w = n - J;
-        SGPR_HIP(hipMemsetAsync(R, 0, (size_t)s.ldr * w * sizeof(double), st));
-        hipLaunchKernelGGL(panel_identity_kernel, dim3((rows + 255) / 256), dim3(256), 0, st, rows, R, (size_t)s.ldr);
-        SGPR_CHECK_LAUNCH();
-        const double *Ltt = L + J + (size_t)J * ldl;
-        if ((rc = trsm_rlt_off(rows, w, Ltt, ldl, R, (size_t)s.ldr, work, J, st))) return rc;   // R := R L_tt^-T
-        if ((rc = trsm_rl_off(rows, w, Ltt, ldl, R, (size_t)s.ldr, work, J, st))) return rc;    // R := R L_tt^-1
+        const int J = p * s.nb, rows = n - J < s.nb ? n - J : s.nb;
+        if ((rc = kyinv_row_panel(n, J, rows, L, ldl, work, R, (size_t)s.ldr, st))) return rc;
         a.J = J; a.rows = rows; a.wg0 = (size_t)p * s.gx * s.gy;
         const dim3 grid(s.gx, s.gy);
         auto launch = [&](auto fam, auto dd, auto hp) {

@@ -203,6 +203,31 @@ class SympFit:
         L.check(self._lib.sgpr_fit_nll_grad_full(self._h, L.dptr(g), len(g)), "sgpr_fit_nll_grad_full")
         return g
 
+    def loo(self, resid=True, cov=False, lpd=True):
+        """Leave-one-point-out cross-validation of a solved fit -> dict with "loo", "press" and the requested arrays.
+        Point i owns D rows of Ky (D = 2d; 1 with reg=True), and leaving it out removes them together.  "resid" (N, D): column c
+        is part c of the observed rows minus their prediction from the fit without point i; "cov" (N, D, D): the covariance of
+        that prediction, noise included, indexed as predict_cov's and exactly symmetric; "lpd" (N,): the log predictive density
+        of the left-out rows.  loo = -sum lpd is an objective to minimise like nll(); press = sum |resid_i|^2.  A point whose
+        block of Ky^-1 is not positive definite to rounding gives NaN in its entries and in loo and press.  Exact (Ky^-1 from
+        the cached factor by row panels, 2 n^3 / 3 flop), deterministic, and the factor, alpha and nll() are left as they are.
+        Not defined for block="qq" / "PP" fits."""
+        N, D = self.n_pts, 1 if self.reg else 2 * self.d
+        two = np.empty(2)
+        r = np.empty(self.n) if resid else None
+        c = np.empty((N, D, D)) if cov else None
+        l = np.empty(N) if lpd else None
+        opt = lambda a: L.dptr(a) if a is not None else None
+        L.check(self._lib.sgpr_fit_loo(self._h, L.dptr(two), opt(r), opt(c), opt(l)), "sgpr_fit_loo")
+        out = {"loo": float(two[0]), "press": float(two[1])}
+        if resid:
+            out["resid"] = np.ascontiguousarray(r.reshape(D, N).T)
+        if cov:
+            out["cov"] = c
+        if lpd:
+            out["lpd"] = l
+        return out
+
     def nll_grad_terms(self):
         """[alpha^T dK_lx alpha, tr(Ky^-1 dK_lx), alpha^T dK_ly alpha, tr(Ky^-1 dK_ly), tr(Ky^-1)]: the
         pieces of Rasmussen (5.9) the per-example nll_grad variants recombine."""
@@ -393,3 +418,26 @@ def fit_batch_grad_mid(family, x, y, z, hyp, sig2n, reg=False, want_alpha=False)
                                                      L.dptr(alpha) if want_alpha else None, L.dptr(nll), L.dptr(grad),
                                                      info.ctypes.data_as(C.POINTER(C.c_int))), "sgpr_fit_batch_grad_mid")
     return alpha, nll, grad, info
+
+
+def fit_batch_loo(family, x, y, z, hyp, sig2n, reg=False, want_alpha=False):
+    """fit_batch plus leave-one-point-out cross-validation of every problem (SympFit.loo's definitions, D = 2; 1 with reg), for
+    every order up to batch_max_order().  Shapes as fit_batch:
+        x, y (B, n_pts);  z (B, n), n = 2 n_pts (n_pts with reg);  hyp (B, nhyp);  sig2n (B,) or scalar.
+    -> (alpha (B, n) or None, nll (B,), loo (B, 2), info (B,)).  Row b of loo is (loo, press).  Rows with info > 0 are NaN (nll
+    and the loo row).  nll, alpha and info are the same bits fit_batch returns; a row's loo bits do not depend on the batch."""
+    x, y, z, hyp = (np.ascontiguousarray(np.atleast_2d(np.asarray(v, dtype=np.float64))) for v in (x, y, z, hyp))
+    B, n_pts = x.shape
+    n = n_pts if reg else 2 * n_pts
+    if y.shape != (B, n_pts) or z.shape != (B, n) or hyp.shape[0] != B:
+        raise ValueError("fit_batch_loo: x, y (B, n_pts), z (B, n), hyp (B, nhyp)")
+    s2 = np.ascontiguousarray(np.broadcast_to(np.asarray(sig2n, dtype=np.float64), (B,)))
+    alpha = np.empty((B, n)) if want_alpha else None
+    nll = np.empty(B)
+    loo = np.empty((B, 2))
+    info = np.zeros(B, dtype=np.int32)
+    L.check(L.load_library().sgpr_fit_batch_loo(L.family_id(family), B, n_pts, L.dptr(x), L.dptr(y), L.dptr(z), L.dptr(hyp),
+                                                hyp.shape[1], L.dptr(s2), L.FIT_REG if reg else 0,
+                                                L.dptr(alpha) if want_alpha else None, L.dptr(nll), L.dptr(loo),
+                                                info.ctypes.data_as(C.POINTER(C.c_int))), "sgpr_fit_batch_loo")
+    return alpha, nll, loo, info

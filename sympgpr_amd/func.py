@@ -215,6 +215,63 @@ def nll_chol_grad_batch(hyps, x, y, N, reg=False, mid=None):
     return nll, grad
 
 
+def _loo_one(hyp, x, y, N, reg):
+    from .fit import batch_max_order, fit_batch_loo
+    hyp = np.asarray(hyp, dtype=np.float64)
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    if N <= 0:
+        raise ValueError("loo_chol: N must be positive")
+    X, Y, Z = _batch_data(x, y, N, reg)
+    if len(X) != (N if reg else N // 2) or len(Y) != len(X) or len(Z) != (N if reg else 2 * len(X)):
+        raise ValueError("loo_chol: x holds 2 * n_pts coordinates and y the n targets of order N")
+    if len(Z) <= batch_max_order():
+        _, _, loo, info = fit_batch_loo(get_family(), X[None], Y[None], Z[None], hyp[None, :-1], np.abs(hyp[-1:]), reg=reg)
+        if info[0]:
+            raise np.linalg.LinAlgError("%d-th leading minor of the array is not positive definite" % int(info[0]))
+        return float(loo[0, 0])
+    with SympFit(get_family(), X, Y, Z, hyp[:-1], np.abs(hyp[-1]), reg=reg) as f:
+        return f.run().loo(resid=False, lpd=False)["loo"]
+
+
+def loo_chol(hyp, x, y, N):
+    """The leave-one-point-out objective of the symplectic GP, with nll_chol's arguments: minus the sum over the training points
+    of the log predictive density of a point's two observed rows given all other points (SympFit.loo).  Minimised like
+    nll_chol.  Up to order fit.batch_max_order() one batched call with a batch of one, above it a device-resident fit;
+    raises LinAlgError where nll_chol does."""
+    return _loo_one(hyp, x, y, N, False)
+
+
+def loo_chol_reg(hyp, x, y, N):
+    """loo_chol for the scalar-kernel GP, with nll_chol_reg's arguments (one row per point)."""
+    return _loo_one(hyp, x, y, N, True)
+
+
+def loo_chol_batch(hyps, x, y, N, reg=False):
+    """loo_chol (reg=True: loo_chol_reg) for a whole population of hyper-parameter vectors over the same data, the counterpart
+    of nll_chol_batch: hyps (B, nhyp + 1) -> the vector of objectives (B,).  Rows whose Ky is not positive definite come back
+    as NaN.  Orders above fit.batch_max_order(): a loop over the scalar call."""
+    from .fit import batch_max_order, fit_batch_loo
+    hyps = np.atleast_2d(np.asarray(hyps, dtype=np.float64))
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    if N > batch_max_order():
+        out = np.empty(len(hyps))
+        for b, h in enumerate(hyps):
+            try:
+                out[b] = _loo_one(h, x, y, N, reg)
+            except np.linalg.LinAlgError:
+                out[b] = np.nan
+        return out
+    if N <= 0:
+        raise ValueError("loo_chol_batch: N must be positive")
+    X, Y, Z = _batch_data(x, y, N, reg)
+    B = len(hyps)
+    _, _, loo, _ = fit_batch_loo(get_family(), np.broadcast_to(X, (B, len(X))), np.broadcast_to(Y, (B, len(Y))),
+                                 np.broadcast_to(Z, (B, len(Z))), hyps[:, :-1], np.abs(hyps[:, -1]), reg=reg)
+    return loo[:, 0].copy()
+
+
 def guessP(x, y, hypp, xtrainp, ztrainp, Kyinvp):
     """functions/func.py:198-201."""
     Ntrain = len(xtrainp) // 2
