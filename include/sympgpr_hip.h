@@ -199,6 +199,24 @@ int sgpr_fit_predict_nd(sgpr_fit_t f, int m, const double *Xt, size_t ldxt, doub
  * Device scratch: the fit's block-solve scratch plus one n x 256 block of doubles and a 256 x 256 one, kept until
  * sgpr_fit_trim.  Added in ABI 5 (an additional entry point). */
 int sgpr_fit_predict_cov(sgpr_fit_t f, int m, const double *Xt, size_t ldxt, double *mean, double *cov);
+/* The learned generating function F itself (every other prediction entry returns its derivatives) and its variance at m test
+ * points.  Xt (m x 2d, column-major, ldxt >= max(m, 1); (q, P) for a d = 1 pair fit).  With dx = x_j - x* per coordinate,
+ * g_c = f_c'/f_c and E = sig k (product kernels; E_c = sig f_c for the sum kernels), over the N training points x_j:
+ *   F(x*)   = sum_j sum_c E_c g_c alpha[c N + j]                    (dF/dq = sgpr_fit_predict_rows' out_p, dF/dP = its out_q),
+ *   v_t     = the same summands without alpha (n entries), kappa(t, s) = sig k(x_t, x_s),
+ *   var_t   = kappa(t, t) - |L^-1 v_t|^2                                                       without a reference point,
+ *   F_t     = F(x_t) - F(x_0),  var_t = kappa(t, t) - 2 kappa(t, 0) + kappa(0, 0) - |L^-1 (v_t - v_0)|^2    with ref = x_0.
+ * ref: 2d doubles or NULL.  Derivative observations do not fix the constant of F: without ref the variance is dominated by
+ * that constant and does not vanish with data; the variance of a difference does.  F at a point equal to ref is exactly 0.
+ * F (m); var (m) or NULL, which skips the solves.  The variance is the latent posterior (no |sig2n| added) and is returned as
+ * computed: rounding can leave it slightly negative.  A point with a coordinate that is not finite gives NaN in its F and var
+ * only (status 0); a ref that is not finite gives NaN everywhere.  The results are deterministic, and a point's bits do not
+ * depend on the other points of the call.  The factor, alpha, the NLL and the workspace are left as they are.
+ * SGPR_E_ARG -- before any device work, the message names predict_genfun -- for a null handle, m < 0, ldxt < max(m, 1), a null
+ * Xt or F with m > 0, and for an SGPR_FIT_REG fit (which models F directly: sgpr_fit_predict_rows); SGPR_E_STATE before a solve
+ * and for SGPR_FIT_BLOCK_QQ / _PP fits; SGPR_E_HIP if a strip solve gave up on a hand-off.  m = 0 returns 0.
+ * Device scratch (var only): as sgpr_fit_predict_cov, kept until sgpr_fit_trim.  ABI 5 (an additional entry point). */
+int sgpr_fit_predict_genfun(sgpr_fit_t f, int m, const double *Xt, size_t ldxt, const double *ref, double *F, double *var);
 /* Gradient of the fit's NLL (1/2 z^T alpha + sum log L_ii) in every hyperparameter, from the cached factor and alpha:
  * grad_theta = 1/2 sum_ij (Ky^-1 - alpha alpha^T)_ij dKy_ij/dtheta.  ngrad must be nhyp + 1.  grad[0 .. nhyp-1] follow the
  * fit's hyp order -- d = 1 and SGPR_FIT_REG (lx, ly, [p,] sig), create_nd (lq_1..lq_d, lP_1..lP_d, [p_1..p_d,] sig) --, and

@@ -71,6 +71,7 @@ SIGNATURES = {
     "sgpr_fit_inverse": (C.c_int, [_vp, _dp, C.c_size_t]),
     "sgpr_fit_predict_nd": (C.c_int, [_vp, C.c_int, _dp, C.c_size_t, _dp]),
     "sgpr_fit_predict_cov": (C.c_int, [_vp, C.c_int, _dp, C.c_size_t, _dp, _dp]),
+    "sgpr_fit_predict_genfun": (C.c_int, [_vp, C.c_int, _dp, C.c_size_t, _dp, _dp, _dp]),
     "sgpr_fit_nll_grad_full": (C.c_int, [_vp, _dp, C.c_int]),
     "sgpr_fit_loo": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),
     "sgpr_fit_stage_ms": (C.c_int, [_vp, _dp, _dp, _dp]),

@@ -657,6 +657,71 @@ int sgpr_fit_predict_cov(sgpr_fit_t f, int m, const double *Xt, size_t ldxt, dou
     return 0;
 }
 
+/* The generating function F itself at m test points (gram_nd.hip: genfun_nd_kernel), relative to `ref` if one is given, and
+ * with `var` its latent posterior variance, in chunks of mc = 256 points:
+ *   per chunk  V = the cross-covariance columns v_t - v_0 (n x mc, genfun_cross_kernel) and the prior of F(x_t) - F(x_0),
+ *              V := L^-1 V (potrs_mat_fwd, as sgpr_fit_predict_cov), var_t = prior_t - |V_t|^2 (postcov.hip with D = 1: the
+ *              priors lie on the diagonal of its K** argument, so its kernels serve as they are).
+ * The reference point travels as row m of the uploaded points.  Scratch: the fit's rhs_scratch, [solve scratch | V | the
+ * 256 x 256 block whose diagonal holds the priors | stage-1 partial sums].  The factor, alpha, nll and the workspace are only read. */
+int sgpr_fit_predict_genfun(sgpr_fit_t f, int m, const double *Xt, size_t ldxt, const double *ref, double *F, double *var)
+{
+    const char *me = "fit_predict_genfun";
+    int rc = guard(me, f, m >= 0 && ldxt >= (size_t)(m > 0 ? m : 1) && (m == 0 || (Xt && F)));
+    if (rc) return rc;
+    if (f->flags & SGPR_FIT_REG) {
+        set_error("fit_predict_genfun: a scalar-kernel fit models F itself: sgpr_fit_predict_rows returns it");
+        return SGPR_E_ARG;
+    }
+    if ((rc = guard(me, f, true, NEED_SOLVED | NEED_ALL_BLOCKS)) || m == 0) return rc;
+    const int D = 2 * f->d, mc = POSTCOV_COLS;
+    const size_t n = (size_t)f->n, M1 = (size_t)m + 1;
+    DevBuf dT, dF, dVar;
+    if ((rc = dT.alloc(M1 * D * sizeof(double))) || (rc = dF.alloc(M1 * sizeof(double))) ||
+        (var && (rc = dVar.alloc((size_t)m * sizeof(double)))))
+        return rc;
+    double *T = dT.as<double>(), *Fd = dF.as<double>(), *Vr = dVar.as<double>();
+    if ((rc = copy_in(T, M1, Xt, ldxt, (size_t)m, D, f->st))) return rc;
+    if (ref && (rc = copy_in(T + m, M1, ref, 1, 1, D, f->st))) return rc;
+    const double *x0 = ref ? T + m : nullptr;
+    double hyp1[4];
+    int nhyp;
+    const double *hyp = fit_hyp_nd(f, hyp1, &nhyp);   // the d-pair kernels whatever the fit's layout: d = 1 too
+    if ((rc = genfun_nd(f->family, f->d, m, T, M1, ref != nullptr, f->npts, f->dX, (size_t)f->npts, hyp, nhyp, f->dalpha, Fd, f->st)))
+        return rc;
+    if (var) {
+        auto up = [](size_t b) { return (b + 255) / 256 * 256; };   // the layout of sgpr_fit_predict_cov with D mc = 256 columns
+        const size_t solve_raw = potrs_mat_scratch(f->n, mc, f->dA, n), solve_b = up(solve_raw);
+        const size_t v_b = up(n * mc * sizeof(double)), k_b = up((size_t)mc * mc * sizeof(double));
+        const size_t p_b = up(postcov_partial_doubles(f->n, 1, mc) * sizeof(double));
+        double *S;
+        if ((rc = rhs_scratch(f, mc, &S, solve_b - solve_raw + v_b + k_b + p_b))) return rc;
+        char *base = reinterpret_cast<char *>(S);
+        double *V = reinterpret_cast<double *>(base + solve_b), *Kss = reinterpret_cast<double *>(base + solve_b + v_b);
+        double *part = reinterpret_cast<double *>(base + solve_b + v_b + k_b);
+        for (int c0 = 0; c0 < m; c0 += mc) {
+            const int cnt = m - c0 < mc ? m - c0 : mc;
+            if ((rc = genfun_cross_nd(f->family, f->d, cnt, T + c0, M1, x0, M1, f->npts, f->dX, (size_t)f->npts, hyp, nhyp, V, n, Kss,
+                                      (size_t)mc + 1, f->st)))
+                return rc;
+            int ncols = cnt;
+            if (cnt == 1) {   // a single column would take another solve path than a block (potrs_mat_uses_strips) and get
+                              // other bits than the same point has inside a larger call: a column of zeros rides along
+                SGPR_HIP(hipMemsetAsync(V + n, 0, n * sizeof(double), f->st));
+                ncols = 2;
+            }
+            if ((rc = potrs_mat_fwd(f->n, f->dA, n, f->work, V, n, ncols, S, f->st))) return rc;
+            if ((rc = postcov(1, f->n, cnt, V, n, Kss, (size_t)mc, part, Vr + c0, f->st))) return rc;
+            // waits for the chunk; the next chunk's solve clears the give-up words, so they are read here
+            if ((rc = solve_status(f->n, f->dA, n, f->work, f->st))) return rc;
+        }
+        SGPR_HIP(hipMemcpyAsync(var, Vr, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, f->st));
+    }
+    SGPR_HIP(hipMemcpyAsync(F, Fd, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, f->st));
+    SGPR_HIP(hipStreamSynchronize(f->st));
+    return 0;
+}
+
 /* nm steps of the fit's symplectic map (gram_nd.hip: applymap_nd_kernel) for ntest orbits, with the fit's own device-resident
  * training points and alpha; d = 1 fits run the D = 2 instance of the d-pair kernel. */
 int sgpr_fit_applymap_nd(sgpr_fit_t f, int mode, int nm, int ntest, const double *Q0, size_t ldq, const double *P0, size_t ldp,

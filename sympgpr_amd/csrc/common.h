@@ -83,6 +83,13 @@ int applymap_nd(int family, int d, int mode, int nm, int ntest, int n0, const do
 int applymap_nd_tangent(int family, int d, int mode, int nm, int ntest, int n0, const double *Xtr, size_t ldxtr, const double *hyp,
                         int nhyp, const double *alpha, const double *Q0, const double *P0, double *qmap, double *pmap, int *iters,
                         double *jac, double *mono, double *lyap, hipStream_t st);
+// the generating function F itself at m device-resident test points (has_ref: row m of Xt is a reference point, F has m + 1
+// entries and F[t] := F(x_t) - F(x_0)); one chunk of its variance: the cross-covariance columns V (2 d n0 x mc) and the prior
+int genfun_nd(int family, int d, int m, const double *Xt, size_t ldxt, bool has_ref, int n0, const double *Xtr, size_t ldxtr,
+              const double *hyp, int nhyp, const double *alpha, double *F, hipStream_t st);
+int genfun_cross_nd(int family, int d, int mc, const double *Xt, size_t ldxt, const double *x0, size_t ldx0, int n0,
+                    const double *Xtr, size_t ldxtr, const double *hyp, int nhyp, double *V, size_t ldv, double *prior,
+                    size_t prior_stride, hipStream_t st);
 bool family_is_sum(int family);   // k = sum of the factors (family B, or a USER sum kernel): the explicit maps
 
 // ---- gemm_f64.hip : C = beta C + alpha A B^T on fp64 MFMA tiles

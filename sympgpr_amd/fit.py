@@ -100,6 +100,51 @@ class SympFit:
                 "sgpr_fit_predict_cov")
         return mean, cov
 
+    def predict_genfun(self, q, P, ref=None, var=False):
+        """The learned generating function F itself at the test points (q, P) of a d = 1 pair fit -> F (m,), or (F, var) with
+        var=True.  Every other prediction returns derivatives of this F: dF/dq = predict_rows' out_p and dF/dP = its out_q.
+        ref = (q0, P0): F(q, P) - F(q0, P0) and the variance of that difference; at a point equal to ref, F is exactly 0.0.
+        The variance is that of the latent posterior (no |sig2n| added) and is returned as computed, so rounding can leave it
+        slightly negative.  Derivative observations do not fix the constant of F: without ref the variance is dominated by the
+        undetermined constant and does not vanish with data, while the variance of a difference does.  A NaN coordinate gives
+        NaN for that point only.  Needs a solved fit (run()); not defined for reg=True (there predict_rows returns F) and
+        block="qq" / "PP" fits."""
+        if self.d != 1:
+            raise ValueError("predict_genfun is for d = 1 fits: use predict_pairs_genfun")
+        if self.reg:
+            raise ValueError("predict_genfun is not defined for a reg=True fit: predict_rows returns its F")
+        q, P = L.f64(np.atleast_1d(q)), L.f64(np.atleast_1d(P))
+        if q.shape != P.shape or q.ndim != 1:
+            raise ValueError("q and P must be 1-D arrays of equal length")
+        return self._predict_genfun(np.asfortranarray(np.column_stack((q, P)).reshape(len(q), 2)), ref, var)
+
+    def predict_pairs_genfun(self, Xt, ref=None, var=False):
+        """The learned generating function F itself at test points Xt (m, 2d) of a create_nd / pairs fit -> F (m,), or (F, var)
+        with var=True.  predict_pairs returns its gradient: column a is dF/dx_a (for d = 1: dF/dq = predict_rows' out_p and
+        dF/dP = its out_q).  ref (2d,): F(x) - F(ref) and the variance of that difference; at a point equal to ref, F is exactly
+        0.0.  The variance is that of the latent posterior (no |sig2n| added) and is returned as computed, so rounding can
+        leave it slightly negative.  Derivative observations do not fix the constant of F: without ref the variance is
+        dominated by the undetermined constant and does not vanish with data, while the variance of a difference does.  A NaN
+        coordinate gives NaN for that point only.  Needs a solved fit (run()); not defined for reg=True fits."""
+        if self.reg:
+            raise ValueError("predict_pairs_genfun is not defined for a reg=True fit: predict_rows returns its F")
+        Xt = np.asfortranarray(np.atleast_2d(Xt), dtype=np.float64)
+        if Xt.ndim != 2 or Xt.shape[1] != 2 * self.d:
+            raise ValueError("Xt must be (m, %d)" % (2 * self.d))
+        return self._predict_genfun(Xt, ref, var)
+
+    def _predict_genfun(self, Xt, ref, var):
+        m = Xt.shape[0]
+        if ref is not None:
+            ref = L.f64(np.ravel(ref))
+            if ref.shape != (2 * self.d,):
+                raise ValueError("ref must hold %d coordinates" % (2 * self.d))
+        F = np.empty(m)
+        v = np.empty(m) if var else None
+        L.check(self._lib.sgpr_fit_predict_genfun(self._h, m, L.dptr(Xt), max(m, 1), L.dptr(ref) if ref is not None else None,
+                                                  L.dptr(F), L.dptr(v) if var else None), "sgpr_fit_predict_genfun")
+        return (F, v) if var else F
+
     def applymap_pairs(self, nm, Q0, P0, wrap_q=False, explicit=False, return_iters=False):
         """nm - 1 steps of the fit's symplectic map for the start points Q0, P0 (Ntest, d) -- for d = 1 also (Ntest,) --, every
         step on the device: per step the implicit equation G_q(q, P) - p + P = 0 is solved for P by Newton with the analytic

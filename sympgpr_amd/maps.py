@@ -13,6 +13,7 @@ For fits with d canonical pairs (d = 1, 2, 3) the map is run_map_nd / SympFit.ap
 Jacobian on the d unknowns P, one workgroup per orbit (include/sympgpr_hip.h: sgpr_applymap_nd_host).
 run_map_nd_tangent / SympFit.applymap_pairs_tangent return the same orbits with the Jacobian of every step, their product and
 finite-time Lyapunov exponents (sgpr_applymap_nd_tangent_host); symplectic_defect and greene_residue read them.
+genfun_along evaluates the learned generating function itself along computed orbits (sgpr_fit_predict_genfun).
 
 alpha = Kyinv ztrain is formed once (the reference re-multiplies Kyinv inside every calcP / calcQ
 call); a residual of the implicit equation is one block-wide reduction over the training points.
@@ -185,6 +186,23 @@ def run_map_nd_tangent(family, d, mode, nm, hyp, X, alpha, Q0, P0, jac=True, mon
                                               _optr(out, "jac"), _optr(out, "mono"), _optr(out, "lyap")),
             "sgpr_applymap_nd_tangent_host")
     return qmap, pmap, iters, out
+
+
+def genfun_along(fit, qmap, pmap, ref=None):
+    """The fit's learned generating function along computed orbits: F(q_k, P_{k+1}) for k = 0 .. nm-2 -> (nm - 1, Ntest), an
+    energy-like diagnostic that needs no analytic H.  qmap, pmap: (nm, Ntest) or (nm, Ntest, d) as applymap / applymap_pairs
+    return them; ref as SympFit.predict_genfun / predict_pairs_genfun take it.  One device call over all steps and orbits, the
+    bits of predict_genfun / predict_pairs_genfun on the stacked points; a lost (NaN) orbit stays NaN."""
+    qmap, pmap = np.asarray(qmap, dtype=np.float64), np.asarray(pmap, dtype=np.float64)
+    if qmap.shape != pmap.shape or qmap.ndim not in (2, 3) or qmap.shape[0] < 1:
+        raise ValueError("qmap and pmap must both be (nm, Ntest) or (nm, Ntest, d)")
+    nm, Ntest = qmap.shape[:2]
+    d = 1 if qmap.ndim == 2 else qmap.shape[2]
+    if d != fit.d:
+        raise ValueError("the orbits have d = %d, the fit d = %d" % (d, fit.d))
+    Xt = np.asfortranarray(np.hstack((qmap[:-1].reshape(-1, d), pmap[1:].reshape(-1, d))))
+    F = fit.predict_genfun(Xt[:, 0], Xt[:, 1], ref=ref) if qmap.ndim == 2 else fit.predict_pairs_genfun(Xt, ref=ref)
+    return F.reshape(nm - 1, Ntest)
 
 
 def symplectic_defect(M):
