@@ -450,6 +450,28 @@ int sgpr_applymap_host(int family, int mode, int nm, int ntest, const double *hy
                        const double *hypp, int nhypp, int n0p, const double *xtrainp,
                        const double *ytrainp, const double *alphap, const double *Q0,
                        const double *P0, double *qmap, double *pmap, double *pdiff);
+/* The SECTIONED map (05_tokamak/Split_SympGPR/func.py:184-219): nsec independent GP pairs of one size, one per toroidal
+ * section, applied in turn -- step i -> i + 1 of every orbit uses section (first + i) mod nsec -- with all nm - 1 steps of all
+ * ntest orbits in ONE launch.  The step is sgpr_applymap_host's (same secant, tol, maxiter, acceptance rule, mode bits, pdiff,
+ * NaN for a lost orbit), and with nsec == 1 the outputs have that entry's bits wherever it runs one workgroup per orbit.  One
+ * 256-thread workgroup per orbit at every n0; no workgroup waits for another.  An orbit's bits depend on nothing but its own
+ * start point, `first` and the sections: a map continued from row i with first' = (first + i) mod nsec repeats the bits of
+ * the uninterrupted one.
+ * Layout (host arrays, column-major and tight, one column per section):
+ *   hyp      nhyp x nsec: section s at hyp + s * nhyp, (lx, ly, sig) -- (lx, ly, p, sig) for family D
+ *   xtrain, ytrain  n0 x nsec;  alpha  2 n0 x nsec (column s = Ky_s^-1 ztrain_s: what sgpr_fit_batch returns, stacked)
+ *   hypp     nhypp x nsec;  xtrainp, ytrainp, alphap  n0p x nsec: the regular GPs of the first guess.  With
+ *            SGPR_MAP_EXPLICIT they are ignored (n0p treated as 0) and may be NULL
+ *   Q0, P0   ntest;  qmap, pmap, pdiff (may be NULL)  [nm][ntest] C-ordered, row 0 = the start points
+ * Checked before any device call (SGPR_E_ARG): nsec < 1, first outside [0, nsec), nm < 1, negative ntest / n0 / n0p, an
+ * unknown mode bit, SGPR_MAP_EXPLICIT | SGPR_MAP_LOSS_NEGP, a null required pointer, an unknown family, a wrong nhyp / nhypp
+ * for the family.  Then SGPR_E_NODEVICE without a device; ntest == 0 returns 0; nm == 1 writes the start row only.
+ * Added in ABI 5 (additional entry point). */
+int sgpr_applymap_sections_host(int family, int mode, int nsec, int first, int nm, int ntest,
+                                const double *hyp, int nhyp, int n0, const double *xtrain, const double *ytrain,
+                                const double *alpha, const double *hypp, int nhypp, int n0p, const double *xtrainp,
+                                const double *ytrainp, const double *alphap, const double *Q0, const double *P0,
+                                double *qmap, double *pmap, double *pdiff);
 /* The symplectic map of a fit with d canonical pairs (d = 1, 2, 3), nm - 1 steps for ntest orbits with every step on the
  * device: one workgroup per orbit, no workgroup waits on another.  With x = (q_1..q_d, P_1..P_d) and G(x) = K*(x) alpha (what
  * sgpr_fit_predict_nd returns: G_q = dF/dq = p - P, G_P = dF/dP = Q - q) a step solves

@@ -393,6 +393,54 @@ int sgpr_applymap_host(int family, int mode, int nm, int ntest, const double *hy
     return applymap_status(tw.p, ntest, n0);
 }
 
+/* The sectioned map (05_tokamak/Split_SympGPR/func.py:184-219): nsec GP pairs applied in turn, every step of every orbit in
+ * one launch.  Every argument is checked before any device call. */
+int sgpr_applymap_sections_host(int family, int mode, int nsec, int first, int nm, int ntest, const double *hyp, int nhyp, int n0,
+                                const double *xtrain, const double *ytrain, const double *alpha, const double *hypp, int nhypp,
+                                int n0p, const double *xtrainp, const double *ytrainp, const double *alphap, const double *Q0,
+                                const double *P0, double *qmap, double *pmap, double *pdiff)
+{
+    auto E = [](const char *what) { set_error(std::string("applymap_sections_host: ") + what); return SGPR_E_ARG; };
+    const bool expl = (mode & SGPR_MAP_EXPLICIT) != 0;
+    if (expl) n0p = 0;                       /* no first-guess GPs in the explicit map */
+    if (mode & ~(SGPR_MAP_WRAP_Q | SGPR_MAP_WRAP_P | SGPR_MAP_EXPLICIT | SGPR_MAP_LOSS_NEGP)) return E("unknown mode bit");
+    if (expl && (mode & SGPR_MAP_LOSS_NEGP)) return E("SGPR_MAP_LOSS_NEGP belongs to the implicit map");
+    if (nsec < 1) return E("nsec < 1");
+    if (first < 0 || first >= nsec) return E("first outside [0, nsec)");
+    if (nm < 1) return E("nm < 1");
+    if (ntest < 0 || n0 < 0 || n0p < 0) return E("negative ntest, n0 or n0p");
+    if (!hyp || (!expl && !hypp) || !Q0 || !P0 || !qmap || !pmap) return E("null hyp, hypp, Q0, P0, qmap or pmap");
+    if ((n0 > 0 && (!xtrain || !ytrain || !alpha)) || (n0p > 0 && (!xtrainp || !ytrainp || !alphap)))
+        return E("null training points or alpha");
+    int rc;
+    std::vector<KConst> kc(2 * (size_t)nsec);           /* the sections' constants: nsec for the map, nsec for the guess */
+    for (int s = 0; s < nsec; ++s) {
+        if ((rc = make_kconst(family, hyp + (size_t)s * nhyp, nhyp, &kc[s]))) return rc;
+        if (!expl && (rc = make_kconst(family, hypp + (size_t)s * nhypp, nhypp, &kc[nsec + s]))) return rc;
+    }
+    if ((rc = need_device())) return rc;
+    if (ntest == 0) return 0;
+    DevBuf x, y, al, xp, yp, alp, dk, q0, p0, qm, pm, pd;
+    hipStream_t st = nullptr;
+    const size_t ns = (size_t)nsec, out_bytes = (size_t)nm * ntest * sizeof(double);
+    static_assert(sizeof(KConst) % sizeof(double) == 0, "KConst is uploaded as doubles");
+    if ((rc = upload(x, xtrain, ns * n0, st)) || (rc = upload(y, ytrain, ns * n0, st)) || (rc = upload(al, alpha, 2 * ns * n0, st)) ||
+        (rc = upload(xp, xtrainp, ns * n0p, st)) || (rc = upload(yp, ytrainp, ns * n0p, st)) || (rc = upload(alp, alphap, ns * n0p, st)) ||
+        (rc = upload(dk, reinterpret_cast<const double *>(kc.data()), kc.size() * (sizeof(KConst) / sizeof(double)), st)) ||
+        (rc = upload(q0, Q0, ntest, st)) || (rc = upload(p0, P0, ntest, st)) || (rc = qm.alloc(out_bytes)) ||
+        (rc = pm.alloc(out_bytes)) || (pdiff && (rc = pd.alloc(out_bytes))))
+        return rc;
+    rc = applymap_sections(family, mode, nsec, first, nm, ntest, n0, x.as<double>(), y.as<double>(), al.as<double>(),
+                           dk.as<KConst>(), n0p, xp.as<double>(), yp.as<double>(), alp.as<double>(), dk.as<KConst>() + nsec,
+                           q0.as<double>(), p0.as<double>(), qm.as<double>(), pm.as<double>(), pdiff ? pd.as<double>() : nullptr, st);
+    if (rc) return rc;
+    SGPR_HIP(hipMemcpyAsync(qmap, qm.p, out_bytes, hipMemcpyDeviceToHost, st));
+    SGPR_HIP(hipMemcpyAsync(pmap, pm.p, out_bytes, hipMemcpyDeviceToHost, st));
+    if (pdiff) SGPR_HIP(hipMemcpyAsync(pdiff, pd.p, out_bytes, hipMemcpyDeviceToHost, st));
+    SGPR_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
 /* The d-pair map from caller-supplied training points and alpha (the counterpart of sgpr_applymap_host for d canonical pairs):
  * every argument is checked before any device call. */
 int sgpr_applymap_nd_host(int family, int d, int mode, int nm, int ntest, const double *hyp, int nhyp, int n0, const double *X,

@@ -65,6 +65,12 @@ int applymap(int family, int mode, int nm, int ntest, int n0, const double *xtr,
              double *pmap, double *pdiff, void *team_ws, hipStream_t st);
 int applymap_status(const void *team_ws, int ntest, int n0);
 unsigned applymap_last_calls();                 // K*-row evaluations (all orbits) of the last applymap of this process   // after the stream has been waited for: SGPR_E_HIP if a team gave up
+// the sectioned map (Split_SympGPR): step i uses section (first + i) mod nsec.  Device buffers: xtr / ytr n0 x nsec, alpha
+// 2 n0 x nsec, the guess GPs' n0p x nsec, column-major and tight; kcs / kcps: nsec constants each, in device memory too
+int applymap_sections(int family, int mode, int nsec, int first, int nm, int ntest, int n0, const double *xtr, const double *ytr,
+                      const double *alpha, const KConst *kcs, int n0p, const double *xtrp, const double *ytrp,
+                      const double *alphap, const KConst *kcps, const double *Q0, const double *P0, double *qmap, double *pmap,
+                      double *pdiff, hipStream_t st);
 
 // ---- gram_nd.hip : d canonical pairs per point (X: points x 2d, column-major)
 int gram_nd(int family, int d, int mi, int mj, const double *Xb, size_t ldxb, const double *Xa, size_t ldxa,

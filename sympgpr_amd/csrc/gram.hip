@@ -538,6 +538,153 @@ __global__ __launch_bounds__(TT) void applymap_kernel(const MapArgs a)
     if (threadIdx.x == 0 && me == 0) atomicAdd((unsigned *)(a.err + 1), ncalls);
 }
 
+// ---- applymap over sections: 05_tokamak/Split_SympGPR/func.py:184-219 -- nsec independent GP pairs, one per toroidal
+// section, applied in turn: step i -> i + 1 of every orbit uses section (first + i) mod nsec.  The step is applymap_kernel's,
+// restated (that kernel stays as it is): the same sums in the same order per thread (j = tid, tid + TT, ...), the same
+// block_sum2 with the alternating halves, so a step has the bits of a one-step applymap_kernel launch with S == 1 on that
+// section's data.  One workgroup per orbit at every size: sections exist to keep each fit small, and a kernel in which no
+// workgroup waits for another has nothing that can hang.
+constexpr long MAPSEC_STAGE = 8960;   // doubles of LDS for the staged sections: the 70 KB applymap_kernel reserves (7 * MAP_STAGE * 256)
+struct MapSecArgs {
+    int nm, ntest, n0, n0p, mode, maxiter;
+    int nsec, first;
+    int staged;                           // all sections' points and weights fit into MAPSEC_STAGE doubles of (dynamic) LDS
+    double tol;
+    const double *xtr, *ytr, *alpha;      // symplectic GPs: n0 x nsec, n0 x nsec, 2 n0 x nsec, column-major, tight
+    const double *xtrp, *ytrp, *alphap;   // regular GPs (guess): n0p x nsec each
+    const double *Q0, *P0;
+    double *qmap, *pmap, *pdiff;          // [nm][ntest], C order; pdiff may be null
+};
+
+// kcs, kcps: the sections' constants (make_kconst) in device memory, nsec each; a step reads its pair with block-uniform loads
+// (__restrict__: nothing the kernel writes can alias them, so the compiler fetches them with scalar loads, into SGPRs, where
+// applymap_kernel has its kernel arguments)
+template <int FAM, int TT>
+__global__ __launch_bounds__(TT) void applymap_sections_kernel(const MapSecArgs a, const KConst *__restrict__ kcs,
+                                                               const KConst *__restrict__ kcps)
+{
+    __shared__ double sh[2][2 * (TT / 64)];
+    extern __shared__ double sec_st[];                  // [section]{x, y, alpha (two halves): n0 each; guess x, y, alpha: n0p each}
+    const int k = blockIdx.x, tid = threadIdx.x, n0 = a.n0, n0p = a.n0p;
+    const int per = 4 * n0 + 3 * n0p;                   // (staged only: nsec * per <= MAPSEC_STAGE)
+    const bool staged = a.staged != 0;
+    if (staged) {
+        for (int s = 0; s < a.nsec; ++s) {
+            double *d = sec_st + s * per;
+            const double *x = a.xtr + (size_t)s * n0, *y = a.ytr + (size_t)s * n0, *al = a.alpha + (size_t)s * 2 * n0;
+            for (int j = tid; j < n0; j += TT) {
+                d[j] = x[j]; d[n0 + j] = y[j];
+                d[2 * n0 + j] = al[j]; d[3 * n0 + j] = al[n0 + j];
+            }
+            const double *xp = a.xtrp + (size_t)s * n0p, *yp = a.ytrp + (size_t)s * n0p, *alp = a.alphap + (size_t)s * n0p;
+            for (int j = tid; j < n0p; j += TT) {
+                d[4 * n0 + j] = xp[j]; d[4 * n0 + n0p + j] = yp[j]; d[4 * n0 + 2 * n0p + j] = alp[j];
+            }
+        }
+        // (every thread reads back what it wrote itself: no barrier needed)
+    }
+    unsigned seq = 0;
+    auto sum2 = [&](double &x, double &y) {
+        ++seq;
+        block_sum2<TT>(x, y, sh[seq & 1u]);
+    };
+    auto rows = [&](int m, const KConst &kc, double q, double P, double &r1, double &r2) {   // Kstar(1,:).alpha, Kstar(2,:).alpha
+        r1 = 0.0; r2 = 0.0;
+        if (staged) {
+            const double *d = sec_st + m * per;
+            for (int j = tid; j < n0; j += TT) {
+                double kxx, kxy, kyy;
+                pair_eval<FAM, false>(d[j], d[n0 + j], q, P, kc, kxx, kxy, kyy);
+                const double a1 = d[2 * n0 + j], a2 = d[3 * n0 + j];
+                r1 += kxx * a1 + kxy * a2;
+                r2 += kxy * a1 + kyy * a2;
+            }
+        } else {
+            const double *x = a.xtr + (size_t)m * n0, *y = a.ytr + (size_t)m * n0, *al = a.alpha + (size_t)m * 2 * n0;
+            for (int j = tid; j < n0; j += TT) {
+                double kxx, kxy, kyy;
+                pair_eval<FAM, false>(x[j], y[j], q, P, kc, kxx, kxy, kyy);
+                const double a1 = al[j], a2 = al[n0 + j];
+                r1 += kxx * a1 + kxy * a2;
+                r2 += kxy * a1 + kyy * a2;
+            }
+        }
+        sum2(r1, r2);
+    };
+    auto guess = [&](int m, const KConst &kcp, double q, double p) {
+        double r = 0.0, z = 0.0;
+        if (staged) {
+            const double *d = sec_st + m * per + 4 * n0;
+            for (int j = tid; j < n0p; j += TT)
+                r += kcp.sig * kern_eval<FAM, false>(d[j], d[n0p + j], q, p, kcp) * d[2 * n0p + j];
+        } else {
+            const double *xp = a.xtrp + (size_t)m * n0p, *yp = a.ytrp + (size_t)m * n0p, *alp = a.alphap + (size_t)m * n0p;
+            for (int j = tid; j < n0p; j += TT)
+                r += kcp.sig * kern_eval<FAM, false>(xp[j], yp[j], q, p, kcp) * alp[j];
+        }
+        sum2(r, z);
+        return r;
+    };
+    double q = a.Q0[k], p = a.P0[k], pd = p;
+    if (tid == 0) {
+        a.qmap[k] = q;
+        a.pmap[k] = p;
+        if (a.pdiff) a.pdiff[k] = pd;
+    }
+    const double nan = __builtin_nan("");
+    const double twopi = 6.283185307179586477;
+    int m = a.first;
+    for (int i = 0; i + 1 < a.nm; ++i) {
+        double qn = nan, pn = nan, pdn = nan;
+        if (!(q != q) && !(p != p)) {                      // NaN = lost orbit stays lost (func.py:199-200)
+            const KConst kc = kcs[m];
+            double r1, r2, Praw = nan;
+            bool have_r2 = false;
+            if (a.mode & SGPR_MAP_EXPLICIT) {
+                rows(m, kc, q, p, r1, r2);
+                Praw = p - r1;
+            } else {
+                const KConst kcp = kcps[m];
+                double P0 = guess(m, kcp, q, p);
+                rows(m, kc, q, P0, r1, r2);
+                double f0 = r1 - p + P0;
+                double P1 = P0 - f0;                            // f'(P) ~ 1 near the identity map
+                rows(m, kc, q, P1, r1, r2);
+                double f1 = r1 - p + P1;
+                for (int it = 0; it < a.maxiter; ++it) {        // secant; every quantity is block-uniform
+                    if (!(fabs(P1 - P0) > a.tol * fmax(1.0, fabs(P1))) || !(f1 == f1)) break;
+                    const double d = f1 - f0;
+                    if (d == 0.0) break;
+                    const double Pn = P1 - f1 * (P1 - P0) / d;
+                    P0 = P1; f0 = f1; P1 = Pn;
+                    rows(m, kc, q, P1, r1, r2);
+                    f1 = r1 - p + P1;
+                }
+                if ((f1 == f1) && fabs(f1) <= 1e-8 * fmax(1.0, fabs(p))) {
+                    Praw = P1;
+                    have_r2 = true;                              // r2 belongs to (q, P1)
+                }
+            }
+            if ((a.mode & SGPR_MAP_LOSS_NEGP) && Praw < 0.0) Praw = nan;   // Split_SympGPR/func.py:215, its P < 0 half
+            if (Praw == Praw) {
+                pdn = pd + (Praw - p);
+                pn = Praw;
+                if (a.mode & SGPR_MAP_WRAP_P) pn -= twopi * floor(pn / twopi);
+                if (!have_r2 || pn != Praw) rows(m, kc, q, pn, r1, r2);
+                qn = r2 + q;
+                if (a.mode & SGPR_MAP_WRAP_Q) qn -= twopi * floor(qn / twopi);
+            }
+        }
+        q = qn; p = pn; pd = pdn;
+        if (++m == a.nsec) m = 0;
+        if (tid == 0) {
+            a.qmap[(size_t)(i + 1) * a.ntest + k] = q;
+            a.pmap[(size_t)(i + 1) * a.ntest + k] = p;
+            if (a.pdiff) a.pdiff[(size_t)(i + 1) * a.ntest + k] = pd;
+        }
+    }
+}
+
 template <typename F>
 int dispatch_family(int family, F &&f)
 {
@@ -755,6 +902,30 @@ int applymap_status(const void *team_ws, int ntest, int n0)
     const int h = hh[0];
     if (h) { set_error("applymap: a workgroup of an orbit's team did not answer in time"); return SGPR_E_HIP; }
     return 0;
+}
+
+// The sectioned map: one launch, one 256-thread workgroup per orbit.  Dynamic LDS: the drivers' size (4 sections of 70 points)
+// reserves 15.7 KB, not the 70 KB of the limit, so several orbits share a CU.
+int applymap_sections(int family, int mode, int nsec, int first, int nm, int ntest, int n0, const double *xtr, const double *ytr,
+                      const double *alpha, const KConst *kcs, int n0p, const double *xtrp, const double *ytrp,
+                      const double *alphap, const KConst *kcps, const double *Q0, const double *P0, double *qmap, double *pmap,
+                      double *pdiff, hipStream_t st)
+{
+    if (nm <= 0 || ntest <= 0) return 0;
+    const long need = (long)nsec * (4L * n0 + 3L * n0p);
+    const bool staged = need <= MAPSEC_STAGE;
+    const size_t lds = staged ? (size_t)need * sizeof(double) : 0;
+    MapSecArgs a{nm, ntest, n0, n0p, mode, 60, nsec, first, staged ? 1 : 0, 1e-13, xtr, ytr, alpha, xtrp, ytrp, alphap, Q0, P0,
+                 qmap, pmap, pdiff};
+    return dispatch_family(family, [&](auto fam) {
+        constexpr int F = decltype(fam)::value;
+        auto kern = applymap_sections_kernel<F, GT>;
+        if (lds > 48 * 1024)
+            SGPR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(kern, dim3(ntest), dim3(GT), lds, st, a, kcs, kcps);
+        SGPR_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 int predict_reg(int family, int m, const double *q, const double *P, int n0, const double *xtr,

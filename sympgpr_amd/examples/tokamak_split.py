@@ -27,12 +27,80 @@ def nll_chol(hyp, x, y, N):
     return _c.nll_fit(FAMILY, hyp, x, y, N, neig=len(x) // 2)
 
 
+def map_in_chunks(run, nphmap, nm, Ntest, Q0map, P0map, compute_r=None, steps_per_launch=None):
+    """The bookkeeping of applymap_tok around a stepper `run(first, steps, Q0, P0) -> (q, p)`, each [steps + 1, len(Q0)] with
+    row 0 the start points and NaN from the step at which an orbit is lost: `steps` steps of the sectioned map whose first
+    step uses section `first`.  The reference's loop quirk is kept (func.py:196-197: the while loop advances nphmap steps at
+    a time): ceil((nm - nphmap) / nphmap) nphmap steps are run and the rows beyond them stay 0.  Without a callback the
+    whole map is one call of `run`; with one, `steps_per_launch` steps per call, each continued with first = i mod nphmap from
+    the orbits still alive, and compute_r is applied to the new rows step by step and orbit by orbit in the reference's
+    order (func.py:212-217).  What a chunk computed for an orbit beyond the step that lost it is dropped."""
+    pmap = np.zeros([nm, Ntest])
+    qmap = np.zeros([nm, Ntest])
+    pmap[0, :] = P0map
+    qmap[0, :] = Q0map
+    steps = -(-(nm - nphmap) // nphmap) * nphmap if nm > nphmap else 0
+    if steps == 0:
+        return qmap, pmap
+    k = steps if compute_r is None else max(1, int(steps_per_launch or 1))
+    pmap[1:steps + 1, :] = np.nan
+    qmap[1:steps + 1, :] = np.nan
+    i = 0
+    while i < steps:
+        kk = min(k, steps - i)
+        idx = np.nonzero(~np.isnan(pmap[i, :]))[0]
+        if len(idx):
+            qq, pp = run(i % nphmap, kk, qmap[i, idx], pmap[i, idx])
+            if compute_r is None:
+                pmap[i + 1:i + kk + 1, idx], qmap[i + 1:i + kk + 1, idx] = pp[1:], qq[1:]
+            else:
+                alive = np.ones(len(idx), dtype=bool)
+                for s in range(1, kk + 1):
+                    ph = (2 * np.pi) / nphmap * np.mod(i + s, nphmap)
+                    for j, orbit in enumerate(idx):
+                        if not alive[j]:
+                            continue
+                        if np.isnan(pp[s, j]):                  # the solve failed or P < 0: lost inside the kernel
+                            alive[j] = False
+                            continue
+                        if compute_r(np.array([pp[s, j] * 1e-2, qq[s, j], ph]), 0.3) > 0.5:
+                            alive[j] = False
+                            continue
+                        pmap[i + s, orbit], qmap[i + s, orbit] = pp[s, j], qq[s, j]
+        i += kk
+    return qmap, pmap
+
+
 def applymap_tok(nphmap, nm, Ntest, Q0map, P0map, xtrainp, ztrainp, Kyinvp, hypp, xtrain, ztrain, Kyinv, hyp,
-                 compute_r=None):
+                 compute_r=None, steps_per_launch=None):
     """func.py:184-219: section m's GP pair maps step i -> i+1 for i = m (mod nphmap).
     xtrainp (2N x nphmap), ztrainp (N x nphmap), Kyinvp (nphmap x N x N), hypp (nphmap x 3) and the
     same for the symplectic GP.  `compute_r(zk, r_gss)`: the reference's fieldlines.compute_r; an
-    orbit with compute_r > 0.5 or P < 0 is lost (without it only P < 0)."""
+    orbit with compute_r > 0.5 or P < 0 is lost (without it only P < 0).
+    Every time step runs on the device (maps.run_map_sections: the implicit P, the P < 0 test and the q update of all
+    sections inside one kernel): without a callback the whole map is ONE launch; with a callback and steps_per_launch = k,
+    k steps per launch with the callback applied to the new rows on the host (map_in_chunks).  With a callback and
+    steps_per_launch = None every step is driven from the host (one batched device call per residual of the secant)."""
+    if compute_r is not None and steps_per_launch is None:
+        return _applymap_tok_host(nphmap, nm, Ntest, Q0map, P0map, xtrainp, ztrainp, Kyinvp, hypp, xtrain, ztrain, Kyinv, hyp,
+                                  compute_r)
+    from .. import maps
+    f = lambda a: np.asarray(a, dtype=np.float64)
+    xtrain, ztrain, xtrainp, ztrainp, hyp, hypp = (f(a) for a in (xtrain, ztrain, xtrainp, ztrainp, hyp, hypp))
+    N, Np = xtrain.shape[0] // 2, xtrainp.shape[0] // 2
+    sec = range(nphmap)
+    alpha = np.stack([f(Kyinv[m]) @ ztrain[:, m] for m in sec], axis=1)           # once per section, not per step
+    alphap = np.stack([f(Kyinvp[m]) @ ztrainp[:, m] for m in sec], axis=1)
+    mode = maps.WRAP_Q | maps.LOSS_NEGP
+    run = lambda first, steps, Q0, P0: maps.run_map_sections(
+        mode, steps + 1, len(Q0), hyp[:nphmap], xtrain[:N, :nphmap], xtrain[N:2 * N, :nphmap], alpha, Q0, P0, hypp[:nphmap],
+        xtrainp[:Np, :nphmap], xtrainp[Np:2 * Np, :nphmap], alphap, first=first, family=FAMILY)
+    return map_in_chunks(run, nphmap, nm, Ntest, np.broadcast_to(Q0map, (Ntest,)), np.broadcast_to(P0map, (Ntest,)), compute_r,
+                         steps_per_launch)
+
+
+def _applymap_tok_host(nphmap, nm, Ntest, Q0map, P0map, xtrainp, ztrainp, Kyinvp, hypp, xtrain, ztrain, Kyinv, hyp, compute_r):
+    """the host-driven form of applymap_tok: a Python loop over the time steps"""
     preds = [_c.predictor_pair(FAMILY, hyp[m, :], hypp[m, :], xtrainp[:, m], ztrainp[:, m], Kyinvp[m], xtrain[:, m],
                                ztrain[:, m], Kyinv[m]) for m in range(nphmap)]
     pmap = np.zeros([nm, Ntest])

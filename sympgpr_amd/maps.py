@@ -8,6 +8,8 @@ One recurrence, the variants the reference's drivers carry in their own func.py 
     applymap_expl     04_standard_map/func.py:256-285     explicit, P mod 2 pi, + pdiff
     applymap          01_pendulum/explicit/func_expl.py:113-128   explicit, q mod 2 pi
     applymap_tok      05_tokamak/SympGPR/func.py:182-211  implicit, q mod 2 pi, an orbit with P < 0 is lost (LOSS_NEGP)
+    applymap_tok      05_tokamak/Split_SympGPR/func.py:184-219   the same with one GP pair per toroidal section, applied in
+                                                                 turn: run_map_sections (sgpr_applymap_sections_host)
 
 For fits with d canonical pairs (d = 1, 2, 3) the map is run_map_nd / SympFit.applymap_pairs: Newton with the analytic
 Jacobian on the d unknowns P, one workgroup per orbit (include/sympgpr_hip.h: sgpr_applymap_nd_host).
@@ -75,6 +77,67 @@ def run_map(mode, nm, Ntest, l, Q0map, P0map, xtrain, ztrain, Kyinv, hypp=None, 
                                    L.dptr(xt), L.dptr(yt), L.dptr(alpha), L.dptr(hp), len(hp), Ntrainp, L.dptr(xp),
                                    L.dptr(yp), L.dptr(alphap), L.dptr(Q0), L.dptr(P0), L.dptr(qmap), L.dptr(pmap),
                                    L.dptr(pdiff) if want_pdiff else None), "sgpr_applymap_host")
+    return (qmap, pmap, pdiff) if want_pdiff else (qmap, pmap)
+
+
+def _section_columns(name, a, rows, nsec):
+    """`a` as a float64 array with one tight column per section: (rows, nsec), F-ordered"""
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim != 2 or a.shape[1] != nsec:
+        raise ValueError("%s must have one column per section: (%s, %d)" % (name, "rows" if rows is None else rows, nsec))
+    if rows is not None and a.shape[0] != rows:
+        raise ValueError("%s must be (%d, %d), not %s" % (name, rows, nsec, a.shape))
+    return np.asfortranarray(a)
+
+
+def run_map_sections(mode, nm, Ntest, hyp, xt, yt, alpha, Q0, P0, hypp=None, xp=None, yp=None, alphap=None, first=0,
+                     want_pdiff=False, family=None):
+    """The sectioned map of 05_tokamak/Split_SympGPR/func.py:184-219 in ONE launch: nsec independent GP pairs of one size,
+    applied in turn -- step i -> i + 1 uses section (first + i) mod nsec (sgpr_applymap_sections_host).
+
+    hyp (nsec, nhyp), row s = section s's (lx, ly, sig) -- (lx, ly, p, sig) for family D; xt, yt (N0, nsec) and alpha
+    (2 N0, nsec), one column per section; hypp (nsec, nhyp), xp, yp, alphap (N0p, nsec) the regular GPs of the first guess
+    (not needed with EXPLICIT).  alpha and alphap are the posterior weights Ky^-1 z of the sections' fits: what fit.fit_batch
+    returns for them or sections.gather_sections collects, stacked as columns (np.stack(alphas, axis=1)).
+    -> (qmap, pmap) or (qmap, pmap, pdiff), each [nm, Ntest]; NaN from the step at which an orbit is lost.  A map continued
+    from row i with first = (first + i) mod nsec has the bits of the uninterrupted one.  Shape errors are ValueError before
+    any device call."""
+    family = get_family() if family is None else family
+    mode, nm, Ntest, first = int(mode), int(nm), int(Ntest), int(first)
+    hyp = np.asarray(hyp, dtype=np.float64)
+    if hyp.ndim != 2 or hyp.shape[0] < 1:
+        raise ValueError("hyp must be (nsec, nhyp) with at least one section")
+    nsec = hyp.shape[0]
+    if not 0 <= first < nsec:
+        raise ValueError("first must lie in [0, nsec = %d)" % nsec)
+    if nm < 1 or Ntest < 0:
+        raise ValueError("nm must be at least 1 and Ntest non-negative")
+    xt = _section_columns("xt", xt, None, nsec)
+    N0 = xt.shape[0]
+    yt = _section_columns("yt", yt, N0, nsec)
+    alpha = _section_columns("alpha", alpha, 2 * N0, nsec)
+    if mode & EXPLICIT:
+        N0p, hp = 0, np.zeros((nsec, 0))
+        xp = yp = alphap = np.zeros((0, nsec), order="F")
+    else:
+        if hypp is None or xp is None or yp is None or alphap is None:
+            raise ValueError("the implicit map needs the guess GPs: hypp, xp, yp and alphap")
+        hp = np.asarray(hypp, dtype=np.float64)
+        if hp.ndim != 2 or hp.shape[0] != nsec:
+            raise ValueError("hypp must be (nsec = %d, nhyp)" % nsec)
+        xp = _section_columns("xp", xp, None, nsec)
+        N0p = xp.shape[0]
+        yp = _section_columns("yp", yp, N0p, nsec)
+        alphap = _section_columns("alphap", alphap, N0p, nsec)
+    hyp, hp = L.f64(hyp), L.f64(hp)                     # C order: section s at hyp + s * nhyp
+    Q0, P0 = L.f64(np.broadcast_to(Q0, (Ntest,))), L.f64(np.broadcast_to(P0, (Ntest,)))
+    qmap, pmap = np.zeros([nm, Ntest]), np.zeros([nm, Ntest])
+    pdiff = np.zeros([nm, Ntest]) if want_pdiff else None
+    lib = L.load_library()
+    L.check(lib.sgpr_applymap_sections_host(L.family_id(family), mode, nsec, first, nm, Ntest, L.dptr(hyp), hyp.shape[1], N0,
+                                            L.dptr(xt), L.dptr(yt), L.dptr(alpha), L.dptr(hp), hp.shape[1], N0p, L.dptr(xp),
+                                            L.dptr(yp), L.dptr(alphap), L.dptr(Q0), L.dptr(P0), L.dptr(qmap), L.dptr(pmap),
+                                            L.dptr(pdiff) if want_pdiff else None), "sgpr_applymap_sections_host")
     return (qmap, pmap, pdiff) if want_pdiff else (qmap, pmap)
 
 
