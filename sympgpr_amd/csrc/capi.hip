@@ -73,6 +73,47 @@ static int gram_host(const char *bad, bool shape_ok, int family, int n, int n0, 
     return 0;
 }
 
+// The output half of the two d = 1 map entries: qmap / pmap / optional pdiff [nm][ntest] on the device, filled by
+// launch(dqmap, dpmap, dpdiff), their download and the wait.
+template <typename Launch>
+static int map_outputs(int nm, int ntest, double *qmap, double *pmap, double *pdiff, hipStream_t st, Launch launch)
+{
+    int rc;
+    DevBuf qm, pm, pd;
+    const size_t out_bytes = (size_t)nm * ntest * sizeof(double);
+    if ((rc = qm.alloc(out_bytes)) || (rc = pm.alloc(out_bytes)) || (pdiff && (rc = pd.alloc(out_bytes)))) return rc;
+    if ((rc = launch(qm.as<double>(), pm.as<double>(), pdiff ? pd.as<double>() : nullptr))) return rc;
+    SGPR_HIP(hipMemcpyAsync(qmap, qm.p, out_bytes, hipMemcpyDeviceToHost, st));
+    SGPR_HIP(hipMemcpyAsync(pmap, pm.p, out_bytes, hipMemcpyDeviceToHost, st));
+    if (pdiff) SGPR_HIP(hipMemcpyAsync(pdiff, pd.p, out_bytes, hipMemcpyDeviceToHost, st));
+    SGPR_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+// sgpr_applymap_nd_host (tan null) and sgpr_applymap_nd_tangent_host: every argument is checked before any device call
+static int applymap_nd_host(const char *me, int family, int d, int mode, int nm, int ntest, const double *hyp, int nhyp, int n0,
+                            const double *X, size_t ldx, const double *alpha, const double *Q0, size_t ldq, const double *P0,
+                            size_t ldp, double *qmap, double *pmap, int *iters, const MapTangentOut *tan)
+{
+    int rc = applymap_nd_kernel_check(me, family, d, hyp, nhyp);
+    if (rc || (rc = applymap_nd_call_check(me, mode, nm, ntest, Q0, ldq, P0, ldp, qmap, pmap)) ||
+        (tan && (rc = applymap_nd_tangent_check(me, family, mode, nm, tan->lyap))))
+        return rc;
+    if (n0 < 0 || (n0 > 0 && (!X || !alpha || ldx < (size_t)n0))) {
+        set_error(std::string(me) + ": n0 < 0, null X or alpha, or ldx < n0");
+        return SGPR_E_ARG;
+    }
+    if ((rc = need_device())) return rc;
+    if (ntest == 0) return 0;
+    DevBuf dX, dal;
+    hipStream_t st = nullptr;
+    const int D = 2 * d;
+    if ((rc = dX.alloc((size_t)n0 * D * sizeof(double))) || (rc = upload(dal, alpha, (size_t)D * n0, st))) return rc;
+    if (n0 > 0 && (rc = copy_in(dX.p, (size_t)n0, X, ldx, (size_t)n0, D, st))) return rc;
+    return applymap_nd_io(family, d, mode, nm, ntest, n0, dX.as<double>(), (size_t)n0, hyp, nhyp, dal.as<double>(), Q0, ldq, P0, ldp,
+                          qmap, pmap, iters, st, tan);
+}
+
 extern "C" {
 
 int sgpr_abi_version(void) { return SGPR_ABI_VERSION; }
@@ -373,24 +414,18 @@ int sgpr_applymap_host(int family, int mode, int nm, int ntest, const double *hy
         set_error("applymap: null argument");
         return SGPR_E_ARG;
     }
-    DevBuf x, y, al, xp, yp, alp, q0, p0, qm, pm, pd, tw;
+    DevBuf x, y, al, xp, yp, alp, q0, p0, tw;
     hipStream_t st = nullptr;
-    const size_t out_bytes = (size_t)nm * ntest * sizeof(double);
     if ((rc = tw.alloc(applymap_team_ws(ntest, n0)))) return rc;
     if ((rc = upload(x, xtrain, n0, st)) || (rc = upload(y, ytrain, n0, st)) || (rc = upload(al, alpha, 2 * (size_t)n0, st)) ||
         (rc = upload(xp, xtrainp, n0p, st)) || (rc = upload(yp, ytrainp, n0p, st)) || (rc = upload(alp, alphap, n0p, st)) ||
-        (rc = upload(q0, Q0, ntest, st)) || (rc = upload(p0, P0, ntest, st)) || (rc = qm.alloc(out_bytes)) ||
-        (rc = pm.alloc(out_bytes)) || (pdiff && (rc = pd.alloc(out_bytes))))
+        (rc = upload(q0, Q0, ntest, st)) || (rc = upload(p0, P0, ntest, st)))
         return rc;
-    rc = applymap(family, mode, nm, ntest, n0, x.as<double>(), y.as<double>(), kc, al.as<double>(), n0p,
-                  xp.as<double>(), yp.as<double>(), kcp, alp.as<double>(), q0.as<double>(), p0.as<double>(),
-                  qm.as<double>(), pm.as<double>(), pdiff ? pd.as<double>() : nullptr, tw.p, st);
-    if (rc) return rc;
-    SGPR_HIP(hipMemcpyAsync(qmap, qm.p, out_bytes, hipMemcpyDeviceToHost, st));
-    SGPR_HIP(hipMemcpyAsync(pmap, pm.p, out_bytes, hipMemcpyDeviceToHost, st));
-    if (pdiff) SGPR_HIP(hipMemcpyAsync(pdiff, pd.p, out_bytes, hipMemcpyDeviceToHost, st));
-    SGPR_HIP(hipStreamSynchronize(st));
-    return applymap_status(tw.p, ntest, n0);
+    rc = map_outputs(nm, ntest, qmap, pmap, pdiff, st, [&](double *qm, double *pm, double *pd) {
+        return applymap(family, mode, nm, ntest, n0, x.as<double>(), y.as<double>(), kc, al.as<double>(), n0p, xp.as<double>(),
+                        yp.as<double>(), kcp, alp.as<double>(), q0.as<double>(), p0.as<double>(), qm, pm, pd, tw.p, st);
+    });
+    return rc ? rc : applymap_status(tw.p, ntest, n0);
 }
 
 /* The sectioned map (05_tokamak/Split_SympGPR/func.py:184-219): nsec GP pairs applied in turn, every step of every orbit in
@@ -420,48 +455,29 @@ int sgpr_applymap_sections_host(int family, int mode, int nsec, int first, int n
     }
     if ((rc = need_device())) return rc;
     if (ntest == 0) return 0;
-    DevBuf x, y, al, xp, yp, alp, dk, q0, p0, qm, pm, pd;
+    DevBuf x, y, al, xp, yp, alp, dk, q0, p0;
     hipStream_t st = nullptr;
-    const size_t ns = (size_t)nsec, out_bytes = (size_t)nm * ntest * sizeof(double);
+    const size_t ns = (size_t)nsec;
     static_assert(sizeof(KConst) % sizeof(double) == 0, "KConst is uploaded as doubles");
     if ((rc = upload(x, xtrain, ns * n0, st)) || (rc = upload(y, ytrain, ns * n0, st)) || (rc = upload(al, alpha, 2 * ns * n0, st)) ||
         (rc = upload(xp, xtrainp, ns * n0p, st)) || (rc = upload(yp, ytrainp, ns * n0p, st)) || (rc = upload(alp, alphap, ns * n0p, st)) ||
         (rc = upload(dk, reinterpret_cast<const double *>(kc.data()), kc.size() * (sizeof(KConst) / sizeof(double)), st)) ||
-        (rc = upload(q0, Q0, ntest, st)) || (rc = upload(p0, P0, ntest, st)) || (rc = qm.alloc(out_bytes)) ||
-        (rc = pm.alloc(out_bytes)) || (pdiff && (rc = pd.alloc(out_bytes))))
+        (rc = upload(q0, Q0, ntest, st)) || (rc = upload(p0, P0, ntest, st)))
         return rc;
-    rc = applymap_sections(family, mode, nsec, first, nm, ntest, n0, x.as<double>(), y.as<double>(), al.as<double>(),
-                           dk.as<KConst>(), n0p, xp.as<double>(), yp.as<double>(), alp.as<double>(), dk.as<KConst>() + nsec,
-                           q0.as<double>(), p0.as<double>(), qm.as<double>(), pm.as<double>(), pdiff ? pd.as<double>() : nullptr, st);
-    if (rc) return rc;
-    SGPR_HIP(hipMemcpyAsync(qmap, qm.p, out_bytes, hipMemcpyDeviceToHost, st));
-    SGPR_HIP(hipMemcpyAsync(pmap, pm.p, out_bytes, hipMemcpyDeviceToHost, st));
-    if (pdiff) SGPR_HIP(hipMemcpyAsync(pdiff, pd.p, out_bytes, hipMemcpyDeviceToHost, st));
-    SGPR_HIP(hipStreamSynchronize(st));
-    return 0;
+    return map_outputs(nm, ntest, qmap, pmap, pdiff, st, [&](double *qm, double *pm, double *pd) {
+        return applymap_sections(family, mode, nsec, first, nm, ntest, n0, x.as<double>(), y.as<double>(), al.as<double>(),
+                                 dk.as<KConst>(), n0p, xp.as<double>(), yp.as<double>(), alp.as<double>(), dk.as<KConst>() + nsec,
+                                 q0.as<double>(), p0.as<double>(), qm, pm, pd, st);
+    });
 }
 
-/* The d-pair map from caller-supplied training points and alpha (the counterpart of sgpr_applymap_host for d canonical pairs):
- * every argument is checked before any device call. */
+/* The d-pair map from caller-supplied training points and alpha (the counterpart of sgpr_applymap_host for d canonical pairs). */
 int sgpr_applymap_nd_host(int family, int d, int mode, int nm, int ntest, const double *hyp, int nhyp, int n0, const double *X,
                           size_t ldx, const double *alpha, const double *Q0, size_t ldq, const double *P0, size_t ldp,
                           double *qmap, double *pmap, int *iters)
 {
-    int rc = applymap_nd_kernel_check("applymap_nd_host", family, d, hyp, nhyp);
-    if (rc || (rc = applymap_nd_call_check("applymap_nd_host", mode, nm, ntest, Q0, ldq, P0, ldp, qmap, pmap))) return rc;
-    if (n0 < 0 || (n0 > 0 && (!X || !alpha || ldx < (size_t)n0))) {
-        set_error("applymap_nd_host: n0 < 0, null X or alpha, or ldx < n0");
-        return SGPR_E_ARG;
-    }
-    if ((rc = need_device())) return rc;
-    if (ntest == 0) return 0;
-    DevBuf dX, dal;
-    hipStream_t st = nullptr;
-    const int D = 2 * d;
-    if ((rc = dX.alloc((size_t)n0 * D * sizeof(double))) || (rc = upload(dal, alpha, (size_t)D * n0, st))) return rc;
-    if (n0 > 0 && (rc = copy_in(dX.p, (size_t)n0, X, ldx, (size_t)n0, D, st))) return rc;
-    return applymap_nd_io(family, d, mode, nm, ntest, n0, dX.as<double>(), (size_t)n0, hyp, nhyp, dal.as<double>(), Q0, ldq, P0, ldp,
-                          qmap, pmap, iters, st);
+    return applymap_nd_host("applymap_nd_host", family, d, mode, nm, ntest, hyp, nhyp, n0, X, ldx, alpha, Q0, ldq, P0, ldp, qmap, pmap,
+                            iters, nullptr);
 }
 
 /* The same with the tangent map (maptan.h): the orbit outputs have the bits of sgpr_applymap_nd_host. */
@@ -469,25 +485,9 @@ int sgpr_applymap_nd_tangent_host(int family, int d, int mode, int nm, int ntest
                                   const double *X, size_t ldx, const double *alpha, const double *Q0, size_t ldq, const double *P0,
                                   size_t ldp, double *qmap, double *pmap, int *iters, double *jac, double *mono, double *lyap)
 {
-    const char *me = "applymap_nd_tangent_host";
-    int rc = applymap_nd_kernel_check(me, family, d, hyp, nhyp);
-    if (rc || (rc = applymap_nd_call_check(me, mode, nm, ntest, Q0, ldq, P0, ldp, qmap, pmap)) ||
-        (rc = applymap_nd_tangent_check(me, family, mode, nm, lyap)))
-        return rc;
-    if (n0 < 0 || (n0 > 0 && (!X || !alpha || ldx < (size_t)n0))) {
-        set_error("applymap_nd_tangent_host: n0 < 0, null X or alpha, or ldx < n0");
-        return SGPR_E_ARG;
-    }
-    if ((rc = need_device())) return rc;
-    if (ntest == 0) return 0;
-    DevBuf dX, dal;
-    hipStream_t st = nullptr;
-    const int D = 2 * d;
-    if ((rc = dX.alloc((size_t)n0 * D * sizeof(double))) || (rc = upload(dal, alpha, (size_t)D * n0, st))) return rc;
-    if (n0 > 0 && (rc = copy_in(dX.p, (size_t)n0, X, ldx, (size_t)n0, D, st))) return rc;
     const MapTangentOut tan = {jac, mono, lyap};
-    return applymap_nd_io(family, d, mode, nm, ntest, n0, dX.as<double>(), (size_t)n0, hyp, nhyp, dal.as<double>(), Q0, ldq, P0, ldp,
-                          qmap, pmap, iters, st, &tan);
+    return applymap_nd_host("applymap_nd_tangent_host", family, d, mode, nm, ntest, hyp, nhyp, n0, X, ldx, alpha, Q0, ldq, P0, ldp,
+                            qmap, pmap, iters, &tan);
 }
 
 int sgpr_release_device_streams(int device)

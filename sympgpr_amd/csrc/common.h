@@ -4,6 +4,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/sympgpr_hip.h"
@@ -41,6 +42,21 @@ int make_kconst(int family, const double *hyp, int nhyp, KConst *out);
 bool family_has_p(int family);   // the family's hyp holds a period parameter p between the lengths and sig
 int make_kconst_l(int family, const double *l, int nl, KConst *out);  // sig = 1
 
+// f(std::integral_constant<int, family>()) for the kernel family chosen at run time (host side: gram.hip, map.hip)
+template <typename F>
+int dispatch_family(int family, F &&f)
+{
+    switch (family) {
+    case SGPR_FAM_A: return f(std::integral_constant<int, SGPR_FAM_A>());
+    case SGPR_FAM_B: return f(std::integral_constant<int, SGPR_FAM_B>());
+    case SGPR_FAM_C: return f(std::integral_constant<int, SGPR_FAM_C>());
+    case SGPR_FAM_D: return f(std::integral_constant<int, SGPR_FAM_D>());
+    case SGPR_FAM_USER: return f(std::integral_constant<int, SGPR_FAM_USER>());
+    }
+    set_error("unknown kernel family");
+    return SGPR_E_ARG;
+}
+
 // ---- gram.hip
 int gram_pairs(int family, int mi, int mj, const double *xb, const double *yb, const double *xa,
                const double *ya, const KConst &kc, double *qq, double *Pq, double *qP, double *PP,
@@ -57,6 +73,7 @@ int predict_reg(int family, int m, const double *q, const double *P, int n0, con
                 const double *ytr, const KConst &kc, const double *alpha, double *out,
                 hipStream_t st);
 
+// ---- map.hip : the d = 1 symplectic map, every time step on the device
 int applymap_team(int ntest, int n0);          // workgroups that share one orbit
 size_t applymap_team_ws(int ntest, int n0);    // bytes of device scratch applymap needs
 int applymap(int family, int mode, int nm, int ntest, int n0, const double *xtr, const double *ytr,

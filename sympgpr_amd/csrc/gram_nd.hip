@@ -243,7 +243,7 @@ struct MapNdArgs {
 // v[s] := the sum over the workgroup of every thread's v[s], the same bits in every thread: wave shuffle, one row of NS sums
 // per wave in LDS, folded in wave order.  8 waves: lanes 0 .. NS-1 fold one sum each and publish it (NS instead of 8 NS
 // reads per thread).  `part` (W NS doubles) and `res` (NS) are the halves the call before did NOT use -- the callers alternate,
-// as block_sum2 of gram.hip does: the barrier of call n + 1 lies between the reads of call n and the writes of call n + 2.
+// as block_sum2 of map.hip does: the barrier of call n + 1 lies between the reads of call n and the writes of call n + 2.
 template <int NS, int TT>
 __device__ __forceinline__ void block_sum_n(double (&v)[NS], double *part, double *res)
 {

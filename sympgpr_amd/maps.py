@@ -30,9 +30,11 @@ from .ops import get_family
 WRAP_Q, WRAP_P, EXPLICIT, LOSS_NEGP = L.MAP_WRAP_Q, L.MAP_WRAP_P, L.MAP_EXPLICIT, L.MAP_LOSS_NEGP
 
 
-def run_map_alpha(mode, nm, Ntest, l, Q0map, P0map, xt, yt, alpha, hypp=None, xp=None, yp=None, alphap=None, family=None):
+def run_map_alpha(mode, nm, Ntest, l, Q0map, P0map, xt, yt, alpha, hypp=None, xp=None, yp=None, alphap=None, family=None,
+                  want_pdiff=False):
     """The same iteration from the posterior weights themselves (alpha = Ky^-1 ztrain, 2 N0; alphap, N0p) instead of the explicit
-    inverses the drivers carry around: for training sets where Kyinv (8 (2 N0)^2 bytes) is not something to form."""
+    inverses the drivers carry around: for training sets where Kyinv (8 (2 N0)^2 bytes) is not something to form.
+    -> (qmap, pmap) or (qmap, pmap, pdiff), each [nm, Ntest]."""
     lib = L.load_library()
     f = L.f64
     family = get_family() if family is None else family
@@ -43,11 +45,12 @@ def run_map_alpha(mode, nm, Ntest, l, Q0map, P0map, xt, yt, alpha, hypp=None, xp
         xp, yp, alphap, hp = f(xp), f(yp), f(alphap), f(hypp)
     Q0, P0 = f(np.broadcast_to(Q0map, (Ntest,))), f(np.broadcast_to(P0map, (Ntest,)))
     pmap, qmap = np.zeros([nm, Ntest]), np.zeros([nm, Ntest])
+    pdiff = np.zeros([nm, Ntest]) if want_pdiff else None
     L.check(lib.sgpr_applymap_host(L.family_id(family), int(mode), nm, Ntest, L.dptr(hyp), len(hyp), len(xt),
                                    L.dptr(xt), L.dptr(yt), L.dptr(alpha), L.dptr(hp), len(hp), len(xp), L.dptr(xp),
-                                   L.dptr(yp), L.dptr(alphap), L.dptr(Q0), L.dptr(P0), L.dptr(qmap), L.dptr(pmap), None),
-            "sgpr_applymap_host")
-    return qmap, pmap
+                                   L.dptr(yp), L.dptr(alphap), L.dptr(Q0), L.dptr(P0), L.dptr(qmap), L.dptr(pmap),
+                                   L.dptr(pdiff) if want_pdiff else None), "sgpr_applymap_host")
+    return (qmap, pmap, pdiff) if want_pdiff else (qmap, pmap)
 
 
 def run_map(mode, nm, Ntest, l, Q0map, P0map, xtrain, ztrain, Kyinv, hypp=None, xtrainp=None, ztrainp=None,
@@ -55,29 +58,15 @@ def run_map(mode, nm, Ntest, l, Q0map, P0map, xtrain, ztrain, Kyinv, hypp=None, 
     """-> (qmap, pmap) or (qmap, pmap, pdiff), each [nm, Ntest].  `l` = (lx, ly, sig) of the
     symplectic GP, xtrain = (q || P), alpha = Kyinv @ ztrain; the *p arguments describe the
     regular GP that supplies the first guess of the implicit solve (unused with EXPLICIT)."""
-    lib = L.load_library()
-    f = L.f64
-    family = get_family() if family is None else family
     Ntrain = len(xtrain) // 2
-    xt, yt = f(xtrain[:Ntrain]), f(xtrain[Ntrain:2 * Ntrain])
-    alpha = f(np.asarray(Kyinv, dtype=np.float64) @ np.asarray(ztrain, dtype=np.float64))
-    hyp = f(l)
-    if mode & EXPLICIT:
-        Ntrainp, xp, yp, alphap, hp = 0, f([]), f([]), f([]), f([])
-    else:
+    alpha = np.asarray(Kyinv, dtype=np.float64) @ np.asarray(ztrain, dtype=np.float64)
+    xp = yp = alphap = None
+    if not mode & EXPLICIT:
         Ntrainp = len(xtrainp) // 2
-        xp, yp = f(xtrainp[:Ntrainp]), f(xtrainp[Ntrainp:2 * Ntrainp])
-        alphap = f(np.asarray(Kyinvp, dtype=np.float64) @ np.asarray(ztrainp, dtype=np.float64))
-        hp = f(hypp)
-    Q0, P0 = f(np.broadcast_to(Q0map, (Ntest,))), f(np.broadcast_to(P0map, (Ntest,)))
-    pmap = np.zeros([nm, Ntest])
-    qmap = np.zeros([nm, Ntest])
-    pdiff = np.zeros([nm, Ntest]) if want_pdiff else None
-    L.check(lib.sgpr_applymap_host(L.family_id(family), int(mode), nm, Ntest, L.dptr(hyp), len(hyp), Ntrain,
-                                   L.dptr(xt), L.dptr(yt), L.dptr(alpha), L.dptr(hp), len(hp), Ntrainp, L.dptr(xp),
-                                   L.dptr(yp), L.dptr(alphap), L.dptr(Q0), L.dptr(P0), L.dptr(qmap), L.dptr(pmap),
-                                   L.dptr(pdiff) if want_pdiff else None), "sgpr_applymap_host")
-    return (qmap, pmap, pdiff) if want_pdiff else (qmap, pmap)
+        xp, yp = xtrainp[:Ntrainp], xtrainp[Ntrainp:2 * Ntrainp]
+        alphap = np.asarray(Kyinvp, dtype=np.float64) @ np.asarray(ztrainp, dtype=np.float64)
+    return run_map_alpha(mode, nm, Ntest, l, Q0map, P0map, xtrain[:Ntrain], xtrain[Ntrain:2 * Ntrain], alpha, hypp, xp, yp,
+                         alphap, family=family, want_pdiff=want_pdiff)
 
 
 def _section_columns(name, a, rows, nsec):
@@ -177,16 +166,8 @@ def run_map_nd(family, d, mode, nm, hyp, X, alpha, Q0, P0, return_iters=False):
     points, NaN from the step at which an orbit is lost; with return_iters also iters (nm - 1, Ntest): Newton iterations of
     each solve, 0 in explicit mode, -1 for a lost orbit.  Every step runs on the device, one workgroup per orbit."""
     lib = L.load_library()
-    d = int(d)
-    if d not in (1, 2, 3):
-        raise ValueError("d must be 1, 2 or 3")
-    X = np.asfortranarray(X, dtype=np.float64)
-    if X.ndim != 2 or X.shape[1] != 2 * d:
-        raise ValueError("X must be (N0, %d)" % (2 * d))
+    d, X, alpha, hyp = _nd_inputs(d, X, alpha, hyp)
     N0 = X.shape[0]
-    alpha, hyp = L.f64(alpha), L.f64(hyp)
-    if alpha.shape != (2 * d * N0,):
-        raise ValueError("alpha must have length 2 d N0 = %d" % (2 * d * N0))
     mode = map_mode_nd(mode)
     Q0, P0 = start_points_nd(Q0, P0, d)
     Ntest = Q0.shape[0]
