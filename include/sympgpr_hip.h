@@ -132,6 +132,28 @@ int sgpr_syev_host(int n, double *A, size_t lda, double *w);
 /* ---- device-resident fit: the whole nll_chol path without K ever leaving HBM --------------
  * replaces python/functions/func.py:189-196 (nll_chol) / :165-171 (gpsolve) on (x, x). */
 typedef struct sgpr_fit *sgpr_fit_t;
+/* What a handle holds, and what every entry below needs of it (tests/test_gpu_fit_lifecycle.py keeps this as a table).
+ * Three things can be valid: Ky ("built": sgpr_fit_build), the factor L in Ky's place ("factored": sgpr_fit_factor, which
+ * ends "built") and alpha with the NLL ("solved": sgpr_fit_solve).  sgpr_fit_set_hyp ends all three, sgpr_fit_set_targets
+ * ends "solved" only (the factor does not depend on z: sgpr_fit_solve alone refits), sgpr_fit_build ends "factored" and
+ * "solved", a factorisation that fails (info > 0) leaves nothing valid, and neither does sgpr_fit_eig, which overwrites the
+ * matrix with eigenvectors.
+ *   any state:      set_hyp, set_targets, build, run, eig, trim, stage_ms, solve_rhs_ms (-1 for a stage that has not run),
+ *                   device_ptrs, destroy
+ *   needs built:    factor;  get_matrix takes built or factored
+ *   needs factored: solve, ldiag, solve_rhs, solve_rhs_dev, inverse, cond_estimate
+ *   needs solved:   alpha, nll, predict_rows, predict_nd, predict_cov, predict_genfun, nll_grad, nll_grad_terms,
+ *                   nll_grad_full, loo, applymap_nd, applymap_nd_tangent
+ * An entry called without what it needs returns SGPR_E_STATE.  So does one called on a kind of fit it is not defined for:
+ *   SGPR_FIT_BLOCK_QQ / _PP fits: every "needs solved" entry except alpha and nll, and cond_estimate;
+ *   SGPR_FIT_REG fits: predict_nd, applymap_nd, applymap_nd_tangent (predict_genfun: SGPR_E_ARG, see there);
+ *   create_nd fits with d > 1: predict_rows, nll_grad, nll_grad_terms.
+ * Argument errors (SGPR_E_ARG) are reported first.  Every refusal happens before any device call and leaves the handle, the
+ * device buffers and the scratch as they were; its message (sgpr_last_error) begins with the entry's name without "sgpr_"
+ * -- "fit_alpha: not solved".  Apart from the stage and scratch changes named with each entry, the "needs factored" and
+ * "needs solved" entries only read the handle: their results do not depend on which of them ran before, in which order,
+ * or on sgpr_fit_trim / sgpr_trim in between.  (sgpr_fit_get_matrix completes the matrix in place -- the upper triangle of
+ * a SGPR_FIT_LOWER_ONLY Ky filled, the strict upper triangle of L zeroed --, which no other entry reads.) */
 
 /* Allocates HBM for an n = 2*n_pts order system (n = n_pts with SGPR_FIT_REG) and uploads
  * x, y (n_pts each), z (n). */
@@ -188,7 +210,8 @@ int sgpr_fit_nll_grad_terms(sgpr_fit_t f, double *terms5);
  * c (n) = Q^T z.  The fit has to be built / run again before any other query.
  * Returns 0, or 1 if the rotations did not converge. */
 int sgpr_fit_eig(sgpr_fit_t f, double *w, double *c);
-/* K* . alpha for m test points with d pairs each: Xt (m x 2d), out (m x 2d), both column-major */
+/* K* . alpha for m test points with d pairs each: Xt (m x 2d), out (m x 2d), both column-major.  SGPR_E_STATE before a solve
+ * and for SGPR_FIT_REG and SGPR_FIT_BLOCK_QQ / _PP fits (their alpha has n_pts entries, the pair kernel reads 2 d n_pts). */
 int sgpr_fit_predict_nd(sgpr_fit_t f, int m, const double *Xt, size_t ldxt, double *out);
 /* Posterior mean and covariance at m test points from the cached factor: mean_t = K*_t alpha,
  * cov_t = K**_t - K*_t Ky^-1 K*_t^T (latent prior, no noise).  Xt (m x 2d; (q, P) for d = 1 and reg), column-major,

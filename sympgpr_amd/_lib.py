@@ -19,7 +19,10 @@ _vp = C.c_void_p
 
 
 class SympGPRError(RuntimeError):
-    pass
+    """`code`: the SGPR_E_* value the library returned (None when the error was raised on the Python side);
+    `detail`: the library's own message, which begins with the name of the entry that refused."""
+    code = None
+    detail = ""
 
 
 class NoDeviceError(SympGPRError):
@@ -262,9 +265,10 @@ def check(rc, what=""):
     if rc > 0:
         raise np.linalg.LinAlgError("%d-th leading minor of the array is not positive definite" % rc)
     msg = load_library().sgpr_last_error().decode(errors="replace")
-    if rc == E_NODEVICE:
-        raise NoDeviceError(msg)
-    raise SympGPRError("%s failed (%d): %s" % (what or "libsympgpr_hip call", rc, msg))
+    err = (NoDeviceError(msg) if rc == E_NODEVICE else
+           SympGPRError("%s failed (%d): %s" % (what or "libsympgpr_hip call", rc, msg)))
+    err.code, err.detail = rc, msg
+    raise err
 
 
 def dptr(a):

@@ -295,7 +295,10 @@ int sgpr_fit_build(sgpr_fit_t f) { return fit_build_impl(f, f && (f->flags & SGP
  * (a failed factorisation has overwritten it), diagonalised in place, and
  * w (n, ascending eigenvalues) and c = Q^T z (n) come back; the caller forms
  * alpha = Q diag(1/w) c and the log-determinant from whichever eigenpairs it keeps.
- * Two n x n matrices in HBM.  Returns 0, or 1 if the rotations did not converge in 40 sweeps. */
+ * Two n x n matrices in HBM.  Returns 0, or 1 if the rotations did not converge in 100 sweeps.  (The eigenvalues reach their
+ * rounding floor, ~ n eps max|w|, within ~20 sweeps, but Ky has hundreds of eigenvalues crowded just above |sig2n|, and inside
+ * such a cluster the off-diagonal mass falls by only ~0.8 per sweep: the 1e-14 ||Ky||_F of syev_jacobi takes ~45 sweeps at
+ * n = 660 and ~56 at n = 640 of a pair fit; with the former limit of 40 those fits were reported as not converged.) */
 int sgpr_fit_eig(sgpr_fit_t f, double *w, double *c)
 {
     int rc = guard("fit_eig", f, w && c);
@@ -304,7 +307,7 @@ int sgpr_fit_eig(sgpr_fit_t f, double *w, double *c)
     DevBuf V, tmp;
     if ((rc = V.alloc(n * n * sizeof(double))) || (rc = tmp.alloc(n * sizeof(double)))) return rc;
     int sweeps = 0;
-    const int st = syev_jacobi(f->n, f->dA, n, V.as<double>(), n, w, 40, &sweeps, f->st);
+    const int st = syev_jacobi(f->n, f->dA, n, V.as<double>(), n, w, 100, &sweeps, f->st);
     f->built = f->factored = f->solved = false;   // dA now holds the eigenvectors
     if (st < 0) return st;
     SGPR_HIP(hipMemsetAsync(tmp.p, 0, n * sizeof(double), f->st));
@@ -588,10 +591,12 @@ int sgpr_fit_loo(sgpr_fit_t f, double *loo2, double *resid, double *cov, double 
 }
 
 /* K*(2d x 2d N) . alpha for m test points Xt (m x 2d, column-major, leading dimension ldxt):
- * out (m x 2d, column-major, ld m): column a = predicted d F / d x_a */
+ * out (m x 2d, column-major, ld m): column a = predicted d F / d x_a.  The d-pair kernel reads alpha as 2d blocks of n_pts
+ * entries: a scalar-kernel or single-block fit has one such block and is refused, as by the other pair predictions. */
 int sgpr_fit_predict_nd(sgpr_fit_t f, int m, const double *Xt, size_t ldxt, double *out)
 {
-    int rc = guard("fit_predict_nd", f, m >= 0 && Xt && out && ldxt >= (size_t)(m > 0 ? m : 1), NEED_SOLVED);
+    int rc = guard("fit_predict_nd", f, m >= 0 && Xt && out && ldxt >= (size_t)(m > 0 ? m : 1),
+                   NEED_SOLVED | NEED_ALL_BLOCKS | NEED_PAIR_KERNEL);
     if (rc || m == 0) return rc;
     const int D = 2 * f->d;
     DevBuf dT, dO;

@@ -60,7 +60,8 @@ class SympFit:
         return self
 
     def predict_pairs(self, Xt):
-        """K* . alpha for test points Xt (m, 2d) -> (m, 2d): column a = predicted dF/dx_a."""
+        """K* . alpha for test points Xt (m, 2d) -> (m, 2d): column a = predicted dF/dx_a.  Needs a solved fit (run()); not
+        defined for reg=True and block="qq" / "PP" fits (SympGPRError, SGPR_E_STATE): predict_rows serves a reg=True fit."""
         Xt = np.asfortranarray(np.atleast_2d(Xt), dtype=np.float64)
         m = Xt.shape[0]
         out = np.empty((m, Xt.shape[1]), order="F")
