@@ -84,6 +84,9 @@ class HipOps:
     """Block operations on torch CUDA tensors through libsympgpr_hip.so (device pointers)."""
 
     device_type = "cuda"
+    # The factor workspace sits behind L_KK in one buffer and the panels start at block offsets: the kernels store the leaf
+    # inverses and load their operands as 16-byte pairs, so every block offset must be an even number of doubles.
+    block_align = 2
 
     def __init__(self, device):
         self.lib = L.load_library()
@@ -225,7 +228,12 @@ class DistFit:
         # 128-row leaf (any divisor for small test problems); any N / nb, for one pair per point and for d > 1
         # alike (see build()).
         self.nb = self._pick_nb(self.N, nb, 1)
-        nb = self.nb
+        want_nb, nb = nb, self.nb
+        # every rank derives the same nb, so every rank raises here, before the first collective
+        align = getattr(ops, "block_align", 1)
+        if nb % align:
+            raise ValueError("block size %d (the largest divisor of N = %d up to the %d asked for) is not a multiple of %d, which "
+                             "this backend needs to keep its blocks 16-byte aligned: ask for another nb" % (nb, self.N, want_nb, align))
         self.nbk = self.n // nb
         self.hyp = np.asarray(hyp, dtype=np.float64)
         self.sig2n = abs(float(sig2n))

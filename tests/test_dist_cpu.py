@@ -94,10 +94,12 @@ def _run(world, N, nb, fam="A", singular=False):
     return dict(out)
 
 
-# the last four: N / nb NOT a multiple of the grid dimensions (the q-rows and the P-rows a rank holds
+# from (2, 20, 4) on: N / nb NOT a multiple of the grid dimensions (the q-rows and the P-rows a rank holds
 # then belong to different points: the four parts of K are built over their own selections)
+# (6, 4, 4): two block rows on three process rows -- a process row that holds no rows at all
+# (8, 20, 4): ten block rows on 4 x 2 -- the column exchange with gcd 2 and period 2, four ranks without a diagonal block
 @pytest.mark.parametrize("world,N,nb", [(2, 32, 4), (4, 32, 4), (4, 64, 8), (6, 48, 4), (1, 24, 4), (8, 64, 4),
-                                        (2, 20, 4), (4, 36, 4), (6, 40, 4), (3, 28, 4)])
+                                        (2, 20, 4), (4, 36, 4), (6, 40, 4), (3, 28, 4), (6, 4, 4), (8, 20, 4)])
 def test_block_cyclic_fit_matches_oracle(oracle, world, N, nb):
     res = _run(world, N, nb)
     rng = np.random.default_rng(1234)
@@ -199,6 +201,48 @@ def test_block_size_is_picked_to_divide():
     assert DistFit._pick_nb(40, 16, 1) == 10
     with pytest.raises(ValueError):
         DistFit._pick_nb(7, 4, 2)
+
+
+def _worker_odd_nb(rank, world, port, out):
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    os.environ["SYMPGPR_NO_TORCH_PRELOAD"] = "1"
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from sympgpr_amd.dist import DistFit, HipOps
+        from tests.ref_ops import RefOps
+
+        class Aligned(RefOps):
+            block_align = HipOps.block_align
+
+        rng = np.random.default_rng(1234)
+        N = 20
+        q, P, z = rng.uniform(0, 2 * np.pi, N), rng.uniform(-3, 3, N), rng.standard_normal(2 * N)
+        got = []
+        for ops, nb in ((Aligned(), 5), (Aligned(), 7), (Aligned(), 4), (RefOps(), 5)):
+            try:
+                got.append(DistFit(ops, "A", q, P, z, [1.0, 1.0, 1.0], 0.05, nb=nb).nb)
+            except ValueError as e:
+                got.append(str(e))
+        out[rank] = (HipOps.block_align, got)
+    finally:
+        dist.destroy_process_group()
+
+
+def test_odd_block_size_is_refused_by_a_backend_that_needs_alignment():
+    """HipOps keeps L_KK and the factor workspace back to back and the panels at block offsets, and its kernels move 16-byte
+    pairs: an odd nb would put them on odd offsets.  A backend that declares block_align gets a ValueError on every rank (before
+    any collective) instead; one that declares none (the NumPy backend) takes any divisor."""
+    out = mp.Manager().dict()
+    mp.spawn(_worker_odd_nb, args=(2, _free_port(), out), nprocs=2, join=True)
+    for r in range(2):
+        align, got = out[r]
+        assert align == 2
+        assert "block size 5" in got[0] and "multiple of 2" in got[0]         # 5 asked for, 5 divides 20
+        assert "block size 5" in got[1]                                       # 7 asked for: the largest divisor below is 5
+        assert got[2:] == [4, 5]
 
 
 def test_grid_shape():

@@ -365,6 +365,9 @@ def _dist_worker(rank, world, port, backend, N, nb, out):
         dist.destroy_process_group()
 
 
+_DIST_ORACLE = {}
+
+
 @pytest.mark.parametrize("world,backend,N,nb", [(1, "nccl", 2048, 256), (2, "gloo", 1024, 128),
                                                 (4, "gloo", 2048, 256)])
 def test_block_cyclic_hip_ops(oracle, world, backend, N, nb):
@@ -387,10 +390,15 @@ def test_block_cyclic_hip_ops(oracle, world, backend, N, nb):
     with SympFit("A", q, P, z, [l, l, 1.0], 1e-2 / l**2) as f:
         a_ref, nll_ref = f.run().alpha(), f.nll()
         X_ref = f.solve_rhs(Bm)
+    if N not in _DIST_ORACLE:          # (two of the cases share N)
+        _DIST_ORACLE[N] = oracle.fit("A", q, P, z, [l, l, 1.0], 1e-2 / l**2, threads=8)[:2]
+    a_o, nll_o = _DIST_ORACLE[N]
     for r in range(world):
         a, nll, Xs = out[r]
         assert np.linalg.norm(a - a_ref) / np.linalg.norm(a_ref) < 1e-10
         assert nll == pytest.approx(nll_ref, rel=1e-11)
+        assert np.linalg.norm(a - a_o) / np.linalg.norm(a_o) < 1e-10       # and against the CPU oracle: not HIP against HIP alone
+        assert nll == pytest.approx(nll_o, rel=1e-11)
         assert np.linalg.norm(Xs - X_ref) <= 1e-10 * np.linalg.norm(X_ref)
         assert np.linalg.norm(Xs[:, 0] - a) <= 1e-12 * np.linalg.norm(a)
 
