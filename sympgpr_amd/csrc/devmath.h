@@ -1,4 +1,4 @@
-// devmath.h -- fp64 exp / sincos for the Gram kernels (gfx950 has no fp64 transcendental
+// devmath.h -- fp64 exp / sincos / cos for the Gram kernels (gfx950 has no fp64 transcendental
 // hardware; everything is FMA chains on the fp64 VALU, so instruction count is what matters).
 //
 // The reference evaluates exp/sin/cos three times per matrix ENTRY (kernels.f90:58-94); the
@@ -99,6 +99,21 @@ SGPR_DEV void sincos_fast(double h, double &s, double &c)
     c = ((q + 1) & 2) ? -c0 : c0;
 }
 
+// cos(x) alone, with a reduction of its own: within 2 ulp of its own size next to its zeros (cos2h_sel below).
+SGPR_DEV double cos_fast(double x)
+{
+    if (__builtin_expect(!(__builtin_fabs(x) < 1.0e9), 0)) return ::cos(x);
+    const double TWO_OVER_PI = 6.36619772367581382433e-01;
+    const double PIO2_HI = 1.57079632679489655800e+00;
+    const double PIO2_MID = 6.12323399573676603587e-17;
+    const double n = __builtin_rint(x * TWO_OVER_PI);
+    double r = __builtin_fma(-n, PIO2_HI, x);
+    r = __builtin_fma(-n, PIO2_MID, r);
+    const int q = (int)n;
+    const double c0 = (q & 1) ? ksin(r) : kcos(r);
+    return ((q + 1) & 2) ? -c0 : c0;
+}
+
 template <bool OCML>
 SGPR_DEV double exp_sel(double x)
 {
@@ -110,6 +125,24 @@ SGPR_DEV void sincos_sel(double h, double &s, double &c)
 {
     if constexpr (OCML) ::sincos(h, &s, &c);
     else sincos_fast(h, s, c);
+}
+
+template <bool OCML>
+SGPR_DEV double cos_sel(double x)
+{
+    if constexpr (OCML) return ::cos(x);
+    else return cos_fast(x);
+}
+
+// cos 2h for  l^2 cos 2h - (sin h cos h)^2,  given s2 = sin^2 h.  1 - 2 s2 is off by up to 3 eps s2 (absolute), which the
+// entry carries as 3 eps l^2 s2 against terms of size l^2 |cos 2h| + s2 c2: at the zero of cos 2h that is 6 l^2 eps of them.
+// Harmless while l^2 <= 1, so there the one FMA stays; above, cos 2h gets its own reduction.  l2 is a constant of the launch
+// (of the problem, in the batched kernels): the branch is uniform.
+template <bool OCML>
+SGPR_DEV double cos2h_sel(double h, double s2, double l2)
+{
+    if (l2 > 1.0) return cos_sel<OCML>(2.0 * h);
+    return __builtin_fma(-2.0, s2, 1.0);
 }
 
 }  // namespace sgpr

@@ -48,11 +48,12 @@ __device__ __forceinline__ void coord(const NdArgs &a, double dx, double &arg, d
         arg = o[0]; g = o[1]; nh = o[2];
     } else if constexpr (FAM != SGPR_FAM_C && M < D / 2) {
         double s, c;
-        sincos_fast(a.hs[M] * dx, s, c);
+        const double h = a.hs[M] * dx;
+        sincos_fast(h, s, c);
         const double s2 = s * s, sc = s * c;
         arg = -0.5 * a.inv_l2[M] * s2;
         g = -a.hs[M] * sc * a.inv_l2[M];
-        nh = (a.hs[M] * a.hs[M]) * (a.l2[M] * __builtin_fma(-2.0, s2, 1.0) - sc * sc) * a.inv_l4[M];
+        nh = (a.hs[M] * a.hs[M]) * (a.l2[M] * cos2h_sel<false>(h, s2, a.l2[M]) - sc * sc) * a.inv_l4[M];   // devmath.h
     } else {
         const double d2 = dx * dx;
         arg = -0.5 * a.inv_l2[M] * d2;

@@ -44,7 +44,9 @@ __device__ __forceinline__ void pair_eval(double xa, double ya, double xb, doubl
         sincos_sel<OCML>(h, s, c);
         const double s2 = s * s;
         const double sc = s * c;
-        const double cos2h = __builtin_fma(-2.0, s2, 1.0);  // cos(x_a - x_b) resp. cos(2p dx)
+        // cos(x_a - x_b) resp. cos(2p dx): 1 - 2 s^2 while lx^2 <= 1, reduced on its own above (devmath.h; the zero of
+        // kxx at lx = 100, tests/test_gpu_range.py)
+        const double cos2h = cos2h_sel<OCML>(h, s2, kc.lx2);
         if constexpr (FAM == SGPR_FAM_B) {
             // kernels_sum.f90:58-88: the q and P factors separate, mixed block is zero.
             const double Ex = exp_sel<OCML>(-0.5 * (s2 * kc.inv_lx2));
@@ -74,10 +76,24 @@ template <int FAM, int DL>
 __device__ __forceinline__ void pair_eval_d(double xa, double ya, double xb, double yb,
                                             const KConst &kc, double &dxx, double &dxy, double &dyy)
 {
-    if constexpr (FAM == SGPR_FAM_B || FAM == SGPR_FAM_USER) {
-        // the sum kernel's dl-functions (kernels_sum.f90:133-208) come straight from the generator
-        // (tools/gen_kernels.py): no driver differentiates this family, nothing to hand-optimise; the user slot has
-        // nothing but generated code
+    if constexpr (FAM == SGPR_FAM_B && DL == DERIV_LX) {
+        // the sum kernel's q factor is family A's with its own exp (kernels_sum.f90:133-160): the factored form below,
+        // not the generated one, whose sin^2 h - cos^2 h loses cos 2h near its zeros at every lx
+        const double h = kc.hscale * (xa - xb);
+        double s, c;
+        sincos_fast(h, s, c);
+        const double u = s * s, sc = s * c;
+        const double cos2h = cos2h_sel<false>(h, u, kc.lx2);
+        const double E = exp_fast(-0.5 * (u * kc.inv_lx2));
+        const double kxx = kc.cxx * (kc.lx2 * cos2h - sc * sc) * E;
+        const double gp = (-2.0 * cos2h + 4.0 * (sc * sc) * kc.inv_lx2) * kc.inv_lx3;
+        dxx = __builtin_fma(kxx, u * kc.inv_lx3, kc.gxx * gp * E);
+        dyy = 0.0;
+        dxy = 0.0;
+        return;
+    } else if constexpr (FAM == SGPR_FAM_B || FAM == SGPR_FAM_USER) {
+        // the sum kernel's d/dly functions (kernels_sum.f90:161-208) come straight from the generator
+        // (tools/gen_kernels.py); the user slot has nothing but generated code
         double o[4];
         if constexpr (DL == DERIV_LX) gen::pair_dlx<FAM>(xa, ya, xb, yb, kc.lx, kc.ly, kc.p, o);
         else                          gen::pair_dly<FAM>(xa, ya, xb, yb, kc.lx, kc.ly, kc.p, o);
@@ -102,7 +118,7 @@ __device__ __forceinline__ void pair_eval_d(double xa, double ya, double xb, dou
         sincos_fast(h, s, c);
         u = s * s;
         const double sc = s * c;
-        const double cos2h = __builtin_fma(-2.0, u, 1.0);
+        const double cos2h = cos2h_sel<false>(h, u, kc.lx2);
         E = exp_fast(-0.5 * (v * kc.inv_ly2) - 0.5 * (u * kc.inv_lx2));
         kxx = kc.cxx * (kc.lx2 * cos2h - sc * sc) * E;
         kxy = kc.cxy * (dy * sc) * E;
