@@ -144,6 +144,7 @@ typedef struct sgpr_fit *sgpr_fit_t;
  *   needs factored: solve, ldiag, solve_rhs, solve_rhs_dev, inverse, cond_estimate
  *   needs solved:   alpha, nll, predict_rows, predict_nd, predict_cov, predict_genfun, nll_grad, nll_grad_terms,
  *                   nll_grad_full, loo, applymap_nd, applymap_nd_tangent
+ *                   loo_grad (as nll_grad_full: SGPR_FIT_BLOCK_QQ / _PP fits refused; grows the fit's scratch block)
  * An entry called without what it needs returns SGPR_E_STATE.  So does one called on a kind of fit it is not defined for:
  *   SGPR_FIT_BLOCK_QQ / _PP fits: every "needs solved" entry except alpha and nll, and cond_estimate;
  *   SGPR_FIT_REG fits: predict_nd, applymap_nd, applymap_nd_tangent (predict_genfun: SGPR_E_ARG, see there);
@@ -265,6 +266,23 @@ int sgpr_fit_nll_grad_full(sgpr_fit_t f, double *grad, int ngrad);
  * panel (min(n, 2048 or 4096) x n doubles), 8 N D (D + 1) / 2 bytes of blocks, the outputs and the partial sums, in the
  * fit's own scratch block, kept until sgpr_fit_trim.  ABI 5 (an additional entry point). */
 int sgpr_fit_loo(sgpr_fit_t f, double *loo2, double *resid, double *cov, double *lpd);
+/* One of sgpr_fit_loo's two objectives and its exact gradient in every hyperparameter.  which = SGPR_LOO_LPD: *value = loo;
+ * SGPR_LOO_PRESS: *value = press.  grad, its order and ngrad = nhyp + 1 are those of sgpr_fit_nll_grad_full; the last entry
+ * is d/dsig2n and carries sign(sig2n).  With S_i = C_i^-1, r_i = S_i a_i (sgpr_fit_loo's notation):
+ *   d value / d theta = 1/2 sum_jk (M - beta alpha^T - alpha beta^T)_jk dKy_jk / d theta,  M = Ky^-1 W Ky^-1,  beta = Ky^-1 v,
+ *   loo:   W[B_i, B_i] = r_i r_i^T + S_i,             v[B_i] = r_i;
+ *   press: W[B_i, B_i] = 2 (r_i s_i^T + s_i r_i^T),   v[B_i] = 2 s_i,  s_i = S_i r_i;   W is zero outside the N blocks.
+ * One weight matrix serves all hyperparameters: Ky^-1 is formed densely on the device (n^3 / 3 + n^3 / 3 flop), M by row
+ * panels (n^3 flop), each contracted with dKy evaluated pair by pair; the sums are deterministic.  If a point's block has a
+ * pivot that is not positive and finite, *value and every entry of grad are NaN and the call returns 0.  The factor, alpha,
+ * the NLL and the workspace are left as they are.  SGPR_E_ARG for a null handle, value or grad, a wrong ngrad or an unknown
+ * which (before any device call); SGPR_E_STATE before a solve and for SGPR_FIT_BLOCK_QQ / _PP fits; SGPR_E_NOMEM -- the
+ * message names the bytes needed, the handle keeps what it had -- if the scratch does not fit; SGPR_E_HIP if the fit's strip
+ * solve gave up on a hand-off.  Device scratch: two n x n blocks, one panel (min(n, 2048 or 4096) x n doubles) and a few
+ * vectors, in the fit's own scratch block, kept until sgpr_fit_trim: n <= ~98 304 on one card.  ABI 5 (an additional entry
+ * point). */
+enum { SGPR_LOO_LPD = 0, SGPR_LOO_PRESS = 1 };
+int sgpr_fit_loo_grad(sgpr_fit_t f, int which, double *value, double *grad, int ngrad);
 /* cond_2(Ky) estimated from below with the device's own kernels (needs a valid factor): lambda_max by `iters` power iterations on
  * Ky v -- the rows of K re-evaluated from the training points by the prediction kernel, plus |sig2n| v --, lambda_min by `iters`
  * inverse iterations with the cached factor.  out4 = {lambda_max, lambda_min, cond, relative change of the quotients in the last

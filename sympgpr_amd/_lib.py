@@ -12,6 +12,7 @@ G_QQ, G_PQ, G_QP, G_PP, G_ALL, G_LOWER, G_OCML, G_DLX, G_DLY = 1, 2, 4, 8, 15, 1
 FIT_LOWER_ONLY, FIT_REG, FIT_BLOCK_QQ, FIT_BLOCK_PP = 1, 4, 8, 16
 MAP_WRAP_Q, MAP_WRAP_P, MAP_EXPLICIT, MAP_LOSS_NEGP = 1, 2, 4, 8
 E_ARG, E_NODEVICE, E_HIP, E_NOMEM, E_STATE = -1, -2, -3, -4, -5
+LOO_LPD, LOO_PRESS = 0, 1
 
 ABI_VERSION = 5      # include/sympgpr_hip.h: SGPR_ABI_VERSION
 _dp = C.POINTER(C.c_double)
@@ -77,6 +78,7 @@ SIGNATURES = {
     "sgpr_fit_predict_genfun": (C.c_int, [_vp, C.c_int, _dp, C.c_size_t, _dp, _dp, _dp]),
     "sgpr_fit_nll_grad_full": (C.c_int, [_vp, _dp, C.c_int]),
     "sgpr_fit_loo": (C.c_int, [_vp, _dp, _dp, _dp, _dp]),
+    "sgpr_fit_loo_grad": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_int]),
     "sgpr_fit_stage_ms": (C.c_int, [_vp, _dp, _dp, _dp]),
     "sgpr_fit_cond_estimate": (C.c_int, [_vp, C.c_int, _dp]),
     "sgpr_fit_trim": (C.c_int, [_vp]),

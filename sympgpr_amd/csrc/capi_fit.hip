@@ -590,6 +590,62 @@ int sgpr_fit_loo(sgpr_fit_t f, double *loo2, double *resid, double *cov, double 
     return strip_give_up("fit_loo", h);
 }
 
+/* The gradient of loo or press in every hyperparameter and sig2n (loograd.hip): the dense Ky^-1, one weight matrix
+ * M = Ky^-1 W Ky^-1 by row panels, each contracted with dK by the rank-2 instances of nllgrad.hip's kernels; the raw sums
+ * are scaled as sgpr_fit_nll_grad_full scales its own.  The scratch is the fit's own block: a block that is too small is
+ * replaced only once the larger one exists, so a failed allocation leaves the handle as it was. */
+int sgpr_fit_loo_grad(sgpr_fit_t f, int which, double *value, double *grad, int ngrad)
+{
+    int rc = guard("fit_loo_grad", f, value && grad);
+    if (rc) return rc;
+    const bool reg = f->flags & SGPR_FIT_REG, hasp = family_has_p(f->family);
+    const int nhyp = f->d > 1 ? f->nhyp_nd : (hasp ? 4 : 3);
+    if (ngrad != nhyp + 1) { set_error("fit_loo_grad: ngrad must be nhyp + 1 = " + std::to_string(nhyp + 1)); return SGPR_E_ARG; }
+    if (which != SGPR_LOO_LPD && which != SGPR_LOO_PRESS) { set_error("fit_loo_grad: which must be SGPR_LOO_LPD or SGPR_LOO_PRESS"); return SGPR_E_ARG; }
+    if ((rc = guard("fit_loo_grad", f, true, NEED_SOLVED | NEED_ALL_BLOCKS))) return rc;
+    const int d = f->d, nl = reg ? 2 : 2 * d, D = reg ? 1 : 2 * d;
+    double l[6], pp[3] = {0.0, 0.0, 0.0}, sig;
+    if (d > 1) {
+        for (int m = 0; m < nl; ++m) l[m] = f->hyp_nd[m];
+        for (int m = 0; m < d && hasp; ++m) pp[m] = f->hyp_nd[nl + m];
+        sig = f->hyp_nd[nhyp - 1];
+    } else {
+        l[0] = f->kc.lx; l[1] = f->kc.ly; pp[0] = f->kc.p; sig = f->kc.sig;
+    }
+    const int nacc = nhyp + 1;
+    const LooGradLayout o = loo_grad_layout(f->n, f->npts, D, nacc);
+    const size_t need = o.total * sizeof(double);
+    if (need > f->rhs_scratch_bytes) {
+        void *p = nullptr;
+        if (hipMalloc(&p, need) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("fit_loo_grad: " + std::to_string(need) + " bytes of device scratch (two n x n blocks and a panel) do not fit");
+            return SGPR_E_NOMEM;
+        }
+        if (f->rhs_scratch) { SGPR_HIP(hipStreamSynchronize(f->st)); (void)hipFree(f->rhs_scratch); }
+        f->rhs_scratch = p;
+        f->rhs_scratch_bytes = need;
+    }
+    double *S = static_cast<double *>(f->rhs_scratch);
+    if ((rc = fit_loo_grad(f->family, d, reg, which, f->npts, f->n, f->dA, (size_t)f->n, f->work, f->dX, f->dalpha, l, pp, nacc, S,
+                           f->st)))
+        return rc;
+    double raw[13];
+    int h[8] = {};   // the strip solves' state words, fetched in the results' synchronisation
+    SGPR_HIP(hipMemcpyAsync(raw, S + o.sums, (nacc + 1) * sizeof(double), hipMemcpyDeviceToHost, f->st));
+    if (trsv_uses_strips(f->n, f->dA, (size_t)f->n))
+        SGPR_HIP(hipMemcpyAsync(h, trsv_state(f->n, f->work), sizeof(h), hipMemcpyDeviceToHost, f->st));
+    SGPR_HIP(hipStreamSynchronize(f->st));
+    if ((rc = strip_give_up("fit_loo_grad", h))) return rc;
+    *value = which == SGPR_LOO_LPD ? -raw[nacc] : raw[nacc];
+    for (int k = 0; k < nhyp - 1; ++k) grad[k] = 0.5 * sig * raw[k];
+    grad[nhyp - 1] = 0.5 * raw[nhyp - 1];
+    grad[nhyp] = (f->sig2n < 0.0 ? -0.5 : 0.5) * raw[nhyp];
+    if (std::isnan(*value))   // a point without a positive definite block: its NaN reaches every sum through M; made explicit
+        for (int k = 0; k <= nhyp; ++k) grad[k] = *value;
+    return 0;
+}
+
 /* K*(2d x 2d N) . alpha for m test points Xt (m x 2d, column-major, leading dimension ldxt):
  * out (m x 2d, column-major, ld m): column a = predicted d F / d x_a.  The d-pair kernel reads alpha as 2d blocks of n_pts
  * entries: a scalar-kernel or single-block fit has one such block and is refused, as by the other pair predictions. */

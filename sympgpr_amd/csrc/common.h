@@ -235,6 +235,14 @@ int nll_grad_full(int family, int d, bool reg, int N, int n, const double *L, si
 int kyinv_panel_width(int n, const char *knob);                   // 2048 rows up to n = 8192, 4096 above; tunable `knob` overrides
 int kyinv_row_panel(int n, int J, int rows, const double *L, size_t ldl, const void *work, double *R, size_t ldr, hipStream_t st);
 
+// the contraction for loograd.hip: the workgroups of one panel of ldr rows; one launch with the rank-2 weight
+// Mp - (beta alpha^T + alpha beta^T) on Mp = M[J:J+rows, J:] (partials as nll_grad_full's, workgroup wg0 on); the fold
+size_t grad_contract_wgs(int ldr, int N);
+int grad_contract_rank2(int family, int d, bool reg, int N, int J, int rows, const double *Mp, size_t ldr, const double *alpha,
+                        const double *beta, const double *X, const double *l, const double *pp, double *part, size_t nwg,
+                        size_t wg0, hipStream_t st);
+int grad_fold(const double *part, size_t nwg, int nacc, double *out, hipStream_t st);   // out[k] = sum_w part[k nwg + w]
+
 // ---- loo.hip : leave-one-point-out cross-validation of a solved fit from the same row panels (sgpr_fit_loo)
 struct LooLayout { size_t panel, blocks, part, resid, cov, lpd, sums, total; };   // offsets in doubles into the scratch
 LooLayout loo_layout(int n, int N, int D);
@@ -242,6 +250,17 @@ LooLayout loo_layout(int n, int N, int D);
 // scratch + sums, the residuals (n, the layout of z) at + resid, the covariances (N x D x D) at + cov, lpd (N) at + lpd.
 int fit_loo(int D, int N, int n, const double *L, size_t ldl, const void *work, const double *alpha, double *scratch,
             hipStream_t st);
+
+// ---- loograd.hip : the gradient of loo / press in all hyperparameters from the dense Ky^-1 (sgpr_fit_loo_grad)
+struct LooGradLayout {   // offsets in doubles into the scratch; nb / ldr: the rows of a panel of M and its leading dimension
+    size_t kinv, y, panel, w, v, beta, part, part_obj, sums, total, nwg, nwg_points;
+    int nb, ldr;
+};
+LooGradLayout loo_grad_layout(int n, int N, int D, int nacc);
+// scratch: loo_grad_layout(...).total doubles.  Leaves the nacc raw sums of nll_grad_full's layout at scratch + sums and the
+// objective's raw sum (sum lpd = -loo, or press) behind them; the caller scales them.  `work`: the factor's workspace (potrs_vec)
+int fit_loo_grad(int family, int d, bool reg, int which, int N, int n, const double *L, size_t ldl, void *work, const double *X,
+                 const double *alpha, const double *l, const double *pp, int nacc, double *scratch, hipStream_t st);
 
 // ---- batch.hip : many small fits (order <= 256 each) in one launch, one workgroup per problem
 int fit_batch_max_order();

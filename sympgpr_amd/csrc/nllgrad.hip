@@ -17,6 +17,8 @@
 // The sums are deterministic, with no atomics: per-workgroup partials (a fixed wave order), folded at the end by one
 // workgroup per component in a fixed order.  Per panel the contraction costs nb N pair evaluations against
 // 2 nb (n - J)^2 flop of the solves: a small part of the whole.
+// The same kernels with their last template flag set contract the weight of the LOO gradient (loograd.hip), whose panel
+// holds M = Ky^-1 W~ Ky^-1 and whose rank-1 term is the rank-2 beta alpha^T + alpha beta^T: everything after W is shared.
 #include <type_traits>
 
 #include "common.h"
@@ -40,6 +42,9 @@ struct GradArgs {
     double l[6], pp[3];        // the lengths, the q factors' periods (unused without one)
     double *part;              // accumulator k of workgroup w at part[k nwg + w]
     size_t nwg, wg0;           // workgroups of all panels, this panel's first
+};
+struct GradArgs2 : GradArgs {  // the rank-2 weight of the LOO gradient (loograd.hip): R holds a panel of M = Ky^-1 W~ Ky^-1
+    const double *beta;        // n
 };
 
 template <int FAM> constexpr bool sum_kernel() { return FAM == SGPR_FAM_B || (FAM == SGPR_FAM_USER && gen::user_is_sum); }
@@ -66,12 +71,14 @@ __device__ __forceinline__ void store_partials(const GradArgs &a, double (&acc)[
 
 // pair fits, D = 2d parts; accumulators: l_0 .. l_{D-1}, [p_0 .. p_{d-1},] sig, noise (sig factor applied by the caller).
 // nllgrad_pair.h's pair_grad is this loop body for the batched gradient; it stays inline here (see that header)
-template <int FAM, int D, bool HASP>
-__global__ __launch_bounds__(NG_T) void nllgrad_pairs_kernel(const GradArgs a)
+// R2: the weight is R - (beta_i alpha_col + alpha_i beta_col) (loograd.hip: R holds a panel of M) instead of R - alpha_i alpha_col
+template <int FAM, int D, bool HASP, bool R2 = false>
+__global__ __launch_bounds__(NG_T) void nllgrad_pairs_kernel(const std::conditional_t<R2, GradArgs2, GradArgs> a)
 {
     constexpr int d = D / 2, NP = HASP ? d : 0, NACC = D + NP + 2;
     __shared__ double sx[NG_CJ][D];
     __shared__ double sal[D][NG_CJ];
+    __shared__ double sbe[R2 ? D : 1][R2 ? NG_CJ : 1];
     const int p0 = blockIdx.y * NG_CJ, np = min(NG_CJ, a.N - p0);
     const int li = blockIdx.x * NG_T + threadIdx.x;                  // row inside the panel
     const long i = (long)a.J + li;                                   // row of Ky
@@ -79,6 +86,7 @@ __global__ __launch_bounds__(NG_T) void nllgrad_pairs_kernel(const GradArgs a)
         const int j = e % np, m = e / np;
         sx[j][m] = a.X[(size_t)(p0 + j) + (size_t)m * a.N];
         sal[m][j] = a.alpha[(size_t)m * a.N + p0 + j];
+        if constexpr (R2) sbe[m][j] = a.beta[(size_t)m * a.N + p0 + j];
     }
     __syncthreads();
     double acc[NACC];
@@ -91,6 +99,8 @@ __global__ __launch_bounds__(NG_T) void nllgrad_pairs_kernel(const GradArgs a)
 #pragma unroll
         for (int m = 0; m < D; ++m) xi[m] = a.X[(size_t)pi + (size_t)m * a.N];
         const double ai = a.alpha[i];
+        double bi = 0.0;
+        if constexpr (R2) bi = a.beta[i];
         const double *Rrow = a.R + li;
         for (int jj = 0; jj < np; ++jj) {
             const long pj = p0 + jj;
@@ -101,7 +111,9 @@ __global__ __launch_bounds__(NG_T) void nllgrad_pairs_kernel(const GradArgs a)
                 const long col = (long)c * a.N + pj;
                 w[c] = 0.0;
                 if (col >= i) {
-                    const double W = Rrow[(size_t)(col - a.J) * a.ldr] - ai * sal[c][jj];
+                    double W;
+                    if constexpr (R2) W = Rrow[(size_t)(col - a.J) * a.ldr] - __builtin_fma(bi, sal[c][jj], ai * sbe[c][jj]);
+                    else W = Rrow[(size_t)(col - a.J) * a.ldr] - ai * sal[c][jj];
                     if (col == i) { w[c] = W; acc[NACC - 1] += W; }
                     else w[c] = 2.0 * W;
                     any = true;
@@ -177,11 +189,12 @@ __global__ __launch_bounds__(NG_T) void nllgrad_pairs_kernel(const GradArgs a)
 }
 
 // reg fits (one part); accumulators: lx, ly, [p,] sig, noise
-template <int FAM, bool HASP>
-__global__ __launch_bounds__(NG_T) void nllgrad_reg_kernel(const GradArgs a)
+template <int FAM, bool HASP, bool R2 = false>
+__global__ __launch_bounds__(NG_T) void nllgrad_reg_kernel(const std::conditional_t<R2, GradArgs2, GradArgs> a)
 {
     constexpr int NACC = HASP ? 5 : 4;
     __shared__ double sx[NG_CJ], sy[NG_CJ], sal[NG_CJ];
+    __shared__ double sbe[R2 ? NG_CJ : 1];
     const int p0 = blockIdx.y * NG_CJ, np = min(NG_CJ, a.N - p0);
     const int li = blockIdx.x * NG_T + threadIdx.x;
     const long i = (long)a.J + li;
@@ -189,6 +202,7 @@ __global__ __launch_bounds__(NG_T) void nllgrad_reg_kernel(const GradArgs a)
         sx[j] = a.X[p0 + j];
         sy[j] = a.X[(size_t)a.N + p0 + j];
         sal[j] = a.alpha[p0 + j];
+        if constexpr (R2) sbe[j] = a.beta[p0 + j];
     }
     __syncthreads();
     double acc[NACC];
@@ -196,11 +210,15 @@ __global__ __launch_bounds__(NG_T) void nllgrad_reg_kernel(const GradArgs a)
     for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
     if (li < a.rows && (long)p0 + np - 1 >= i) {
         const double xi = a.X[i], yi = a.X[(size_t)a.N + i], ai = a.alpha[i];
+        double bi = 0.0;
+        if constexpr (R2) bi = a.beta[i];
         const double *Rrow = a.R + li;
         for (int jj = 0; jj < np; ++jj) {
             const long col = p0 + jj;
             if (col < i) continue;
-            const double W = Rrow[(size_t)(col - a.J) * a.ldr] - ai * sal[jj];
+            double W;
+            if constexpr (R2) W = Rrow[(size_t)(col - a.J) * a.ldr] - __builtin_fma(bi, sal[jj], ai * sbe[jj]);
+            else W = Rrow[(size_t)(col - a.J) * a.ldr] - ai * sal[jj];
             const double w = col == i ? W : 2.0 * W;
             if (col == i) acc[NACC - 1] += W;
             nllg::reg_grad<FAM, HASP>(sx[jj], sy[jj], xi, yi, w, a.l, a.pp[0], acc);      // nllgrad_pair.h
@@ -248,6 +266,45 @@ Shape shape_of(int n, int N)
     return s;
 }
 
+// one contraction launch of the family's instance: with beta, the R2 instances (the rank-2 weight)
+int launch_contract(int family, int d, bool reg, const double *beta, dim3 grid, const GradArgs &a, hipStream_t st)
+{
+    const bool rank2 = beta != nullptr;
+    GradArgs2 a2{};
+    static_cast<GradArgs &>(a2) = a;
+    a2.beta = beta;
+    auto launch = [&](auto fam, auto dd, auto hp) {
+        constexpr int F = decltype(fam)::value, DD = decltype(dd)::value;
+        constexpr bool HP = decltype(hp)::value;
+        if constexpr (DD == 0) {
+            if (rank2) hipLaunchKernelGGL((nllgrad_reg_kernel<F, HP, true>), grid, dim3(NG_T), 0, st, a2);
+            else hipLaunchKernelGGL((nllgrad_reg_kernel<F, HP>), grid, dim3(NG_T), 0, st, a);
+        } else {
+            if (rank2) hipLaunchKernelGGL((nllgrad_pairs_kernel<F, DD, HP, true>), grid, dim3(NG_T), 0, st, a2);
+            else hipLaunchKernelGGL((nllgrad_pairs_kernel<F, DD, HP>), grid, dim3(NG_T), 0, st, a);
+        }
+        SGPR_CHECK_LAUNCH();
+        return 0;
+    };
+    auto by_d = [&](auto fam, auto hp) {
+        if (reg) return launch(fam, std::integral_constant<int, 0>{}, hp);
+        if (d == 1) return launch(fam, std::integral_constant<int, 2>{}, hp);
+        if (d == 2) return launch(fam, std::integral_constant<int, 4>{}, hp);
+        return launch(fam, std::integral_constant<int, 6>{}, hp);
+    };
+    using T = std::true_type;
+    using F = std::false_type;
+    switch (family) {
+    case SGPR_FAM_A: return by_d(std::integral_constant<int, SGPR_FAM_A>{}, F{});
+    case SGPR_FAM_B: return by_d(std::integral_constant<int, SGPR_FAM_B>{}, F{});
+    case SGPR_FAM_C: return by_d(std::integral_constant<int, SGPR_FAM_C>{}, F{});
+    case SGPR_FAM_D: return by_d(std::integral_constant<int, SGPR_FAM_D>{}, T{});
+    case SGPR_FAM_USER: return by_d(std::integral_constant<int, SGPR_FAM_USER>{}, std::integral_constant<bool, gen::user_has_p>{});
+    }
+    set_error("nll_grad_full: unknown kernel family");
+    return SGPR_E_ARG;
+}
+
 }  // namespace
 
 // the rows of a panel of Ky^-1 (shape_of's rule, shared with loo.hip); `knob`: the caller's tunable
@@ -268,6 +325,32 @@ int kyinv_row_panel(int n, int J, int rows, const double *L, size_t ldl, const v
     const double *Ltt = L + J + (size_t)J * ldl;
     if ((rc = trsm_rlt_off(rows, w, Ltt, ldl, R, ldr, work, J, st))) return rc;   // R := R L_tt^-T
     if ((rc = trsm_rl_off(rows, w, Ltt, ldl, R, ldr, work, J, st))) return rc;    // R := R L_tt^-1
+    return 0;
+}
+
+// what loograd.hip needs of the contraction: the workgroups of one panel of ldr rows, one launch with the rank-2 weight
+// M_p - (beta alpha^T + alpha beta^T) on the panel Mp = M[J:J+rows, J:] (the geometry of R above), and the fold
+size_t grad_contract_wgs(int ldr, int N) { return (size_t)((ldr + NG_T - 1) / NG_T) * (size_t)((N + NG_CJ - 1) / NG_CJ); }
+
+int grad_contract_rank2(int family, int d, bool reg, int N, int J, int rows, const double *Mp, size_t ldr, const double *alpha,
+                        const double *beta, const double *X, const double *l, const double *pp, double *part, size_t nwg,
+                        size_t wg0, hipStream_t st)
+{
+    const int gx = ((int)ldr + NG_T - 1) / NG_T, gy = (N + NG_CJ - 1) / NG_CJ;
+    if (gy > 65535) { set_error("loo_grad: too many points for one launch"); return SGPR_E_ARG; }
+    const bool hasp = family_has_p(family);
+    GradArgs a{};
+    a.N = N; a.J = J; a.rows = rows; a.ldr = ldr; a.R = Mp; a.alpha = alpha; a.X = X;
+    for (int m = 0; m < (reg ? 2 : 2 * d); ++m) a.l[m] = l[m];
+    for (int m = 0; m < (reg ? 1 : d); ++m) a.pp[m] = hasp ? pp[m] : 0.0;
+    a.part = part; a.nwg = nwg; a.wg0 = wg0;
+    return launch_contract(family, d, reg, beta, dim3(gx, gy), a, st);
+}
+
+int grad_fold(const double *part, size_t nwg, int nacc, double *out, hipStream_t st)
+{
+    hipLaunchKernelGGL(nllgrad_fold_kernel, dim3(nacc), dim3(NG_FOLD), 0, st, part, nwg, out);
+    SGPR_CHECK_LAUNCH();
     return 0;
 }
 
@@ -301,34 +384,7 @@ int nll_grad_full(int family, int d, bool reg, int N, int n, const double *L, si
         const int J = p * s.nb, rows = n - J < s.nb ? n - J : s.nb;
         if ((rc = kyinv_row_panel(n, J, rows, L, ldl, work, R, (size_t)s.ldr, st))) return rc;
         a.J = J; a.rows = rows; a.wg0 = (size_t)p * s.gx * s.gy;
-        const dim3 grid(s.gx, s.gy);
-        auto launch = [&](auto fam, auto dd, auto hp) {
-            constexpr int F = decltype(fam)::value, DD = decltype(dd)::value;
-            constexpr bool HP = decltype(hp)::value;
-            if constexpr (DD == 0) hipLaunchKernelGGL((nllgrad_reg_kernel<F, HP>), grid, dim3(NG_T), 0, st, a);
-            else hipLaunchKernelGGL((nllgrad_pairs_kernel<F, DD, HP>), grid, dim3(NG_T), 0, st, a);
-            SGPR_CHECK_LAUNCH();
-            return 0;
-        };
-        auto by_d = [&](auto fam, auto hp) {
-            if (reg) return launch(fam, std::integral_constant<int, 0>{}, hp);
-            if (d == 1) return launch(fam, std::integral_constant<int, 2>{}, hp);
-            if (d == 2) return launch(fam, std::integral_constant<int, 4>{}, hp);
-            return launch(fam, std::integral_constant<int, 6>{}, hp);
-        };
-        using T = std::true_type;
-        using F = std::false_type;
-        switch (family) {
-        case SGPR_FAM_A: rc = by_d(std::integral_constant<int, SGPR_FAM_A>{}, F{}); break;
-        case SGPR_FAM_B: rc = by_d(std::integral_constant<int, SGPR_FAM_B>{}, F{}); break;
-        case SGPR_FAM_C: rc = by_d(std::integral_constant<int, SGPR_FAM_C>{}, F{}); break;
-        case SGPR_FAM_D: rc = by_d(std::integral_constant<int, SGPR_FAM_D>{}, T{}); break;
-        case SGPR_FAM_USER:
-            rc = by_d(std::integral_constant<int, SGPR_FAM_USER>{}, std::integral_constant<bool, gen::user_has_p>{});
-            break;
-        default: set_error("nll_grad_full: unknown kernel family"); return SGPR_E_ARG;
-        }
-        if (rc) return rc;
+        if ((rc = launch_contract(family, d, reg, nullptr, dim3(s.gx, s.gy), a, st))) return rc;
     }
     hipLaunchKernelGGL(nllgrad_fold_kernel, dim3(nacc), dim3(NG_FOLD), 0, st, a.part, s.nwg, out);
     SGPR_CHECK_LAUNCH();

@@ -274,6 +274,27 @@ class SympFit:
             out["lpd"] = l
         return out
 
+    def loo_grad(self, objective="loo"):
+        """One of loo()'s objectives and its exact gradient in every hyperparameter, on a solved fit -> (value, grad).
+        objective "loo" (-sum lpd) or "press"; grad has shape (nhyp + 1,) in nll_grad_full's order, the last entry d/dsig2n with
+        the sign of sig2n.  One weight matrix M = Ky^-1 W Ky^-1 serves all hyperparameters (about 5 n^3 / 3 flop, two n x n
+        blocks of device scratch that release_scratch() gives back); deterministic, and the factor, alpha and nll() are left as
+        they are.  A point whose block of Ky^-1 is not positive definite to rounding gives NaN in the value and the whole
+        gradient.  Not defined for block="qq" / "PP" fits.  With SciPy's L-BFGS-B over (hyp, sig2n):
+
+            def fun(h):
+                f.set_hyp(h[:-1], h[-1]); f.run()
+                return f.loo_grad()
+            res = scipy.optimize.minimize(fun, np.append(hyp, sig2n), jac=True, method="L-BFGS-B")
+        """
+        if objective not in ("loo", "press"):
+            raise ValueError('loo_grad: objective is "loo" or "press"')
+        v = C.c_double()
+        g = np.empty(self.nhyp + 1)
+        L.check(self._lib.sgpr_fit_loo_grad(self._h, L.LOO_PRESS if objective == "press" else L.LOO_LPD,
+                                            C.cast(C.byref(v), L._dp), L.dptr(g), len(g)), "sgpr_fit_loo_grad")
+        return v.value, g
+
     def nll_grad_terms(self):
         """[alpha^T dK_lx alpha, tr(Ky^-1 dK_lx), alpha^T dK_ly alpha, tr(Ky^-1 dK_ly), tr(Ky^-1)]: the
         pieces of Rasmussen (5.9) the per-example nll_grad variants recombine."""

@@ -247,6 +247,26 @@ def loo_chol_reg(hyp, x, y, N):
     return _loo_one(hyp, x, y, N, True)
 
 
+def loo_chol_grad(hyp, x, y, N, reg=False, objective="loo"):
+    """loo_chol (reg=True: loo_chol_reg) and its exact gradient -> (value, grad), grad[k] = d value / d hyp[k] for every entry
+    of hyp, the last being sig2_n (Ky holds |hyp[-1]|, so that entry carries its sign).  objective="press": the sum of squared
+    leave-one-point-out residuals instead.  Arguments checked and sliced like nll_chol_grad; raises LinAlgError where loo_chol
+    does.  The objective for scipy.optimize.minimize(..., jac=True).  Every order goes through a device-resident fit and
+    SympFit.loo_grad (there is no batched LOO gradient)."""
+    if objective not in ("loo", "press"):
+        raise ValueError('loo_chol_grad: objective is "loo" or "press"')
+    hyp = np.asarray(hyp, dtype=np.float64)
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    if N <= 0:
+        raise ValueError("loo_chol_grad: N must be positive")
+    X, Y, Z = _batch_data(x, y, N, reg)
+    if len(X) != (N if reg else N // 2) or len(Y) != len(X) or len(Z) != (N if reg else 2 * len(X)):
+        raise ValueError("loo_chol_grad: x holds 2 * n_pts coordinates and y the n targets of order N")
+    with SympFit(get_family(), X, Y, Z, hyp[:-1], hyp[-1], reg=reg) as f:
+        return f.run().loo_grad(objective)
+
+
 def loo_chol_batch(hyps, x, y, N, reg=False):
     """loo_chol (reg=True: loo_chol_reg) for a whole population of hyper-parameter vectors over the same data, the counterpart
     of nll_chol_batch: hyps (B, nhyp + 1) -> the vector of objectives (B,).  Rows whose Ky is not positive definite come back
