@@ -113,6 +113,23 @@ int sgpr_probe_gemm_nt4_dev(int m, int n, int k, const double *A, size_t lda, co
                             double *const *C, const size_t *ldc, const double *alpha, void *stream);
 /* the last sgpr_applymap_host of this process: K*-row evaluations (residuals of the implicit equation + q updates) summed over
  * its orbits, and the number of workgroups that share one orbit for ntest orbits on n0 training points */
+/* The recursive factorisation (potrf_rec / trsm_rec) gives each of its products thresholds of its own: tunables
+ * rec_strassen_min_gemm / rec_strassen_min_syrk (inner threshold of trsm_rec's products / of the lower updates),
+ * rec_strassen2_min_gemm / rec_strassen2_min_syrk (outer threshold), rec_strassen2_kslab_short (outer k slab of a call whose k is
+ * below the long outer slab and at least this; 0: none); rec_strassen_kslab / rec_strassen2_kslab (inner and long outer k slab:
+ * gemm_strassen_kslab / gemm_strassen2_kslab unless set).  Read at
+ * every factorisation.  With SGPR_GEMM_STRASSEN set in the environment the recursion uses the library's values instead.
+ * sgpr_probe_strassen_rec_plan: the list of ONE call (m x n x k, lower) under the thresholds the recursion gives it, in the record
+ * format above; cfg_out (may be null): smin, kslab, smin2, kslab2 and the inner threshold that holds under an outer product
+ * (= min(smin, smin2 / 2): the inner plan of a kind-5 record is sgpr_probe_strassen_plan with THAT smin).
+ * sgpr_probe_strassen_rec_scratch: doubles of operand-sum scratch potrf() reserves at order n: out[0] both levels, out[1] one.
+ * sgpr_probe_gemm_strassen_rec_dev: one product on device pointers as the recursion would issue it.
+ * tools/strassen_rec_plan.py replays the list. */
+int sgpr_probe_strassen_rec_plan(int m, int n, int k, int lower, long scratch_doubles, long cfg_out[5], long long *out,
+                                 int max_records, int *count);
+int sgpr_probe_strassen_rec_scratch(int n, unsigned long long out[2]);
+int sgpr_probe_gemm_strassen_rec_dev(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb,
+                                     double beta, double *C, size_t ldc, int lower, void *stream);
 unsigned sgpr_probe_map_calls(void);
 int sgpr_probe_map_team(int ntest, int n0);
 

@@ -179,6 +179,11 @@ PROBE_SIGNATURES = {
                                           C.c_double, C.c_void_p, C.c_size_t, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p]),
     "sgpr_probe_strassen2_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.c_long, C.c_long, C.c_long, C.c_long,
                                             C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_int)]),
+    "sgpr_probe_strassen_rec_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.POINTER(C.c_long),
+                                               C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_int)]),
+    "sgpr_probe_strassen_rec_scratch": (C.c_int, [C.c_int, C.POINTER(C.c_ulonglong)]),
+    "sgpr_probe_gemm_strassen_rec_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                   C.c_double, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     "sgpr_probe_gemm_nt4_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_double, C.c_int,
                                           C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_double), C.c_void_p]),
     "sgpr_probe_census": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint), C.c_int,

@@ -959,6 +959,7 @@ struct Ctx {
     int *flags = nullptr;   // hand-off flags of the panel kernel: PFLAG_STRIDE ints per leaf column, zeroed by potrf()
     void *qws = nullptr;    // the task-queue driver's part of the workspace (cholq.h), or null
     bool strassen = false;  // the deep products of the recursion go through gemm_nt_strassen (potrf() only: the solves' do not)
+    StrassenRec rec;        // ... each with thresholds of its own, chosen per call from these (strassen_rec_cfg)
 };
 
 int potrf_lookahead(int n, double *A, size_t lda, const Ctx &c, int nb, int off0);
@@ -977,7 +978,7 @@ int trsm_rec(int m, int n, const double *L, size_t ldl, double *B, size_t ldb, i
     int rc = trsm_rec(m, n1, L, ldl, B, ldb, off, c);
     if (rc) return rc;
     // B2 -= B1 L21^T
-    if (c.strassen) rc = gemm_nt_strassen(m, n2, n1, -1.0, B, ldb, L + n1, ldl, 1.0, B + (size_t)n1 * ldb, ldb, 0, c.st);
+    if (c.strassen) rc = gemm_nt_strassen_cfg(m, n2, n1, -1.0, B, ldb, L + n1, ldl, 1.0, B + (size_t)n1 * ldb, ldb, 0, strassen_rec_cfg(c.rec, n1, 0), c.st);
     else            rc = gemm_nt(m, n2, n1, -1.0, B, ldb, L + n1, ldl, 1.0, B + (size_t)n1 * ldb, ldb, 0, 0, c.st);
     if (rc) return rc;
     return trsm_rec(m, n2, L + n1 + (size_t)n1 * ldl, ldl, B + (size_t)n1 * ldb, ldb, off + n1, c);
@@ -1017,7 +1018,7 @@ int potrf_rec(int n, double *A, size_t lda, int off, const Ctx &c)
     rc = trsm_rec(n2, n1, A, lda, A21, lda, off, c);
     if (rc) return rc;
     // SYRK, lower (large ones: split around their square off-diagonal part, which takes the Strassen front end)
-    if (c.strassen) rc = gemm_nt_strassen(n2, n2, n1, -1.0, A21, lda, A21, lda, 1.0, A22, lda, 1, c.st);
+    if (c.strassen) rc = gemm_nt_strassen_cfg(n2, n2, n1, -1.0, A21, lda, A21, lda, 1.0, A22, lda, 1, strassen_rec_cfg(c.rec, n1, 1), c.st);
     else            rc = gemm_nt(n2, n2, n1, -1.0, A21, lda, A21, lda, 1.0, A22, lda, 1, 0, c.st);
     if (rc) return rc;
     return potrf_rec(n2, A22, lda, off + n1, c);
@@ -1737,6 +1738,45 @@ int release_device_streams(int dev)
     return release_streams(dev);
 }
 
+namespace {
+// blocks of order <= la_max go to the blocked look-ahead driver, larger ones split recursively
+// (SGPR_LA_MAX overrides; measured crossover of round 1)
+// tunable "la_max": the same through sgpr_probe_tune (tests that need the recursive driver at a small order)
+int la_max_value()
+{
+    static const int v = [] { const char *e = getenv("SGPR_LA_MAX"); return (int)tune("la_max", e ? atoi(e) : 57344); }();
+    return v;
+}
+// The largest scratch over the products the recursion will issue (the same walk as potrf_rec / trsm_rec, sizes only): every
+// call plans with thresholds of its own, so the largest product need not be the one with the largest need.
+void need_trsm(int m, int n, const StrassenRec &v, int levels, size_t &need)
+{
+    if (n <= LEAF || std::min(m, n) < 256) return;      // below: nothing qualifies under any threshold (>= 128 per half)
+    const int n1 = split(n), n2 = n - n1;
+    need_trsm(m, n1, v, levels, need);
+    need = std::max(need, strassen_scratch_doubles_cfg(m, n2, n1, 0, levels, strassen_rec_cfg(v, n1, 0)));
+    need_trsm(m, n2, v, levels, need);
+}
+void need_potrf(int n, int la_max, const StrassenRec &v, int levels, size_t &need)
+{
+    if (n <= LEAF || (n > 4 * LEAF && n <= la_max)) return;
+    const int n1 = split(n), n2 = n - n1;
+    need_potrf(n1, la_max, v, levels, need);
+    need_trsm(n2, n1, v, levels, need);
+    need = std::max(need, strassen_scratch_doubles_cfg(n2, n2, n1, 1, levels, strassen_rec_cfg(v, n1, 1)));
+    need_potrf(n2, la_max, v, levels, need);
+}
+}  // namespace
+
+void potrf_strassen_need(int n, size_t out[2])
+{
+    static const bool rec_mode = [] { const char *e = getenv("SGPR_POTRF"); return e && e[0] == 'r'; }();
+    const StrassenRec v = strassen_rec_values();
+    out[0] = out[1] = 0;
+    need_potrf(n, rec_mode ? 0 : la_max_value(), v, 2, out[0]);
+    need_potrf(n, rec_mode ? 0 : la_max_value(), v, 1, out[1]);
+}
+
 int potrf(int n, double *A, size_t lda, void *work, size_t lwork, int *dinfo, hipStream_t st)
 {
     if (n < 0 || (n > 0 && lda < (size_t)n)) { set_error("potrf: bad n / lda"); return SGPR_E_ARG; }
@@ -1750,21 +1790,17 @@ int potrf(int n, double *A, size_t lda, void *work, size_t lwork, int *dinfo, hi
     // factorisation, recursive above (measured crossover; SGPR_POTRF=rec|la overrides)
     static const int mode = [] { const char *e = getenv("SGPR_POTRF"); return !e ? 0 : (e[0] == 'r' ? 1 : 2); }();
     static const int nb_env = [] { const char *e = getenv("SGPR_POTRF_NB"); return e ? atoi(e) : 0; }();
-    // blocks of order <= la_max go to the blocked look-ahead driver, larger ones split recursively
-    // (SGPR_LA_MAX overrides; measured crossover of round 1)
-    // tunable "la_max": the same through sgpr_probe_tune (tests that need the recursive driver at a small order)
-    static const int la_max_env = [] { const char *e = getenv("SGPR_LA_MAX"); return (int)tune("la_max", e ? atoi(e) : 57344); }();
+    const int la_max_env = la_max_value();
     t_last_potrf_used_queue = false;
     Ctx c{static_cast<double *>(work), dinfo, st, mode == 1 ? 0 : la_max_env, flags};
     if (cholq::ws_bytes(n) > 0) c.qws = static_cast<char *>(work) + inv_bytes(n) + flag_bytes(n) + pub_bytes(n);
     c.strassen = true;
+    c.rec = strassen_rec_values();
     if (n > c.la_max && n > LEAF) {
-        // the two largest products of the recursion (every later one is smaller): size the operand-sum scratch once
-        const int n1 = split(n), n2 = n - n1, n11 = split(n1);
-        auto need = [&](int levels) {
-            return std::max(strassen_scratch_doubles(n2, n2, n1, 1, levels), strassen_scratch_doubles(n2, n1 - n11, n11, 0, levels));
-        };
-        strassen_reserve(need(2), need(1), st);   // both levels' operand sums, or the inner level's alone if that does not fit
+        // size the operand-sum scratch once, before the first launch: the largest need over the plans of this order
+        size_t need[2];
+        potrf_strassen_need(n, need);
+        strassen_reserve(need[0], need[1], st);   // both levels' operand sums, or the inner level's alone if that does not fit
     }
     const bool dbg = PANEL_DBG && getenv("SGPR_PANEL_DBG") != nullptr;
     const int T = (n + LEAF - 1) / LEAF;

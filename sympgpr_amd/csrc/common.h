@@ -141,6 +141,25 @@ int strassen_outer_plan(int m, int n, int k, int lower, long smin, long kslab, l
 int gemm_nt_multi(int m, int n, int k, const double *A, size_t lda, const double *B, size_t ldb, double beta, int count,
                   double *const *C, const size_t *ldc, const double *alpha, hipStream_t st);
 size_t strassen_scratch_doubles(int m, int n, int k, int lower, int levels);
+// The thresholds of ONE call of the front end; a negative member: the library's value (gemm_strassen_* / gemm_strassen2_*).
+// smin_under: the inner threshold that holds under an outer product (negative: smin).
+struct StrassenCfg { long smin = -1, kslab = -1, smin2 = -1, kslab2 = -1, smin_under = -1; };
+int gemm_nt_strassen_cfg(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb, double beta,
+                         double *C, size_t ldc, int lower, const StrassenCfg &cfg, hipStream_t st);
+size_t strassen_scratch_doubles_cfg(int m, int n, int k, int lower, int levels, const StrassenCfg &cfg);
+// The recursive factorisation's own values (potrf_rec / trsm_rec; tunables "rec_strassen_*"): inner and outer
+// threshold for the products of trsm_rec and for the lower updates, and the outer k slab of a call whose k is shorter than
+// the long outer slab (0: such a call takes no outer level); the inner and the long outer k slab are the library's unless
+// tuned.  on = false (SGPR_GEMM_STRASSEN set): the library's values.
+struct StrassenRec { bool on = false; long smin_gemm = 0, smin_syrk = 0, smin2_gemm = 0, smin2_syrk = 0, kslab = 0, kslab2 = 0, kslab2_short = 0; };
+StrassenRec strassen_rec_values();
+StrassenCfg strassen_rec_cfg(const StrassenRec &v, int k, int lower);
+// the third probe entry: the list of one call as the recursion would plan it; cfg_out (may be null): the thresholds it resolved
+// to (smin, kslab, smin2, kslab2, smin_under); and the product itself on device pointers
+int strassen_rec_plan(int m, int n, int k, int lower, long cfg_out[5], size_t scratch_doubles, std::vector<long long> &out);
+int gemm_nt_strassen_rec(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb, double beta,
+                         double *C, size_t ldc, int lower, hipStream_t st);
+void potrf_strassen_need(int n, size_t out[2]);  // chol.hip: what potrf() reserves at order n (both levels, one level)
 void strassen_reserve(size_t both, size_t one, hipStream_t st);
 int strassen_trim();                             // release the scratch of the operand sums (every device)
 int gemm_profile_begin();

@@ -525,7 +525,9 @@ size_t plan_need(const std::vector<long long> &plan)
     return need[0] + need[1];
 }
 
-// 0: classical only, 1: one level (bit for bit what the tree did before the outer level existed), 2: both (unset)
+// 0: classical only, 1: one level (bit for bit what the tree did before the outer level existed), 2: both at the library's
+// thresholds everywhere (bit for bit the tree before the recursion had thresholds of its own); unset: both, and the recursive
+// factorisation plans each of its products with its own thresholds (strassen_rec_values)
 int strassen_levels()
 {
     static const int lv = [] { const char *e = getenv("SGPR_GEMM_STRASSEN"); return !e ? 2 : (e[0] == '0' ? 0 : (e[0] == '1' ? 1 : 2)); }();
@@ -556,7 +558,17 @@ struct Plan2Cfg {
     long smin2;     // smallest half-size of m and n that takes the outer level
     long kslab2;    // its k slab: exactly this many columns, a multiple of 64 (quarters stay multiples of the k-step)
     size_t scratch; // doubles available for the inner and the outer pair together
+    long smin_under = -1;   // the inner threshold UNDER an outer product (negative: in.smin); the recursion's calls set it
 };
+// the inner level as it holds under an outer product (its scratch member is the caller's business)
+PlanCfg under_of(const Plan2Cfg &c)
+{
+    PlanCfg ci = c.in;
+    if (c.smin_under >= 0) ci.smin = c.smin_under;
+    return ci;
+}
+// the recursion's shipped values (strassen_rec_values below)
+constexpr long REC_SMIN_GEMM = 4096, REC_SMIN_SYRK = 8192, REC_SMIN2_GEMM = 8192, REC_SMIN2_SYRK = 8192, REC_KSLAB2_SHORT = 16384;
 // Default thresholds: profiles/strassen2/sweep.txt.  Tunables "gemm_strassen2_min", "gemm_strassen2_kslab",
 // "gemm_strassen2_noscratch" (tests: the allocation of the outer part is reported as failed -> one level).
 Plan2Cfg default_cfg2()
@@ -579,7 +591,7 @@ bool qualifies2(long m, long n, long k, const Plan2Cfg &c)
     const size_t pair = (size_t)(m / 2 + n / 2) * (size_t)(c.kslab2 / 2);
     if (pair > c.scratch) return false;
     // ... and everything the inner level asks of an outer product, with the scratch that is left
-    PlanCfg ci = c.in;
+    PlanCfg ci = under_of(c);
     ci.scratch = c.scratch - pair;
     return qualifies(m / 2, n / 2, c.kslab2 / 2, ci);
 }
@@ -630,7 +642,7 @@ Need2 plan2_need(const std::vector<long long> &plan, const Plan2Cfg &c)
         size_t &v = nd.v[base + r[1]];
         v = std::max(v, (size_t)r[2] * (size_t)r[3]);
     };
-    PlanCfg ci = c.in;
+    PlanCfg ci = under_of(c);
     ci.scratch = ~(size_t)0;
     for (size_t i = 0; i + STRASSEN_REC <= plan.size(); i += STRASSEN_REC) {
         const long long *r = &plan[i];
@@ -750,7 +762,7 @@ int run_plan2(const std::vector<long long> &plan, const Plan2Cfg &c, const Need2
               const double *B, size_t ldb, double beta, double *C, size_t ldc, double *S, hipStream_t st)
 {
     double *const SA = S, *const SB = S + nd.v[0], *const OA = SB + nd.v[1], *const OB = OA + nd.v[2];
-    PlanCfg ci = c.in;
+    PlanCfg ci = under_of(c);
     ci.scratch = nd.inner();
     std::vector<long long> in;
     for (size_t i = 0; i + STRASSEN_REC <= plan.size(); i += STRASSEN_REC) {
@@ -802,6 +814,18 @@ Plan2Cfg cfg2_of(long smin, long kslab, long smin2, long kslab2, size_t scratch_
     c.scratch = scratch_doubles;
     return c;
 }
+Plan2Cfg cfg2_of(const StrassenCfg &cfg, size_t scratch_doubles)
+{
+    Plan2Cfg c = cfg2_of(cfg.smin, cfg.kslab, cfg.smin2, cfg.kslab2, scratch_doubles);
+    if (cfg.smin_under >= 0) c.smin_under = std::max(128L, cfg.smin_under);
+    return c;
+}
+void outer_plan_of(int m, int n, int k, int lower, const Plan2Cfg &c, std::vector<long long> &out)
+{
+    out.clear();
+    if (lower) plan2_syrk(n, k, 0, c, out);
+    else       plan2_gemm(m, n, k, 0, 0, 0, 0, c, out);
+}
 }  // namespace
 
 // ... and the list with the outer level around it (smin2 / kslab2 < 0 = the built-in values or tunables)
@@ -809,23 +833,69 @@ int strassen_outer_plan(int m, int n, int k, int lower, long smin, long kslab, l
                    std::vector<long long> &out)
 {
     if (m < 0 || n < 0 || k < 0 || (lower && m != n)) { set_error("strassen_outer_plan: bad extents"); return SGPR_E_ARG; }
-    const Plan2Cfg c = cfg2_of(smin, kslab, smin2, kslab2, scratch_doubles);
-    out.clear();
-    if (lower) plan2_syrk(n, k, 0, c, out);
-    else       plan2_gemm(m, n, k, 0, 0, 0, 0, c, out);
+    outer_plan_of(m, n, k, lower, cfg2_of(smin, kslab, smin2, kslab2, scratch_doubles), out);
+    return 0;
+}
+
+// The recursion's values.  Tunables "rec_strassen_min_gemm" / "rec_strassen_min_syrk" (inner threshold of trsm_rec's products /
+// of the lower updates), "rec_strassen2_min_gemm" / "rec_strassen2_min_syrk" (outer threshold), "rec_strassen2_kslab_short" (outer
+// k slab of a call whose k is below the long one; 0: none), "rec_strassen_kslab" / "rec_strassen2_kslab" (inner and long outer
+// k slab: the library's unless set).  Read at every factorisation, not once per process.
+// Defaults: profiles/strassen_rec/sweep.txt, class by class.  SGPR_GEMM_STRASSEN set to anything: the library's.
+StrassenRec strassen_rec_values()
+{
+    StrassenRec v;
+    v.on = getenv("SGPR_GEMM_STRASSEN") == nullptr;
+    const Plan2Cfg lib = default_cfg2();
+    // (a library threshold lowered below the recursion's own -- tests at small orders do that -- holds for the recursion too)
+    v.smin_gemm = std::max(128L, (long)tune("rec_strassen_min_gemm", std::min(REC_SMIN_GEMM, lib.in.smin)));
+    v.smin_syrk = std::max(128L, (long)tune("rec_strassen_min_syrk", std::min(REC_SMIN_SYRK, lib.in.smin)));
+    v.smin2_gemm = std::max(256L, (long)tune("rec_strassen2_min_gemm", std::min(REC_SMIN2_GEMM, lib.smin2)));
+    v.smin2_syrk = std::max(256L, (long)tune("rec_strassen2_min_syrk", std::min(REC_SMIN2_SYRK, lib.smin2)));
+    v.kslab = std::max(32L, (long)tune("rec_strassen_kslab", lib.in.kslab));
+    v.kslab2 = std::max(64L, (long)tune("rec_strassen2_kslab", lib.kslab2));
+    v.kslab2_short = (long)tune("rec_strassen2_kslab_short", REC_KSLAB2_SHORT);
+    if (v.kslab2_short < 64 || v.kslab2_short % 64 != 0 || v.kslab2_short >= v.kslab2) v.kslab2_short = 0;
+    return v;
+}
+// One call's thresholds: k at least the library's outer slab keeps that slab (measured two points better on the two largest
+// products, profiles/strassen2/sweep.txt); a shorter k that holds a whole short slab takes the short one.  Under an outer
+// product the inner level applies wherever the outer threshold let the product in: min(smin, smin2 / 2).
+StrassenCfg strassen_rec_cfg(const StrassenRec &v, int k, int lower)
+{
+    StrassenCfg c;
+    if (!v.on) return c;
+    c.smin = lower ? v.smin_syrk : v.smin_gemm;
+    c.smin2 = lower ? v.smin2_syrk : v.smin2_gemm;
+    c.smin_under = std::min(c.smin, c.smin2 / 2);
+    c.kslab = v.kslab;
+    c.kslab2 = (k < v.kslab2 && v.kslab2_short > 0 && k >= v.kslab2_short) ? v.kslab2_short : v.kslab2;
+    return c;
+}
+int strassen_rec_plan(int m, int n, int k, int lower, long cfg_out[5], size_t scratch_doubles, std::vector<long long> &out)
+{
+    if (m < 0 || n < 0 || k < 0 || (lower && m != n)) { set_error("strassen_rec_plan: bad extents"); return SGPR_E_ARG; }
+    const Plan2Cfg c = cfg2_of(strassen_rec_cfg(strassen_rec_values(), k, lower), scratch_doubles);
+    if (cfg_out) { cfg_out[0] = c.in.smin; cfg_out[1] = c.in.kslab; cfg_out[2] = c.smin2; cfg_out[3] = c.kslab2; cfg_out[4] = under_of(c).smin; }
+    outer_plan_of(m, n, k, lower, c, out);
     return 0;
 }
 
 // scratch of one call: levels = 1 the inner pair alone, 2 both pairs (as far as SGPR_GEMM_STRASSEN allows)
 size_t strassen_scratch_doubles(int m, int n, int k, int lower, int levels)
 {
+    return strassen_scratch_doubles_cfg(m, n, k, lower, levels, StrassenCfg{});
+}
+size_t strassen_scratch_doubles_cfg(int m, int n, int k, int lower, int levels, const StrassenCfg &cfg)
+{
     std::vector<long long> plan;
-    if (!strassen_on()) return 0;
+    if (!strassen_on() || m < 0 || n < 0 || k < 0 || (lower && m != n)) return 0;
+    const Plan2Cfg c2 = cfg2_of(cfg, ~(size_t)0);
     if (levels >= 2 && strassen_levels() >= 2) {
-        if (strassen_outer_plan(m, n, k, lower, -1, -1, -1, -1, ~(size_t)0, plan)) return 0;
-        return plan2_need(plan, default_cfg2()).total();
+        outer_plan_of(m, n, k, lower, c2, plan);
+        return plan2_need(plan, c2).total();
     }
-    if (strassen_plan(m, n, k, lower, -1, -1, ~(size_t)0, plan)) return 0;
+    if (strassen_plan(m, n, k, lower, c2.in.smin, c2.in.kslab, ~(size_t)0, plan)) return 0;
     return plan_need(plan);
 }
 
@@ -859,9 +929,21 @@ int strassen_trim()
 int gemm_nt_strassen(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb, double beta,
                      double *C, size_t ldc, int lower, hipStream_t st)
 {
+    return gemm_nt_strassen_cfg(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, lower, StrassenCfg{}, st);
+}
+int gemm_nt_strassen_rec(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb, double beta,
+                         double *C, size_t ldc, int lower, hipStream_t st)
+{
+    return gemm_nt_strassen_cfg(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, lower, strassen_rec_cfg(strassen_rec_values(), k, lower), st);
+}
+// ... with the thresholds of this one call (the recursive factorisation's calls: chol.hip)
+int gemm_nt_strassen_cfg(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb, double beta,
+                         double *C, size_t ldc, int lower, const StrassenCfg &cfg, hipStream_t st)
+{
+    const Plan2Cfg c2 = cfg2_of(cfg, ~(size_t)0);
     const bool aligned = ((((uintptr_t)A | (uintptr_t)B) & 15) == 0) && (((lda | ldb) & 1) == 0);
     // (the size test first: the short products of the panel solves come through here by the thousand)
-    if (std::min(m, n) / 2 < default_cfg().smin || !strassen_on() || !aligned || beta != 1.0 || (lower && m != n))
+    if (std::min(m, n) / 2 < std::min(c2.in.smin, under_of(c2).smin) || !strassen_on() || !aligned || beta != 1.0 || (lower && m != n))
         return gemm_nt(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, lower, 0, st);
     std::vector<long long> plan;
     int rc = 0;
@@ -876,9 +958,8 @@ int gemm_nt_strassen(int m, int n, int k, double alpha, const double *A, size_t 
         return r;
     };
     // both levels, where a product is large enough for the outer one and its scratch can be had
-    const Plan2Cfg c2 = default_cfg2();
     if (strassen_levels() >= 2 && dev >= 0 && !outer_noscratch() && std::min(lower ? m / 2 : m, lower ? n / 2 : n) / 2 >= c2.smin2) {
-        if ((rc = strassen_outer_plan(m, n, k, lower, -1, -1, -1, -1, ~(size_t)0, plan))) return rc;
+        outer_plan_of(m, n, k, lower, c2, plan);
         const Need2 nd = plan2_need(plan, c2);
         if (nd.v[2] + nd.v[3]) {
             Scratch &s = g_scratch[dev];
@@ -887,7 +968,7 @@ int gemm_nt_strassen(int m, int n, int k, double alpha, const double *A, size_t 
                 return enqueue(s, [&] { return run_plan2(plan, c2, nd, alpha, A, lda, B, ldb, beta, C, ldc, s.p, st); });
         }
     }
-    rc = strassen_plan(m, n, k, lower, -1, -1, ~(size_t)0, plan);
+    rc = strassen_plan(m, n, k, lower, c2.in.smin, c2.in.kslab, ~(size_t)0, plan);
     if (rc) return rc;
     const size_t need = plan_need(plan);
     if (!need) return run_plan(plan, alpha, A, lda, B, ldb, beta, C, ldc, nullptr, nullptr, st);
@@ -896,7 +977,7 @@ int gemm_nt_strassen(int m, int n, int k, double alpha, const double *A, size_t 
     std::lock_guard<std::mutex> lock(s.mu);
     if (!scratch_ensure(s, need)) {
         // plan again with what there is (possibly nothing): smaller products of a SYRK may still fit
-        if ((rc = strassen_plan(m, n, k, lower, -1, -1, s.cap, plan))) return rc;
+        if ((rc = strassen_plan(m, n, k, lower, c2.in.smin, c2.in.kslab, s.cap, plan))) return rc;
         if (!plan_need(plan)) return run_plan(plan, alpha, A, lda, B, ldb, beta, C, ldc, nullptr, nullptr, st);
     }
     size_t na = 0;

@@ -561,6 +561,33 @@ extern "C" int sgpr_probe_strassen2_plan(int m, int n, int k, int lower, long sm
     for (size_t i = 0; out && i < plan.size() && (int)(i / STRASSEN_REC) < max_records; ++i) out[i] = plan[i];
     return 0;
 }
+// ---- the recursive factorisation's own thresholds: the list of one of its calls, the thresholds that call resolved to
+// (smin, kslab, smin2, kslab2, the inner threshold under an outer product), and the scratch potrf() reserves at an order
+extern "C" int sgpr_probe_strassen_rec_plan(int m, int n, int k, int lower, long scratch_doubles, long cfg_out[5], long long *out,
+                                            int max_records, int *count)
+{
+    if (!count || scratch_doubles < 0) { set_error("probe_strassen_rec_plan: bad arguments"); return SGPR_E_ARG; }
+    std::vector<long long> plan;
+    const int rc = strassen_rec_plan(m, n, k, lower, cfg_out, (size_t)scratch_doubles, plan);
+    if (rc) return rc;
+    *count = (int)(plan.size() / STRASSEN_REC);
+    for (size_t i = 0; out && i < plan.size() && (int)(i / STRASSEN_REC) < max_records; ++i) out[i] = plan[i];
+    return 0;
+}
+extern "C" int sgpr_probe_strassen_rec_scratch(int n, unsigned long long out[2])
+{
+    if (n < 0 || !out) { set_error("probe_strassen_rec_scratch: bad arguments"); return SGPR_E_ARG; }
+    size_t need[2];
+    potrf_strassen_need(n, need);
+    out[0] = need[0]; out[1] = need[1];
+    return 0;
+}
+// one product as the recursion would issue it (its thresholds for this k and kind), on device pointers
+extern "C" int sgpr_probe_gemm_strassen_rec_dev(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb,
+                                                double beta, double *C, size_t ldc, int lower, void *stream)
+{
+    return gemm_nt_strassen_rec(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, lower, static_cast<hipStream_t>(stream));
+}
 extern "C" int sgpr_probe_gemm_nt4_dev(int m, int n, int k, const double *A, size_t lda, const double *B, size_t ldb, double beta,
                                        int count, double *const *C, const size_t *ldc, const double *alpha, void *stream)
 {
