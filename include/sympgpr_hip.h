@@ -357,10 +357,30 @@ int sgpr_fit_batch_grad_mid(int family, int nbatch, int n_pts, const double *x, 
 int sgpr_fit_batch_loo(int family, int nbatch, int n_pts, const double *x, const double *y, const double *z,
                        const double *hyp, int nhyp, const double *sig2n, unsigned flags, double *alpha,
                        double *nll, double *loo, int *info);
+/* sgpr_fit_batch plus one of sgpr_fit_batch_loo's two objectives and its exact gradient in (hyp, sig2n) per problem.  Order per
+ * problem n = 2 n_pts (n_pts with SGPR_FIT_REG) <= 256.  Arguments, hyp layout and flags as sgpr_fit_batch_grad; which =
+ * SGPR_LOO_LPD: value[b] = loo, SGPR_LOO_PRESS: value[b] = press (value: nbatch doubles).  grad: nbatch x (nhyp + 1), row-major;
+ * row b = (d/dhyp_0 .. d/dhyp_{nhyp-1}, d/dsig2n) of value[b], by the formulas of sgpr_fit_loo_grad (D = 2; 1 with SGPR_FIT_REG).
+ * The noise enters as |sig2n[b]|, so the last entry carries sign(sig2n[b]), with sign(0) = +1.  nll, alpha (may be NULL) and info
+ * are bit-identical to sgpr_fit_batch's; value[b] is bit-identical to the `which` column of sgpr_fit_batch_loo's row b (the same
+ * code); a problem's value and gradient bits do not depend on its place in the batch, the batch size or a repetition (no atomics,
+ * no waiting between workgroups).  info[b] > 0: nll[b], value[b] and the whole row grad[b] are NaN, nothing is computed for that
+ * problem and the others are untouched.  A point whose block has a pivot that is not positive and finite makes value[b] and the
+ * whole row grad[b] NaN through the arithmetic; the call still returns 0.  One launch, one workgroup per problem: after the fit
+ * it forms Ky^-1 as sgpr_fit_batch_grad does, takes one thread per point as sgpr_fit_batch_loo does and keeps the point's weight
+ * block and v in LDS, then beta = Ky^-1 v (n^2 flop), Y = W Ky^-1 over L^-T, M = Ky^-1 Y (lower triangle, n^3 flop) and
+ * the contraction of M - beta alpha^T - alpha beta^T with dKy pair by pair, the code of sgpr_fit_batch_grad's last step.
+ * SGPR_E_ARG (before any device call) for an unknown family, a wrong nhyp, an unknown flag, an unknown which, nbatch < 0,
+ * n_pts <= 0, an order above 256 and a null pointer other than alpha; nbatch == 0 returns 0.  Device scratch: the sgpr_fit_batch
+ * arena grows to three 256 x 256 blocks (Ky^-1, L^-T / Y, M) beside the leaf inverses, ~1.8 MiB per workgroup (up to 1024
+ * workgroups: ~1.8 GiB), kept until sgpr_trim.  ABI 5 (an additional entry point). */
+int sgpr_fit_batch_loo_grad(int family, int nbatch, int n_pts, const double *x, const double *y, const double *z,
+                            const double *hyp, int nhyp, const double *sig2n, unsigned flags, int which, double *alpha,
+                            double *nll, double *value, double *grad, int *info);
 
 /* Gives back what the CALLING thread's earlier calls keep for re-use: the device arena and page-locked staging block of
  * sgpr_fit_batch and sgpr_fit_batch_grad (up to ~2 GiB after a large batch of order-2048 problems, ~1.3 GiB after a gradient batch
- * of 1024 problems or more; they also shrink by themselves when a much smaller batch
+ * of 1024 problems or more, ~1.8 GiB after such a batch of sgpr_fit_batch_loo_grad; they also shrink by themselves when a much smaller batch
  * follows) and the pooled events of its factorisations.  Never needed for correctness; call it between a hyper-parameter search
  * over small problems and a fit that wants the whole HBM.  No call of this thread may be in flight. */
 int sgpr_trim(void);

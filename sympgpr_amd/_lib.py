@@ -143,6 +143,8 @@ SIGNATURES = {
                                           C.POINTER(C.c_int)]),
     "sgpr_fit_batch_loo": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_uint, _dp, _dp, _dp,
                                      C.POINTER(C.c_int)]),
+    "sgpr_fit_batch_loo_grad": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_uint, C.c_int, _dp,
+                                          _dp, _dp, _dp, C.POINTER(C.c_int)]),
 }
 
 # include/sympgpr_probe.h: measurement aids in their own library (never loaded by a product path)

@@ -38,22 +38,26 @@ struct BatchArgs {
     const KConst *kc;                     // per problem
     const double *noise;                  // per problem, >= 0
     double *scratch;                      // per workgroup: BMAX*BMAX (Ky / L) + 2*LEAF*LEAF (leaf inverses) + 2*BMAX
-                                          // [+ BMAX*BMAX (U = L^-T) for the gradient]
+                                          // [+ BMAX*BMAX (U = L^-T) for the gradient and loo] [+ BMAX*BMAX (M) for the loo gradient]
     double *alpha, *nll;                  // outputs (alpha may be null); the gradient kernel writes problem b's raw sums at
-                                          // nll + nbatch + b * grad_nacc<FAM>(), the loo kernel {loo, press} at nll + nbatch + 2 b
+                                          // nll + nbatch + b * grad_nacc<FAM>(), the loo kernel {loo, press} at nll + nbatch + 2 b,
+                                          // the loo gradient kernel {loo, press, raw sums} at nll + nbatch + b * (2 + grad_nacc<FAM>())
     int *info;                            // per problem, zero on entry
+    int which;                            // the loo gradient's objective (SGPR_LOO_LPD / SGPR_LOO_PRESS), the same for the launch
 };
 
 template <int FAM> constexpr bool grad_has_p() { return FAM == SGPR_FAM_D || (FAM == SGPR_FAM_USER && gen::user_has_p); }
 template <int FAM> constexpr int grad_nacc() { return grad_has_p<FAM>() ? 5 : 4; }    // lx, ly, [p,] sig, sig2n
 
-template <int FAM, bool LOO = false>
+enum { MODE_FIT = 0, MODE_GRAD = 1, MODE_LOO = 2, MODE_LOOGRAD = 3 };
+
+template <int FAM, int MODE>
 __device__ void grad_problem(const BatchArgs &a, int b, double *s, double *A, const double *inv, double *U, const double *al);
 
-enum { MODE_FIT = 0, MODE_GRAD = 1, MODE_LOO = 2 };
-
 // MODE_GRAD: after the fit, the gradient of problem b's nll (grad_problem below); MODE_LOO: its leave-one-point-out sums
-// (grad_problem's Ky^-1, then one thread per point).  Scratch then PER_WG + BMAX^2 doubles per workgroup
+// (grad_problem's Ky^-1, then one thread per point).  Scratch then PER_WG + BMAX^2 doubles per workgroup.  MODE_LOOGRAD: the sums
+// and the gradient of one of them; a third block (M): PER_WG + 2 BMAX^2 doubles = 1 839 104 bytes (~1.8 MiB) per workgroup, ~1.8 GiB at
+// the 1024-workgroup grid
 template <int FAM, int MODE = MODE_FIT>
 __global__ __launch_bounds__(LT) void fit_batch_kernel(const BatchArgs a)
 {
@@ -61,7 +65,8 @@ __global__ __launch_bounds__(LT) void fit_batch_kernel(const BatchArgs a)
     __shared__ double red[LT / 64];
     const int tid = threadIdx.x;
     const int n = a.n, N = a.npts;
-    const size_t per_wg = (size_t)BMAX * BMAX + 2 * (size_t)LEAF * LEAF + 2 * BMAX + (MODE != MODE_FIT ? (size_t)BMAX * BMAX : 0);   // PER_WG [+ U]
+    const size_t per_wg = (size_t)BMAX * BMAX + 2 * (size_t)LEAF * LEAF + 2 * BMAX + (MODE != MODE_FIT ? (size_t)BMAX * BMAX : 0) +
+                          (MODE == MODE_LOOGRAD ? (size_t)BMAX * BMAX : 0);                    // PER_WG [+ U] [+ M]
     double *A = a.scratch + (size_t)blockIdx.x * per_wg;     // column-major, ld = BMAX
     double *inv = A + (size_t)BMAX * BMAX;
     double *v = inv + 2 * (size_t)LEAF * LEAF;                // y, then alpha
@@ -184,9 +189,112 @@ __global__ __launch_bounds__(LT) void fit_batch_kernel(const BatchArgs a)
             for (int i = tid; i < n; i += LT) a.alpha[(size_t)b * n + i] = al[i];
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if constexpr (MODE == MODE_GRAD) grad_problem<FAM>(a, b, s, A, inv, v + 2 * BMAX, al);
-        if constexpr (MODE == MODE_LOO) grad_problem<FAM, true>(a, b, s, A, inv, v + 2 * BMAX, al);
+        if constexpr (MODE != MODE_FIT) grad_problem<FAM, MODE>(a, b, s, A, inv, v + 2 * BMAX, al);
     }
+}
+
+// Point i's leave-one-point-out quantities from the lower triangle of Ky^-1 (A) and alpha: its block {A[i,i], A[N+i,i], A[N+i,N+i]}
+// (one entry for reg) through loo_block.h -> r, S (packed lower; the entries a reg fit does not have are zero), lpd and |r|^2.
+__device__ __forceinline__ void loo_point(const double *A, const double *al, int i, int N, int reg, double (&r)[2], double (&S)[3],
+                                          double &lpd, double &rr)
+{
+    constexpr size_t ld = BMAX;
+    if (reg) {
+        const double C[1] = {A[i + i * ld]}, ai[1] = {al[i]};
+        double r1[1], S1[1];
+        loo::block<1>(C, ai, r1, S1, lpd);
+        rr = r1[0] * r1[0];
+        r[0] = r1[0]; r[1] = 0.0;
+        S[0] = S1[0]; S[1] = 0.0; S[2] = 0.0;
+    } else {
+        const double C[3] = {A[i + i * ld], A[(N + i) + i * ld], A[(N + i) + (N + i) * ld]}, ai[2] = {al[i], al[N + i]};
+        loo::block<2>(C, ai, r, S, lpd);
+        rr = __builtin_fma(r[1], r[1], r[0] * r[0]);
+    }
+}
+
+// The per-thread {lpd, |r|^2} fold wave by wave in a fixed order (through s[0 .. 7]) into out = {loo, press}.  Ends on a barrier.
+__device__ __forceinline__ void loo_fold(const double (&lv)[2], double *s, double *out)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        double v = lv[k];
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+        if (lane == 0) s[wave * 2 + k] = v;
+    }
+    __syncthreads();
+    if (tid < 2) {
+        const double v = s[tid] + s[2 + tid] + s[4 + tid] + s[6 + tid];
+        out[tid] = tid == 0 ? -v : v;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+}
+
+// Step (3) of grad_problem, for any symmetric weight: thread i owns row i of W, given as wf(i, alpha_i, col) for col <= i, and walks
+// the column points j, each pair evaluated once with dK from the generated forms (nllgrad_pair.h), entries on and below the
+// diagonal weighted W_ii and 2 W_ij; W_ii also goes to the noise sum.  The points and alpha go to LDS first (s: x | y | alpha at
+// multiples of BMAX, the wave partials behind them).  The per-thread sums fold wave by wave in a fixed order into out[0 .. NACC).
+template <int FAM, class WF>
+__device__ __forceinline__ void contract_rows(const BatchArgs &a, int b, double *s, const double *al, double *out, WF wf)
+{
+    constexpr bool HASP = grad_has_p<FAM>();
+    constexpr int NACC = grad_nacc<FAM>();
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = tid;
+    const int n = a.n, N = a.npts;
+    double *sx = s, *sy = s + BMAX, *sal = s + 2 * BMAX, *red = s + 3 * BMAX;
+    for (int e = tid; e < N; e += LT) { sx[e] = a.x[(size_t)b * N + e]; sy[e] = a.y[(size_t)b * N + e]; }
+    for (int e = tid; e < n; e += LT) sal[e] = al[e];
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    const KConst kc = a.kc[b];
+    const double l[2] = {kc.lx, kc.ly}, pp[1] = {kc.p};
+    double acc[NACC];
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
+    if (i < n) {
+        const double ai = sal[i];
+        if (a.reg) {
+            const double xi = sx[i], yi = sy[i];
+            for (int j = 0; j <= i; ++j) {
+                const double W = wf(i, ai, j);
+                if (j == i) acc[NACC - 1] += W;
+                nllg::reg_grad<FAM, HASP>(sx[j], sy[j], xi, yi, j == i ? W : 2.0 * W, l, kc.p, acc);
+            }
+        } else {
+            const int r = i < N ? 0 : 1, pi = i - r * N;
+            const double xi[2] = {sx[pi], sy[pi]};
+            for (int pj = 0; pj < N; ++pj) {
+                double w[2];
+                bool any = false;
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {                 // columns pj (q part) and N + pj (P part)
+                    const int col = c * N + pj;
+                    w[c] = 0.0;
+                    if (col <= i) {
+                        const double W = wf(i, ai, col);
+                        if (col == i) { w[c] = W; acc[NACC - 1] += W; }
+                        else w[c] = 2.0 * W;
+                        any = true;
+                    }
+                }
+                if (!any) break;                              // column pj > i: so are all after it
+                const double xj[2] = {sx[pj], sy[pj]};
+                nllg::pair_grad<FAM, 2, HASP>(xi, xj, w, r, l, pp, acc);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) {
+        double v = acc[k];
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+        if (lane == 0) red[wave * NACC + k] = v;
+    }
+    __syncthreads();
+    if (tid < NACC) out[tid] = red[tid] + red[NACC + tid] + red[2 * NACC + tid] + red[3 * NACC + tid];
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();                                      // A, U and s are the next problem's
 }
 
 // The gradient of problem b's nll in (lx, ly, [p,] sig, sig2n), by the workgroup that has just fitted it: A holds L, inv the
@@ -197,15 +305,28 @@ __global__ __launch_bounds__(LT) void fit_batch_kernel(const BatchArgs a)
 //       the generated forms (nllgrad_pair.h), entries on and below the diagonal weighted W_ii and 2 W_ij.  The per-thread
 //       sums fold wave by wave in a fixed order: a problem's bits do not depend on its place in the batch or on the grid.
 // The sums leave unscaled, as nll_grad_full's (nllgrad.hip): the host applies sig / 2, 1/2 and sign(sig2n) / 2.
-// LOO: steps (1) and (2), then in place of (3) thread i < N takes point i's block {A[i,i], A[N+i,i], A[N+i,N+i]} of Ky^-1 (one
+// MODE_LOO: steps (1) and (2), then in place of (3) thread i < N takes point i's block {A[i,i], A[N+i,i], A[N+i,N+i]} of Ky^-1 (one
 // entry for reg) through loo_block.h; lpd and |r|^2 fold wave by wave in the same fixed order into {loo, press}.
-template <int FAM, bool LOO>
+// MODE_LOOGRAD: MODE_LOO's steps and sums by the same code (the same bits), then the gradient of loo or press (a.which) by the
+// formulas of loograd.hip, with a third BMAX^2 block M behind U:
+//   (L1) thread i < N keeps point i's weight block W~_i (packed lower, 3 doubles; 1 for reg) and v[B_i] in LDS:
+//        loo  W~_i = r_i r_i^T + S_i, v = r_i;   press  W~_i = 2 (r_i s_i^T + s_i r_i^T), v = 2 s_i, s_i = S_i r_i.
+//        Meanwhile thread i MIRRORS row i of Ky^-1 into column i: A is full and symmetric from here on, every later read of
+//        Ky^-1 is a plain A[row + col ld] with the row on the lanes;
+//   (L2) beta = Ky^-1 v, thread i its entry (n^2 flop), into LDS;  Y = W~ Ky^-1 over U (dead after (2)): row c N + i of Y is
+//        sum_e W~_i[c, e] (row e N + i of Ky^-1), two rows of Ky^-1 per row of Y;
+//   (L3) M = Ky^-1 Y, lower triangle, thread i its row, four columns at a time, k = 0 .. n - 1 in order: n^3 flop; what is stored
+//        in the third block is W' = M - beta alpha^T - alpha beta^T (the weight is then one load per entry in (L4): with the three
+//        terms formed there the family D instance spilled 20 bytes per lane);
+//   (L4) step (3) on W' (contract_rows: the same code as the nll gradient's).
+// A point whose block has a pivot that is not positive and finite has NaN in W~_i: two rows of Y, so all of M, so every sum.
+// Output: {loo, press, the NACC raw sums}, unscaled.
+template <int FAM, int MODE>
 __device__ void grad_problem(const BatchArgs &a, int b, double *s, double *A, const double *inv, double *U, const double *al)
 {
-    constexpr bool HASP = grad_has_p<FAM>();
-    constexpr int NACC = grad_nacc<FAM>(), NOUT = LOO ? 2 : NACC;     // LOO returns before step (3)
+    constexpr int NACC = grad_nacc<FAM>(), NOUT = MODE == MODE_LOO ? 2 : MODE == MODE_LOOGRAD ? 2 + NACC : NACC;
     constexpr size_t ld = BMAX;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int n = a.n, N = a.npts, n1 = min(n, (int)LEAF), n2 = n - n1;
     double *out = a.nll + a.nbatch + (size_t)b * NOUT;
     // not positive definite (leaf_body's flag, read from L2: the same value for every thread): NaN, nothing computed
@@ -253,93 +374,91 @@ __device__ void grad_problem(const BatchArgs &a, int b, double *s, double *A, co
             A[i + j * ld] = acc;
         }
     }
-    if constexpr (LOO) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();                                  // point i's block has entries written by thread N + i; T is dead
-        double lv[2] = {0.0, 0.0};
-        if (i < N) {
-            double lpd, rr;
-            if (a.reg) {
-                const double C[1] = {A[i + i * ld]}, ai[1] = {al[i]};
-                double r[1], S[1];
-                loo::block<1>(C, ai, r, S, lpd);
-                rr = r[0] * r[0];
-            } else {
-                const double C[3] = {A[i + i * ld], A[(N + i) + i * ld], A[(N + i) + (N + i) * ld]}, ai[2] = {al[i], al[N + i]};
-                double r[2], S[3];
-                loo::block<2>(C, ai, r, S, lpd);
-                rr = __builtin_fma(r[1], r[1], r[0] * r[0]);
-            }
-            lv[0] = lpd; lv[1] = rr;
-        }
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            double v = lv[k];
-            for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-            if (lane == 0) s[wave * 2 + k] = v;
-        }
-        __syncthreads();
-        if (tid < 2) {
-            const double v = s[tid] + s[2 + tid] + s[4 + tid] + s[6 + tid];
-            out[tid] = tid == 0 ? -v : v;
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();                                  // A, U and s are the next problem's
+    [[maybe_unused]] double *sal = s + 2 * BMAX;          // contract_rows' alpha
+    if constexpr (MODE == MODE_GRAD) {
+        // ---- (3) the points and alpha into LDS (T is dead), then the contraction
+        contract_rows<FAM>(a, b, s, al, out, [=](int row, double ai, int col) { return A[row + col * ld] - ai * sal[col]; });
         return;
     }
-    // ---- (3) the points and alpha into LDS (T is dead), then the contraction
-    double *sx = s, *sy = s + BMAX, *sal = s + 2 * BMAX, *red = s + 3 * BMAX;
-    for (int e = tid; e < N; e += LT) { sx[e] = a.x[(size_t)b * N + e]; sy[e] = a.y[(size_t)b * N + e]; }
-    for (int e = tid; e < n; e += LT) sal[e] = al[e];
+    // ---- the points of leave-one-point-out; LDS behind contract_rows' part: W~ (3 BMAX), v, beta
+    [[maybe_unused]] double *sW = s + 4 * BMAX, *sv = s + 7 * BMAX, *sbeta = s + 8 * BMAX;
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const KConst kc = a.kc[b];
-    const double l[2] = {kc.lx, kc.ly}, pp[1] = {kc.p};
-    double acc[NACC];
+    __syncthreads();                                      // point i's block has entries written by thread N + i; T is dead
+    double lv[2] = {0.0, 0.0};
+    if (i < N) {
+        double r[2], S[3], lpd, rr;
+        loo_point(A, al, i, N, a.reg, r, S, lpd, rr);
+        lv[0] = lpd; lv[1] = rr;
+        if constexpr (MODE == MODE_LOOGRAD) {
+            // (L1) W~_i and v[B_i]
+            double w[3], v[2];
+            if (a.which == SGPR_LOO_PRESS) {
+                const double sr[2] = {__builtin_fma(S[1], r[1], S[0] * r[0]), __builtin_fma(S[2], r[1], S[1] * r[0])};   // s = S r
 #pragma unroll
-    for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
-    if (i < n) {
-        const double ai = sal[i];
-        if (a.reg) {
-            const double xi = sx[i], yi = sy[i];
-            for (int j = 0; j <= i; ++j) {
-                const double W = A[i + j * ld] - ai * sal[j];
-                if (j == i) acc[NACC - 1] += W;
-                nllg::reg_grad<FAM, HASP>(sx[j], sy[j], xi, yi, j == i ? W : 2.0 * W, l, kc.p, acc);
-            }
-        } else {
-            const int r = i < N ? 0 : 1, pi = i - r * N;
-            const double xi[2] = {sx[pi], sy[pi]};
-            for (int pj = 0; pj < N; ++pj) {
-                double w[2];
-                bool any = false;
+                for (int e = 0; e < 2; ++e) {
 #pragma unroll
-                for (int c = 0; c < 2; ++c) {                 // columns pj (q part) and N + pj (P part)
-                    const int col = c * N + pj;
-                    w[c] = 0.0;
-                    if (col <= i) {
-                        const double W = A[i + col * ld] - ai * sal[col];
-                        if (col == i) { w[c] = W; acc[NACC - 1] += W; }
-                        else w[c] = 2.0 * W;
-                        any = true;
-                    }
+                    for (int c = 0; c <= e; ++c) w[loo::pk(e, c)] = 2.0 * __builtin_fma(r[e], sr[c], sr[e] * r[c]);
+                    v[e] = 2.0 * sr[e];
                 }
-                if (!any) break;                              // column pj > i: so are all after it
-                const double xj[2] = {sx[pj], sy[pj]};
-                nllg::pair_grad<FAM, 2, HASP>(xi, xj, w, r, l, pp, acc);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+#pragma unroll
+                    for (int c = 0; c <= e; ++c) w[loo::pk(e, c)] = __builtin_fma(r[e], r[c], S[loo::pk(e, c)]);
+                    v[e] = r[e];
+                }
             }
+            sW[i] = w[0]; sW[BMAX + i] = w[1]; sW[2 * BMAX + i] = w[2];
+            sv[i] = v[0];
+            if (!a.reg) sv[N + i] = v[1];
         }
     }
-#pragma unroll
-    for (int k = 0; k < NACC; ++k) {
-        double v = acc[k];
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-        if (lane == 0) red[wave * NACC + k] = v;
+    if constexpr (MODE == MODE_LOOGRAD) {
+        // the mirror: strictly above the diagonal, which no thread reads in this phase
+        if (i < n)
+            for (int j = 0; j < i; ++j) A[j + i * ld] = A[i + j * ld];
     }
-    __syncthreads();
-    if (tid < NACC) out[tid] = red[tid] + red[NACC + tid] + red[2 * NACC + tid] + red[3 * NACC + tid];
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();                                      // A, U and s are the next problem's
+    loo_fold(lv, s, out);                                 // ends on the fence: the mirror and the LDS vectors are visible
+    if constexpr (MODE == MODE_LOOGRAD) {
+        // ---- (L2) beta and Y
+        if (i < n) {
+            double acc = 0.0;
+            for (int j = 0; j < n; ++j) acc = __builtin_fma(A[i + j * ld], sv[j], acc);
+            sbeta[i] = acc;
+            // row i = c N + pi of Y from the point's rows r0 = pi and r1 = N + pi of Ky^-1 (reg: its one row, the second weight is 0)
+            const int c = (!a.reg && i >= N) ? 1 : 0, pi = i - c * N;
+            const int r0 = pi, r1 = a.reg ? pi : N + pi;
+            const double wa = sW[c * BMAX + pi], wb = sW[(c + 1) * BMAX + pi];
+            for (int k = 0; k < n; ++k) U[i + k * ld] = __builtin_fma(wa, A[r0 + k * ld], wb * A[r1 + k * ld]);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        // ---- (L3) W'[i, j] from M[i, j] = sum_k Ky^-1[i, k] Y[k, j], i >= j: thread i, columns j0 .. j0 + 3 from one pass over
+        // its row (a column past n - 1 is clamped: computed again, not stored)
+        double *M = U + (size_t)BMAX * BMAX;
+        for (int j0 = 0; j0 < n; j0 += 4) {
+            if (i < n && i >= j0) {
+                const double *y0 = U + j0 * ld, *y1 = U + min(j0 + 1, n - 1) * ld, *y2 = U + min(j0 + 2, n - 1) * ld,
+                             *y3 = U + min(j0 + 3, n - 1) * ld;
+                double m0 = 0.0, m1 = 0.0, m2 = 0.0, m3 = 0.0;
+                for (int k = 0; k < n; ++k) {
+                    const double kik = A[i + k * ld];
+                    m0 = __builtin_fma(kik, y0[k], m0);
+                    m1 = __builtin_fma(kik, y1[k], m1);
+                    m2 = __builtin_fma(kik, y2[k], m2);
+                    m3 = __builtin_fma(kik, y3[k], m3);
+                }
+                const double bi = sbeta[i], ali = al[i];
+                auto wp = [=](double m, int j) { return m - bi * al[j] - ali * sbeta[j]; };
+                M[i + j0 * ld] = wp(m0, j0);
+                if (j0 + 1 <= i) M[i + (j0 + 1) * ld] = wp(m1, j0 + 1);
+                if (j0 + 2 <= i) M[i + (j0 + 2) * ld] = wp(m2, j0 + 2);
+                if (j0 + 3 <= i) M[i + (j0 + 3) * ld] = wp(m3, j0 + 3);
+            }
+        }
+        // ---- (L4) thread i reads the row of W' it wrote
+        contract_rows<FAM>(a, b, s, al, out + 2, [=](int row, double, int col) { return M[row + col * ld]; });
+    }
 }
 
 // ---- mid-size problems: 256 < n <= 2048 (a CMA-ES generation at N = 512 ... 1024 points) --------------------------
@@ -963,15 +1082,16 @@ namespace {
 
 // problems of order n <= BMAX: one launch of fit_batch_kernel, one workgroup per problem.  grad (nbatch x (nhyp + 1)) non-null:
 // the gradient kernel, whose raw sums come back behind nll in the same device-to-host copy and are scaled here.  loo (nbatch x 2)
-// non-null: the loo kernel, whose {loo, press} come back the same way.
+// non-null: the loo kernel, whose {loo, press} come back the same way.  value (nbatch) non-null beside grad: the loo gradient
+// kernel for the objective `which` -- {loo, press, raw sums} per problem, a third BMAX^2 block of scratch per workgroup.
 int fit_batch_small(int family, int nbatch, int npts, int n, int reg, const double *x, const double *y, const double *z,
                     const double *hyp, int nhyp, const double *sig2n, double *alpha, double *nll, int *info, double *grad,
-                    double *loo = nullptr)
+                    double *loo = nullptr, double *value = nullptr, int which = SGPR_LOO_LPD)
 {
     const size_t B = (size_t)nbatch;
     const int grid = nbatch < 1024 ? nbatch : 1024;
-    const size_t per_wg = PER_WG + (grad || loo ? (size_t)BMAX * BMAX : 0);
-    const size_t nacc = grad ? (size_t)nhyp + 1 : loo ? 2 : 0;
+    const size_t per_wg = PER_WG + (grad || loo ? (size_t)BMAX * BMAX : 0) + (value ? (size_t)BMAX * BMAX : 0);
+    const size_t ngrad = (size_t)nhyp + 1, nacc = grad ? ngrad + (value ? 2 : 0) : loo ? 2 : 0;     // doubles behind nll per problem
     // input block (one H2D): x | y | z | KConst | noise ; output block (one D2H): alpha | nll [| raw gradient sums] | info
     const size_t o_x = 0, o_y = o_x + up256(B * npts * 8), o_z = o_y + up256(B * npts * 8), o_kc = o_z + up256(B * n * 8),
                  o_no = o_kc + up256(B * sizeof(KConst)), in_bytes = o_no + up256(B * 8);
@@ -999,9 +1119,17 @@ int fit_batch_small(int family, int nbatch, int npts, int n, int reg, const doub
                 reinterpret_cast<double *>(din + o_z), reinterpret_cast<KConst *>(din + o_kc),
                 reinterpret_cast<double *>(din + o_no), reinterpret_cast<double *>(dscr),
                 reinterpret_cast<double *>(dout + o_al), reinterpret_cast<double *>(dout + o_nll),
-                reinterpret_cast<int *>(dout + o_info)};
+                reinterpret_cast<int *>(dout + o_info), which};
     const dim3 g(grid), t(LT);
-    if (grad) {
+    if (value) {
+        switch (family) {
+        case SGPR_FAM_A: hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_A, MODE_LOOGRAD>), g, t, 0, st, a); break;
+        case SGPR_FAM_B: hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_B, MODE_LOOGRAD>), g, t, 0, st, a); break;
+        case SGPR_FAM_C: hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_C, MODE_LOOGRAD>), g, t, 0, st, a); break;
+        case SGPR_FAM_USER: hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_USER, MODE_LOOGRAD>), g, t, 0, st, a); break;
+        default:         hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_D, MODE_LOOGRAD>), g, t, 0, st, a); break;
+        }
+    } else if (grad) {
         switch (family) {
         case SGPR_FAM_A: hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_A, MODE_GRAD>), g, t, 0, st, a); break;
         case SGPR_FAM_B: hipLaunchKernelGGL((fit_batch_kernel<SGPR_FAM_B, MODE_GRAD>), g, t, 0, st, a); break;
@@ -1037,17 +1165,19 @@ int fit_batch_small(int family, int nbatch, int npts, int n, int reg, const doub
     if (grad) {
         const double *raw = reinterpret_cast<const double *>(hout + o_nll) + B;
         for (size_t b = 0; b < B; ++b) {
-            const double *r = raw + b * nacc;
-            double *g = grad + b * nacc;
+            const double *r = raw + b * nacc + (value ? 2 : 0);
+            double *g = grad + b * ngrad;
             if (info[b] != 0) {
                 nll[b] = std::nan("");
-                for (size_t k = 0; k < nacc; ++k) g[k] = std::nan("");
+                if (value) value[b] = std::nan("");
+                for (size_t k = 0; k < ngrad; ++k) g[k] = std::nan("");
                 continue;
             }
             const double sig = kcs[b].sig;
             for (int k = 0; k < nhyp - 1; ++k) g[k] = 0.5 * sig * r[k];
             g[nhyp - 1] = 0.5 * r[nhyp - 1];
             g[nhyp] = (sig2n[b] < 0.0 ? -0.5 : 0.5) * r[nhyp];
+            if (value) value[b] = raw[b * nacc + (which == SGPR_LOO_PRESS ? 1 : 0)];
         }
     }
     if (loo) {
@@ -1105,6 +1235,16 @@ int fit_batch_loo(int family, int nbatch, int npts, const double *x, const doubl
     const int reg = (flags & SGPR_FIT_REG) ? 1 : 0, n = reg ? npts : 2 * npts;
     if (n > BMAX) return fit_batch_mid(family, nbatch, npts, n, reg, x, y, z, hyp, nhyp, sig2n, alpha, nll, info, nullptr, loo);
     return fit_batch_small(family, nbatch, npts, n, reg, x, y, z, hyp, nhyp, sig2n, alpha, nll, info, nullptr, loo);
+}
+
+// sgpr_fit_batch_loo_grad: the arguments have been checked (capi.hip), nbatch > 0, n <= BMAX
+int fit_batch_loo_grad(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
+                       int nhyp, const double *sig2n, unsigned flags, int which, double *alpha, double *nll, double *value,
+                       double *grad, int *info)
+{
+    const int reg = (flags & SGPR_FIT_REG) ? 1 : 0;
+    return fit_batch_small(family, nbatch, npts, reg ? npts : 2 * npts, reg, x, y, z, hyp, nhyp, sig2n, alpha, nll, info, grad,
+                           nullptr, value, which);
 }
 
 }  // namespace sgpr

@@ -389,6 +389,31 @@ int sgpr_fit_batch_loo(int family, int nbatch, int n_pts, const double *x, const
     return fit_batch_loo(family, nbatch, n_pts, x, y, z, hyp, nhyp, sig2n, flags, alpha, nll, loo, info);
 }
 
+/* sgpr_fit_batch plus one leave-one-point-out objective and its gradient per problem, orders up to 256 (batch.hip: the loograd
+ * mode of fit_batch_kernel).  Checked like sgpr_fit_batch_grad, before any device call. */
+int sgpr_fit_batch_loo_grad(int family, int nbatch, int n_pts, const double *x, const double *y, const double *z,
+                            const double *hyp, int nhyp, const double *sig2n, unsigned flags, int which, double *alpha,
+                            double *nll, double *value, double *grad, int *info)
+{
+    auto E = [](const std::string &what) { set_error("fit_batch_loo_grad: " + what); return SGPR_E_ARG; };
+    if (family < SGPR_FAM_A || family > SGPR_FAM_USER) return E("unknown kernel family");
+    const int need = family_has_p(family) ? 4 : 3;
+    if (nhyp != need) return E("nhyp must be " + std::to_string(need) + " for this family");
+    if (flags & ~(unsigned)SGPR_FIT_REG) return E("unknown flag (only SGPR_FIT_REG)");
+    if (which != SGPR_LOO_LPD && which != SGPR_LOO_PRESS) return E("which must be SGPR_LOO_LPD or SGPR_LOO_PRESS");
+    if (nbatch < 0) return E("nbatch < 0");
+    if (n_pts <= 0) return E("n_pts <= 0");
+    const long n = (flags & SGPR_FIT_REG) ? (long)n_pts : 2L * n_pts;
+    const int nmax = fit_batch_grad_max_order();
+    if (n > nmax) return E("order per problem " + std::to_string(n) + " exceeds " + std::to_string(nmax));
+    if (!nll || !value || !grad || !info) return E("null nll, value, grad or info");
+    if (!x || !y || !z || !hyp || !sig2n) return E("null input");
+    if (nbatch == 0) return 0;
+    int rc = need_device();
+    if (rc) return rc;
+    return fit_batch_loo_grad(family, nbatch, n_pts, x, y, z, hyp, nhyp, sig2n, flags, which, alpha, nll, value, grad, info);
+}
+
 /* applymap / applymap_henon (functions/func.py:216-260) and the per-example variants for all Ntest
  * orbits, every time step on the device.  alpha = Kyinv ztrain (2 n0), alphap = Kyinvp ztrainp (n0p);
  * qmap, pmap, pdiff: [nm][ntest] C-ordered host arrays (row 0 = initial conditions), pdiff optional.

@@ -297,6 +297,11 @@ int fit_batch_grad_mid(int family, int nbatch, int npts, const double *x, const 
 // row b = {loo, press}; the arguments have been checked (capi.hip), nbatch > 0
 int fit_batch_loo(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
                   int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, double *loo, int *info);
+// one of the two objectives (which: SGPR_LOO_LPD / SGPR_LOO_PRESS) and its gradient, order <= fit_batch_grad_max_order(): value is
+// nbatch doubles, grad nbatch x (nhyp + 1); the arguments have been checked (capi.hip), nbatch > 0
+int fit_batch_loo_grad(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
+                       int nhyp, const double *sig2n, unsigned flags, int which, double *alpha, double *nll, double *value,
+                       double *grad, int *info);
 
 // ---- blas_small.hip
 int zero_strict_upper(int n, double *A, size_t lda, hipStream_t st);

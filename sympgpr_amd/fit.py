@@ -508,3 +508,45 @@ def fit_batch_loo(family, x, y, z, hyp, sig2n, reg=False, want_alpha=False):
                                                 L.dptr(alpha) if want_alpha else None, L.dptr(nll), L.dptr(loo),
                                                 info.ctypes.data_as(C.POINTER(C.c_int))), "sgpr_fit_batch_loo")
     return alpha, nll, loo, info
+
+
+def fit_batch_loo_grad(family, x, y, z, hyp, sig2n, reg=False, objective="loo", want_alpha=False):
+    """fit_batch plus one leave-one-point-out objective of every problem and its exact gradient in (hyp, sig2n): objective="loo"
+    (minus the summed log predictive densities) or "press" (the summed squared residuals), SympFit.loo_grad's definitions.
+    Shapes as fit_batch:
+        x, y (B, n_pts);  z (B, n), n = 2 n_pts (n_pts with reg);  hyp (B, nhyp);  sig2n (B,) or scalar.
+    -> (alpha (B, n) or None, nll (B,), value (B,), grad (B, nhyp + 1), info (B,)).  Row b of grad is (d/dhyp_0 ..
+    d/dhyp_{nhyp-1}, d/dsig2n) of value[b]; Ky holds |sig2n[b]|, so the last entry carries sign(sig2n[b]) (sign(0) = +1).  Rows
+    with info > 0 are NaN (nll, value and the whole gradient row).  nll, alpha and info are the same bits fit_batch returns,
+    value the bits of fit_batch_loo's column.
+    n <= 256: ONE launch (sgpr_fit_batch_loo_grad), one workgroup per problem.
+    256 < n <= 2048 (the slow path): nll, alpha, info and value from one fit_batch_loo call, and the gradient of every
+    positive-definite row from SympFit(...).run().loo_grad(objective), one device-resident fit per row."""
+    if objective not in ("loo", "press"):
+        raise ValueError('fit_batch_loo_grad: objective is "loo" or "press"')
+    which = L.LOO_PRESS if objective == "press" else L.LOO_LPD
+    x, y, z, hyp = (np.ascontiguousarray(np.atleast_2d(np.asarray(v, dtype=np.float64))) for v in (x, y, z, hyp))
+    B, n_pts = x.shape
+    n = n_pts if reg else 2 * n_pts
+    if y.shape != (B, n_pts) or z.shape != (B, n) or hyp.shape[0] != B:
+        raise ValueError("fit_batch_loo_grad: x, y (B, n_pts), z (B, n), hyp (B, nhyp)")
+    s2 = np.ascontiguousarray(np.broadcast_to(np.asarray(sig2n, dtype=np.float64), (B,)))
+    nhyp = hyp.shape[1]
+    if n > batch_grad_max_order():
+        alpha, nll, loo, info = fit_batch_loo(family, x, y, z, hyp, s2, reg=reg, want_alpha=want_alpha)
+        grad = np.full((B, nhyp + 1), np.nan)
+        for b in np.flatnonzero(info == 0):
+            with SympFit(family, x[b], y[b], z[b], hyp[b], s2[b], reg=reg) as f:
+                grad[b] = f.run().loo_grad(objective)[1]
+        return alpha, nll, loo[:, which].copy(), grad, info
+    alpha = np.empty((B, n)) if want_alpha else None
+    nll = np.empty(B)
+    value = np.empty(B)
+    grad = np.empty((B, nhyp + 1))
+    info = np.zeros(B, dtype=np.int32)
+    L.check(L.load_library().sgpr_fit_batch_loo_grad(L.family_id(family), B, n_pts, L.dptr(x), L.dptr(y), L.dptr(z), L.dptr(hyp),
+                                                     nhyp, L.dptr(s2), L.FIT_REG if reg else 0, which,
+                                                     L.dptr(alpha) if want_alpha else None, L.dptr(nll), L.dptr(value),
+                                                     L.dptr(grad), info.ctypes.data_as(C.POINTER(C.c_int))),
+            "sgpr_fit_batch_loo_grad")
+    return alpha, nll, value, grad, info

@@ -252,7 +252,7 @@ def loo_chol_grad(hyp, x, y, N, reg=False, objective="loo"):
     of hyp, the last being sig2_n (Ky holds |hyp[-1]|, so that entry carries its sign).  objective="press": the sum of squared
     leave-one-point-out residuals instead.  Arguments checked and sliced like nll_chol_grad; raises LinAlgError where loo_chol
     does.  The objective for scipy.optimize.minimize(..., jac=True).  Every order goes through a device-resident fit and
-    SympFit.loo_grad (there is no batched LOO gradient)."""
+    SympFit.loo_grad; a population's gradients in one launch: loo_chol_grad_batch."""
     if objective not in ("loo", "press"):
         raise ValueError('loo_chol_grad: objective is "loo" or "press"')
     hyp = np.asarray(hyp, dtype=np.float64)
@@ -290,6 +290,32 @@ def loo_chol_batch(hyps, x, y, N, reg=False):
     _, _, loo, _ = fit_batch_loo(get_family(), np.broadcast_to(X, (B, len(X))), np.broadcast_to(Y, (B, len(Y))),
                                  np.broadcast_to(Z, (B, len(Z))), hyps[:, :-1], np.abs(hyps[:, -1]), reg=reg)
     return loo[:, 0].copy()
+
+
+def loo_chol_grad_batch(hyps, x, y, N, reg=False, objective="loo"):
+    """loo_chol_batch with gradients: hyps (B, nhyp + 1) rows like loo_chol's hyp -> (value (B,), grad (B, nhyp + 1)), grad[b, k]
+    = d value[b] / d hyps[b, k]; the last column is sig2_n, which enters as |hyps[b, -1]| and gives that entry its sign.
+    objective="press": the sum of squared leave-one-point-out residuals instead.  Sliced and checked like nll_chol_grad_batch.
+    Rows whose Ky is not positive definite give NaN in the value and the whole gradient row, as in loo_chol_batch.  Up to order
+    256 one launch (fit.fit_batch_loo_grad); above it the values from one fit_batch_loo call and the gradients row by row."""
+    from .fit import fit_batch_loo_grad
+    if objective not in ("loo", "press"):
+        raise ValueError('loo_chol_grad_batch: objective is "loo" or "press"')
+    hyps = np.atleast_2d(np.asarray(hyps, dtype=np.float64))
+    x = np.asarray(x, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64)
+    if hyps.ndim != 2 or hyps.shape[1] < 2:
+        raise ValueError("loo_chol_grad_batch: hyps (B, nhyp + 1)")
+    if N <= 0:
+        raise ValueError("loo_chol_grad_batch: N must be positive")
+    X, Y, Z = _batch_data(x, y, N, reg)
+    if len(X) != (N if reg else N // 2) or len(Y) != len(X) or len(Z) != (N if reg else 2 * len(X)):
+        raise ValueError("loo_chol_grad_batch: x holds 2 * n_pts coordinates and y the n targets of order N")
+    B = len(hyps)
+    _, _, value, grad, _ = fit_batch_loo_grad(get_family(), np.broadcast_to(X, (B, len(X))), np.broadcast_to(Y, (B, len(Y))),
+                                              np.broadcast_to(Z, (B, len(Z))), hyps[:, :-1], hyps[:, -1], reg=reg,
+                                              objective=objective)
+    return value, grad
 
 
 def guessP(x, y, hypp, xtrainp, ztrainp, Kyinvp):
