@@ -314,6 +314,28 @@ int sgpr_fit_batch_max_order(void);
 int sgpr_fit_batch(int family, int nbatch, int n_pts, const double *x, const double *y, const double *z,
                    const double *hyp, int nhyp, const double *sig2n, unsigned flags, double *alpha,
                    double *nll, int *info);
+/* sgpr_fit_batch for problems with d canonical pairs per point (d = 1, 2, 3; sgpr_fit_create_nd's kernels, block order and hyp):
+ * a population of hyper-parameter vectors, or many small data sets, of a d-pair fit in one call.  Order per problem
+ * n = 2 d n_pts <= sgpr_fit_batch_max_order() (2048).
+ *   X:   nbatch x 2d x n_pts; coordinate m of point i of problem b at X[(b 2d + m) n_pts + i], columns q_1..q_d, P_1..P_d --
+ *        sgpr_fit_create_nd's column-major X with ldx = n_pts, problem after problem (d = 1: sgpr_fit_batch's x | y);
+ *   z:   nbatch x n in the block order of the matrix (row a n_pts + i), as a d-pair handle takes it;
+ *   hyp: nbatch x nhyp, each row (lq_1..lq_d, lP_1..lP_d, sig), nhyp = 2d + 1, or (lq.., lP.., p_1..p_d, sig), nhyp = 3d + 1, for
+ *        families with a period; noise |sig2n[b]|.
+ * alpha (nbatch x n, may be NULL), nll, info exactly as sgpr_fit_batch: info[b] > 0 is the index of the first non-positive
+ * pivot of problem b and the call still returns 0; a NaN target poisons its own problem only.  A problem's bits do not depend on
+ * its place in the batch or on the batch size.
+ * n <= 256: ONE launch, one workgroup per problem -- each point pair is evaluated once (one exp, d sincos) and feeds its entry
+ * of every block of the lower triangle; the factor, solves and nll behind it are sgpr_fit_batch's own code.  Scratch: 512 KiB +
+ * 260 KiB per workgroup, at most 1024 workgroups.  256 < n <= 2048: sgpr_fit_batch's mid path with a d-pair build: per chunk of
+ * problems one build, one or three factor launches, the right-hand sides, two strip solves and the finish (6 or 8 launches);
+ * scratch per chunk: one npad x npad image per problem (npad = n rounded up to 128), at most ~2 GiB, plus the leaf inverses and
+ * solve vectors.  All of it lives in the sgpr_fit_batch arena of the calling thread; sgpr_trim gives it back.
+ * SGPR_E_ARG (before any device call) for d outside 1..3, an unknown family, a wrong nhyp, flags != 0 (there is no scalar-kernel
+ * d-pair fit), nbatch < 0, n_pts <= 0, n above the maximum and a null pointer other than alpha; nbatch == 0 returns 0.  There
+ * is no batched d-pair gradient or leave-one-out yet.  ABI 5 (an additional entry point). */
+int sgpr_fit_batch_nd(int family, int d, int nbatch, int n_pts, const double *X, const double *z, const double *hyp,
+                      int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, int *info);
 /* sgpr_fit_batch plus d nll / d(hyp, sig2n) per problem.  Order per problem n = 2 n_pts (n_pts with SGPR_FIT_REG) <= 256.
  * grad: nbatch x (nhyp + 1), row-major; row b = (d/dhyp_0 .. d/dhyp_{nhyp-1}, d/dsig2n).  hyp layout and nhyp as
  * sgpr_fit_batch: (lx, ly, sig), or (lx, ly, p, sig) for families with a period.  Ky holds |sig2n[b]|, so the last entry is

@@ -12,6 +12,8 @@
 // workgroup);  L11 = leaf(A11) in LDS (leaf.h), X11 = inv(L11);  L21 = A21 X11^T;  A22 -= L21 L21^T;
 // L22 = leaf(A22);  y = L^-1 z and alpha = L^-T y through the leaf inverses.  Latency-bound by
 // construction: throughput comes from the number of problems in flight, not from the matrix cores.
+// Problems with d canonical pairs per point (sgpr_fit_batch_nd) take the same path behind a Gram stage of their own: the entry
+// formulas of nd_eval.h, fit_batch_nd_kernel / mid_build_nd_kernel below.
 #include <cmath>
 #include <cstring>
 
@@ -20,6 +22,7 @@
 #include "leaf.h"
 #include "loo_block.h"
 #include "nllgrad_pair.h"
+#include "nd_eval.h"
 #include "pair_eval.h"
 
 namespace sgpr {
@@ -53,6 +56,109 @@ enum { MODE_FIT = 0, MODE_GRAD = 1, MODE_LOO = 2, MODE_LOOGRAD = 3 };
 
 template <int FAM, int MODE>
 __device__ void grad_problem(const BatchArgs &a, int b, double *s, double *A, const double *inv, double *U, const double *al);
+
+// Everything of one problem behind its Gram stage, for the workgroup that has just written the lower triangle of Ky (order n, n1 =
+// min(n, LEAF), n2 = n - n1) into A (ld = BMAX): the fence, both leaves, L21, the SYRK, y = L^-1 z and alpha = L^-T y through the
+// leaf inverses, nll and the alpha write-out (alpha: the problem's row of the output or null).  Shared by the d = 1 kernel and
+// the d-pair one (fit_batch_nd_kernel): one text, one sequence of operations.  s: LEAF_LDS doubles, red: LT / 64; v: y, then alpha
+// at v + BMAX (al).  Ends on the fence and barrier that free A, inv and s for the next problem.
+__device__ __forceinline__ void fit_solve_body(double *s, double *red, double *A, double *inv, double *v, double *al, const double *z,
+                                               int n, int n1, int n2, double *alpha, double *nll, int *info)
+{
+    constexpr size_t ld = BMAX;
+    const int tid = threadIdx.x;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    // ---- L11, X11 = inv(L11)
+    leaf_body(s, n1, A, ld, inv, info, 0, (int)LEAF_FACTOR,
+              nullptr);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (n2 > 0) {
+        // L21 = A21 X11^T  (X11 lower: k >= c), staged through LDS so that A21 can be overwritten
+        for (int e = tid; e < n2 * n1; e += LT) {
+            const int i = e % n2, c = e / n2;
+            double acc = 0.0;
+            for (int k = 0; k <= c; ++k) acc = __builtin_fma(A[(n1 + i) + k * ld], inv[c + k * LEAF], acc);
+            s[e] = acc;
+        }
+        __syncthreads();
+        for (int e = tid; e < n2 * n1; e += LT) A[(n1 + e % n2) + (e / n2) * ld] = s[e];
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        // A22 -= L21 L21^T (lower)
+        for (int e = tid; e < n2 * n2; e += LT) {
+            const int i = e % n2, j = e / n2;
+            if (i < j) continue;
+            double acc = A[(n1 + i) + (n1 + j) * ld];
+            for (int k = 0; k < n1; ++k) acc = __builtin_fma(-A[(n1 + i) + k * ld], A[(n1 + j) + k * ld], acc);
+            A[(n1 + i) + (n1 + j) * ld] = acc;
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        leaf_body(s, n2, A + n1 + n1 * ld, ld, inv + LEAF * LEAF,
+                  info, n1, (int)LEAF_FACTOR, nullptr);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+    }
+    // ---- y = L^-1 z:  y1 = X11 z1;  y2 = X22 (z2 - L21 y1)
+    double *yv = v;
+    if (tid < n1) {
+        double acc = 0.0;
+        for (int k = 0; k <= tid; ++k) acc = __builtin_fma(inv[tid + k * LEAF], z[k], acc);
+        yv[tid] = acc;
+    }
+    __syncthreads();
+    if (n2 > 0) {
+        if (tid < n2) {
+            double acc = z[n1 + tid];
+            for (int k = 0; k < n1; ++k) acc = __builtin_fma(-A[(n1 + tid) + k * ld], yv[k], acc);
+            s[tid] = acc;
+        }
+        __syncthreads();
+        if (tid < n2) {
+            double acc = 0.0;
+            const double *X22 = inv + LEAF * LEAF;
+            for (int k = 0; k <= tid; ++k) acc = __builtin_fma(X22[tid + k * LEAF], s[k], acc);
+            yv[n1 + tid] = acc;
+        }
+        __syncthreads();
+        // ---- alpha = L^-T y:  a2 = X22^T y2;  a1 = X11^T (y1 - L21^T a2)
+        if (tid < n2) {
+            double acc = 0.0;
+            const double *X22 = inv + LEAF * LEAF;
+            for (int k = tid; k < n2; ++k) acc = __builtin_fma(X22[k + tid * LEAF], yv[n1 + k], acc);
+            al[n1 + tid] = acc;
+        }
+        __syncthreads();
+        if (tid < n1) {
+            double acc = yv[tid];
+            for (int k = 0; k < n2; ++k) acc = __builtin_fma(-A[(n1 + k) + tid * ld], al[n1 + k], acc);
+            s[tid] = acc;
+        }
+        __syncthreads();
+    } else {
+        if (tid < n1) s[tid] = yv[tid];
+        __syncthreads();
+    }
+    if (tid < n1) {
+        double acc = 0.0;
+        for (int k = tid; k < n1; ++k) acc = __builtin_fma(inv[k + tid * LEAF], s[k], acc);
+        al[tid] = acc;
+    }
+    __syncthreads();
+    // ---- nll = z.alpha / 2 + sum log L_ii  (func.py:195)
+    double q = 0.0;
+    for (int i = tid; i < n; i += LT) q += 0.5 * z[i] * al[i] + log(A[i + i * ld]);
+    for (int o = 32; o > 0; o >>= 1) q += __shfl_down(q, o, 64);
+    if ((tid & 63) == 0) red[tid >> 6] = q;
+    __syncthreads();
+    if (tid == 0) *nll = red[0] + red[1] + red[2] + red[3];
+    if (alpha)
+        for (int i = tid; i < n; i += LT) alpha[i] = al[i];
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+}
 
 // MODE_GRAD: after the fit, the gradient of problem b's nll (grad_problem below); MODE_LOO: its leave-one-point-out sums
 // (grad_problem's Ky^-1, then one thread per point).  Scratch then PER_WG + BMAX^2 doubles per workgroup.  MODE_LOOGRAD: the sums
@@ -98,98 +204,71 @@ __global__ __launch_bounds__(LT) void fit_batch_kernel(const BatchArgs a)
                 }
             }
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        // ---- L11, X11 = inv(L11)
-        leaf_body(s, n1, A, ld, inv, a.info + b, 0, (int)LEAF_FACTOR,
-                  nullptr);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (n2 > 0) {
-            // L21 = A21 X11^T  (X11 lower: k >= c), staged through LDS so that A21 can be overwritten
-            for (int e = tid; e < n2 * n1; e += LT) {
-                const int i = e % n2, c = e / n2;
-                double acc = 0.0;
-                for (int k = 0; k <= c; ++k) acc = __builtin_fma(A[(n1 + i) + k * ld], inv[c + k * LEAF], acc);
-                s[e] = acc;
-            }
-            __syncthreads();
-            for (int e = tid; e < n2 * n1; e += LT) A[(n1 + e % n2) + (e / n2) * ld] = s[e];
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            // A22 -= L21 L21^T (lower)
-            for (int e = tid; e < n2 * n2; e += LT) {
-                const int i = e % n2, j = e / n2;
-                if (i < j) continue;
-                double acc = A[(n1 + i) + (n1 + j) * ld];
-                for (int k = 0; k < n1; ++k) acc = __builtin_fma(-A[(n1 + i) + k * ld], A[(n1 + j) + k * ld], acc);
-                A[(n1 + i) + (n1 + j) * ld] = acc;
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            leaf_body(s, n2, A + n1 + n1 * ld, ld, inv + LEAF * LEAF,
-                      a.info + b, n1, (int)LEAF_FACTOR, nullptr);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-        }
-        // ---- y = L^-1 z:  y1 = X11 z1;  y2 = X22 (z2 - L21 y1)
-        double *yv = v, *al = v + BMAX;
-        if (tid < n1) {
-            double acc = 0.0;
-            for (int k = 0; k <= tid; ++k) acc = __builtin_fma(inv[tid + k * LEAF], z[k], acc);
-            yv[tid] = acc;
-        }
-        __syncthreads();
-        if (n2 > 0) {
-            if (tid < n2) {
-                double acc = z[n1 + tid];
-                for (int k = 0; k < n1; ++k) acc = __builtin_fma(-A[(n1 + tid) + k * ld], yv[k], acc);
-                s[tid] = acc;
-            }
-            __syncthreads();
-            if (tid < n2) {
-                double acc = 0.0;
-                const double *X22 = inv + LEAF * LEAF;
-                for (int k = 0; k <= tid; ++k) acc = __builtin_fma(X22[tid + k * LEAF], s[k], acc);
-                yv[n1 + tid] = acc;
-            }
-            __syncthreads();
-            // ---- alpha = L^-T y:  a2 = X22^T y2;  a1 = X11^T (y1 - L21^T a2)
-            if (tid < n2) {
-                double acc = 0.0;
-                const double *X22 = inv + LEAF * LEAF;
-                for (int k = tid; k < n2; ++k) acc = __builtin_fma(X22[k + tid * LEAF], yv[n1 + k], acc);
-                al[n1 + tid] = acc;
-            }
-            __syncthreads();
-            if (tid < n1) {
-                double acc = yv[tid];
-                for (int k = 0; k < n2; ++k) acc = __builtin_fma(-A[(n1 + k) + tid * ld], al[n1 + k], acc);
-                s[tid] = acc;
-            }
-            __syncthreads();
-        } else {
-            if (tid < n1) s[tid] = yv[tid];
-            __syncthreads();
-        }
-        if (tid < n1) {
-            double acc = 0.0;
-            for (int k = tid; k < n1; ++k) acc = __builtin_fma(inv[k + tid * LEAF], s[k], acc);
-            al[tid] = acc;
-        }
-        __syncthreads();
-        // ---- nll = z.alpha / 2 + sum log L_ii  (func.py:195)
-        double q = 0.0;
-        for (int i = tid; i < n; i += LT) q += 0.5 * z[i] * al[i] + log(A[i + i * ld]);
-        for (int o = 32; o > 0; o >>= 1) q += __shfl_down(q, o, 64);
-        if ((tid & 63) == 0) red[tid >> 6] = q;
-        __syncthreads();
-        if (tid == 0) a.nll[b] = red[0] + red[1] + red[2] + red[3];
-        if (a.alpha)
-            for (int i = tid; i < n; i += LT) a.alpha[(size_t)b * n + i] = al[i];
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
+        double *al = v + BMAX;
+        fit_solve_body(s, red, A, inv, v, al, z, n, n1, n2, a.alpha ? a.alpha + (size_t)b * n : nullptr, a.nll + b, a.info + b);
         if constexpr (MODE != MODE_FIT) grad_problem<FAM, MODE>(a, b, s, A, inv, v + 2 * BMAX, al);
+    }
+}
+
+// ---- d canonical pairs per point (D = 2 d coordinates, order n = D N <= BMAX): the fit of fit_batch_kernel with the Gram
+// stage of gram_nd.hip.  Ky is (D)^2 blocks of N x N, block (ca, cb) at rows ca N, columns cb N; a point pair (i, j) is evaluated
+// once (one exp, d sincos: nd_eval.h) and feeds its entry of every block of the LOWER triangle: blocks ca > cb whole, blocks
+// ca = cb for i >= j, blocks ca < cb not at all; the noise sits on the diagonal of the blocks ca = cb.  The sum kernels' blocks
+// ca > cb are written as the zeros they are (the scratch holds the previous problem's factor).
+struct BatchNdArgs {
+    int nbatch, npts, n;
+    const double *X, *z;                  // nbatch x D x npts (coordinate m of point i of problem b at (b D + m) npts + i), nbatch x n
+    const nd::NdConst *nc;                // per problem
+    const double *noise;                  // per problem, >= 0
+    double *scratch;                      // per workgroup: PER_WG doubles, as fit_batch_kernel<FAM, MODE_FIT>
+    double *alpha, *nll;                  // outputs (alpha may be null)
+    int *info;                            // per problem, zero on entry
+};
+
+// entry (i, j) of the blocks (ca, 0 .. ca) of one evaluated pair into the lower triangle at P = A + i + j ld (ld: the leading
+// dimension, N the block size); one row of blocks is live at a time
+template <int FAM, int D>
+__device__ __forceinline__ void store_pair_lower(double *P, size_t ld, int N, bool on_or_below, bool diag, double noise,
+                                                 const double (&E)[D], const double (&g)[D], const double (&nh)[D])
+{
+#pragma unroll
+    for (int ca = 0; ca < D; ++ca) {
+#pragma unroll
+        for (int cb = 0; cb < ca; ++cb)
+            P[(size_t)ca * N + (size_t)cb * N * ld] = nd::is_sum<FAM>() ? 0.0 : -E[ca] * (g[ca] * g[cb]);
+        if (on_or_below) P[(size_t)ca * N + (size_t)ca * N * ld] = __builtin_fma(E[ca], nh[ca], diag ? noise : 0.0);
+    }
+}
+
+template <int FAM, int D>
+__global__ __launch_bounds__(LT) void fit_batch_nd_kernel(const BatchNdArgs a)
+{
+    __shared__ double s[LEAF_LDS];
+    __shared__ double red[LT / 64];
+    const int tid = threadIdx.x;
+    const int n = a.n, N = a.npts;
+    double *A = a.scratch + (size_t)blockIdx.x * PER_WG;      // column-major, ld = BMAX
+    double *inv = A + (size_t)BMAX * BMAX;
+    double *v = inv + 2 * (size_t)LEAF * LEAF;                // y, then alpha
+    constexpr size_t ld = BMAX;
+    const int n1 = min(n, (int)LEAF), n2 = n - n1;
+    for (int b = blockIdx.x; b < a.nbatch; b += gridDim.x) {
+        const nd::NdConst nc = a.nc[b];
+        const double *X = a.X + (size_t)b * D * N, *z = a.z + (size_t)b * n;
+        const double noise = a.noise[b];
+        // the problem's points into LDS (D N <= BMAX doubles; fit_solve_body's closing barrier has freed s)
+        for (int e = tid; e < D * N; e += LT) s[e] = X[e];
+        __syncthreads();
+        for (int e = tid; e < N * N; e += LT) {
+            const int i = e % N, j = e / N;                   // pair (row point i, column point j)
+            double xa[D], xb[D], arg[D], g[D], nh[D], E[D];
+#pragma unroll
+            for (int m = 0; m < D; ++m) { xa[m] = s[m * N + j]; xb[m] = s[m * N + i]; }
+            nd::all_coords<FAM, D>(nc, xa, xb, arg, g, nh);
+            nd::weights<FAM, D>(nc, arg, E);
+            store_pair_lower<FAM, D>(A + i + j * ld, ld, N, i >= j, i == j, noise, E, g, nh);
+        }
+        fit_solve_body(s, red, A, inv, v, v + BMAX, z, n, n1, n2, a.alpha ? a.alpha + (size_t)b * n : nullptr, a.nll + b, a.info + b);
     }
 }
 
@@ -522,6 +601,47 @@ __global__ __launch_bounds__(MT) void mid_build_kernel(const MidArgs a)
             A[i + j * ld] = kxx;
             A[(N + i) + (N + j) * ld] = kyy;
         }
+    }
+}
+
+// The build for d canonical pairs per point (D = 2 d, n = D N): mid_build_kernel's tiling -- MT point rows per workgroup, one per
+// thread, MJ point columns in LDS, now D coordinates each, blockIdx.z the problem -- and fit_batch_nd_kernel's entries and
+// lower-triangle rule (store_pair_lower) at ld = npad.
+struct MidNdArgs {
+    int npts, n, npad;
+    const double *X;                      // nbatch x D x npts
+    const nd::NdConst *nc;
+    const double *noise;
+    double *A;                            // problem b at A + b * npad * npad, ld = npad
+};
+
+template <int FAM, int D>
+__global__ __launch_bounds__(MT) void mid_build_nd_kernel(const MidNdArgs a)
+{
+    __shared__ double sxa[MJ][D];
+    const int b = blockIdx.z, N = a.npts, t = threadIdx.x;
+    const int i0 = blockIdx.x * MT, j0 = blockIdx.y * MJ;
+    const size_t ld = (size_t)a.npad;
+    double *A = a.A + (size_t)b * ld * ld;
+    if (blockIdx.x == 0 && blockIdx.y == 0)
+        for (int r = a.n + t; r < a.npad; r += MT) A[r + r * ld] = 1.0;     // the padding's diagonal (the rest was cleared)
+    const double *X = a.X + (size_t)b * D * N;
+    const int nj = min(MJ, N - j0);
+    for (int e = t; e < nj * D; e += MT) sxa[e / D][e % D] = X[(size_t)(e % D) * N + j0 + e / D];
+    __syncthreads();
+    const int i = i0 + t;
+    if (i >= N) return;
+    const nd::NdConst nc = a.nc[b];
+    const double noise = a.noise[b];
+    double xb[D];
+#pragma unroll
+    for (int m = 0; m < D; ++m) xb[m] = X[(size_t)m * N + i];
+    for (int jj = 0; jj < nj; ++jj) {
+        const int j = j0 + jj;
+        double arg[D], g[D], nh[D], E[D];
+        nd::all_coords<FAM, D>(nc, sxa[jj], xb, arg, g, nh);
+        nd::weights<FAM, D>(nc, arg, E);
+        store_pair_lower<FAM, D>(A + i + (size_t)j * ld, ld, N, i >= j, i == j, noise, E, g, nh);
     }
 }
 
@@ -893,9 +1013,13 @@ void launch_mid_grad(const MidGrad &g, dim3 grid, hipStream_t st) { hipLaunchKer
 // fold in place of the contraction, {loo, press} behind nll in the same copy.
 int fit_batch_mid(int family, int nbatch, int npts, int n, int reg, const double *x, const double *y, const double *z,
                   const double *hyp, int nhyp, const double *sig2n, double *alpha, double *nll, int *info, double *grad = nullptr,
-                  double *loo = nullptr)
+                  double *loo = nullptr, int d = 0, const double *X = nullptr)
 {
     const bool kinv = grad || loo;         // the phase behind the solves that forms Ky^-1
+    // d > 0: problems with d canonical pairs per point (sgpr_fit_batch_nd) -- X (nbatch x 2d x npts) in place of x | y, one NdConst
+    // per problem in place of its KConst, mid_build_nd_kernel in place of mid_build_kernel; no gradient or loo phase
+    const size_t D = 2 * (size_t)d;
+    const size_t xb = d ? D * npts * 8 : (size_t)npts * 8, yb = d ? 0 : (size_t)npts * 8, kcb = d ? sizeof(nd::NdConst) : sizeof(KConst);
     const int npad = (n + (int)LEAF - 1) / (int)LEAF * (int)LEAF, W = npad / (int)LEAF;
     const size_t img = (size_t)npad * npad * 8, invb = (size_t)W * LEAF * LEAF * 8;
     const size_t nimg = kinv ? 2 : 1, nacc = grad ? (size_t)nhyp + 1 : loo ? 2 : 0;
@@ -910,8 +1034,8 @@ int fit_batch_mid(int family, int nbatch, int npts, int n, int reg, const double
     const size_t C = (size_t)chunk;
     const int ggx = (n + GT - 1) / GT, ggy = (npts + GCJ - 1) / GCJ, gnwg = ggx * ggy;      // contraction workgroups per problem
     const int lnwg = (npts + GT - 1) / GT;                                                   // loo workgroups per problem
-    const size_t o_x = 0, o_y = o_x + up256(C * npts * 8), o_z = o_y + up256(C * npts * 8), o_kc = o_z + up256(C * n * 8),
-                 o_no = o_kc + up256(C * sizeof(KConst)), in_bytes = o_no + up256(C * 8);
+    const size_t o_x = 0, o_y = o_x + up256(C * xb), o_z = o_y + up256(C * yb), o_kc = o_z + up256(C * n * 8),
+                 o_no = o_kc + up256(C * kcb), in_bytes = o_no + up256(C * 8);
     // (with the gradient: problem b's raw sums at nll + chunk + b * nacc)
     const size_t o_al = 0, o_nll = o_al + up256(C * n * 8), o_info = o_nll + up256(C * (1 + nacc) * 8),
                  out_bytes = o_info + up256(C * sizeof(int));
@@ -929,13 +1053,19 @@ int fit_batch_mid(int family, int nbatch, int npts, int n, int reg, const double
     for (int b0 = 0; b0 < nbatch; b0 += chunk) {
         const int nb = std::min(chunk, nbatch - b0);
         const size_t B = (size_t)nb;
-        memcpy(hin + o_x, x + (size_t)b0 * npts, B * npts * 8);
-        memcpy(hin + o_y, y + (size_t)b0 * npts, B * npts * 8);
+        if (d) memcpy(hin + o_x, X + (size_t)b0 * D * npts, B * xb);
+        else {
+            memcpy(hin + o_x, x + (size_t)b0 * npts, B * npts * 8);
+            memcpy(hin + o_y, y + (size_t)b0 * npts, B * npts * 8);
+        }
         memcpy(hin + o_z, z + (size_t)b0 * n, B * n * 8);
         KConst *kcs = reinterpret_cast<KConst *>(hin + o_kc);
+        nd::NdConst *ncs = reinterpret_cast<nd::NdConst *>(hin + o_kc);
         double *noise = reinterpret_cast<double *>(hin + o_no);
         for (int b = 0; b < nb; ++b) {
-            if ((rc = make_kconst(family, hyp + (size_t)(b0 + b) * nhyp, nhyp, &kcs[b]))) return rc;
+            if (d) rc = nd::fill_consts(family, d, hyp + (size_t)(b0 + b) * nhyp, nhyp, ncs[b]);
+            else rc = make_kconst(family, hyp + (size_t)(b0 + b) * nhyp, nhyp, &kcs[b]);
+            if (rc) return rc;
             noise[b] = std::fabs(sig2n[b0 + b]);
         }
         SGPR_HIP(hipMemcpyAsync(din, hin, in_bytes, hipMemcpyHostToDevice, st));
@@ -953,6 +1083,15 @@ int fit_batch_mid(int family, int nbatch, int npts, int n, int reg, const double
                   reinterpret_cast<double *>(din + o_no), dA, dinv, alpha ? reinterpret_cast<double *>(dout + o_al) : nullptr,
                   reinterpret_cast<double *>(dout + o_nll), dinfo};
         const dim3 grid((npts + MT - 1) / MT, (npts + MJ - 1) / MJ, nb);
+        if (d) {
+            const MidNdArgs an{npts, n, npad, reinterpret_cast<double *>(din + o_x), reinterpret_cast<nd::NdConst *>(din + o_kc),
+                               reinterpret_cast<double *>(din + o_no), dA};
+            if ((rc = nd::dispatch_nd(family, d, [&](auto fam, auto dd) {
+                    hipLaunchKernelGGL((mid_build_nd_kernel<decltype(fam)::value, decltype(dd)::value>), grid, dim3(MT), 0, st, an);
+                    return 0;
+                })))
+                return rc;
+        } else
         switch (family) {
         case SGPR_FAM_A: hipLaunchKernelGGL(mid_build_kernel<SGPR_FAM_A>, grid, dim3(MT), 0, st, a); break;
         case SGPR_FAM_B: hipLaunchKernelGGL(mid_build_kernel<SGPR_FAM_B>, grid, dim3(MT), 0, st, a); break;
@@ -1208,6 +1347,67 @@ int fit_batch(int family, int nbatch, int npts, const double *x, const double *y
     if (family < SGPR_FAM_A || family > SGPR_FAM_USER) { set_error("fit_batch: unknown kernel family"); return SGPR_E_ARG; }
     if (n > BMAX) return fit_batch_mid(family, nbatch, npts, n, reg, x, y, z, hyp, nhyp, sig2n, alpha, nll, info);
     return fit_batch_small(family, nbatch, npts, n, reg, x, y, z, hyp, nhyp, sig2n, alpha, nll, info, nullptr);
+}
+
+namespace {
+
+// sgpr_fit_batch_nd, orders n = 2 d npts <= BMAX: one launch of fit_batch_nd_kernel, one workgroup per problem; the staging of
+// fit_batch_small with X in place of x | y and one NdConst per problem
+int fit_batch_nd_small(int family, int d, int nbatch, int npts, int n, const double *X, const double *z, const double *hyp, int nhyp,
+                       const double *sig2n, double *alpha, double *nll, int *info)
+{
+    const size_t B = (size_t)nbatch;
+    const int grid = nbatch < 1024 ? nbatch : 1024;
+    // input block (one H2D): X | z | NdConst | noise ; output block (one D2H): alpha | nll | info
+    const size_t o_x = 0, o_z = o_x + up256(B * n * 8), o_nc = o_z + up256(B * n * 8), o_no = o_nc + up256(B * sizeof(nd::NdConst)),
+                 in_bytes = o_no + up256(B * 8);
+    const size_t o_al = 0, o_nll = o_al + up256(B * n * 8), o_info = o_nll + up256(B * 8), out_bytes = o_info + up256(B * sizeof(int));
+    const size_t scr_bytes = (size_t)grid * PER_WG * 8;
+    Arena &ar = t_arena;
+    int rc = ar.reserve(in_bytes + out_bytes + scr_bytes, in_bytes + out_bytes);
+    if (rc) return rc;
+    char *hin = ar.host, *hout = ar.host + in_bytes;
+    char *din = ar.dev, *dout = ar.dev + in_bytes, *dscr = ar.dev + in_bytes + out_bytes;
+    memcpy(hin + o_x, X, B * n * 8);           // 2 d npts = n doubles per problem
+    memcpy(hin + o_z, z, B * n * 8);
+    nd::NdConst *ncs = reinterpret_cast<nd::NdConst *>(hin + o_nc);
+    double *noise = reinterpret_cast<double *>(hin + o_no);
+    for (int b = 0; b < nbatch; ++b) {
+        if ((rc = nd::fill_consts(family, d, hyp + (size_t)b * nhyp, nhyp, ncs[b]))) return rc;
+        noise[b] = std::fabs(sig2n[b]);
+    }
+    hipStream_t st = nullptr;
+    SGPR_HIP(hipMemcpyAsync(din, hin, in_bytes, hipMemcpyHostToDevice, st));
+    SGPR_HIP(hipMemsetAsync(dout + o_info, 0, B * sizeof(int), st));
+    const BatchNdArgs a{nbatch, npts, n, reinterpret_cast<double *>(din + o_x), reinterpret_cast<double *>(din + o_z),
+                        reinterpret_cast<nd::NdConst *>(din + o_nc), reinterpret_cast<double *>(din + o_no),
+                        reinterpret_cast<double *>(dscr), alpha ? reinterpret_cast<double *>(dout + o_al) : nullptr,
+                        reinterpret_cast<double *>(dout + o_nll), reinterpret_cast<int *>(dout + o_info)};
+    if ((rc = nd::dispatch_nd(family, d, [&](auto fam, auto dd) {
+            hipLaunchKernelGGL((fit_batch_nd_kernel<decltype(fam)::value, decltype(dd)::value>), dim3(grid), dim3(LT), 0, st, a);
+            return 0;
+        })))
+        return rc;
+    SGPR_CHECK_LAUNCH();
+    const size_t from = alpha ? 0 : o_nll;     // without alpha only the tail of the output block comes back
+    SGPR_HIP(hipMemcpyAsync(hout + from, dout + from, out_bytes - from, hipMemcpyDeviceToHost, st));
+    SGPR_HIP(hipStreamSynchronize(st));
+    if (alpha) memcpy(alpha, hout + o_al, B * n * 8);
+    memcpy(nll, hout + o_nll, B * 8);
+    memcpy(info, hout + o_info, B * sizeof(int));
+    return 0;
+}
+
+}  // namespace
+
+// sgpr_fit_batch_nd: the arguments have been checked (capi.hip), nbatch > 0, n = 2 d npts <= fit_batch_max_order()
+int fit_batch_nd(int family, int d, int nbatch, int npts, const double *X, const double *z, const double *hyp, int nhyp,
+                 const double *sig2n, double *alpha, double *nll, int *info)
+{
+    const int n = 2 * d * npts;
+    if (n > BMAX)
+        return fit_batch_mid(family, nbatch, npts, n, 0, nullptr, nullptr, z, hyp, nhyp, sig2n, alpha, nll, info, nullptr, nullptr, d, X);
+    return fit_batch_nd_small(family, d, nbatch, npts, n, X, z, hyp, nhyp, sig2n, alpha, nll, info);
 }
 
 int fit_batch_grad_max_order() { return BMAX; }

@@ -315,6 +315,30 @@ int sgpr_fit_batch(int family, int nbatch, int n_pts, const double *x, const dou
     return fit_batch(family, nbatch, n_pts, x, y, z, hyp, nhyp, sig2n, flags, alpha, nll, info);
 }
 
+/* sgpr_fit_batch for problems with d canonical pairs per point (batch.hip: fit_batch_nd_kernel up to order 256, fit_batch_mid
+ * with mid_build_nd_kernel above).  Checked like sgpr_fit_batch_grad, before any device call. */
+int sgpr_fit_batch_nd(int family, int d, int nbatch, int n_pts, const double *X, const double *z, const double *hyp, int nhyp,
+                      const double *sig2n, unsigned flags, double *alpha, double *nll, int *info)
+{
+    auto E = [](const std::string &what) { set_error("fit_batch_nd: " + what); return SGPR_E_ARG; };
+    if (d < 1 || d > 3) return E("d must be 1, 2 or 3");
+    if (family < SGPR_FAM_A || family > SGPR_FAM_USER) return E("unknown kernel family");
+    const int need = family_has_p(family) ? 3 * d + 1 : 2 * d + 1;
+    if (nhyp != need) return E("nhyp must be " + std::to_string(need) + " for this family and d");
+    if (flags) return E("flags must be 0 (there is no scalar-kernel d-pair fit)");
+    if (nbatch < 0) return E("nbatch < 0");
+    if (n_pts <= 0) return E("n_pts <= 0");
+    const long n = 2L * d * n_pts;
+    const int nmax = fit_batch_max_order();
+    if (n > nmax) return E("order per problem " + std::to_string(n) + " exceeds " + std::to_string(nmax));
+    if (!nll || !info) return E("null nll or info");
+    if (!X || !z || !hyp || !sig2n) return E("null input");
+    if (nbatch == 0) return 0;
+    int rc = need_device();
+    if (rc) return rc;
+    return fit_batch_nd(family, d, nbatch, n_pts, X, z, hyp, nhyp, sig2n, alpha, nll, info);
+}
+
 /* sgpr_fit_batch plus the gradient of every problem's nll (batch.hip: fit_batch_kernel<FAM, true>).  The arguments are checked
  * before any device call: an argument error is SGPR_E_ARG on any machine, the message names the entry. */
 int sgpr_fit_batch_grad(int family, int nbatch, int n_pts, const double *x, const double *y, const double *z,

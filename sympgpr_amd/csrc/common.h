@@ -287,6 +287,10 @@ int fit_batch_trim();                            // release the calling thread's
 int potrf_trim();                                // ... and its pooled events
 int fit_batch(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
               int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, int *info);
+// the fit for problems with d canonical pairs per point (X: nbatch x 2d x npts), n = 2 d npts <= fit_batch_max_order(); the
+// arguments have been checked (capi.hip), nbatch > 0
+int fit_batch_nd(int family, int d, int nbatch, int npts, const double *X, const double *z, const double *hyp, int nhyp,
+                 const double *sig2n, double *alpha, double *nll, int *info);
 int fit_batch_grad_max_order();                  // 256: one workgroup holds the whole problem
 int fit_batch_grad(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
                    int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, double *grad, int *info);

@@ -14,14 +14,18 @@
 #include "common.h"
 #include "devmath.h"
 #include "generated/pair_generated.h"
+#include "nd_eval.h"
 
 namespace sgpr {
 
 namespace {
 
+using namespace nd;         // coord, all_coords, weights, is_sum, NdConst, fill_consts, dispatch_nd
+
 constexpr int NT = 256, NTI = 2 * NT, NTJ = 16;
 typedef double double2_t __attribute__((ext_vector_type(2)));
 
+// the geometry of one call and, last, the constants of the fit (nd_eval.h)
 struct NdArgs {
     int mi, mj;
     const double *Xb, *Xa;   // row points (mi x D), column points (mj x D), column-major
@@ -31,66 +35,9 @@ struct NdArgs {
     int sel;                       // 1: block (a, b) goes to K + roff[a] + coff[b] * ld instead, skipped when either is < 0
     long roff[6], coff[6];
     long diag_off;
-    double noise, sig;
-    double l[6], l2[6], inv_l2[6], inv_l4[6];
-    double hs[6];            // periodic coordinates: sin(hs (x - x')), hs = 1/2 (A, B) or p_m (D)
+    double noise;
+    NdConst c;
 };
-
-// per coordinate: exponent of f_m, g = f'/f, nh = -f''/f
-template <int FAM, int D, int M>
-__device__ __forceinline__ void coord(const NdArgs &a, double dx, double &arg, double &g, double &nh)
-{
-    if constexpr (FAM == SGPR_FAM_USER) {
-        // the user's kernel: its generated factor forms (tools/gen_kernels.py), the q's with hs = p_m when it has one
-        double o[3];
-        if constexpr (M < D / 2) gen::factor<SGPR_FAM_USER, 1>(dx, a.l[M], a.hs[M], o);
-        else                     gen::factor<SGPR_FAM_USER, 0>(dx, a.l[M], 0.0, o);
-        arg = o[0]; g = o[1]; nh = o[2];
-    } else if constexpr (FAM != SGPR_FAM_C && M < D / 2) {
-        double s, c;
-        const double h = a.hs[M] * dx;
-        sincos_fast(h, s, c);
-        const double s2 = s * s, sc = s * c;
-        arg = -0.5 * a.inv_l2[M] * s2;
-        g = -a.hs[M] * sc * a.inv_l2[M];
-        nh = (a.hs[M] * a.hs[M]) * (a.l2[M] * cos2h_sel<false>(h, s2, a.l2[M]) - sc * sc) * a.inv_l4[M];   // devmath.h
-    } else {
-        const double d2 = dx * dx;
-        arg = -0.5 * a.inv_l2[M] * d2;
-        g = -dx * a.inv_l2[M];
-        nh = (a.l2[M] - d2) * a.inv_l4[M];
-    }
-}
-
-template <int FAM, int D, int M = 0>
-__device__ __forceinline__ void all_coords(const NdArgs &a, const double *xa, const double (&xb)[D],
-                                           double (&arg)[D], double (&g)[D], double (&nh)[D])
-{
-    if constexpr (M < D) {
-        coord<FAM, D, M>(a, xa[M] - xb[M], arg[M], g[M], nh[M]);
-        all_coords<FAM, D, M + 1>(a, xa, xb, arg, g, nh);
-    }
-}
-
-// E[m]: the factor that multiplies nh[m] on the diagonal blocks -- sig k for the product kernels (one exp
-// per pair), sig f_m for the sum kernel (one exp per coordinate)
-template <int FAM> constexpr bool is_sum() { return FAM == SGPR_FAM_B || (FAM == SGPR_FAM_USER && gen::user_is_sum); }
-
-template <int FAM, int D>
-__device__ __forceinline__ void weights(const NdArgs &a, const double (&arg)[D], double (&E)[D])
-{
-    if constexpr (is_sum<FAM>()) {
-#pragma unroll
-        for (int m = 0; m < D; ++m) E[m] = a.sig * exp_fast(arg[m]);
-    } else {
-        double t = 0.0;
-#pragma unroll
-        for (int m = 0; m < D; ++m) t += arg[m];
-        const double e = a.sig * exp_fast(t);
-#pragma unroll
-        for (int m = 0; m < D; ++m) E[m] = e;
-    }
-}
 
 template <int FAM, int D>
 __global__ __launch_bounds__(NT) void gram_nd_kernel(const NdArgs a)
@@ -118,10 +65,10 @@ __global__ __launch_bounds__(NT) void gram_nd_kernel(const NdArgs a)
     const long d0 = (long)i + a.diag_off;
     for (int jj = 0; jj < nj; ++jj) {
         double g0[D], nh0[D], g1[D], nh1[D], arg0[D], arg1[D], E0[D], E1[D];
-        all_coords<FAM, D>(a, sxa[jj], xb0, arg0, g0, nh0);
-        all_coords<FAM, D>(a, sxa[jj], xb1, arg1, g1, nh1);
-        weights<FAM, D>(a, arg0, E0);
-        weights<FAM, D>(a, arg1, E1);
+        all_coords<FAM, D>(a.c, sxa[jj], xb0, arg0, g0, nh0);
+        all_coords<FAM, D>(a.c, sxa[jj], xb1, arg1, g1, nh1);
+        weights<FAM, D>(a.c, arg0, E0);
+        weights<FAM, D>(a.c, arg1, E1);
         const long j = j0 + jj;
         const double n0 = (d0 == j) ? a.noise : 0.0, n1 = (d0 + 1 == j) ? a.noise : 0.0;
 #pragma unroll
@@ -159,8 +106,8 @@ __global__ __launch_bounds__(NT) void predict_nd_kernel(const NdArgs a, int m, c
         double xa[D], g[D], nh[D], arg[D], E[D];
 #pragma unroll
         for (int c = 0; c < D; ++c) xa[c] = a.Xa[(size_t)j + (size_t)c * a.ldxa];
-        all_coords<FAM, D>(a, xa, xb, arg, g, nh);
-        weights<FAM, D>(a, arg, E);
+        all_coords<FAM, D>(a.c, xa, xb, arg, g, nh);
+        weights<FAM, D>(a.c, arg, E);
         double al[D], S = 0.0;
 #pragma unroll
         for (int c = 0; c < D; ++c) { al[c] = alpha[(size_t)c * a.mj + j]; S = __builtin_fma(g[c], al[c], S); }
@@ -185,40 +132,8 @@ __global__ __launch_bounds__(NT) void predict_nd_kernel(const NdArgs a, int m, c
     }
 }
 
-int fill_args(int family, int d, const double *hyp, int nhyp, NdArgs &a)
-{
-    if (d < 1 || d > 3) { set_error("d must be 1, 2 or 3"); return SGPR_E_ARG; }
-    if (family < SGPR_FAM_A || family > SGPR_FAM_USER) { set_error("unknown kernel family"); return SGPR_E_ARG; }
-    const bool has_p = family_has_p(family);
-    const int need = has_p ? 3 * d + 1 : 2 * d + 1;
-    if (!hyp || nhyp != need) {
-        set_error("hyp must hold (lq_1..lq_d, lP_1..lP_d, sig) -- (lq.., lP.., p_1..p_d, sig) for family D");
-        return SGPR_E_ARG;
-    }
-    for (int m = 0; m < 2 * d; ++m) {
-        a.l[m] = hyp[m];
-        a.l2[m] = hyp[m] * hyp[m];
-        a.inv_l2[m] = 1.0 / a.l2[m];
-        a.inv_l4[m] = a.inv_l2[m] * a.inv_l2[m];
-        a.hs[m] = (has_p && m < d) ? hyp[2 * d + m] : 0.5;
-    }
-    a.sig = hyp[nhyp - 1];
-    return 0;
-}
-
-template <typename F>
-int dispatch_nd(int family, int d, F &&f)
-{
-#define SGPR_ND_CASE(FAMV, DV) if (family == FAMV && d == DV) return f(std::integral_constant<int, FAMV>(), std::integral_constant<int, 2 * DV>())
-    SGPR_ND_CASE(SGPR_FAM_A, 1); SGPR_ND_CASE(SGPR_FAM_A, 2); SGPR_ND_CASE(SGPR_FAM_A, 3);
-    SGPR_ND_CASE(SGPR_FAM_C, 1); SGPR_ND_CASE(SGPR_FAM_C, 2); SGPR_ND_CASE(SGPR_FAM_C, 3);
-    SGPR_ND_CASE(SGPR_FAM_B, 1); SGPR_ND_CASE(SGPR_FAM_B, 2); SGPR_ND_CASE(SGPR_FAM_B, 3);
-    SGPR_ND_CASE(SGPR_FAM_D, 1); SGPR_ND_CASE(SGPR_FAM_D, 2); SGPR_ND_CASE(SGPR_FAM_D, 3);
-    SGPR_ND_CASE(SGPR_FAM_USER, 1); SGPR_ND_CASE(SGPR_FAM_USER, 2); SGPR_ND_CASE(SGPR_FAM_USER, 3);
-#undef SGPR_ND_CASE
-    set_error("unsupported (family, d)");
-    return SGPR_E_ARG;
-}
+// the hyper-parameters of the call into the constants of its argument block (nd_eval.h)
+int fill_args(int family, int d, const double *hyp, int nhyp, NdArgs &a) { return fill_consts(family, d, hyp, nhyp, a.c); }
 
 // ---- applymap_nd: the symplectic map of a d-pair fit, every step of one orbit inside one workgroup ------------------------
 // x = (q_1..q_d, P_1..P_d), G(x) = K*(x) alpha as predict_nd_kernel forms it: G_q = dF/dq = p - P, G_P = dF/dP = Q - q.  One step
@@ -300,8 +215,8 @@ __device__ __forceinline__ void mapnd_pass(const MapNdArgs &a, const double (&x)
 #pragma unroll
             for (int c = 0; c < D; ++c) { xa[c] = a.k.Xa[(size_t)j + (size_t)c * a.k.ldxa]; al[c] = a.alpha[(size_t)c * n0 + j]; }
         }
-        all_coords<FAM, D>(a.k, xa, x, arg, g, nh);
-        weights<FAM, D>(a.k, arg, E);
+        all_coords<FAM, D>(a.k.c, xa, x, arg, g, nh);
+        weights<FAM, D>(a.k.c, arg, E);
         double S = 0.0;
 #pragma unroll
         for (int c = 0; c < D; ++c) S = __builtin_fma(g[c], al[c], S);
@@ -509,8 +424,8 @@ template <int FAM, int D>
 __device__ __forceinline__ void genfun_pair(const NdArgs &a, const double *xa, const double (&xb)[D], double (&v)[D], double &kap)
 {
     double arg[D], g[D], nh[D], E[D];
-    all_coords<FAM, D>(a, xa, xb, arg, g, nh);
-    weights<FAM, D>(a, arg, E);
+    all_coords<FAM, D>(a.c, xa, xb, arg, g, nh);
+    weights<FAM, D>(a.c, arg, E);
     kap = E[0];
     if constexpr (is_sum<FAM>()) {
 #pragma unroll

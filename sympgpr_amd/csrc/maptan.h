@@ -40,9 +40,9 @@ __device__ __forceinline__ double coord_th(const NdArgs &a, double dx, double g,
 {
     constexpr int Q = M < D / 2 ? 1 : 0;
     if constexpr (FAM == SGPR_FAM_USER || MAPTAN_GEN_TH) {
-        return gen::factor3<FAM, Q>(dx, a.l[M], Q ? a.hs[M] : 0.0);
+        return gen::factor3<FAM, Q>(dx, a.c.l[M], Q ? a.c.hs[M] : 0.0);
     } else if constexpr (FAM != SGPR_FAM_C && Q) {
-        return -g * __builtin_fma(4.0 * a.hs[M], a.hs[M], __builtin_fma(2.0 * g, g, 3.0 * nh));
+        return -g * __builtin_fma(4.0 * a.c.hs[M], a.c.hs[M], __builtin_fma(2.0 * g, g, 3.0 * nh));
     } else {
         return -g * __builtin_fma(2.0 * g, g, 3.0 * nh);
     }
@@ -88,8 +88,8 @@ __device__ __forceinline__ void maptan_hess_pass(const MapNdArgs &a, const doubl
 #pragma unroll
             for (int c = 0; c < D; ++c) { xa[c] = a.k.Xa[(size_t)j + (size_t)c * a.k.ldxa]; al[c] = a.alpha[(size_t)c * n0 + j]; }
         }
-        all_coords<FAM, D>(a.k, xa, x, arg, g, nh);
-        weights<FAM, D>(a.k, arg, E);
+        all_coords<FAM, D>(a.k.c, xa, x, arg, g, nh);
+        weights<FAM, D>(a.k.c, arg, E);
         all_th<FAM, D>(a.k, xa, x, g, nh, th);
         if constexpr (SUM) {
 #pragma unroll

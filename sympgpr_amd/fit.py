@@ -418,6 +418,46 @@ def fit_batch(family, x, y, z, hyp, sig2n, reg=False, want_alpha=True):
     return alpha, nll, info
 
 
+def fit_batch_pairs(family, X, z, hyp, sig2n, want_alpha=True):
+    """fit_batch for problems with d canonical pairs per point (SympFit.pairs' kernels and layouts), every order
+    n = 2 d n_pts up to batch_max_order(): one launch up to order 256, the mid path above it.
+        X (B, n_pts, 2d), columns (q_1..q_d, P_1..P_d) -- or (n_pts, 2d), broadcast over the rows of hyp: one data set,
+        a population of hyper-parameters;  z (B, n) or (n,), block by block like the rows of K;
+        hyp (B, nhyp), rows as SympFit.pairs takes them;  sig2n (B,) or scalar.
+    -> (alpha (B, n) or None, nll (B,), info (B,)): info[b] > 0 where Ky_b is not positive definite (nll[b] is NaN there)."""
+    X = np.asarray(X, dtype=np.float64)
+    z = np.asarray(z, dtype=np.float64)
+    hyp = np.asarray(hyp, dtype=np.float64)
+    if hyp.ndim != 2:
+        raise ValueError("fit_batch_pairs: hyp (B, nhyp)")
+    B = hyp.shape[0]
+    if X.ndim == 2:
+        X = np.broadcast_to(X, (B,) + X.shape)
+    if X.ndim != 3 or X.shape[0] != B or X.shape[2] % 2 or X.shape[2] == 0:
+        raise ValueError("fit_batch_pairs: X (B, n_pts, 2d) or (n_pts, 2d), B the rows of hyp")
+    n_pts, D = X.shape[1], X.shape[2]
+    n = D * n_pts
+    if z.ndim == 1:
+        z = np.broadcast_to(z, (B,) + z.shape)
+    if z.shape != (B, n):
+        raise ValueError("fit_batch_pairs: z (B, n) or (n,), n = 2 d n_pts")
+    if np.ndim(sig2n) > 1 or (np.ndim(sig2n) == 1 and np.shape(sig2n) != (B,)):
+        raise ValueError("fit_batch_pairs: sig2n scalar or (B,)")
+    # the library's layout: coordinate m of point i of problem b at (b 2d + m) n_pts + i
+    Xl = np.ascontiguousarray(np.swapaxes(X, 1, 2))
+    z = np.ascontiguousarray(z)
+    hyp = np.ascontiguousarray(hyp)
+    s2 = np.ascontiguousarray(np.broadcast_to(np.asarray(sig2n, dtype=np.float64), (B,)))
+    alpha = np.empty((B, n)) if want_alpha else None
+    nll = np.empty(B)
+    info = np.zeros(B, dtype=np.int32)
+    L.check(L.load_library().sgpr_fit_batch_nd(L.family_id(family), D // 2, B, n_pts, L.dptr(Xl), L.dptr(z), L.dptr(hyp),
+                                               hyp.shape[1], L.dptr(s2), 0, L.dptr(alpha) if want_alpha else None,
+                                               L.dptr(nll), info.ctypes.data_as(C.POINTER(C.c_int))), "sgpr_fit_batch_nd")
+    nll[info != 0] = np.nan
+    return alpha, nll, info
+
+
 def batch_grad_max_order():
     """largest matrix order per problem sgpr_fit_batch_grad takes on the device (256)"""
     return 256

@@ -155,6 +155,50 @@ def nll_chol_batch(hyps, x, y, N, reg=False):
     return nll
 
 
+def nll_chol_pairs_batch(hyps, X, z):
+    """nll_chol_batch for a fit with d canonical pairs per point: the negative log-posterior of SympFit.pairs(family, X, z, ...)
+    for a whole POPULATION of hyper-parameter vectors over one data set.  X (n_pts, 2d), columns (q_1..q_d, P_1..P_d); z the
+    2 d n_pts targets, block by block; hyps (B, nhyp + 1), rows (lq_1..lq_d, lP_1..lP_d, [p_1..p_d,] sig, sig2_n) -- the
+    d-pair counterpart of nll_chol's hyp.  Up to order fit.batch_max_order() (2048) one batched call (fit.fit_batch_pairs);
+    above it a loop over ONE device-resident handle (set_hyp / run).  Rows whose Ky is not positive definite come back
+    as +inf."""
+    from .fit import batch_max_order, fit_batch_pairs
+    hyps = np.atleast_2d(np.asarray(hyps, dtype=np.float64))
+    X = np.asarray(X, dtype=np.float64)
+    z = np.asarray(z, dtype=np.float64)
+    if X.ndim != 2 or X.shape[1] % 2 or X.shape[1] == 0:
+        raise ValueError("nll_chol_pairs: X must be (n_pts, 2d)")
+    n = X.shape[0] * X.shape[1]
+    if z.shape != (n,):
+        raise ValueError("nll_chol_pairs: z must have length %d" % n)
+    if hyps.shape[1] < 2:
+        raise ValueError("nll_chol_pairs: rows (lq.., lP.., [p..,] sig, sig2_n)")
+    if n <= batch_max_order():
+        _, nll, info = fit_batch_pairs(get_family(), X, z, hyps[:, :-1], np.abs(hyps[:, -1]), want_alpha=False)
+        nll[info != 0] = np.inf
+        return nll
+    out = np.empty(len(hyps))
+    if len(hyps) == 0:
+        return out
+    with SympFit.pairs(get_family(), X, z, hyps[0, :-1], np.abs(hyps[0, -1])) as f:
+        for b, h in enumerate(hyps):
+            try:
+                f.set_hyp(h[:-1], np.abs(h[-1]))
+                out[b] = f.run().nll()
+            except np.linalg.LinAlgError:
+                out[b] = np.inf
+    return out
+
+
+def nll_chol_pairs(hyp, X, z):
+    """nll_chol for a fit with d canonical pairs per point: one row of nll_chol_pairs_batch (+inf where Ky is not positive
+    definite) -- the objective of an optimiser over (lq.., lP.., [p..,] sig, sig2_n)."""
+    hyp = np.asarray(hyp, dtype=np.float64)
+    if hyp.ndim != 1:
+        raise ValueError("nll_chol_pairs: hyp is one row (lq.., lP.., [p..,] sig, sig2_n)")
+    return float(nll_chol_pairs_batch(hyp[None], X, z)[0])
+
+
 def _batch_data(x, y, N, reg):
     npts = N if reg else N // 2
     return x[0:npts], x[npts:2 * npts], y[:N if reg else 2 * npts]
