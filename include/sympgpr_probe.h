@@ -130,6 +130,15 @@ int sgpr_probe_strassen_rec_plan(int m, int n, int k, int lower, long scratch_do
 int sgpr_probe_strassen_rec_scratch(int n, unsigned long long out[2]);
 int sgpr_probe_gemm_strassen_rec_dev(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb,
                                      double beta, double *C, size_t ldc, int lower, void *stream);
+/* The arena layout of a batched fit as the drivers compute it (csrc/batch.hip: batch_layout), without a device call.  path: 0 the
+ * one-launch path (order <= 256), 1 the mid path (256 < order <= 2048); mode: 0 fit, 1 nll gradient, 2 loo, 3 loo gradient (path 0
+ * only); d: 0 for sgpr_fit_batch's x | y, 1 .. 3 for sgpr_fit_batch_nd (mode 0, reg 0).  The tunable batch_gradmid_chunk applies.
+ * out: [0] problems per chunk, [1] doubles behind nll per problem; byte offsets [2 .. 6] x, y, z, consts, noise of the input block
+ * and [7] its size; [8 .. 10] alpha, nll, info of the output block and [11] its size; [12 .. 19] the mid path's scratch regions L / U
+ * images, leaf inverses, flags of panel 1, of panel 2, solve vectors, publication buffers, state words, partials (0 on path 0) and
+ * [20] the scratch size; [21] sizeof KConst, [22] sizeof NdConst, [23] the flag bytes of one panel for a chunk (0 on path 0).
+ * tests/test_batch_layout_cpu.py checks it against the formulas. */
+int sgpr_probe_batch_layout(int path, int mode, int d, int reg, int nbatch, int n_pts, int nhyp, unsigned long long out[24]);
 unsigned sgpr_probe_map_calls(void);
 int sgpr_probe_map_team(int ntest, int n0);
 

@@ -190,6 +190,8 @@ PROBE_SIGNATURES = {
                                                    C.c_double, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     "sgpr_probe_gemm_nt4_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_double, C.c_int,
                                           C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_double), C.c_void_p]),
+    "sgpr_probe_batch_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.POINTER(C.c_ulonglong)]),
     "sgpr_probe_census": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint), C.c_int,
                                     C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint), C.c_int,
                                     C.POINTER(C.c_ulonglong)]),

@@ -1,0 +1,423 @@
+// batch_mid.h -- device code of the batched fits of order 256 < n <= 2048: build, the rank-k update between two panels, the
+// solves' ends, and the Ky^-1, gradient and leave-one-point-out phases.  Included only by batch.hip, behind batch_small.h.
+#pragma once
+
+namespace sgpr {
+
+namespace {
+
+// ---- mid-size problems: 256 < n <= 2048 (a CMA-ES generation at N = 512 ... 1024 points) --------------------------
+// Three launches for the whole batch: (1) every Ky_b, lower triangle, into an npad x npad image (npad = n rounded up to
+// 128; the padding is an identity block: det 1, alpha 0 there); (2) chol.hip's panel_batch_kernel: W = npad / 128
+// workgroups per problem run the leaf chain on their own matrix, problems side by side; (3) one workgroup per problem:
+// y = L^-1 z and alpha = L^-T y through the leaf inverses, and the negative log-likelihood.
+constexpr int MT = 256;                   // build: pair rows per tile (one per thread)
+constexpr int MJ = 16;                    // build: pair columns per tile
+constexpr int ST = 512;                   // solve: threads per problem
+
+struct MidArgs {
+    int nbatch, npts, n, npad, reg;
+    const double *x, *y, *z;              // nbatch x npts, nbatch x npts, nbatch x n
+    const KConst *kc;
+    const double *noise;
+    double *A;                            // problem b at A + b * npad * npad, ld = npad
+    const double *inv;                    // leaf inverses: problem b at inv + b * (npad / 128) * 128 * 128
+    double *alpha, *nll;
+    const int *info;
+};
+
+template <int FAM>
+__global__ __launch_bounds__(MT) void mid_build_kernel(const MidArgs a)
+{
+    __shared__ double sx[MJ], sy[MJ];
+    const int b = blockIdx.z, N = a.npts, t = threadIdx.x;
+    const int i0 = blockIdx.x * MT, j0 = blockIdx.y * MJ;
+    const size_t ld = (size_t)a.npad;
+    double *A = a.A + (size_t)b * ld * ld;
+    if (blockIdx.x == 0 && blockIdx.y == 0)
+        for (int r = a.n + t; r < a.npad; r += MT) A[r + r * ld] = 1.0;     // the padding's diagonal (the rest was cleared)
+    const bool tile_lower = i0 + MT - 1 >= j0;        // some (i, j) of the tile has i >= j
+    if (a.reg && !tile_lower) return;
+    const double *x = a.x + (size_t)b * N, *y = a.y + (size_t)b * N;
+    const int nj = min(MJ, N - j0);
+    if (t < nj) { sx[t] = x[j0 + t]; sy[t] = y[j0 + t]; }
+    __syncthreads();
+    const int i = i0 + t;
+    if (i >= N) return;
+    const KConst kc = a.kc[b];
+    const double noise = a.noise[b];
+    const double xi = x[i], yi = y[i];
+    if (a.reg) {
+        for (int jj = 0; jj < nj; ++jj) {
+            const int j = j0 + jj;
+            if (i < j) break;
+            double k = kc.sig * kern_eval<FAM, false>(sx[jj], sy[jj], xi, yi, kc);
+            if (i == j) k += noise;
+            A[i + j * ld] = k;
+        }
+        return;
+    }
+    for (int jj = 0; jj < nj; ++jj) {
+        const int j = j0 + jj;
+        double kxx, kxy, kyy;
+        pair_eval<FAM, false>(sx[jj], sy[jj], xi, yi, kc, kxx, kxy, kyy);
+        if (i == j) { kxx += noise; kyy += noise; }
+        A[(N + i) + j * ld] = kxy;                     // Pq block: always below the diagonal
+        if (i >= j) {
+            A[i + j * ld] = kxx;
+            A[(N + i) + (N + j) * ld] = kyy;
+        }
+    }
+}
+
+// The build for d canonical pairs per point (D = 2 d, n = D N): mid_build_kernel's tiling -- MT point rows per workgroup, one per
+// thread, MJ point columns in LDS, now D coordinates each, blockIdx.z the problem -- and fit_batch_nd_kernel's entries and
+// lower-triangle rule (store_pair_lower) at ld = npad.
+struct MidNdArgs {
+    int npts, n, npad;
+    const double *X;                      // nbatch x D x npts
+    const nd::NdConst *nc;
+    const double *noise;
+    double *A;                            // problem b at A + b * npad * npad, ld = npad
+};
+
+template <int FAM, int D>
+__global__ __launch_bounds__(MT) void mid_build_nd_kernel(const MidNdArgs a)
+{
+    __shared__ double sxa[MJ][D];
+    const int b = blockIdx.z, N = a.npts, t = threadIdx.x;
+    const int i0 = blockIdx.x * MT, j0 = blockIdx.y * MJ;
+    const size_t ld = (size_t)a.npad;
+    double *A = a.A + (size_t)b * ld * ld;
+    if (blockIdx.x == 0 && blockIdx.y == 0)
+        for (int r = a.n + t; r < a.npad; r += MT) A[r + r * ld] = 1.0;     // the padding's diagonal (the rest was cleared)
+    const double *X = a.X + (size_t)b * D * N;
+    const int nj = min(MJ, N - j0);
+    for (int e = t; e < nj * D; e += MT) sxa[e / D][e % D] = X[(size_t)(e % D) * N + j0 + e / D];
+    __syncthreads();
+    const int i = i0 + t;
+    if (i >= N) return;
+    const nd::NdConst nc = a.nc[b];
+    const double noise = a.noise[b];
+    double xb[D];
+#pragma unroll
+    for (int m = 0; m < D; ++m) xb[m] = X[(size_t)m * N + i];
+    for (int jj = 0; jj < nj; ++jj) {
+        const int j = j0 + jj;
+        double arg[D], g[D], nh[D], E[D];
+        nd::all_coords<FAM, D>(nc, sxa[jj], xb, arg, g, nh);
+        nd::weights<FAM, D>(nc, arg, E);
+        store_pair_lower<FAM, D>(A + i + (size_t)j * ld, ld, N, i >= j, i == j, noise, E, g, nh);
+    }
+}
+
+// Above order 1024 a problem is factored as two panels; between them, for every problem, the rank-k update of the block that
+// is left: A22 -= L21 L21^T (lower tiles only), 128 x 128 tiles of the grid-wide MFMA kernel's LDS-DMA body (gemm_tile.h).
+struct MidSyrk {
+    double *A;            // problem b at A + b * stride (column-major, ld)
+    size_t stride, ld;
+    int k, m2;            // width of the first panel; order of the block behind it (multiples of 128)
+};
+
+__global__ __launch_bounds__(256, 2) void mid_syrk_kernel(const MidSyrk a)
+{
+    __shared__ double smem[2 * tile::BK * (2 * (128 + tile::PAD))];
+    int t = (int)blockIdx.x, r = 0;            // lower tiles row by row: row r holds r + 1 of them
+    while (t > r) { t -= r + 1; ++r; }
+    double *base = a.A + (size_t)blockIdx.y * a.stride;
+    tile::GemmArgs g{};
+    g.m = a.m2; g.n = a.m2; g.k = a.k;
+    g.alpha = -1.0; g.beta = 1.0;
+    g.A = base + a.k; g.lda = a.ld;
+    g.B = base + a.k; g.ldb = a.ld;
+    g.C = base + a.k + (size_t)a.k * a.ld; g.ldc = a.ld;
+    tile::gemm_body_dma<128, 128, 2>(g, smem, r, t);
+}
+
+__device__ __forceinline__ double wave_sum(double v)
+{
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;      // lane 0 holds the sum
+}
+
+// The solves of the batch: the right-hand sides padded to npad ...
+__global__ __launch_bounds__(256) void mid_rhs_kernel(const MidArgs a, double *r)
+{
+    const int b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i < a.npad) r[(size_t)b * a.npad + i] = i < a.n ? a.z[(size_t)b * a.n + i] : 0.0;
+}
+// ... two launches of trsv.hip's strip solve over all problems (one workgroup per 128-row strip and problem, W x nbatch of
+// them; round 3 ran both solves of a problem in ONE workgroup: 64 problems of order 1024 kept 64 CUs busy for 0.6 ms, a third
+// of the whole call) ... and, per problem, nll = z.alpha / 2 + sum log L_ii (func.py:195) and alpha.
+__global__ __launch_bounds__(ST) void mid_finish_kernel(const MidArgs a, const double *r, const int *state, int *info)
+{
+    __shared__ double red[ST / 64];
+    const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int n = a.n;
+    const size_t ld = (size_t)a.npad;
+    const double *A = a.A + (size_t)b * ld * ld;
+    const double *z = a.z + (size_t)b * n;
+    const double *al = r + (size_t)b * ld;
+    // a strip solve that gave up on a hand-off (state word 2 of either pass): an error of the call, not a result
+    if (a.info[b] == 0 && (state[8 * b + 2] | state[8 * b + 6]) != 0) {
+        if (t == 0) { info[b] = SOLVE_HANDOFF_TIMEOUT; a.nll[b] = __builtin_nan(""); }
+        return;
+    }
+    if (a.info[b] != 0) {                  // not positive definite: the host turns info into NaN / +inf
+        if (t == 0) a.nll[b] = __builtin_nan("");
+        if (a.alpha)
+            for (int i = t; i < n; i += ST) a.alpha[(size_t)b * n + i] = __builtin_nan("");
+        return;
+    }
+    double q = 0.0;
+    for (int i = t; i < n; i += ST) q += 0.5 * z[i] * al[i] + log(A[i + i * ld]);
+    q = wave_sum(q);
+    if (lane == 0) red[wave] = q;
+    __syncthreads();
+    if (t == 0) {
+        double v = 0.0;
+        for (int w = 0; w < ST / 64; ++w) v += red[w];
+        a.nll[b] = v;
+    }
+    if (a.alpha)
+        for (int i = t; i < n; i += ST) a.alpha[(size_t)b * n + i] = al[i];
+}
+
+// ---- the gradient of the mid-size problems (sgpr_fit_batch_grad_mid) -------------------------------------------------
+// After the solves a problem's image holds L, `inv` its 128 x 128 leaf inverses and r its alpha.  Three steps, every one a
+// grid over all problems of the chunk, ordered by the stream alone (no workgroup waits for another one):
+//   (a) U = L^-T into a second image, U[i + k ld] = (L^-1)[k, i] as grad_problem's: the diagonal tiles are the transposed
+//       leaf inverses (mid_udiag_kernel); then the block size doubles, 128, 256, ... : for adjacent diagonal blocks 1, 2
+//           T = U11 L21^T   (STEP 0, NT, into the block (1, 2) of the L image: its strict upper triangle is free),
+//           U12 = -T U22    (STEP 1, the TRANSB form),
+//       one 128 x 128 tile per workgroup; the last block 2 is ragged when W is no power of two.  The k range of a tile stops
+//       at the zeros of the triangular operand: U11's tile row ti starts at k = 128 ti, U22's tile column tj ends at
+//       128 (tj + 1).
+//   (b) Ky^-1 = U U^T, lower tiles, over L (mid_kinv_kernel): tile (I, J) sums k >= 128 I.
+//   (c) the contraction of W = Ky^-1 - alpha alpha^T with dK (mid_grad_kernel) in per-workgroup partials, folded per problem in
+//       a fixed order (mid_grad_fold_kernel).
+// A problem that is not positive definite has an arbitrary image: every loop bound here comes from the shape alone.
+constexpr int GT = 256;                   // contraction: rows per workgroup (one per thread)
+constexpr int GCJ = 64;                   // contraction: column points per workgroup
+constexpr int GPART = 8;                  // doubles per workgroup partial (>= grad_nacc)
+
+struct MidInv {
+    double *L, *U;        // problem b at L / U + b * stride (column-major, ld)
+    const double *inv;    // its leaf inverses at inv + b * stride_inv
+    size_t stride, ld, stride_inv;
+    int W, S;             // 128-tiles per side; tiles per side of a (full) diagonal block of this level
+};
+
+__global__ __launch_bounds__(256) void mid_udiag_kernel(const MidInv a)
+{
+    const double *X = a.inv + (size_t)blockIdx.y * a.stride_inv + (size_t)blockIdx.x * LEAF * LEAF;
+    double *U = a.U + (size_t)blockIdx.y * a.stride + (size_t)blockIdx.x * LEAF * (a.ld + 1);
+    for (int e = threadIdx.x; e < (int)(LEAF * LEAF); e += 256) {
+        const int i = e % (int)LEAF, k = e / (int)LEAF;
+        U[i + k * a.ld] = k >= i ? X[k + i * LEAF] : 0.0;         // the tile's lower part: zeros that (b) reads
+    }
+}
+
+template <int STEP>
+__global__ __launch_bounds__(256, 2) void mid_inv_level_kernel(const MidInv a)
+{
+    __shared__ double smem[2 * tile::BK * (2 * (128 + tile::PAD))];
+    const int S = a.S, per = S * S;
+    const int p = (int)blockIdx.x / per, rem = (int)blockIdx.x - p * per, ti = rem % S, tj = rem / S;
+    const int t1 = 2 * S * p, t2 = t1 + S;            // first tile of block 1 (S tiles, full) and of block 2
+    if (t2 + tj >= a.W) return;                       // past the ragged last block (the whole workgroup)
+    double *L = a.L + (size_t)blockIdx.y * a.stride, *U = a.U + (size_t)blockIdx.y * a.stride;
+    const size_t ld = a.ld, r1 = (size_t)t1 * LEAF, r2 = (size_t)t2 * LEAF, ri = r1 + (size_t)ti * LEAF, cj = r2 + (size_t)tj * LEAF;
+    tile::GemmArgs g{};
+    g.m = 128; g.n = 128; g.beta = 0.0;
+    g.lda = ld; g.ldb = ld; g.ldc = ld;
+    if constexpr (STEP == 0) {
+        // T(ti, tj) = sum_{k >= 128 ti} U11[ti, k] L21[tj, k]
+        g.k = (S - ti) * (int)LEAF; g.alpha = 1.0;
+        g.A = U + ri + ri * ld;
+        g.B = L + cj + ri * ld;
+        g.C = L + ri + cj * ld;
+        tile::gemm_body_dma<128, 128, 2>(g, smem, 0, 0);
+    } else {
+        // U12(ti, tj) = -sum_{k < 128 (tj + 1)} T[ti, k] U22[k, tj]
+        g.k = (tj + 1) * (int)LEAF; g.alpha = -1.0; g.transb = 1;
+        g.A = L + ri + r2 * ld;
+        g.B = U + r2 + cj * ld;
+        g.C = U + ri + cj * ld;
+        tile::gemm_body<128, 128, true, true>(g, smem, 0, 0);
+    }
+}
+
+__global__ __launch_bounds__(256, 2) void mid_kinv_kernel(const MidInv a)
+{
+    __shared__ double smem[2 * tile::BK * (2 * (128 + tile::PAD))];
+    int t = (int)blockIdx.x, r = 0;            // lower tiles row by row, as mid_syrk_kernel
+    while (t > r) { t -= r + 1; ++r; }
+    const double *U = a.U + (size_t)blockIdx.y * a.stride;
+    const size_t ld = a.ld, ri = (size_t)r * LEAF, cj = (size_t)t * LEAF;
+    tile::GemmArgs g{};
+    g.m = 128; g.n = 128; g.k = (a.W - r) * (int)LEAF;
+    g.alpha = 1.0; g.beta = 0.0;
+    g.A = U + ri + ri * ld; g.lda = ld;        // U[I, k] = 0 for k < 128 I
+    g.B = U + cj + ri * ld; g.ldb = ld;
+    g.C = a.L + (size_t)blockIdx.y * a.stride + ri + cj * ld; g.ldc = ld;
+    tile::gemm_body_dma<128, 128, 2>(g, smem, 0, 0);
+}
+
+struct MidGrad {
+    int npts, n, reg, nwg, nacc;
+    size_t ld;                            // npad: Ky^-1 (lower) of problem b at K + b ld^2, its alpha at alpha + b ld
+    const double *x, *y;
+    const KConst *kc;
+    const double *K, *alpha;
+    double *part;                         // sum k of workgroup w of problem b at part[(b nwg + w) GPART + k]
+    const int *info;
+    double *out;                          // problem b's raw sums at out + b nacc
+};
+
+// rows i0 .. i0 + GT (one per thread) x column points p0 .. p0 + GCJ of problem blockIdx.z: entries on and below the diagonal,
+// weighted W_ii and 2 W_ij, as grad_problem's step (3); rows and columns below n only
+template <int FAM>
+__global__ __launch_bounds__(GT) void mid_grad_kernel(const MidGrad a)
+{
+    constexpr bool HASP = grad_has_p<FAM>();
+    constexpr int NACC = grad_nacc<FAM>();
+    __shared__ double sx[GCJ], sy[GCJ], sal[2][GCJ];
+    __shared__ double red[GT / 64][NACC];
+    const int b = blockIdx.z, N = a.npts, n = a.n, tid = threadIdx.x;
+    const int p0 = blockIdx.y * GCJ, np = min(GCJ, N - p0);
+    const int i = blockIdx.x * GT + tid;
+    const double *K = a.K + (size_t)b * a.ld * a.ld, *al = a.alpha + (size_t)b * a.ld;
+    if (tid < np) {
+        sx[tid] = a.x[(size_t)b * N + p0 + tid];
+        sy[tid] = a.y[(size_t)b * N + p0 + tid];
+        sal[0][tid] = al[p0 + tid];
+        sal[1][tid] = a.reg ? 0.0 : al[N + p0 + tid];
+    }
+    __syncthreads();
+    const KConst kc = a.kc[b];
+    const double l[2] = {kc.lx, kc.ly}, pp[1] = {kc.p};
+    double acc[NACC];
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
+    if (i < n && p0 <= i) {
+        const double ai = al[i];
+        const double *Krow = K + i;
+        if (a.reg) {
+            const double xi = a.x[(size_t)b * N + i], yi = a.y[(size_t)b * N + i];
+            for (int jj = 0; jj < np; ++jj) {
+                const int j = p0 + jj;
+                if (j > i) break;
+                const double W = Krow[(size_t)j * a.ld] - ai * sal[0][jj];
+                if (j == i) acc[NACC - 1] += W;
+                nllg::reg_grad<FAM, HASP>(sx[jj], sy[jj], xi, yi, j == i ? W : 2.0 * W, l, kc.p, acc);
+            }
+        } else {
+            const int r = i < N ? 0 : 1, pi = i - r * N;
+            const double xi[2] = {a.x[(size_t)b * N + pi], a.y[(size_t)b * N + pi]};
+            for (int jj = 0; jj < np; ++jj) {
+                const int pj = p0 + jj;
+                double w[2];
+                bool any = false;
+#pragma unroll
+                for (int c = 0; c < 2; ++c) {                 // columns pj (q part) and N + pj (P part)
+                    const int col = c * N + pj;
+                    w[c] = 0.0;
+                    if (col <= i) {
+                        const double W = Krow[(size_t)col * a.ld] - ai * sal[c][jj];
+                        if (col == i) { w[c] = W; acc[NACC - 1] += W; }
+                        else w[c] = 2.0 * W;
+                        any = true;
+                    }
+                }
+                if (!any) break;                              // column pj > i: so are all after it
+                const double xj[2] = {sx[jj], sy[jj]};
+                nllg::pair_grad<FAM, 2, HASP>(xi, xj, w, r, l, pp, acc);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) {
+        const double v = wave_sum(acc[k]);
+        if ((tid & 63) == 0) red[tid >> 6][k] = v;
+    }
+    __syncthreads();
+    if (tid < NACC) {
+        double v = red[0][tid];
+#pragma unroll
+        for (int w = 1; w < GT / 64; ++w) v += red[w][tid];
+        a.part[((size_t)b * a.nwg + (size_t)blockIdx.y * gridDim.x + blockIdx.x) * GPART + tid] = v;
+    }
+}
+
+// problem blockIdx.x: its workgroups' partials in their fixed order; NaN where the factorisation failed
+__global__ __launch_bounds__(64) void mid_grad_fold_kernel(const MidGrad a)
+{
+    const int b = blockIdx.x, k = threadIdx.x;
+    if (k >= a.nacc) return;
+    const double *p = a.part + (size_t)b * a.nwg * GPART + k;
+    double v = 0.0;
+    for (int w = 0; w < a.nwg; ++w) v += p[(size_t)w * GPART];
+    a.out[(size_t)b * a.nacc + k] = a.info[b] != 0 ? __builtin_nan("") : v;
+}
+
+// ---- leave-one-point-out sums of the mid-size problems (sgpr_fit_batch_loo): behind step (b) above, in place of (c) ----------
+struct MidLoo {
+    int npts, reg, nwg;
+    size_t ld;                            // npad: Ky^-1 (lower) of problem b at K + b ld^2, its alpha at alpha + b ld
+    const double *K, *alpha;
+    double *part;                         // sum k of workgroup w of problem b at part[(b nwg + w) 2 + k]: k = 0 lpd, 1 |r|^2
+    const int *info;
+    double *out;                          // problem b's {loo, press} at out + 2 b
+};
+
+// points blockIdx.x GT .. + GT (one per thread) of problem blockIdx.z: the point's block from the lower triangle of Ky^-1
+__global__ __launch_bounds__(GT) void mid_loo_kernel(const MidLoo a)
+{
+    __shared__ double red[GT / 64][2];
+    const int b = blockIdx.z, N = a.npts, tid = threadIdx.x, i = blockIdx.x * GT + tid;
+    const double *K = a.K + (size_t)b * a.ld * a.ld, *al = a.alpha + (size_t)b * a.ld;
+    double lv[2] = {0.0, 0.0};
+    if (i < N) {
+        double lpd, rr;
+        if (a.reg) {
+            const double C[1] = {K[i + i * a.ld]}, ai[1] = {al[i]};
+            double r[1], S[1];
+            loo::block<1>(C, ai, r, S, lpd);
+            rr = r[0] * r[0];
+        } else {
+            const double C[3] = {K[i + i * a.ld], K[(N + i) + i * a.ld], K[(N + i) + (N + i) * a.ld]}, ai[2] = {al[i], al[N + i]};
+            double r[2], S[3];
+            loo::block<2>(C, ai, r, S, lpd);
+            rr = __builtin_fma(r[1], r[1], r[0] * r[0]);
+        }
+        lv[0] = lpd; lv[1] = rr;
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const double v = wave_sum(lv[k]);
+        if ((tid & 63) == 0) red[tid >> 6][k] = v;
+    }
+    __syncthreads();
+    if (tid < 2) {
+        double v = red[0][tid];
+#pragma unroll
+        for (int w = 1; w < GT / 64; ++w) v += red[w][tid];
+        a.part[((size_t)b * a.nwg + blockIdx.x) * 2 + tid] = v;
+    }
+}
+
+// problem blockIdx.x: its workgroups' partials in their fixed order; NaN where the factorisation failed
+__global__ __launch_bounds__(64) void mid_loo_fold_kernel(const MidLoo a)
+{
+    const int b = blockIdx.x, k = threadIdx.x;
+    if (k >= 2) return;
+    const double *p = a.part + (size_t)b * a.nwg * 2 + k;
+    double v = 0.0;
+    for (int w = 0; w < a.nwg; ++w) v += p[(size_t)w * 2];
+    a.out[(size_t)b * 2 + k] = a.info[b] != 0 ? __builtin_nan("") : (k == 0 ? -v : v);
+}
+
+}  // namespace
+
+}  // namespace sgpr

@@ -315,126 +315,91 @@ int sgpr_fit_batch(int family, int nbatch, int n_pts, const double *x, const dou
     return fit_batch(family, nbatch, n_pts, x, y, z, hyp, nhyp, sig2n, flags, alpha, nll, info);
 }
 
-/* sgpr_fit_batch for problems with d canonical pairs per point (batch.hip: fit_batch_nd_kernel up to order 256, fit_batch_mid
- * with mid_build_nd_kernel above).  Checked like sgpr_fit_batch_grad, before any device call. */
+/* The argument check of the batched entries below, before any device call: an argument error is SGPR_E_ARG on any machine, and
+ * the message names the entry.  d: null for the entries that take x | y (nhyp 4 or 3, flags SGPR_FIT_REG or none), else the
+ * canonical pairs per point (nhyp 3d + 1 or 2d + 1, no flags).  which: null, or the loo objective to check.  The order per problem
+ * must be above nmin (0: no lower limit) and at most nmax.  outs names the required output pointers; outs_ok / ins_ok: none of
+ * them / of the inputs is null. */
+static int check_batch_args(const char *entry, int family, const int *d, int nhyp, unsigned flags, const int *which, int nbatch,
+                            int n_pts, int nmin, int nmax, const char *outs, bool outs_ok, bool ins_ok)
+{
+    auto E = [entry](const std::string &what) { set_error(std::string(entry) + ": " + what); return SGPR_E_ARG; };
+    if (d && (*d < 1 || *d > 3)) return E("d must be 1, 2 or 3");
+    if (family < SGPR_FAM_A || family > SGPR_FAM_USER) return E("unknown kernel family");
+    const int need = d ? (family_has_p(family) ? 3 * *d + 1 : 2 * *d + 1) : (family_has_p(family) ? 4 : 3);
+    if (nhyp != need) return E("nhyp must be " + std::to_string(need) + (d ? " for this family and d" : " for this family"));
+    if (d && flags) return E("flags must be 0 (there is no scalar-kernel d-pair fit)");
+    if (flags & ~(unsigned)SGPR_FIT_REG) return E("unknown flag (only SGPR_FIT_REG)");
+    if (which && *which != SGPR_LOO_LPD && *which != SGPR_LOO_PRESS) return E("which must be SGPR_LOO_LPD or SGPR_LOO_PRESS");
+    if (nbatch < 0) return E("nbatch < 0");
+    if (n_pts <= 0) return E("n_pts <= 0");
+    const long n = d ? 2L * *d * n_pts : (flags & SGPR_FIT_REG) ? (long)n_pts : 2L * n_pts;
+    if (n <= nmin) return E("order per problem " + std::to_string(n) + " is at most " + std::to_string(nmin) + ": sgpr_fit_batch_grad's range");
+    if (n > nmax) return E("order per problem " + std::to_string(n) + " exceeds " + std::to_string(nmax));
+    if (!outs_ok) return E(std::string("null ") + outs);
+    if (!ins_ok) return E("null input");
+    return 0;
+}
+
+/* sgpr_fit_batch for problems with d canonical pairs per point (batch.hip: fit_batch_nd_kernel up to order 256, the mid path
+ * with mid_build_nd_kernel above). */
 int sgpr_fit_batch_nd(int family, int d, int nbatch, int n_pts, const double *X, const double *z, const double *hyp, int nhyp,
                       const double *sig2n, unsigned flags, double *alpha, double *nll, int *info)
 {
-    auto E = [](const std::string &what) { set_error("fit_batch_nd: " + what); return SGPR_E_ARG; };
-    if (d < 1 || d > 3) return E("d must be 1, 2 or 3");
-    if (family < SGPR_FAM_A || family > SGPR_FAM_USER) return E("unknown kernel family");
-    const int need = family_has_p(family) ? 3 * d + 1 : 2 * d + 1;
-    if (nhyp != need) return E("nhyp must be " + std::to_string(need) + " for this family and d");
-    if (flags) return E("flags must be 0 (there is no scalar-kernel d-pair fit)");
-    if (nbatch < 0) return E("nbatch < 0");
-    if (n_pts <= 0) return E("n_pts <= 0");
-    const long n = 2L * d * n_pts;
-    const int nmax = fit_batch_max_order();
-    if (n > nmax) return E("order per problem " + std::to_string(n) + " exceeds " + std::to_string(nmax));
-    if (!nll || !info) return E("null nll or info");
-    if (!X || !z || !hyp || !sig2n) return E("null input");
-    if (nbatch == 0) return 0;
-    int rc = need_device();
-    if (rc) return rc;
+    int rc = check_batch_args("fit_batch_nd", family, &d, nhyp, flags, nullptr, nbatch, n_pts, 0, fit_batch_max_order(), "nll or info",
+                              nll && info, X && z && hyp && sig2n);
+    if (rc || nbatch == 0) return rc;
+    if ((rc = need_device())) return rc;
     return fit_batch_nd(family, d, nbatch, n_pts, X, z, hyp, nhyp, sig2n, alpha, nll, info);
 }
 
-/* sgpr_fit_batch plus the gradient of every problem's nll (batch.hip: fit_batch_kernel<FAM, true>).  The arguments are checked
- * before any device call: an argument error is SGPR_E_ARG on any machine, the message names the entry. */
+/* sgpr_fit_batch plus the gradient of every problem's nll (batch.hip: the gradient mode of fit_batch_kernel). */
 int sgpr_fit_batch_grad(int family, int nbatch, int n_pts, const double *x, const double *y, const double *z,
                         const double *hyp, int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll,
                         double *grad, int *info)
 {
-    auto E = [](const std::string &what) { set_error("fit_batch_grad: " + what); return SGPR_E_ARG; };
-    if (family < SGPR_FAM_A || family > SGPR_FAM_USER) return E("unknown kernel family");
-    const int need = family_has_p(family) ? 4 : 3;
-    if (nhyp != need) return E("nhyp must be " + std::to_string(need) + " for this family");
-    if (flags & ~(unsigned)SGPR_FIT_REG) return E("unknown flag (only SGPR_FIT_REG)");
-    if (nbatch < 0) return E("nbatch < 0");
-    if (n_pts <= 0) return E("n_pts <= 0");
-    const long n = (flags & SGPR_FIT_REG) ? (long)n_pts : 2L * n_pts;
-    const int nmax = fit_batch_grad_max_order();
-    if (n > nmax) return E("order per problem " + std::to_string(n) + " exceeds " + std::to_string(nmax));
-    if (!nll || !grad || !info) return E("null nll, grad or info");
-    if (!x || !y || !z || !hyp || !sig2n) return E("null input");
-    if (nbatch == 0) return 0;
-    int rc = need_device();
-    if (rc) return rc;
+    int rc = check_batch_args("fit_batch_grad", family, nullptr, nhyp, flags, nullptr, nbatch, n_pts, 0, fit_batch_grad_max_order(),
+                              "nll, grad or info", nll && grad && info, x && y && z && hyp && sig2n);
+    if (rc || nbatch == 0) return rc;
+    if ((rc = need_device())) return rc;
     return fit_batch_grad(family, nbatch, n_pts, x, y, z, hyp, nhyp, sig2n, flags, alpha, nll, grad, info);
 }
 
-/* The same above order 256, up to sgpr_fit_batch_max_order() (batch.hip: fit_batch_mid with its gradient phase).  Checked like
- * sgpr_fit_batch_grad, before any device call. */
+/* The same above order 256, up to sgpr_fit_batch_max_order() (batch.hip: the mid path with its gradient phase). */
 int sgpr_fit_batch_grad_mid(int family, int nbatch, int n_pts, const double *x, const double *y, const double *z,
                             const double *hyp, int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll,
                             double *grad, int *info)
 {
-    auto E = [](const std::string &what) { set_error("fit_batch_grad_mid: " + what); return SGPR_E_ARG; };
-    if (family < SGPR_FAM_A || family > SGPR_FAM_USER) return E("unknown kernel family");
-    const int need = family_has_p(family) ? 4 : 3;
-    if (nhyp != need) return E("nhyp must be " + std::to_string(need) + " for this family");
-    if (flags & ~(unsigned)SGPR_FIT_REG) return E("unknown flag (only SGPR_FIT_REG)");
-    if (nbatch < 0) return E("nbatch < 0");
-    if (n_pts <= 0) return E("n_pts <= 0");
-    const long n = (flags & SGPR_FIT_REG) ? (long)n_pts : 2L * n_pts;
-    const int nmin = fit_batch_grad_max_order(), nmax = fit_batch_max_order();
-    if (n <= nmin) return E("order per problem " + std::to_string(n) + " is at most " + std::to_string(nmin) + ": sgpr_fit_batch_grad's range");
-    if (n > nmax) return E("order per problem " + std::to_string(n) + " exceeds " + std::to_string(nmax));
-    if (!nll || !grad || !info) return E("null nll, grad or info");
-    if (!x || !y || !z || !hyp || !sig2n) return E("null input");
-    if (nbatch == 0) return 0;
-    int rc = need_device();
-    if (rc) return rc;
+    int rc = check_batch_args("fit_batch_grad_mid", family, nullptr, nhyp, flags, nullptr, nbatch, n_pts, fit_batch_grad_max_order(),
+                              fit_batch_max_order(), "nll, grad or info", nll && grad && info, x && y && z && hyp && sig2n);
+    if (rc || nbatch == 0) return rc;
+    if ((rc = need_device())) return rc;
     return fit_batch_grad_mid(family, nbatch, n_pts, x, y, z, hyp, nhyp, sig2n, flags, alpha, nll, grad, info);
 }
 
 /* sgpr_fit_batch plus leave-one-point-out cross-validation per problem, every order up to sgpr_fit_batch_max_order() (batch.hip:
- * the loo mode of fit_batch_kernel up to order 256, fit_batch_mid with its loo phase above).  Checked like sgpr_fit_batch_grad,
- * before any device call. */
+ * the loo mode of fit_batch_kernel up to order 256, the mid path with its loo phase above). */
 int sgpr_fit_batch_loo(int family, int nbatch, int n_pts, const double *x, const double *y, const double *z,
                        const double *hyp, int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll,
                        double *loo, int *info)
 {
-    auto E = [](const std::string &what) { set_error("fit_batch_loo: " + what); return SGPR_E_ARG; };
-    if (family < SGPR_FAM_A || family > SGPR_FAM_USER) return E("unknown kernel family");
-    const int need = family_has_p(family) ? 4 : 3;
-    if (nhyp != need) return E("nhyp must be " + std::to_string(need) + " for this family");
-    if (flags & ~(unsigned)SGPR_FIT_REG) return E("unknown flag (only SGPR_FIT_REG)");
-    if (nbatch < 0) return E("nbatch < 0");
-    if (n_pts <= 0) return E("n_pts <= 0");
-    const long n = (flags & SGPR_FIT_REG) ? (long)n_pts : 2L * n_pts;
-    const int nmax = fit_batch_max_order();
-    if (n > nmax) return E("order per problem " + std::to_string(n) + " exceeds " + std::to_string(nmax));
-    if (!nll || !loo || !info) return E("null nll, loo or info");
-    if (!x || !y || !z || !hyp || !sig2n) return E("null input");
-    if (nbatch == 0) return 0;
-    int rc = need_device();
-    if (rc) return rc;
+    int rc = check_batch_args("fit_batch_loo", family, nullptr, nhyp, flags, nullptr, nbatch, n_pts, 0, fit_batch_max_order(),
+                              "nll, loo or info", nll && loo && info, x && y && z && hyp && sig2n);
+    if (rc || nbatch == 0) return rc;
+    if ((rc = need_device())) return rc;
     return fit_batch_loo(family, nbatch, n_pts, x, y, z, hyp, nhyp, sig2n, flags, alpha, nll, loo, info);
 }
 
 /* sgpr_fit_batch plus one leave-one-point-out objective and its gradient per problem, orders up to 256 (batch.hip: the loograd
- * mode of fit_batch_kernel).  Checked like sgpr_fit_batch_grad, before any device call. */
+ * mode of fit_batch_kernel). */
 int sgpr_fit_batch_loo_grad(int family, int nbatch, int n_pts, const double *x, const double *y, const double *z,
                             const double *hyp, int nhyp, const double *sig2n, unsigned flags, int which, double *alpha,
                             double *nll, double *value, double *grad, int *info)
 {
-    auto E = [](const std::string &what) { set_error("fit_batch_loo_grad: " + what); return SGPR_E_ARG; };
-    if (family < SGPR_FAM_A || family > SGPR_FAM_USER) return E("unknown kernel family");
-    const int need = family_has_p(family) ? 4 : 3;
-    if (nhyp != need) return E("nhyp must be " + std::to_string(need) + " for this family");
-    if (flags & ~(unsigned)SGPR_FIT_REG) return E("unknown flag (only SGPR_FIT_REG)");
-    if (which != SGPR_LOO_LPD && which != SGPR_LOO_PRESS) return E("which must be SGPR_LOO_LPD or SGPR_LOO_PRESS");
-    if (nbatch < 0) return E("nbatch < 0");
-    if (n_pts <= 0) return E("n_pts <= 0");
-    const long n = (flags & SGPR_FIT_REG) ? (long)n_pts : 2L * n_pts;
-    const int nmax = fit_batch_grad_max_order();
-    if (n > nmax) return E("order per problem " + std::to_string(n) + " exceeds " + std::to_string(nmax));
-    if (!nll || !value || !grad || !info) return E("null nll, value, grad or info");
-    if (!x || !y || !z || !hyp || !sig2n) return E("null input");
-    if (nbatch == 0) return 0;
-    int rc = need_device();
-    if (rc) return rc;
+    int rc = check_batch_args("fit_batch_loo_grad", family, nullptr, nhyp, flags, &which, nbatch, n_pts, 0, fit_batch_grad_max_order(),
+                              "nll, value, grad or info", nll && value && grad && info, x && y && z && hyp && sig2n);
+    if (rc || nbatch == 0) return rc;
+    if ((rc = need_device())) return rc;
     return fit_batch_loo_grad(family, nbatch, n_pts, x, y, z, hyp, nhyp, sig2n, flags, which, alpha, nll, value, grad, info);
 }
 

@@ -285,6 +285,20 @@ int fit_loo_grad(int family, int d, bool reg, int which, int N, int n, const dou
 int fit_batch_max_order();
 int fit_batch_trim();                            // release the calling thread's batch arena (device + pinned host)
 int potrf_trim();                                // ... and its pooled events
+// The arena layout of one batched call: byte offsets into its input block (one H2D copy), its output block (one D2H copy) and the
+// device scratch behind them, every region a multiple of 256 bytes.  Host arithmetic only, no device call.  mid: the path of orders
+// above 256 (in chunks of problems), else the one-launch path (one chunk); mode: 0 fit, 1 nll gradient, 2 loo, 3 loo gradient;
+// d: 0 for points as x | y, else the canonical pairs per point.
+struct BatchLayout {
+    int chunk;                                       // problems per pass over the arena
+    int npad, W, ggx, ggy, lnwg;                     // mid path: padded order, 128-strips, contraction grid, loo workgroups per problem
+    size_t nacc;                                     // doubles behind nll per problem (raw sums)
+    size_t const_bytes, flag_bytes;                  // per-problem constants; potrf_batch_flag_bytes(chunk) (mid path)
+    size_t o_x, o_y, o_z, o_kc, o_no, in_bytes;      // x | y | z | consts | noise
+    size_t o_al, o_nll, o_info, out_bytes;           // alpha | nll [+ sums] | info
+    size_t o_A, o_inv, o_fl, o_fl2, o_r, o_pub, o_st, o_part, scr_bytes;     // mid path's scratch regions; the total of either path
+};
+BatchLayout batch_layout(int mid, int mode, int d, int reg, int nbatch, int npts, int nhyp);
 int fit_batch(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
               int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, int *info);
 // the fit for problems with d canonical pairs per point (X: nbatch x 2d x npts), n = 2 d npts <= fit_batch_max_order(); the

@@ -9,6 +9,7 @@
 #include "common.h"
 #include "../../include/sympgpr_probe.h"
 #include "generated/pair_generated.h"
+#include "nd_eval.h"
 
 namespace sgpr {
 namespace {
@@ -592,6 +593,22 @@ extern "C" int sgpr_probe_gemm_nt4_dev(int m, int n, int k, const double *A, siz
                                        int count, double *const *C, const size_t *ldc, const double *alpha, void *stream)
 {
     return gemm_nt_multi(m, n, k, A, lda, B, ldb, beta, count, C, ldc, alpha, static_cast<hipStream_t>(stream));
+}
+// ---- the arena layout of a batched fit (batch.hip: batch_layout), host arithmetic only: no device call
+extern "C" int sgpr_probe_batch_layout(int path, int mode, int d, int reg, int nbatch, int n_pts, int nhyp, unsigned long long out[24])
+{
+    const long n = d ? 2L * d * n_pts : reg ? (long)n_pts : 2L * n_pts;
+    if (path < 0 || path > 1 || mode < 0 || mode > 3 || (path && mode == 3) || d < 0 || d > 3 || (d && (reg || mode)) || nbatch < 1 ||
+        n_pts < 1 || nhyp < 1 || (path ? n <= 256 || n > 2048 : n > 256) || !out) {
+        set_error("probe_batch_layout: bad arguments");
+        return SGPR_E_ARG;
+    }
+    const BatchLayout l = batch_layout(path, mode, d, reg, nbatch, n_pts, nhyp);
+    const size_t v[24] = {(size_t)l.chunk, l.nacc, l.o_x, l.o_y, l.o_z, l.o_kc, l.o_no, l.in_bytes, l.o_al, l.o_nll, l.o_info, l.out_bytes,
+                          l.o_A, l.o_inv, l.o_fl, l.o_fl2, l.o_r, l.o_pub, l.o_st, l.o_part, l.scr_bytes,
+                          sizeof(KConst), sizeof(nd::NdConst), l.flag_bytes};
+    for (int i = 0; i < 24; ++i) out[i] = v[i];
+    return 0;
 }
 extern "C" unsigned sgpr_probe_map_calls(void) { return applymap_last_calls(); }
 extern "C" int sgpr_probe_map_team(int ntest, int n0) { return applymap_team(ntest, n0); }

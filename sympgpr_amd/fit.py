@@ -395,25 +395,44 @@ def batch_max_order():
     return L.load_library().sgpr_fit_batch_max_order()
 
 
+def _batch_inputs(name, x, y, z, hyp, sig2n, reg):
+    """The inputs of the wrappers that take points as x | y: contiguous float64 (B, .) arrays, sig2n broadcast to (B,), the shapes
+    checked (the ValueError names the wrapper).  -> (x, y, z, hyp, s2), B, n_pts, n, nhyp"""
+    x, y, z, hyp = (np.ascontiguousarray(np.atleast_2d(np.asarray(v, dtype=np.float64))) for v in (x, y, z, hyp))
+    B, n_pts = x.shape
+    n = n_pts if reg else 2 * n_pts
+    if y.shape != (B, n_pts) or z.shape != (B, n) or hyp.shape[0] != B:
+        raise ValueError("%s: x, y (B, n_pts), z (B, n), hyp (B, nhyp)" % name)
+    s2 = np.ascontiguousarray(np.broadcast_to(np.asarray(sig2n, dtype=np.float64), (B,)))
+    return (x, y, z, hyp, s2), B, n_pts, n, hyp.shape[1]
+
+
+def _batch_lead(family, arrays, B, n_pts, reg):
+    """the arguments every x | y entry starts with: family, nbatch, n_pts, x, y, z, hyp, nhyp, sig2n, flags"""
+    x, y, z, hyp, s2 = arrays
+    return (L.family_id(family), B, n_pts, L.dptr(x), L.dptr(y), L.dptr(z), L.dptr(hyp), hyp.shape[1], L.dptr(s2),
+            L.FIT_REG if reg else 0)
+
+
+def _batch_run(entry, lead, B, n, want_alpha, extra=(), which=None):
+    """Allocate alpha (B, n) or None, nll (B,), info (B,) and call entry(*lead [, which], alpha, nll, *extra, info)."""
+    alpha = np.empty((B, n)) if want_alpha else None
+    nll = np.empty(B)
+    info = np.zeros(B, dtype=np.int32)
+    args = list(lead) + ([] if which is None else [which]) + [L.dptr(alpha) if want_alpha else None, L.dptr(nll)]
+    args += [L.dptr(e) for e in extra] + [info.ctypes.data_as(C.POINTER(C.c_int))]
+    L.check(getattr(L.load_library(), entry)(*args), entry)
+    return alpha, nll, info
+
+
 def fit_batch(family, x, y, z, hyp, sig2n, reg=False, want_alpha=True):
     """Many small independent fits in ONE launch (one workgroup per problem): the body of nll_chol
     (python/functions/func.py:189-196; reg=True: nll_chol_reg) for every row b of
         x, y (B, n_pts);  z (B, n), n = 2 n_pts (n_pts with reg);  hyp (B, nhyp);  sig2n (B,) or scalar.
     -> (alpha (B, n) or None, nll (B,), info (B,)): info[b] > 0 where Ky_b is not positive definite
     (nll[b] is NaN there, like the LinAlgError scipy raises for that problem)."""
-    x, y, z, hyp = (np.ascontiguousarray(np.atleast_2d(np.asarray(v, dtype=np.float64))) for v in (x, y, z, hyp))
-    B, n_pts = x.shape
-    n = n_pts if reg else 2 * n_pts
-    if y.shape != (B, n_pts) or z.shape != (B, n) or hyp.shape[0] != B:
-        raise ValueError("fit_batch: x, y (B, n_pts), z (B, n), hyp (B, nhyp)")
-    s2 = np.ascontiguousarray(np.broadcast_to(np.asarray(sig2n, dtype=np.float64), (B,)))
-    alpha = np.empty((B, n)) if want_alpha else None
-    nll = np.empty(B)
-    info = np.zeros(B, dtype=np.int32)
-    L.check(L.load_library().sgpr_fit_batch(L.family_id(family), B, n_pts, L.dptr(x), L.dptr(y), L.dptr(z), L.dptr(hyp),
-                                            hyp.shape[1], L.dptr(s2), L.FIT_REG if reg else 0,
-                                            L.dptr(alpha) if want_alpha else None, L.dptr(nll),
-                                            info.ctypes.data_as(C.POINTER(C.c_int))), "sgpr_fit_batch")
+    arrays, B, n_pts, n, _ = _batch_inputs("fit_batch", x, y, z, hyp, sig2n, reg)
+    alpha, nll, info = _batch_run("sgpr_fit_batch", _batch_lead(family, arrays, B, n_pts, reg), B, n, want_alpha)
     nll[info != 0] = np.nan
     return alpha, nll, info
 
@@ -448,12 +467,8 @@ def fit_batch_pairs(family, X, z, hyp, sig2n, want_alpha=True):
     z = np.ascontiguousarray(z)
     hyp = np.ascontiguousarray(hyp)
     s2 = np.ascontiguousarray(np.broadcast_to(np.asarray(sig2n, dtype=np.float64), (B,)))
-    alpha = np.empty((B, n)) if want_alpha else None
-    nll = np.empty(B)
-    info = np.zeros(B, dtype=np.int32)
-    L.check(L.load_library().sgpr_fit_batch_nd(L.family_id(family), D // 2, B, n_pts, L.dptr(Xl), L.dptr(z), L.dptr(hyp),
-                                               hyp.shape[1], L.dptr(s2), 0, L.dptr(alpha) if want_alpha else None,
-                                               L.dptr(nll), info.ctypes.data_as(C.POINTER(C.c_int))), "sgpr_fit_batch_nd")
+    lead = (L.family_id(family), D // 2, B, n_pts, L.dptr(Xl), L.dptr(z), L.dptr(hyp), hyp.shape[1], L.dptr(s2), 0)
+    alpha, nll, info = _batch_run("sgpr_fit_batch_nd", lead, B, n, want_alpha)
     nll[info != 0] = np.nan
     return alpha, nll, info
 
@@ -472,13 +487,8 @@ def fit_batch_grad(family, x, y, z, hyp, sig2n, reg=False, want_alpha=False):
     n <= 256: ONE launch (sgpr_fit_batch_grad), one workgroup per problem.
     256 < n <= 2048 (the slow path): nll, alpha and info from one fit_batch call, and the gradient of every positive-definite
     row from SympFit(...).run().nll_grad_full(), one device-resident fit per row."""
-    x, y, z, hyp = (np.ascontiguousarray(np.atleast_2d(np.asarray(v, dtype=np.float64))) for v in (x, y, z, hyp))
-    B, n_pts = x.shape
-    n = n_pts if reg else 2 * n_pts
-    if y.shape != (B, n_pts) or z.shape != (B, n) or hyp.shape[0] != B:
-        raise ValueError("fit_batch_grad: x, y (B, n_pts), z (B, n), hyp (B, nhyp)")
-    s2 = np.ascontiguousarray(np.broadcast_to(np.asarray(sig2n, dtype=np.float64), (B,)))
-    nhyp = hyp.shape[1]
+    arrays, B, n_pts, n, nhyp = _batch_inputs("fit_batch_grad", x, y, z, hyp, sig2n, reg)
+    x, y, z, hyp, s2 = arrays
     if n > batch_grad_max_order():
         alpha, nll, info = fit_batch(family, x, y, z, hyp, s2, reg=reg, want_alpha=want_alpha)
         grad = np.full((B, nhyp + 1), np.nan)
@@ -486,14 +496,8 @@ def fit_batch_grad(family, x, y, z, hyp, sig2n, reg=False, want_alpha=False):
             with SympFit(family, x[b], y[b], z[b], hyp[b], s2[b], reg=reg) as f:
                 grad[b] = f.run().nll_grad_full()
         return alpha, nll, grad, info
-    alpha = np.empty((B, n)) if want_alpha else None
-    nll = np.empty(B)
     grad = np.empty((B, nhyp + 1))
-    info = np.zeros(B, dtype=np.int32)
-    L.check(L.load_library().sgpr_fit_batch_grad(L.family_id(family), B, n_pts, L.dptr(x), L.dptr(y), L.dptr(z), L.dptr(hyp),
-                                                 nhyp, L.dptr(s2), L.FIT_REG if reg else 0,
-                                                 L.dptr(alpha) if want_alpha else None, L.dptr(nll), L.dptr(grad),
-                                                 info.ctypes.data_as(C.POINTER(C.c_int))), "sgpr_fit_batch_grad")
+    alpha, nll, info = _batch_run("sgpr_fit_batch_grad", _batch_lead(family, arrays, B, n_pts, reg), B, n, want_alpha, (grad,))
     return alpha, nll, grad, info
 
 
@@ -507,23 +511,11 @@ def fit_batch_grad_mid(family, x, y, z, hyp, sig2n, reg=False, want_alpha=False)
     the returned (alpha or None, nll, grad, info) and the NaN rows for info > 0 as fit_batch_grad; nll, alpha and info are the
     bits fit_batch returns.  Per chunk of problems: L^-T from the leaf inverses by block doubling, Ky^-1 = L^-T L^-1 on the
     matrix cores, one contraction launch.  ValueError for n <= 256: fit_batch_grad serves that range in one launch."""
-    x, y, z, hyp = (np.ascontiguousarray(np.atleast_2d(np.asarray(v, dtype=np.float64))) for v in (x, y, z, hyp))
-    B, n_pts = x.shape
-    n = n_pts if reg else 2 * n_pts
-    if y.shape != (B, n_pts) or z.shape != (B, n) or hyp.shape[0] != B:
-        raise ValueError("fit_batch_grad_mid: x, y (B, n_pts), z (B, n), hyp (B, nhyp)")
+    arrays, B, n_pts, n, nhyp = _batch_inputs("fit_batch_grad_mid", x, y, z, hyp, sig2n, reg)
     if n <= batch_grad_max_order():
         raise ValueError("fit_batch_grad_mid: order %d <= %d is fit_batch_grad's range" % (n, batch_grad_max_order()))
-    s2 = np.ascontiguousarray(np.broadcast_to(np.asarray(sig2n, dtype=np.float64), (B,)))
-    nhyp = hyp.shape[1]
-    alpha = np.empty((B, n)) if want_alpha else None
-    nll = np.empty(B)
     grad = np.empty((B, nhyp + 1))
-    info = np.zeros(B, dtype=np.int32)
-    L.check(L.load_library().sgpr_fit_batch_grad_mid(L.family_id(family), B, n_pts, L.dptr(x), L.dptr(y), L.dptr(z), L.dptr(hyp),
-                                                     nhyp, L.dptr(s2), L.FIT_REG if reg else 0,
-                                                     L.dptr(alpha) if want_alpha else None, L.dptr(nll), L.dptr(grad),
-                                                     info.ctypes.data_as(C.POINTER(C.c_int))), "sgpr_fit_batch_grad_mid")
+    alpha, nll, info = _batch_run("sgpr_fit_batch_grad_mid", _batch_lead(family, arrays, B, n_pts, reg), B, n, want_alpha, (grad,))
     return alpha, nll, grad, info
 
 
@@ -533,20 +525,9 @@ def fit_batch_loo(family, x, y, z, hyp, sig2n, reg=False, want_alpha=False):
         x, y (B, n_pts);  z (B, n), n = 2 n_pts (n_pts with reg);  hyp (B, nhyp);  sig2n (B,) or scalar.
     -> (alpha (B, n) or None, nll (B,), loo (B, 2), info (B,)).  Row b of loo is (loo, press).  Rows with info > 0 are NaN (nll
     and the loo row).  nll, alpha and info are the same bits fit_batch returns; a row's loo bits do not depend on the batch."""
-    x, y, z, hyp = (np.ascontiguousarray(np.atleast_2d(np.asarray(v, dtype=np.float64))) for v in (x, y, z, hyp))
-    B, n_pts = x.shape
-    n = n_pts if reg else 2 * n_pts
-    if y.shape != (B, n_pts) or z.shape != (B, n) or hyp.shape[0] != B:
-        raise ValueError("fit_batch_loo: x, y (B, n_pts), z (B, n), hyp (B, nhyp)")
-    s2 = np.ascontiguousarray(np.broadcast_to(np.asarray(sig2n, dtype=np.float64), (B,)))
-    alpha = np.empty((B, n)) if want_alpha else None
-    nll = np.empty(B)
+    arrays, B, n_pts, n, _ = _batch_inputs("fit_batch_loo", x, y, z, hyp, sig2n, reg)
     loo = np.empty((B, 2))
-    info = np.zeros(B, dtype=np.int32)
-    L.check(L.load_library().sgpr_fit_batch_loo(L.family_id(family), B, n_pts, L.dptr(x), L.dptr(y), L.dptr(z), L.dptr(hyp),
-                                                hyp.shape[1], L.dptr(s2), L.FIT_REG if reg else 0,
-                                                L.dptr(alpha) if want_alpha else None, L.dptr(nll), L.dptr(loo),
-                                                info.ctypes.data_as(C.POINTER(C.c_int))), "sgpr_fit_batch_loo")
+    alpha, nll, info = _batch_run("sgpr_fit_batch_loo", _batch_lead(family, arrays, B, n_pts, reg), B, n, want_alpha, (loo,))
     return alpha, nll, loo, info
 
 
@@ -565,13 +546,8 @@ def fit_batch_loo_grad(family, x, y, z, hyp, sig2n, reg=False, objective="loo", 
     if objective not in ("loo", "press"):
         raise ValueError('fit_batch_loo_grad: objective is "loo" or "press"')
     which = L.LOO_PRESS if objective == "press" else L.LOO_LPD
-    x, y, z, hyp = (np.ascontiguousarray(np.atleast_2d(np.asarray(v, dtype=np.float64))) for v in (x, y, z, hyp))
-    B, n_pts = x.shape
-    n = n_pts if reg else 2 * n_pts
-    if y.shape != (B, n_pts) or z.shape != (B, n) or hyp.shape[0] != B:
-        raise ValueError("fit_batch_loo_grad: x, y (B, n_pts), z (B, n), hyp (B, nhyp)")
-    s2 = np.ascontiguousarray(np.broadcast_to(np.asarray(sig2n, dtype=np.float64), (B,)))
-    nhyp = hyp.shape[1]
+    arrays, B, n_pts, n, nhyp = _batch_inputs("fit_batch_loo_grad", x, y, z, hyp, sig2n, reg)
+    x, y, z, hyp, s2 = arrays
     if n > batch_grad_max_order():
         alpha, nll, loo, info = fit_batch_loo(family, x, y, z, hyp, s2, reg=reg, want_alpha=want_alpha)
         grad = np.full((B, nhyp + 1), np.nan)
@@ -579,14 +555,8 @@ def fit_batch_loo_grad(family, x, y, z, hyp, sig2n, reg=False, objective="loo", 
             with SympFit(family, x[b], y[b], z[b], hyp[b], s2[b], reg=reg) as f:
                 grad[b] = f.run().loo_grad(objective)[1]
         return alpha, nll, loo[:, which].copy(), grad, info
-    alpha = np.empty((B, n)) if want_alpha else None
-    nll = np.empty(B)
     value = np.empty(B)
     grad = np.empty((B, nhyp + 1))
-    info = np.zeros(B, dtype=np.int32)
-    L.check(L.load_library().sgpr_fit_batch_loo_grad(L.family_id(family), B, n_pts, L.dptr(x), L.dptr(y), L.dptr(z), L.dptr(hyp),
-                                                     nhyp, L.dptr(s2), L.FIT_REG if reg else 0, which,
-                                                     L.dptr(alpha) if want_alpha else None, L.dptr(nll), L.dptr(value),
-                                                     L.dptr(grad), info.ctypes.data_as(C.POINTER(C.c_int))),
-            "sgpr_fit_batch_loo_grad")
+    alpha, nll, info = _batch_run("sgpr_fit_batch_loo_grad", _batch_lead(family, arrays, B, n_pts, reg), B, n, want_alpha,
+                                  (value, grad), which)
     return alpha, nll, value, grad, info
