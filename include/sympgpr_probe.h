@@ -130,6 +130,22 @@ int sgpr_probe_strassen_rec_plan(int m, int n, int k, int lower, long scratch_do
 int sgpr_probe_strassen_rec_scratch(int n, unsigned long long out[2]);
 int sgpr_probe_gemm_strassen_rec_dev(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb,
                                      double beta, double *C, size_t ldc, int lower, void *stream);
+/* The operand sums beside the products.  Tunables, read at every call: gemm_strassen_overlap (1, the built-in value: a call's sums run on
+ * low-priority side streams under the products before the ones that need them; 0: everything on the caller's stream in list
+ * order), gemm_strassen_overlap_slack (doubles of the scratch beyond the call's need that second buffers may take; < 0: all, 0: none),
+ * gemm_strassen_overlap_streams (1, or 2 = the B side's sums on a side stream of their own), gemm_strassen_sum_wgs (most workgroups
+ * of a side-stream sum, 256 = one per CU).
+ * sgpr_probe_strassen_schedule: the schedule of ONE call (planned like sgpr_probe_strassen_rec_plan, with the scratch it needs) for
+ * a scratch buffer of capacity_doubles (< 0: exactly the need; below the need: an error).  32 words per record: [0 .. 15] the list's
+ * record, the inner plan of every kind-5 record expanded behind it; [16] level (0: the list's record, 1: a record of the inner plan
+ * of the kind-5 record before it); [17] stream (0: the caller's, 1 / 2: a side stream; sums only); [18] a sum: the buffer (0 / 1) of
+ * its region it writes; kinds 2 / 5: the buffer of the A-side scratch (inner / outer region) it reads, -1 a raw block; [19] kinds
+ * 2 / 5: likewise for the B side; [20] number of waits; [21 ...] the records (indices into the schedule, all earlier) it waits for.
+ * Under a kind-5 record the inner records' operands "A" / "B" are its operands: the raw block or the outer buffer [18] / [19].
+ * info: [0 .. 3] doubles per region (inner A, inner B, outer A, outer B: the pinned layout; second buffers lie behind it in the
+ * same order), [4 .. 7] buffers per region, [8] side streams, [9] the capacity.  tools/strassen_schedule.py replays it. */
+int sgpr_probe_strassen_schedule(int m, int n, int k, int lower, long capacity_doubles, long long info[12], long long *out,
+                                 int max_records, int *count);
 /* The arena layout of a batched fit as the drivers compute it (csrc/batch.hip: batch_layout), without a device call.  path: 0 the
  * one-launch path (order <= 256), 1 the mid path (256 < order <= 2048); mode: 0 fit, 1 nll gradient, 2 loo, 3 loo gradient (path 0
  * only); d: 0 for sgpr_fit_batch's x | y, 1 .. 3 for sgpr_fit_batch_nd (mode 0, reg 0).  The tunable batch_gradmid_chunk applies.

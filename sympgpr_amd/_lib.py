@@ -186,6 +186,8 @@ PROBE_SIGNATURES = {
     "sgpr_probe_strassen_rec_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.POINTER(C.c_long),
                                                C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_int)]),
     "sgpr_probe_strassen_rec_scratch": (C.c_int, [C.c_int, C.POINTER(C.c_ulonglong)]),
+    "sgpr_probe_strassen_schedule": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.POINTER(C.c_longlong),
+                                               C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_int)]),
     "sgpr_probe_gemm_strassen_rec_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                                    C.c_double, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     "sgpr_probe_gemm_nt4_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_double, C.c_int,

@@ -1212,6 +1212,39 @@ int side_stream(hipStream_t caller, hipStream_t *out, int *dev_out)
     return 0;
 }
 
+// The streams of the Strassen front end's operand sums (gemm_f64.hip: run_schedule): two per device at the LOWEST priority --
+// the sums fill what the products leave free and must never hold one up.  Same life as the side stream above.
+hipStream_t g_sum[64][2] = {};
+}  // namespace
+
+int strassen_sum_streams(hipStream_t caller, int count, hipStream_t *out)
+{
+    int dev = -1;
+    if (caller) {
+        SGPR_HIP(hipStreamGetDevice(caller, &dev));
+    } else {
+        SGPR_HIP(hipGetDevice(&dev));
+    }
+    if (dev < 0 || dev >= 64 || count < 1 || count > 2) { set_error("strassen_sum_streams: bad device or count"); return SGPR_E_ARG; }
+    std::lock_guard<std::mutex> lock(g_side_mu);
+    for (int t = 0; t < count; ++t) {
+        if (!g_sum[dev][t]) {
+            int cur = -1, lo = 0, hi = 0;
+            SGPR_HIP(hipGetDevice(&cur));
+            if (cur != dev) SGPR_HIP(hipSetDevice(dev));
+            hipError_t e = hipDeviceGetStreamPriorityRange(&lo, &hi);
+            if (e == hipSuccess) e = hipStreamCreateWithPriority(&g_sum[dev][t], hipStreamNonBlocking, lo);
+            if (e == hipSuccess) register_exit_release();
+            if (cur != dev) (void)hipSetDevice(cur);
+            SGPR_HIP(e);
+        }
+        out[t] = g_sum[dev][t];
+    }
+    return 0;
+}
+
+namespace {
+
 // ---- task-queue driver (cholq.h) ----------------------------------------------------------------------------------
 // One persistent worker grid runs every trailing-update tile and every rows-below solve of the block from an ordered
 // task list; the chain of diagonal blocks runs as one panel kernel per panel (diagonal strips + the rows of the next
@@ -1404,11 +1437,12 @@ void release_all_streams_at_exit()
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess) { (void)hipGetLastError(); return; }
     for (int dev = 0; dev < ndev && dev < 64; ++dev) {
-        hipStream_t drop[9] = {};
+        hipStream_t drop[11] = {};
         int nd = 0;
         {
             std::lock_guard<std::mutex> lock(g_side_mu);
             if (g_side[dev]) { drop[nd++] = g_side[dev]; g_side[dev] = nullptr; }
+            for (hipStream_t &s : g_sum[dev]) if (s) { drop[nd++] = s; s = nullptr; }
         }
         {
             QueueDevice &qd = g_qdev[dev];
@@ -1438,7 +1472,7 @@ int release_streams(int dev)
         bool any = false;
         {
             std::lock_guard<std::mutex> lock(g_side_mu);
-            any = g_side[dev] != nullptr;
+            any = g_side[dev] != nullptr || g_sum[dev][0] != nullptr || g_sum[dev][1] != nullptr;
         }
         QueueDevice &qd = g_qdev[dev];
         std::lock_guard<std::mutex> lock(qd.mu);
@@ -1460,6 +1494,8 @@ int release_streams(int dev)
     {
         std::lock_guard<std::mutex> lock(g_side_mu);
         drop(g_side[dev]);
+        drop(g_sum[dev][0]);
+        drop(g_sum[dev][1]);
     }
     {
         QueueDevice &qd = g_qdev[dev];

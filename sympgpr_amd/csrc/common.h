@@ -159,6 +159,13 @@ StrassenCfg strassen_rec_cfg(const StrassenRec &v, int k, int lower);
 int strassen_rec_plan(int m, int n, int k, int lower, long cfg_out[5], size_t scratch_doubles, std::vector<long long> &out);
 int gemm_nt_strassen_rec(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb, double beta,
                          double *C, size_t ldc, int lower, hipStream_t st);
+// the fourth probe entry: the schedule by which that list is executed with its operand sums on side streams (tunable
+// "gemm_strassen_overlap"; gemm_f64.hip: schedule_of) for a scratch buffer of cap_doubles (< 0: the call's need)
+constexpr int SCHED_REC = 32;                    // words per schedule record: the plan record + its annotations
+int strassen_schedule(int m, int n, int k, int lower, long long cap_doubles, long long info[12], std::vector<long long> &out);
+// chol.hip: the library's low-priority streams for those sums on the device of `caller` (count = 1 or 2; created on first use,
+// released with the look-ahead driver's side stream)
+int strassen_sum_streams(hipStream_t caller, int count, hipStream_t *out);
 void potrf_strassen_need(int n, size_t out[2]);  // chol.hip: what potrf() reserves at order n (both levels, one level)
 void strassen_reserve(size_t both, size_t one, hipStream_t st);
 int strassen_trim();                             // release the scratch of the operand sums (every device)

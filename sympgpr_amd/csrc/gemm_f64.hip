@@ -667,6 +667,7 @@ struct Scratch {
     hipEvent_t ev = nullptr;
     hipStream_t last = nullptr;
     bool used = false;
+    std::vector<hipEvent_t> pool;   // events of the overlapped execution (run_schedule), timing disabled, created on demand
 };
 Scratch g_scratch[64];
 
@@ -693,10 +694,12 @@ int device_of(hipStream_t st)
     return (dev >= 0 && dev < 64) ? dev : -1;
 }
 
-int block_sum(int rows, int cols, const double *X, size_t ldx, const double *Y, size_t ldy, double sign, double *T, hipStream_t st)
+constexpr long SUM_WGS = 2048;     // most workgroups of one sum (the kernel strides over its pieces)
+int block_sum(int rows, int cols, const double *X, size_t ldx, const double *Y, size_t ldy, double sign, double *T, hipStream_t st,
+              long wgs = SUM_WGS)
 {
     const long pieces = (long)((rows + 511) / 512) * ((cols + 3) / 4);
-    hipLaunchKernelGGL(block_sum_kernel, dim3((unsigned)std::min(pieces, 2048L)), dim3(256), 0, st, rows, cols, X, ldx, Y, ldy, sign, T);
+    hipLaunchKernelGGL(block_sum_kernel, dim3((unsigned)std::min(pieces, wgs)), dim3(256), 0, st, rows, cols, X, ldx, Y, ldy, sign, T);
     SGPR_CHECK_LAUNCH();
     return 0;
 }
@@ -706,7 +709,8 @@ int block_sum(int rows, int cols, const double *X, size_t ldx, const double *Y, 
 // a PLAN_PROD record with two destinations becomes a four-destination launch, one with one destination and a PLAN_CLASSIC
 // record a two-destination launch.
 int run_plan(const long long *recs, size_t nrec, double alpha, const double *A, size_t lda, const double *B, size_t ldb,
-             double beta, double *C, size_t ldc, double alpha2, double *C2, size_t ldc2, double *SA, double *SB, hipStream_t st)
+             double beta, double *C, size_t ldc, double alpha2, double *C2, size_t ldc2, double *SA, double *SB, hipStream_t st,
+             long sum_wgs = SUM_WGS)
 {
     for (size_t i = 0; i < nrec; ++i) {
         const long long *r = recs + i * STRASSEN_REC;
@@ -715,7 +719,7 @@ int run_plan(const long long *recs, size_t nrec, double alpha, const double *A, 
             const double *P = r[1] ? B : A;
             const size_t ld = r[1] ? ldb : lda;
             rc = block_sum((int)r[2], (int)r[3], P + r[4] + (size_t)r[5] * ld, ld, P + r[6] + (size_t)r[7] * ld, ld, (double)r[8],
-                           r[1] ? SB : SA, st);
+                           r[1] ? SB : SA, st, sum_wgs);
         } else if (r[0] == PLAN_PROD) {
             const int m = (int)r[7], n = (int)r[8], k = (int)r[9];
             const double *Ap = r[1] ? SA : A + r[2] + (size_t)r[3] * lda;
@@ -784,6 +788,210 @@ int run_plan2(const std::vector<long long> &plan, const Plan2Cfg &c, const Need2
             rc = run_plan(r, 1, alpha, A, lda, B, ldb, beta, C, ldc, 0.0, nullptr, 0, SA, SB, st);
         }
         if (rc) return rc;
+    }
+    return 0;
+}
+
+// ---- the operand sums beside the products -------------------------------------------------------------
+// The sums are HBM streaming, the products MFMA-bound; a sum needs neither LDS nor more registers than two product waves per
+// SIMD leave.  So a list can be executed with its sums on a low-priority side stream, each under the product before the one
+// that needs it.  Again the decision is host code that emits records and the device path executes exactly those:
+// schedule_of turns a list into a SCHEDULE -- the same records in the same order, the inner plan of every outer product expanded
+// behind it the way run_plan2 expands it, each record annotated (SCHED_REC words):
+//   [0 .. 15] the record   [16] level: 0 a record of the list, 1 a record of the inner plan of the outer product before it
+//   [17] stream: 0 the caller's (products, classical launches, the outer-product headers, which launch nothing), 1 / 2 a side stream
+//   [18] a sum: the buffer of its region it writes; a product: the buffer of the A-side scratch it reads (-1: a raw block) --
+//        PLAN_PROD the inner A region, PLAN2_PROD the outer one (its inner records read THAT buffer where they read "A")
+//   [19] a product: likewise for the B side (-1 otherwise)   [20] number of waits   [21 ...] the records it waits for
+// Regions: inner A, inner B, outer A, outer B, each with one buffer or two; the sums of a region alternate between its buffers.
+// Edges: a product waits for the sums whose buffers it reads; a sum waits for the last product that read the buffer it overwrites
+// (one buffer per region already lets the B sum of M3 run under M2, which reads the A scratch and a raw B block); an inner sum
+// or product that reads an outer buffer waits for the outer sum that wrote it; an outer sum waits for the last inner sum of each
+// side stream and the last inner product that read the buffer it overwrites.  "The last" is enough because a stream runs its
+// records in order; every wait points backwards in the list, so the host records an event before it enqueues a wait on it.
+// tests/test_strassen_overlap_cpu.py replays schedules in numpy in every order these edges allow.
+struct SchedCfg {
+    int nbuf[4] = {1, 1, 1, 1};     // buffers per region
+    size_t off[4][2] = {};          // their offsets in the scratch: the pinned layout first, second buffers behind it
+    int nstreams = 1;               // side streams: 1, or 2 = one per operand side
+};
+// Second buffers come out of the SLACK of the scratch (capacity - the call's need, capped by the tunable
+// "gemm_strassen_overlap_slack": < 0 all of it, 0 none), in the order inner A, inner B, outer A, outer B while it lasts.
+// Tunable "gemm_strassen_overlap_streams": 2 = the sums of the B side on a side stream of their own.
+SchedCfg sched_cfg_of(const Need2 &nd, size_t cap)
+{
+    SchedCfg sc;
+    sc.nstreams = tune("gemm_strassen_overlap_streams", 1) >= 2 ? 2 : 1;
+    const double lim = tune("gemm_strassen_overlap_slack", -1);
+    size_t slack = cap > nd.total() ? cap - nd.total() : 0, pos = 0;
+    if (lim >= 0) slack = std::min(slack, (size_t)lim);
+    for (int r = 0; r < 4; ++r) { sc.off[r][0] = pos; pos += nd.v[r]; }
+    for (int r = 0; r < 4; ++r) {
+        if (!nd.v[r]) continue;
+        if (nd.v[r] > slack) break;
+        sc.nbuf[r] = 2; sc.off[r][1] = pos; pos += nd.v[r]; slack -= nd.v[r];
+    }
+    return sc;
+}
+void schedule_of(const std::vector<long long> &plan, const Plan2Cfg &c, const Need2 &nd, const SchedCfg &sc, std::vector<long long> &out)
+{
+    struct Buf { long long writer = -1, prod_reader = -1, sum_reader[2] = {-1, -1}; };
+    Buf buf[4][2];
+    int next[4] = {0, 0, 0, 0}, cur[4] = {0, 0, 0, 0};
+    out.clear();
+    auto emit = [&](const long long *r, int level) {
+        const size_t at = out.size();
+        out.resize(at + SCHED_REC, 0);
+        for (int j = 0; j < STRASSEN_REC; ++j) out[at + j] = r[j];
+        out[at + 16] = level; out[at + 18] = out[at + 19] = -1;
+        return at;
+    };
+    auto wait = [&](size_t at, long long idx) {
+        if (idx < 0) return;
+        const int nw = (int)out[at + 20];
+        for (int j = 0; j < nw; ++j) if (out[at + 21 + j] == idx) return;
+        if (nw < SCHED_REC - 21) { out[at + 21 + nw] = idx; out[at + 20] = nw + 1; }   // (at most 4 by construction)
+    };
+    // record `at` reads buffer b of region rg as an operand of a launch on the caller's stream
+    auto read = [&](size_t at, int rg, int b) {
+        wait(at, buf[rg][b].writer);
+        buf[rg][b].prod_reader = (long long)(at / SCHED_REC);
+    };
+    // a sum into region rg; src >= 0: its operand is buffer sb of (outer) region src
+    auto sum = [&](const long long *r, int level, int rg, int src, int sb) {
+        const size_t at = emit(r, level);
+        const long long idx = (long long)(at / SCHED_REC);
+        const int stream = sc.nstreams == 2 ? 1 + (int)r[1] : 1, b = next[rg];
+        next[rg] = (b + 1) % sc.nbuf[rg];
+        Buf &t = buf[rg][b];
+        wait(at, t.prod_reader); wait(at, t.sum_reader[0]); wait(at, t.sum_reader[1]);
+        if (!out[at + 20]) wait(at, t.writer);
+        if (src >= 0) { wait(at, buf[src][sb].writer); buf[src][sb].sum_reader[stream - 1] = idx; }
+        t = Buf{};
+        t.writer = idx;
+        cur[rg] = b;
+        out[at + 17] = stream; out[at + 18] = b;
+    };
+    PlanCfg ci = under_of(c);
+    ci.scratch = nd.inner();
+    std::vector<long long> in;
+    for (size_t i = 0; i + STRASSEN_REC <= plan.size(); i += STRASSEN_REC) {
+        const long long *r = &plan[i];
+        if (r[0] == PLAN_SUM || r[0] == PLAN2_SUM) {
+            sum(r, 0, (r[0] == PLAN2_SUM ? 2 : 0) + (int)r[1], -1, 0);
+        } else if (r[0] == PLAN_PROD) {
+            const size_t at = emit(r, 0);
+            if (r[1]) { out[at + 18] = cur[0]; read(at, 0, cur[0]); }
+            if (r[4]) { out[at + 19] = cur[1]; read(at, 1, cur[1]); }
+        } else if (r[0] == PLAN2_PROD) {
+            const size_t hd = emit(r, 0);
+            const int xa = r[1] ? cur[2] : -1, yb = r[4] ? cur[3] : -1;     // the outer buffers its inner records read as A, B
+            out[hd + 18] = xa; out[hd + 19] = yb;
+            inner_plan(r, ci, in);
+            for (size_t j = 0; j + STRASSEN_REC <= in.size(); j += STRASSEN_REC) {
+                const long long *q = &in[j];
+                if (q[0] == PLAN_SUM) {
+                    const int ob = q[1] ? yb : xa;
+                    sum(q, 1, (int)q[1], ob >= 0 ? 2 + (int)q[1] : -1, std::max(ob, 0));
+                    continue;
+                }
+                const size_t at = emit(q, 1);
+                const bool a_scr = q[0] == PLAN_PROD && q[1], b_scr = q[0] == PLAN_PROD && q[4];
+                if (a_scr) { out[at + 18] = cur[0]; read(at, 0, cur[0]); } else if (xa >= 0) read(at, 2, xa);
+                if (b_scr) { out[at + 19] = cur[1]; read(at, 1, cur[1]); } else if (yb >= 0) read(at, 3, yb);
+            }
+        } else {
+            (void)emit(r, 0);       // a classical launch: raw blocks only
+        }
+    }
+}
+
+// On by default: n = 131 072 step 9303.1 / 9309.6 -> 9135.5 / 9137.6 ms (profiles/strassen_overlap/step.txt).  0: everything on the
+// caller's stream in list order (run_plan / run_plan2).
+bool overlap_on() { return tune("gemm_strassen_overlap", 1) != 0; }
+// Workgroups of a side-stream sum: one per CU, so that ONE sum wave (40 registers) sits beside the two product waves of a SIMD,
+// which leave 64 or 48 of 512; a second one (80) would keep the next product workgroup off that CU until the sums have drained.
+// Measured in the step (sweep.txt): 256 -1.8 %, 512 and 2048 (one launch's grid on the caller's stream) 0 ... -0.6 %.
+constexpr long SUM_WGS_SIDE = 256;
+
+// Execute a list through its schedule: S = the scratch (s.p), laid out by sc.  At entry the side streams wait for everything that
+// is on the caller's stream (the operands may have been written by the launches just before the call, and the scratch is
+// whoever used it last until the wait on Scratch::ev in front of this); every sum is consumed by a product of the caller's
+// stream, and on EVERY return, an error part-way through included, the caller's stream waits for the side streams once more:
+// the scratch may be reused or freed next.  All waits of a product are enqueued before gemm_nt* is called, so the start event of
+// an open profile window (gemm_launch) lies behind them.  Tunable "gemm_strassen_sum_wgs": most workgroups of a sum.
+int run_schedule(const std::vector<long long> &plan, const Plan2Cfg &c, const Need2 &nd, double alpha, const double *A, size_t lda,
+                 const double *B, size_t ldb, double beta, double *C, size_t ldc, Scratch &s, hipStream_t st)
+{
+    const SchedCfg sc = sched_cfg_of(nd, s.cap);
+    std::vector<long long> sch;
+    schedule_of(plan, c, nd, sc, sch);
+    const size_t nrec = sch.size() / SCHED_REC;
+    const long wgs = std::min(65535L, std::max(1L, (long)tune("gemm_strassen_sum_wgs", (double)SUM_WGS_SIDE)));
+    hipStream_t str[3] = {st, nullptr, nullptr};
+    int rc = strassen_sum_streams(st, sc.nstreams, str + 1);
+    if (rc) return rc;
+    // events: [0 .. nstreams) entry and exit, 2 + i behind record i where a record of another stream waits for it
+    std::vector<char> needs(nrec, 0);
+    for (size_t i = 0; i < nrec; ++i) {
+        const long long *q = &sch[i * SCHED_REC];
+        for (int j = 0; j < (int)q[20]; ++j)
+            if (sch[(size_t)q[21 + j] * SCHED_REC + 17] != q[17]) needs[(size_t)q[21 + j]] = 1;
+    }
+    if (s.pool.size() < nrec + 2) s.pool.resize(nrec + 2, nullptr);
+    auto event = [&](size_t i) {
+        if (!s.pool[i]) SGPR_HIP(hipEventCreateWithFlags(&s.pool[i], hipEventDisableTiming));
+        return 0;
+    };
+    if ((rc = event(0)) || (rc = event(1))) return rc;
+    SGPR_HIP(hipEventRecord(s.pool[0], st));
+    for (int t = 1; t <= sc.nstreams; ++t) SGPR_HIP(hipStreamWaitEvent(str[t], s.pool[0], 0));
+    struct Join {
+        hipStream_t *str; int n; hipEvent_t *ev;
+        ~Join()
+        {
+            for (int t = 1; t <= n; ++t)
+                if (hipEventRecord(ev[t - 1], str[t]) != hipSuccess || hipStreamWaitEvent(str[0], ev[t - 1], 0) != hipSuccess) {
+                    (void)hipGetLastError();
+                    (void)hipStreamSynchronize(str[t]);
+                }
+        }
+    } join{str, sc.nstreams, s.pool.data()};
+    auto at = [&](int rg, long long b) { return s.p + sc.off[rg][b < 0 ? 0 : b]; };
+    const long long *hd = nullptr;      // the outer product whose inner records are running
+    for (size_t i = 0; i < nrec; ++i) {
+        const long long *q = &sch[i * SCHED_REC];
+        hipStream_t me = str[q[17]];
+        for (int j = 0; j < (int)q[20]; ++j) {
+            const size_t w = (size_t)q[21 + j];
+            if (sch[w * SCHED_REC + 17] != q[17]) SGPR_HIP(hipStreamWaitEvent(me, s.pool[2 + w], 0));
+        }
+        if (q[0] == PLAN2_PROD) {
+            hd = q;
+            continue;
+        }
+        if (q[0] == PLAN2_SUM) {
+            const double *P = q[1] ? B : A;
+            const size_t ld = q[1] ? ldb : lda;
+            rc = block_sum((int)q[2], (int)q[3], P + q[4] + (size_t)q[5] * ld, ld, P + q[6] + (size_t)q[7] * ld, ld, (double)q[8],
+                           at(2 + (int)q[1], q[18]), me, wgs);
+        } else if (q[16] == 0) {
+            // a sum's [18] is the buffer it writes, a product's [18] / [19] the buffers it reads
+            rc = run_plan(q, 1, alpha, A, lda, B, ldb, beta, C, ldc, 0.0, nullptr, 0, at(0, q[0] == PLAN_SUM && q[1] ? 0 : q[18]),
+                          at(1, q[0] == PLAN_SUM ? q[18] : q[19]), me, wgs);
+        } else {
+            const long long *r = hd;
+            const double *X = r[1] ? at(2, r[18]) : A + r[2] + (size_t)r[3] * lda;
+            const double *Y = r[4] ? at(3, r[19]) : B + r[5] + (size_t)r[6] * ldb;
+            rc = run_plan(q, 1, alpha * (double)r[12], X, r[1] ? (size_t)r[7] : lda, Y, r[4] ? (size_t)r[8] : ldb, 1.0,
+                          C + r[10] + (size_t)r[11] * ldc, ldc, alpha * (double)r[15], r[15] ? C + r[13] + (size_t)r[14] * ldc : nullptr, ldc,
+                          at(0, q[0] == PLAN_SUM && q[1] ? 0 : q[18]), at(1, q[0] == PLAN_SUM ? q[18] : q[19]), me, wgs);
+        }
+        if (rc) return rc;
+        if (needs[i]) {
+            if ((rc = event(2 + i))) return rc;
+            SGPR_HIP(hipEventRecord(s.pool[2 + i], me));
+        }
     }
     return 0;
 }
@@ -881,6 +1089,32 @@ int strassen_rec_plan(int m, int n, int k, int lower, long cfg_out[5], size_t sc
     return 0;
 }
 
+// The schedule of that call (schedule_of) for a scratch buffer of cap_doubles: the list as gemm_nt_strassen_cfg plans it with
+// the scratch it needs (both levels, as far as SGPR_GEMM_STRASSEN allows).  info: [0 .. 3] doubles per region (inner A, inner B,
+// outer A, outer B), [4 .. 7] buffers per region, [8] side streams, [9] the capacity.  A capacity below the need is an error.
+int strassen_schedule(int m, int n, int k, int lower, long long cap_doubles, long long info[12], std::vector<long long> &out)
+{
+    if (m < 0 || n < 0 || k < 0 || (lower && m != n)) { set_error("strassen_schedule: bad extents"); return SGPR_E_ARG; }
+    const Plan2Cfg c = cfg2_of(strassen_rec_cfg(strassen_rec_values(), k, lower), ~(size_t)0);
+    std::vector<long long> plan;
+    if (strassen_levels() >= 2 && !outer_noscratch()) outer_plan_of(m, n, k, lower, c, plan);
+    else {
+        const int rc = strassen_plan(m, n, k, lower, c.in.smin, c.in.kslab, ~(size_t)0, plan);
+        if (rc) return rc;
+    }
+    const Need2 nd = plan2_need(plan, c);
+    const size_t cap = cap_doubles < 0 ? nd.total() : (size_t)cap_doubles;
+    if (cap < nd.total()) { set_error("strassen_schedule: the capacity is below the call's need"); return SGPR_E_ARG; }
+    const SchedCfg sc = sched_cfg_of(nd, cap);
+    schedule_of(plan, c, nd, sc, out);
+    if (info) {
+        for (int i = 0; i < 12; ++i) info[i] = 0;
+        for (int r = 0; r < 4; ++r) { info[r] = (long long)nd.v[r]; info[4 + r] = sc.nbuf[r]; }
+        info[8] = sc.nstreams; info[9] = (long long)cap;
+    }
+    return 0;
+}
+
 // scratch of one call: levels = 1 the inner pair alone, 2 both pairs (as far as SGPR_GEMM_STRASSEN allows)
 size_t strassen_scratch_doubles(int m, int n, int k, int lower, int levels)
 {
@@ -917,6 +1151,8 @@ int strassen_trim()
         std::lock_guard<std::mutex> lock(s.mu);
         if (s.p) (void)hipFree(s.p);          // waits for whatever still uses it
         if (s.ev) (void)hipEventDestroy(s.ev);
+        for (hipEvent_t e : s.pool) if (e) (void)hipEventDestroy(e);
+        s.pool.clear();
         s.p = nullptr; s.ev = nullptr; s.cap = 0; s.failed = 0; s.used = false; s.last = nullptr;
     }
     (void)hipGetLastError();
@@ -948,6 +1184,7 @@ int gemm_nt_strassen_cfg(int m, int n, int k, double alpha, const double *A, siz
     std::vector<long long> plan;
     int rc = 0;
     const int dev = device_of(st);
+    const bool overlap = overlap_on();      // the sums on a side stream under the products (run_schedule)
     auto enqueue = [&](Scratch &s, auto &&run) {
         if (!s.ev) SGPR_HIP(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
         if (s.used && s.last != st) SGPR_HIP(hipStreamWaitEvent(st, s.ev, 0));
@@ -965,7 +1202,10 @@ int gemm_nt_strassen_cfg(int m, int n, int k, double alpha, const double *A, siz
             Scratch &s = g_scratch[dev];
             std::lock_guard<std::mutex> lock(s.mu);
             if (scratch_ensure(s, nd.total()))
-                return enqueue(s, [&] { return run_plan2(plan, c2, nd, alpha, A, lda, B, ldb, beta, C, ldc, s.p, st); });
+                return enqueue(s, [&] {
+                    return overlap ? run_schedule(plan, c2, nd, alpha, A, lda, B, ldb, beta, C, ldc, s, st)
+                                   : run_plan2(plan, c2, nd, alpha, A, lda, B, ldb, beta, C, ldc, s.p, st);
+                });
         }
     }
     rc = strassen_plan(m, n, k, lower, c2.in.smin, c2.in.kslab, ~(size_t)0, plan);
@@ -980,10 +1220,10 @@ int gemm_nt_strassen_cfg(int m, int n, int k, double alpha, const double *A, siz
         if ((rc = strassen_plan(m, n, k, lower, c2.in.smin, c2.in.kslab, s.cap, plan))) return rc;
         if (!plan_need(plan)) return run_plan(plan, alpha, A, lda, B, ldb, beta, C, ldc, nullptr, nullptr, st);
     }
-    size_t na = 0;
-    for (size_t i = 0; i + STRASSEN_REC <= plan.size(); i += STRASSEN_REC)
-        if (plan[i] == PLAN_SUM && plan[i + 1] == 0) na = std::max(na, (size_t)plan[i + 2] * (size_t)plan[i + 3]);
-    return enqueue(s, [&] { return run_plan(plan, alpha, A, lda, B, ldb, beta, C, ldc, s.p, s.p + na, st); });
+    // (a list of the inner level alone: plan2_need gives its two regions, the layout is [A | B] either way)
+    const Need2 nd = plan2_need(plan, c2);
+    if (overlap) return enqueue(s, [&] { return run_schedule(plan, c2, nd, alpha, A, lda, B, ldb, beta, C, ldc, s, st); });
+    return enqueue(s, [&] { return run_plan(plan, alpha, A, lda, B, ldb, beta, C, ldc, s.p, s.p + nd.v[0], st); });
 }
 
 }  // namespace sgpr

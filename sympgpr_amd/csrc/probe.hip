@@ -583,6 +583,19 @@ extern "C" int sgpr_probe_strassen_rec_scratch(int n, unsigned long long out[2])
     out[0] = need[0]; out[1] = need[1];
     return 0;
 }
+// ---- the schedule by which that list runs with its operand sums on side streams (32 words per record), for a scratch buffer
+// of capacity_doubles (< 0: the call's need)
+extern "C" int sgpr_probe_strassen_schedule(int m, int n, int k, int lower, long capacity_doubles, long long info[12], long long *out,
+                                            int max_records, int *count)
+{
+    if (!count) { set_error("probe_strassen_schedule: bad arguments"); return SGPR_E_ARG; }
+    std::vector<long long> sched;
+    const int rc = strassen_schedule(m, n, k, lower, (long long)capacity_doubles, info, sched);
+    if (rc) return rc;
+    *count = (int)(sched.size() / SCHED_REC);
+    for (size_t i = 0; out && i < sched.size() && (int)(i / SCHED_REC) < max_records; ++i) out[i] = sched[i];
+    return 0;
+}
 // one product as the recursion would issue it (its thresholds for this k and kind), on device pointers
 extern "C" int sgpr_probe_gemm_strassen_rec_dev(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb,
                                                 double beta, double *C, size_t ldc, int lower, void *stream)
