@@ -332,10 +332,30 @@ int sgpr_fit_batch(int family, int nbatch, int n_pts, const double *x, const dou
  * scratch per chunk: one npad x npad image per problem (npad = n rounded up to 128), at most ~2 GiB, plus the leaf inverses and
  * solve vectors.  All of it lives in the sgpr_fit_batch arena of the calling thread; sgpr_trim gives it back.
  * SGPR_E_ARG (before any device call) for d outside 1..3, an unknown family, a wrong nhyp, flags != 0 (there is no scalar-kernel
- * d-pair fit), nbatch < 0, n_pts <= 0, n above the maximum and a null pointer other than alpha; nbatch == 0 returns 0.  There
- * is no batched d-pair gradient or leave-one-out yet.  ABI 5 (an additional entry point). */
+ * d-pair fit), nbatch < 0, n_pts <= 0, n above the maximum and a null pointer other than alpha; nbatch == 0 returns 0.  The
+ * gradient is sgpr_fit_batch_nd_grad; there is no batched d-pair leave-one-out yet.  ABI 5 (an additional entry point). */
 int sgpr_fit_batch_nd(int family, int d, int nbatch, int n_pts, const double *X, const double *z, const double *hyp,
                       int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, int *info);
+/* sgpr_fit_batch_nd plus d nll / d(hyp, sig2n) per problem, for every order n = 2 d n_pts <= sgpr_fit_batch_max_order() (2048) in
+ * one entry.  X, z, hyp, nhyp, sig2n, alpha (may be NULL), nll and info exactly as sgpr_fit_batch_nd.  grad: nbatch x (nhyp + 1),
+ * row-major; row b = (d/dlq_1..d/dlq_d, d/dlP_1..d/dlP_d, [d/dp_1..d/dp_d,] d/dsig, d/dsig2n), the order of
+ * sgpr_fit_nll_grad_full on an sgpr_fit_create_nd handle.  Ky holds |sig2n[b]|, so the last entry is sign(sig2n[b]) * 1/2 (tr Ky^-1
+ * - alpha^T alpha), with sign(0) = +1.  info[b] > 0: nll[b] and the whole row grad[b] are NaN, the other problems are untouched
+ * and the call returns 0.  nll, alpha and info are bit-identical to sgpr_fit_batch_nd's (the same Gram stage, factor and solves);
+ * a problem's gradient bits do not depend on its place in the batch, the batch size, the chunk it falls into or a repetition of
+ * the call (no atomics, no waiting between workgroups in the gradient phase).
+ * n <= 256: ONE launch, one workgroup per problem: after the fit it forms L^-T from the leaf inverses and Ky^-1 = L^-T L^-1 over L
+ * (the code of sgpr_fit_batch_grad), then thread i takes row i of Ky^-1 - alpha alpha^T -- part i / n_pts of point i % n_pts -- and
+ * walks the column points: each point pair is evaluated once, dK from the generated forms, and feeds its 2d entries of the row
+ * (W_ii on the diagonal, 2 W_ij below it).  Scratch per workgroup as sgpr_fit_batch_grad: ~1.3 MiB, at most 1024 workgroups.
+ * 256 < n <= 2048: sgpr_fit_batch_nd's mid path with both images, then the Ky^-1 stage of sgpr_fit_batch_grad_mid (unchanged) and
+ * one contraction launch over rows x column points with a fold per problem; chunks and scratch as sgpr_fit_batch_grad_mid, the
+ * partials 16 doubles wide (up to 3d + 2 = 11 sums).  The arena is sgpr_fit_batch's; sgpr_trim gives it back.
+ * SGPR_E_ARG (before any device call) for d outside 1..3, an unknown family, a wrong nhyp, flags != 0, nbatch < 0, n_pts <= 0, n
+ * above the maximum and a null pointer other than alpha (grad is required); nbatch == 0 returns 0.  ABI 5 (an additional entry
+ * point). */
+int sgpr_fit_batch_nd_grad(int family, int d, int nbatch, int n_pts, const double *X, const double *z, const double *hyp,
+                           int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, double *grad, int *info);
 /* sgpr_fit_batch plus d nll / d(hyp, sig2n) per problem.  Order per problem n = 2 n_pts (n_pts with SGPR_FIT_REG) <= 256.
  * grad: nbatch x (nhyp + 1), row-major; row b = (d/dhyp_0 .. d/dhyp_{nhyp-1}, d/dsig2n).  hyp layout and nhyp as
  * sgpr_fit_batch: (lx, ly, sig), or (lx, ly, p, sig) for families with a period.  Ky holds |sig2n[b]|, so the last entry is

@@ -148,7 +148,7 @@ int sgpr_probe_strassen_schedule(int m, int n, int k, int lower, long capacity_d
                                  int max_records, int *count);
 /* The arena layout of a batched fit as the drivers compute it (csrc/batch.hip: batch_layout), without a device call.  path: 0 the
  * one-launch path (order <= 256), 1 the mid path (256 < order <= 2048); mode: 0 fit, 1 nll gradient, 2 loo, 3 loo gradient (path 0
- * only); d: 0 for sgpr_fit_batch's x | y, 1 .. 3 for sgpr_fit_batch_nd (mode 0, reg 0).  The tunable batch_gradmid_chunk applies.
+ * only); d: 0 for sgpr_fit_batch's x | y, 1 .. 3 for sgpr_fit_batch_nd[_grad] (mode 0 or 1, reg 0).  The tunable batch_gradmid_chunk applies.
  * out: [0] problems per chunk, [1] doubles behind nll per problem; byte offsets [2 .. 6] x, y, z, consts, noise of the input block
  * and [7] its size; [8 .. 10] alpha, nll, info of the output block and [11] its size; [12 .. 19] the mid path's scratch regions L / U
  * images, leaf inverses, flags of panel 1, of panel 2, solve vectors, publication buffers, state words, partials (0 on path 0) and

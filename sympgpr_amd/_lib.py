@@ -139,6 +139,8 @@ SIGNATURES = {
                                  C.POINTER(C.c_int)]),
     "sgpr_fit_batch_nd": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_uint, _dp, _dp,
                                     C.POINTER(C.c_int)]),
+    "sgpr_fit_batch_nd_grad": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_uint, _dp, _dp, _dp,
+                                         C.POINTER(C.c_int)]),
     "sgpr_fit_batch_grad": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_uint, _dp, _dp, _dp,
                                       C.POINTER(C.c_int)]),
     "sgpr_fit_batch_grad_mid": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_uint, _dp, _dp, _dp,

@@ -13,7 +13,8 @@
 // L22 = leaf(A22);  y = L^-1 z and alpha = L^-T y through the leaf inverses.  Latency-bound by
 // construction: throughput comes from the number of problems in flight, not from the matrix cores.
 // Problems with d canonical pairs per point (sgpr_fit_batch_nd) take the same path behind a Gram stage of their own: the entry
-// formulas of nd_eval.h, fit_batch_nd_kernel / mid_build_nd_kernel.
+// formulas of nd_eval.h, fit_batch_nd_kernel / mid_build_nd_kernel.  Their nll gradient (sgpr_fit_batch_nd_grad) is that path with the
+// Ky^-1 stage of the d = 1 gradient and a contraction over D x D blocks of point pairs: contract_rows_nd / mid_grad_nd_kernel.
 // The device code is in batch_small.h (n <= 256) and batch_mid.h (256 < n <= 2048), included here and only here: one translation
 // unit.  This file holds the arena, its one layout function, the staging of a call and the two host drivers.
 #include <cmath>
@@ -139,11 +140,13 @@ int fetch_out(const BatchCall &c, const BatchLayout &l, const Blocks &m, int b0,
 }
 
 // The sums behind nll (problem b's at nll + chunk + b nacc) into the caller's rows b0 ..: the raw gradient sums scaled (sig from the
-// problem's staged KConst), {loo, press} and the loo gradient's value copied out, NaN rows where the factorisation failed.
+// problem's staged KConst, or NdConst for d > 0), {loo, press} and the loo gradient's value copied out, NaN rows where the
+// factorisation failed.
 void finish_rows(const BatchCall &c, const BatchLayout &l, const Blocks &m, int b0, int nb)
 {
     const double *raw = at<const double>(m.hout, l.o_nll) + l.chunk;
     const KConst *kcs = at<const KConst>(m.hin, l.o_kc);
+    const nd::NdConst *ncs = at<const nd::NdConst>(m.hin, l.o_kc);
     const size_t B = (size_t)nb, nacc = l.nacc, ngrad = (size_t)c.nhyp + 1;
     const int nhyp = c.nhyp;
     if (c.grad) {
@@ -157,7 +160,7 @@ void finish_rows(const BatchCall &c, const BatchLayout &l, const Blocks &m, int 
                 for (size_t k = 0; k < ngrad; ++k) g[k] = std::nan("");
                 continue;
             }
-            const double sig = kcs[b].sig;
+            const double sig = c.d ? ncs[b].sig : kcs[b].sig;
             for (int k = 0; k < nhyp - 1; ++k) g[k] = 0.5 * sig * r[k];
             g[nhyp - 1] = 0.5 * r[nhyp - 1];
             g[nhyp] = (c.sig2n[row] < 0.0 ? -0.5 : 0.5) * r[nhyp];
@@ -240,7 +243,8 @@ BatchLayout batch_layout(int mid, int mode, int d, int reg, int nbatch, int npts
     l.o_pub = l.o_r + up256(C * l.npad * 8);
     l.o_st = l.o_pub + up256(2 * C * l.npad * 8);
     l.o_part = l.o_st + up256(C * 8 * sizeof(int));
-    l.scr_bytes = l.o_part + (mode == MODE_GRAD ? up256(C * l.ggx * l.ggy * GPART * 8) : mode == MODE_LOO ? up256(C * l.lnwg * 2 * 8) : 0);
+    // (GPART doubles per partial; GPART_ND for d > 0, whose sums number up to 11)
+    l.scr_bytes = l.o_part + (mode == MODE_GRAD ? up256(C * l.ggx * l.ggy * (d ? GPART_ND : GPART) * 8) : mode == MODE_LOO ? up256(C * l.lnwg * 2 * 8) : 0);
     return l;
 }
 
@@ -264,7 +268,10 @@ int fit_batch_small(const BatchCall &c)
                             at<double>(m.din, l.o_no), at<double>(m.dscr, 0), c.alpha ? at<double>(m.dout, l.o_al) : nullptr,
                             at<double>(m.dout, l.o_nll), at<int>(m.dout, l.o_info)};
         if ((rc = nd::dispatch_nd(c.family, c.d, [&](auto fam, auto dd) {
-                hipLaunchKernelGGL((fit_batch_nd_kernel<decltype(fam)::value, decltype(dd)::value>), g, t, 0, st, a);
+                if (mode == MODE_GRAD)
+                    hipLaunchKernelGGL((fit_batch_nd_kernel<decltype(fam)::value, decltype(dd)::value, MODE_GRAD>), g, t, 0, st, a);
+                else
+                    hipLaunchKernelGGL((fit_batch_nd_kernel<decltype(fam)::value, decltype(dd)::value, MODE_FIT>), g, t, 0, st, a);
                 return 0;
             })))
             return rc;
@@ -295,7 +302,7 @@ int fit_batch_small(const BatchCall &c)
 // ---- problems of order 256 < n <= 2048 (batch_mid.h): chunks of problems share the scratch images; every chunk runs the stages
 // below on the stream, in this order.  With grad or loo (the Ky^-1 phase) a second image per problem (U = L^-T) stands behind the L
 // images, and the sums come back behind nll in the chunk's one device-to-host copy.  d > 0: X in place of x | y, one NdConst per
-// problem, mid_build_nd_kernel in place of mid_build_kernel; no gradient or loo phase.
+// problem, mid_build_nd_kernel in place of mid_build_kernel and mid_grad_nd_kernel in place of mid_grad_kernel; no loo phase.
 
 // the device pointers of one chunk of nb problems
 struct MidChunk {
@@ -437,12 +444,21 @@ int mid_loo(hipStream_t st, const BatchCall &c, const BatchLayout &l, const MidC
 // (c) the contraction of Ky^-1 - alpha alpha^T with dK and its fold: the raw gradient sums behind nll
 int mid_grad(hipStream_t st, const BatchCall &c, const BatchLayout &l, const MidChunk &k)
 {
-    const MidGrad mg{c.npts, c.n, c.reg, l.ggx * l.ggy, (int)l.nacc, (size_t)l.npad, k.a.x, k.a.y, k.a.kc, k.A, k.r, k.part, k.info, k.sums};
+    const MidGrad mg{c.npts, c.n, c.reg, l.ggx * l.ggy, (int)l.nacc, c.d ? GPART_ND : GPART, (size_t)l.npad, k.a.x, k.a.y, k.a.kc, k.A, k.r,
+                     k.part, k.info, k.sums};
     const dim3 gg((unsigned)l.ggx, (unsigned)l.ggy, (unsigned)k.nb);
-    (void)dispatch_family(c.family, [&](auto fam) {             // the family has been checked
-        hipLaunchKernelGGL(mid_grad_kernel<decltype(fam)::value>, gg, dim3(GT), 0, st, mg);
-        return 0;
-    });
+    if (c.d) {
+        const MidGradNd mn{c.npts, c.n, mg.nwg, mg.ld, k.a.x, reinterpret_cast<const nd::NdConst *>(k.a.kc), k.A, k.r, k.part};
+        const int rc = nd::dispatch_nd(c.family, c.d, [&](auto fam, auto dd) {
+            hipLaunchKernelGGL((mid_grad_nd_kernel<decltype(fam)::value, decltype(dd)::value>), gg, dim3(GT), 0, st, mn);
+            return 0;
+        });
+        if (rc) return rc;
+    } else
+        (void)dispatch_family(c.family, [&](auto fam) {         // the family has been checked
+            hipLaunchKernelGGL(mid_grad_kernel<decltype(fam)::value>, gg, dim3(GT), 0, st, mg);
+            return 0;
+        });
     SGPR_CHECK_LAUNCH();
     hipLaunchKernelGGL(mid_grad_fold_kernel, dim3(k.nb), dim3(64), 0, st, mg);
     SGPR_CHECK_LAUNCH();
@@ -509,6 +525,15 @@ int fit_batch_nd(int family, int d, int nbatch, int npts, const double *X, const
 {
     const BatchCall c{family, d, 0, nbatch, npts, 2 * d * npts, nhyp, X, nullptr, z, hyp, sig2n, alpha, nll, info,
                       nullptr, nullptr, nullptr, SGPR_LOO_LPD};
+    return c.n > BMAX ? fit_batch_mid(c) : fit_batch_small(c);
+}
+
+// sgpr_fit_batch_nd_grad: n = 2 d npts <= fit_batch_max_order()
+int fit_batch_nd_grad(int family, int d, int nbatch, int npts, const double *X, const double *z, const double *hyp, int nhyp,
+                      const double *sig2n, double *alpha, double *nll, double *grad, int *info)
+{
+    const BatchCall c{family, d, 0, nbatch, npts, 2 * d * npts, nhyp, X, nullptr, z, hyp, sig2n, alpha, nll, info,
+                      grad, nullptr, nullptr, SGPR_LOO_LPD};
     return c.n > BMAX ? fit_batch_mid(c) : fit_batch_small(c);
 }
 

@@ -200,6 +200,7 @@ __global__ __launch_bounds__(ST) void mid_finish_kernel(const MidArgs a, const d
 constexpr int GT = 256;                   // contraction: rows per workgroup (one per thread)
 constexpr int GCJ = 64;                   // contraction: column points per workgroup
 constexpr int GPART = 8;                  // doubles per workgroup partial (>= grad_nacc)
+constexpr int GPART_ND = 16;              // the same for d canonical pairs per point (>= grad_nacc_nd: 11 at d = 3 with periods)
 
 struct MidInv {
     double *L, *U;        // problem b at L / U + b * stride (column-major, ld)
@@ -265,12 +266,12 @@ __global__ __launch_bounds__(256, 2) void mid_kinv_kernel(const MidInv a)
 }
 
 struct MidGrad {
-    int npts, n, reg, nwg, nacc;
+    int npts, n, reg, nwg, nacc, gpart;   // gpart: doubles per partial (GPART; GPART_ND behind mid_grad_nd_kernel)
     size_t ld;                            // npad: Ky^-1 (lower) of problem b at K + b ld^2, its alpha at alpha + b ld
     const double *x, *y;
     const KConst *kc;
     const double *K, *alpha;
-    double *part;                         // sum k of workgroup w of problem b at part[(b nwg + w) GPART + k]
+    double *part;                         // sum k of workgroup w of problem b at part[(b nwg + w) gpart + k]
     const int *info;
     double *out;                          // problem b's raw sums at out + b nacc
 };
@@ -350,14 +351,95 @@ __global__ __launch_bounds__(GT) void mid_grad_kernel(const MidGrad a)
     }
 }
 
+// The contraction for d canonical pairs per point (D = 2 d, n = D N): mid_grad_kernel's grid and tiling -- GT rows per workgroup,
+// one per thread, GCJ column points in LDS, now D coordinates and D alpha entries each, blockIdx.z the problem -- and
+// contract_rows_nd's rows (row i is part r = i / N of point i % N), weights and stop.  NACC = grad_nacc_nd (up to 11) sums per
+// workgroup, GPART_ND doubles apart; mid_grad_fold_kernel sums them (MidGrad::gpart).
+struct MidGradNd {
+    int npts, n, nwg;
+    size_t ld;                            // npad: Ky^-1 (lower) of problem b at K + b ld^2, its alpha at alpha + b ld
+    const double *X;                      // nbatch x D x npts
+    const nd::NdConst *nc;
+    const double *K, *alpha;
+    double *part;                         // sum k of workgroup w of problem b at part[(b nwg + w) GPART_ND + k]
+};
+
+template <int FAM, int D>
+__global__ __launch_bounds__(GT) void mid_grad_nd_kernel(const MidGradNd a)
+{
+    constexpr bool HASP = grad_has_p<FAM>();
+    constexpr int NACC = grad_nacc_nd<FAM, D>(), d = D / 2;
+    static_assert(NACC <= GPART_ND, "a workgroup's sums fit in its partial");
+    __shared__ double sxa[GCJ][D], sal[D][GCJ];
+    __shared__ double red[GT / 64][NACC];
+    const int b = blockIdx.z, N = a.npts, n = a.n, tid = threadIdx.x;
+    const int p0 = blockIdx.y * GCJ, np = min(GCJ, N - p0);
+    const int i = blockIdx.x * GT + tid;
+    const double *X = a.X + (size_t)b * D * N;
+    const double *K = a.K + (size_t)b * a.ld * a.ld, *al = a.alpha + (size_t)b * a.ld;
+    for (int e = tid; e < np * D; e += GT) {
+        const int jj = e % np, m = e / np;
+        sxa[jj][m] = X[(size_t)m * N + p0 + jj];
+        sal[m][jj] = al[(size_t)m * N + p0 + jj];
+    }
+    __syncthreads();
+    const nd::NdConst nc = a.nc[b];
+    double l[D], pp[d];
+#pragma unroll
+    for (int m = 0; m < D; ++m) l[m] = nc.l[m];
+#pragma unroll
+    for (int m = 0; m < d; ++m) pp[m] = HASP ? nc.hs[m] : 0.0;
+    double acc[NACC];
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
+    if (i < n && p0 <= i) {
+        const int r = i / N, pi = i - r * N;
+        const double ai = al[i];
+        const double *Krow = K + i;
+        double xi[D];
+#pragma unroll
+        for (int m = 0; m < D; ++m) xi[m] = X[(size_t)m * N + pi];
+        for (int jj = 0; jj < np; ++jj) {
+            const int pj = p0 + jj;
+            if (pj > i) break;                                // column pj > i: so are all after it
+            double w[D], xj[D];
+#pragma unroll
+            for (int c = 0; c < D; ++c) {                     // column c N + pj: part c of the column point
+                const int col = c * N + pj;
+                w[c] = 0.0;
+                if (col <= i) {
+                    const double W = Krow[(size_t)col * a.ld] - ai * sal[c][jj];
+                    if (col == i) { w[c] = W; acc[NACC - 1] += W; }
+                    else w[c] = 2.0 * W;
+                }
+            }
+#pragma unroll
+            for (int m = 0; m < D; ++m) xj[m] = sxa[jj][m];
+            nllg::pair_grad<FAM, D, HASP>(xi, xj, w, r, l, pp, acc);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) {
+        const double v = wave_sum(acc[k]);
+        if ((tid & 63) == 0) red[tid >> 6][k] = v;
+    }
+    __syncthreads();
+    if (tid < NACC) {
+        double v = red[0][tid];
+#pragma unroll
+        for (int w = 1; w < GT / 64; ++w) v += red[w][tid];
+        a.part[((size_t)b * a.nwg + (size_t)blockIdx.y * gridDim.x + blockIdx.x) * GPART_ND + tid] = v;
+    }
+}
+
 // problem blockIdx.x: its workgroups' partials in their fixed order; NaN where the factorisation failed
 __global__ __launch_bounds__(64) void mid_grad_fold_kernel(const MidGrad a)
 {
     const int b = blockIdx.x, k = threadIdx.x;
     if (k >= a.nacc) return;
-    const double *p = a.part + (size_t)b * a.nwg * GPART + k;
+    const double *p = a.part + (size_t)b * a.nwg * a.gpart + k;
     double v = 0.0;
-    for (int w = 0; w < a.nwg; ++w) v += p[(size_t)w * GPART];
+    for (int w = 0; w < a.nwg; ++w) v += p[(size_t)w * a.gpart];
     a.out[(size_t)b * a.nacc + k] = a.info[b] != 0 ? __builtin_nan("") : v;
 }
 

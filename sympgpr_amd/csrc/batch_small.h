@@ -1,6 +1,6 @@
 // batch_small.h -- device code of the one-launch batched fits (order n <= 256, one workgroup per problem): the shared fit body,
-// the d = 1 and d-pair kernels, the leave-one-point-out sums and the gradient phases.  Included only by batch.hip, behind its
-// other headers (one translation unit).
+// the d = 1 and d-pair kernels, the leave-one-point-out sums and the gradient phases (d = 1: grad_problem; d pairs:
+// grad_problem_nd).  Included only by batch.hip, behind its other headers (one translation unit).
 #pragma once
 
 namespace sgpr {
@@ -198,8 +198,9 @@ struct BatchNdArgs {
     const double *X, *z;                  // nbatch x D x npts (coordinate m of point i of problem b at (b D + m) npts + i), nbatch x n
     const nd::NdConst *nc;                // per problem
     const double *noise;                  // per problem, >= 0
-    double *scratch;                      // per workgroup: PER_WG doubles, as fit_batch_kernel<FAM, MODE_FIT>
-    double *alpha, *nll;                  // outputs (alpha may be null)
+    double *scratch;                      // per workgroup: PER_WG doubles [+ BMAX*BMAX (U = L^-T) for the gradient], as fit_batch_kernel
+    double *alpha, *nll;                  // outputs (alpha may be null); the gradient kernel writes problem b's raw sums at
+                                          // nll + nbatch + b * grad_nacc_nd<FAM, D>()
     int *info;                            // per problem, zero on entry
 };
 
@@ -219,13 +220,21 @@ __device__ __forceinline__ void store_pair_lower(double *P, size_t ld, int N, bo
 }
 
 template <int FAM, int D>
+__device__ void grad_problem_nd(const BatchNdArgs &a, int b, const nd::NdConst &nc, double *s, double *A, const double *inv, double *U,
+                                const double *al);
+
+// MODE_GRAD: after the fit, the gradient of problem b's nll (grad_problem_nd below); scratch then PER_WG + BMAX^2 doubles per
+// workgroup, as fit_batch_kernel<FAM, MODE_GRAD>.  There is no d-pair MODE_LOO or MODE_LOOGRAD.
+template <int FAM, int D, int MODE = MODE_FIT>
 __global__ __launch_bounds__(LT) void fit_batch_nd_kernel(const BatchNdArgs a)
 {
+    static_assert(MODE == MODE_FIT || MODE == MODE_GRAD, "the d-pair kernel has the fit and the nll gradient");
     __shared__ double s[LEAF_LDS];
     __shared__ double red[LT / 64];
     const int tid = threadIdx.x;
     const int n = a.n, N = a.npts;
-    double *A = a.scratch + (size_t)blockIdx.x * PER_WG;      // column-major, ld = BMAX
+    const size_t per_wg = PER_WG + (MODE != MODE_FIT ? (size_t)BMAX * BMAX : 0);               // PER_WG [+ U]
+    double *A = a.scratch + (size_t)blockIdx.x * per_wg;      // column-major, ld = BMAX
     double *inv = A + (size_t)BMAX * BMAX;
     double *v = inv + 2 * (size_t)LEAF * LEAF;                // y, then alpha
     constexpr size_t ld = BMAX;
@@ -247,6 +256,7 @@ __global__ __launch_bounds__(LT) void fit_batch_nd_kernel(const BatchNdArgs a)
             store_pair_lower<FAM, D>(A + i + j * ld, ld, N, i >= j, i == j, noise, E, g, nh);
         }
         fit_solve_body(s, red, A, inv, v, v + BMAX, z, n, n1, n2, a.alpha ? a.alpha + (size_t)b * n : nullptr, a.nll + b, a.info + b);
+        if constexpr (MODE == MODE_GRAD) grad_problem_nd<FAM, D>(a, b, nc, s, A, inv, v + 2 * BMAX, v + BMAX);
     }
 }
 
@@ -354,43 +364,14 @@ __device__ __forceinline__ void contract_rows(const BatchArgs &a, int b, double 
     __syncthreads();                                      // A, U and s are the next problem's
 }
 
-// The gradient of problem b's nll in (lx, ly, [p,] sig, sig2n), by the workgroup that has just fitted it: A holds L, inv the
-// leaf inverses X11 = L11^-1 and X22 = L22^-1, al alpha; U is BMAX^2 doubles of the workgroup's scratch.
-//   (1) U = L^-T, column-major, zero below the diagonal:  L^-1 = [[X11, 0], [-X22 L21 X11, X22]];  T = L21 X11 goes through LDS.
-//   (2) Ky^-1 = L^-T L^-1 = U U^T, lower triangle, into A (over L: the nll has read its diagonal):  n^3 / 3 flop.
-//   (3) thread i owns row i of W = Ky^-1 - alpha alpha^T and walks the column points j, each pair evaluated once with dK from
-//       the generated forms (nllgrad_pair.h), entries on and below the diagonal weighted W_ii and 2 W_ij.  The per-thread
-//       sums fold wave by wave in a fixed order: a problem's bits do not depend on its place in the batch or on the grid.
-// The sums leave unscaled, as nll_grad_full's (nllgrad.hip): the host applies sig / 2, 1/2 and sign(sig2n) / 2.
-// MODE_LOO: steps (1) and (2), then in place of (3) thread i < N takes point i's block {A[i,i], A[N+i,i], A[N+i,N+i]} of Ky^-1 (one
-// entry for reg) through loo_block.h; lpd and |r|^2 fold wave by wave in the same fixed order into {loo, press}.
-// MODE_LOOGRAD: MODE_LOO's steps and sums by the same code (the same bits), then the gradient of loo or press (a.which) by the
-// formulas of loograd.hip, with a third BMAX^2 block M behind U:
-//   (L1) thread i < N keeps point i's weight block W~_i (packed lower, 3 doubles; 1 for reg) and v[B_i] in LDS:
-//        loo  W~_i = r_i r_i^T + S_i, v = r_i;   press  W~_i = 2 (r_i s_i^T + s_i r_i^T), v = 2 s_i, s_i = S_i r_i.
-//        Meanwhile thread i MIRRORS row i of Ky^-1 into column i: A is full and symmetric from here on, every later read of
-//        Ky^-1 is a plain A[row + col ld] with the row on the lanes;
-//   (L2) beta = Ky^-1 v, thread i its entry (n^2 flop), into LDS;  Y = W~ Ky^-1 over U (dead after (2)): row c N + i of Y is
-//        sum_e W~_i[c, e] (row e N + i of Ky^-1), two rows of Ky^-1 per row of Y;
-//   (L3) M = Ky^-1 Y, lower triangle, thread i its row, four columns at a time, k = 0 .. n - 1 in order: n^3 flop; what is stored
-//        in the third block is W' = M - beta alpha^T - alpha beta^T (the weight is then one load per entry in (L4): with the three
-//        terms formed there the family D instance spilled 20 bytes per lane);
-//   (L4) step (3) on W' (contract_rows: the same code as the nll gradient's).
-// A point whose block has a pivot that is not positive and finite has NaN in W~_i: two rows of Y, so all of M, so every sum.
-// Output: {loo, press, the NACC raw sums}, unscaled.
-template <int FAM, int MODE>
-__device__ void grad_problem(const BatchArgs &a, int b, double *s, double *A, const double *inv, double *U, const double *al)
+// Steps (1) and (2) of grad_problem, for the workgroup that has just fitted a problem of order n (n1 = min(n, LEAF), n2 = n - n1):
+// A holds L (ld = BMAX), inv the leaf inverses; U = L^-T goes to U (BMAX^2 doubles), then Ky^-1 = U U^T, lower triangle, over L.
+// Neither step needs the points or the kernel's constants: the d = 1 and the d-pair kernels call this one text.  s: LEAF_LDS
+// doubles (T = L21 X11).  No barrier behind step (2): thread i has written row i of Ky^-1.
+__device__ __forceinline__ void kinv_problem(double *s, double *A, const double *inv, double *U, int n, int n1, int n2)
 {
-    constexpr int NACC = grad_nacc<FAM>(), NOUT = MODE == MODE_LOO ? 2 : MODE == MODE_LOOGRAD ? 2 + NACC : NACC;
     constexpr size_t ld = BMAX;
     const int tid = threadIdx.x;
-    const int n = a.n, N = a.npts, n1 = min(n, (int)LEAF), n2 = n - n1;
-    double *out = a.nll + a.nbatch + (size_t)b * NOUT;
-    // not positive definite (leaf_body's flag, read from L2: the same value for every thread): NaN, nothing computed
-    if (__hip_atomic_load(a.info + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-        if (tid < NOUT) out[tid] = __builtin_nan("");
-        return;
-    }
     // ---- (1) U = L^-T.  The diagonal blocks (transposed leaf inverses) and the zeros; U[i + k ld] = (L^-1)[k, i]
     for (int e = tid; e < n * n; e += LT) {
         const int i = e % n, k = e / n;
@@ -431,6 +412,48 @@ __device__ void grad_problem(const BatchArgs &a, int b, double *s, double *A, co
             A[i + j * ld] = acc;
         }
     }
+}
+
+// The gradient of problem b's nll in (lx, ly, [p,] sig, sig2n), by the workgroup that has just fitted it: A holds L, inv the
+// leaf inverses X11 = L11^-1 and X22 = L22^-1, al alpha; U is BMAX^2 doubles of the workgroup's scratch.  (1) and (2) are
+// kinv_problem above.
+//   (1) U = L^-T, column-major, zero below the diagonal:  L^-1 = [[X11, 0], [-X22 L21 X11, X22]];  T = L21 X11 goes through LDS.
+//   (2) Ky^-1 = L^-T L^-1 = U U^T, lower triangle, into A (over L: the nll has read its diagonal):  n^3 / 3 flop.
+//   (3) thread i owns row i of W = Ky^-1 - alpha alpha^T and walks the column points j, each pair evaluated once with dK from
+//       the generated forms (nllgrad_pair.h), entries on and below the diagonal weighted W_ii and 2 W_ij.  The per-thread
+//       sums fold wave by wave in a fixed order: a problem's bits do not depend on its place in the batch or on the grid.
+// The sums leave unscaled, as nll_grad_full's (nllgrad.hip): the host applies sig / 2, 1/2 and sign(sig2n) / 2.
+// MODE_LOO: steps (1) and (2), then in place of (3) thread i < N takes point i's block {A[i,i], A[N+i,i], A[N+i,N+i]} of Ky^-1 (one
+// entry for reg) through loo_block.h; lpd and |r|^2 fold wave by wave in the same fixed order into {loo, press}.
+// MODE_LOOGRAD: MODE_LOO's steps and sums by the same code (the same bits), then the gradient of loo or press (a.which) by the
+// formulas of loograd.hip, with a third BMAX^2 block M behind U:
+//   (L1) thread i < N keeps point i's weight block W~_i (packed lower, 3 doubles; 1 for reg) and v[B_i] in LDS:
+//        loo  W~_i = r_i r_i^T + S_i, v = r_i;   press  W~_i = 2 (r_i s_i^T + s_i r_i^T), v = 2 s_i, s_i = S_i r_i.
+//        Meanwhile thread i MIRRORS row i of Ky^-1 into column i: A is full and symmetric from here on, every later read of
+//        Ky^-1 is a plain A[row + col ld] with the row on the lanes;
+//   (L2) beta = Ky^-1 v, thread i its entry (n^2 flop), into LDS;  Y = W~ Ky^-1 over U (dead after (2)): row c N + i of Y is
+//        sum_e W~_i[c, e] (row e N + i of Ky^-1), two rows of Ky^-1 per row of Y;
+//   (L3) M = Ky^-1 Y, lower triangle, thread i its row, four columns at a time, k = 0 .. n - 1 in order: n^3 flop; what is stored
+//        in the third block is W' = M - beta alpha^T - alpha beta^T (the weight is then one load per entry in (L4): with the three
+//        terms formed there the family D instance spilled 20 bytes per lane);
+//   (L4) step (3) on W' (contract_rows: the same code as the nll gradient's).
+// A point whose block has a pivot that is not positive and finite has NaN in W~_i: two rows of Y, so all of M, so every sum.
+// Output: {loo, press, the NACC raw sums}, unscaled.
+template <int FAM, int MODE>
+__device__ void grad_problem(const BatchArgs &a, int b, double *s, double *A, const double *inv, double *U, const double *al)
+{
+    constexpr int NACC = grad_nacc<FAM>(), NOUT = MODE == MODE_LOO ? 2 : MODE == MODE_LOOGRAD ? 2 + NACC : NACC;
+    constexpr size_t ld = BMAX;
+    const int tid = threadIdx.x;
+    const int n = a.n, N = a.npts, n1 = min(n, (int)LEAF), n2 = n - n1;
+    double *out = a.nll + a.nbatch + (size_t)b * NOUT;
+    // not positive definite (leaf_body's flag, read from L2: the same value for every thread): NaN, nothing computed
+    if (__hip_atomic_load(a.info + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
+        if (tid < NOUT) out[tid] = __builtin_nan("");
+        return;
+    }
+    kinv_problem(s, A, inv, U, n, n1, n2);                // (1) and (2)
+    const int i = tid;
     [[maybe_unused]] double *sal = s + 2 * BMAX;          // contract_rows' alpha
     if constexpr (MODE == MODE_GRAD) {
         // ---- (3) the points and alpha into LDS (T is dead), then the contraction
@@ -516,6 +539,93 @@ __device__ void grad_problem(const BatchArgs &a, int b, double *s, double *A, co
         // ---- (L4) thread i reads the row of W' it wrote
         contract_rows<FAM>(a, b, s, al, out + 2, [=](int row, double, int col) { return M[row + col * ld]; });
     }
+}
+
+// ---- the nll gradient for d canonical pairs per point (D = 2 d): lq_1..lq_d, lP_1..lP_d, [p_1..p_d,] sig, sig2n
+template <int FAM, int D> constexpr int grad_nacc_nd() { return D + (grad_has_p<FAM>() ? D / 2 : 0) + 2; }
+
+// Step (3) for D x D blocks of point pairs: thread i < n owns row i of W = Ky^-1 - alpha alpha^T (Ky^-1: the lower triangle in A),
+// which is part r = i / N of point pi = i % N, and walks the column points pj = 0 .. N - 1.  Each pair is evaluated once
+// (nllg::pair_grad, dK from the generated forms) and feeds the D entries (i, c N + pj): W_ii on the diagonal (also the noise sum),
+// 2 W_ij below it, 0 above it; the walk stops at the first pj with no entry on or below the diagonal (pj > i).  The points (D N <=
+// BMAX doubles, coordinate m of point p at s[m N + p]) and alpha (at s + 2 BMAX) go to LDS first, the wave partials behind them.
+// Lengths and periods as nllgrad.hip fills GradArgs::l / pp, from the problem's NdConst.  The per-thread sums fold wave by wave in a
+// fixed order into out[0 .. NACC), unscaled.
+template <int FAM, int D>
+__device__ __forceinline__ void contract_rows_nd(const double *X, const nd::NdConst &nc, int N, int n, double *s, const double *A,
+                                                 const double *al, double *out)
+{
+    constexpr bool HASP = grad_has_p<FAM>();
+    constexpr int NACC = grad_nacc_nd<FAM, D>(), d = D / 2;
+    static_assert(3 * BMAX + 4 * NACC <= (int)LEAF_LDS, "points | alpha | wave partials fit in the leaf's LDS");
+    constexpr size_t ld = BMAX;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = tid;
+    double *sx = s, *sal = s + 2 * BMAX, *red = s + 3 * BMAX;
+    for (int e = tid; e < n; e += LT) { sx[e] = X[e]; sal[e] = al[e]; }      // D N = n
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    double l[D], pp[d];
+#pragma unroll
+    for (int m = 0; m < D; ++m) l[m] = nc.l[m];
+#pragma unroll
+    for (int m = 0; m < d; ++m) pp[m] = HASP ? nc.hs[m] : 0.0;
+    double acc[NACC];
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
+    if (i < n) {
+        const int r = i / N, pi = i - r * N;
+        const double ai = sal[i];
+        const double *Arow = A + i;
+        double xi[D];
+#pragma unroll
+        for (int m = 0; m < D; ++m) xi[m] = sx[m * N + pi];
+        for (int pj = 0; pj < N; ++pj) {
+            if (pj > i) break;                                // no entry of this column point on or below the diagonal, nor after it
+            double w[D], xj[D];
+#pragma unroll
+            for (int c = 0; c < D; ++c) {                     // column c N + pj: part c of the column point
+                const int col = c * N + pj;
+                w[c] = 0.0;
+                if (col <= i) {
+                    const double W = Arow[col * ld] - ai * sal[col];
+                    if (col == i) { w[c] = W; acc[NACC - 1] += W; }
+                    else w[c] = 2.0 * W;
+                }
+            }
+#pragma unroll
+            for (int m = 0; m < D; ++m) xj[m] = sx[m * N + pj];
+            nllg::pair_grad<FAM, D, HASP>(xi, xj, w, r, l, pp, acc);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NACC; ++k) {
+        double v = acc[k];
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+        if (lane == 0) red[wave * NACC + k] = v;
+    }
+    __syncthreads();
+    if (tid < NACC) out[tid] = red[tid] + red[NACC + tid] + red[2 * NACC + tid] + red[3 * NACC + tid];
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();                                      // A, U and s are the next problem's
+}
+
+// grad_problem's MODE_GRAD for the d-pair kernel: the NaN row of a problem that is not positive definite, kinv_problem (steps (1)
+// and (2), the text the d = 1 kernel runs), then contract_rows_nd.  The sums leave unscaled: the host applies sig / 2 (sig from the
+// staged NdConst), 1/2 and sign(sig2n) / 2.
+template <int FAM, int D>
+__device__ void grad_problem_nd(const BatchNdArgs &a, int b, const nd::NdConst &nc, double *s, double *A, const double *inv, double *U,
+                                const double *al)
+{
+    constexpr int NACC = grad_nacc_nd<FAM, D>();
+    const int tid = threadIdx.x;
+    const int n = a.n, N = a.npts, n1 = min(n, (int)LEAF), n2 = n - n1;
+    double *out = a.nll + a.nbatch + (size_t)b * NACC;
+    if (__hip_atomic_load(a.info + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
+        if (tid < NACC) out[tid] = __builtin_nan("");
+        return;
+    }
+    kinv_problem(s, A, inv, U, n, n1, n2);
+    contract_rows_nd<FAM, D>(a.X + (size_t)b * D * N, nc, N, n, s, A, al, out);
 }
 
 }  // namespace

@@ -353,6 +353,18 @@ int sgpr_fit_batch_nd(int family, int d, int nbatch, int n_pts, const double *X,
     return fit_batch_nd(family, d, nbatch, n_pts, X, z, hyp, nhyp, sig2n, alpha, nll, info);
 }
 
+/* sgpr_fit_batch_nd plus the gradient of every problem's nll, every order up to the maximum (batch.hip: the gradient mode of
+ * fit_batch_nd_kernel up to order 256, the mid path with mid_grad_nd_kernel above). */
+int sgpr_fit_batch_nd_grad(int family, int d, int nbatch, int n_pts, const double *X, const double *z, const double *hyp, int nhyp,
+                           const double *sig2n, unsigned flags, double *alpha, double *nll, double *grad, int *info)
+{
+    int rc = check_batch_args("fit_batch_nd_grad", family, &d, nhyp, flags, nullptr, nbatch, n_pts, 0, fit_batch_max_order(),
+                              "nll, grad or info", nll && grad && info, X && z && hyp && sig2n);
+    if (rc || nbatch == 0) return rc;
+    if ((rc = need_device())) return rc;
+    return fit_batch_nd_grad(family, d, nbatch, n_pts, X, z, hyp, nhyp, sig2n, alpha, nll, grad, info);
+}
+
 /* sgpr_fit_batch plus the gradient of every problem's nll (batch.hip: the gradient mode of fit_batch_kernel). */
 int sgpr_fit_batch_grad(int family, int nbatch, int n_pts, const double *x, const double *y, const double *z,
                         const double *hyp, int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll,

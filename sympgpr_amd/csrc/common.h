@@ -312,6 +312,10 @@ int fit_batch(int family, int nbatch, int npts, const double *x, const double *y
 // arguments have been checked (capi.hip), nbatch > 0
 int fit_batch_nd(int family, int d, int nbatch, int npts, const double *X, const double *z, const double *hyp, int nhyp,
                  const double *sig2n, double *alpha, double *nll, int *info);
+// the same plus the gradient of every problem's nll: grad is nbatch x (nhyp + 1), rows in sgpr_fit_nll_grad_full's order for a
+// d-pair fit; both paths (the one-launch kernel in its gradient mode, the mid path with mid_grad_nd_kernel)
+int fit_batch_nd_grad(int family, int d, int nbatch, int npts, const double *X, const double *z, const double *hyp, int nhyp,
+                      const double *sig2n, double *alpha, double *nll, double *grad, int *info);
 int fit_batch_grad_max_order();                  // 256: one workgroup holds the whole problem
 int fit_batch_grad(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
                    int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, double *grad, int *info);

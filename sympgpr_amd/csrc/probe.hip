@@ -611,7 +611,7 @@ extern "C" int sgpr_probe_gemm_nt4_dev(int m, int n, int k, const double *A, siz
 extern "C" int sgpr_probe_batch_layout(int path, int mode, int d, int reg, int nbatch, int n_pts, int nhyp, unsigned long long out[24])
 {
     const long n = d ? 2L * d * n_pts : reg ? (long)n_pts : 2L * n_pts;
-    if (path < 0 || path > 1 || mode < 0 || mode > 3 || (path && mode == 3) || d < 0 || d > 3 || (d && (reg || mode)) || nbatch < 1 ||
+    if (path < 0 || path > 1 || mode < 0 || mode > 3 || (path && mode == 3) || d < 0 || d > 3 || (d && (reg || mode > 1)) || nbatch < 1 ||
         n_pts < 1 || nhyp < 1 || (path ? n <= 256 || n > 2048 : n > 256) || !out) {
         set_error("probe_batch_layout: bad arguments");
         return SGPR_E_ARG;

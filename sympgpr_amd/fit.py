@@ -437,6 +437,37 @@ def fit_batch(family, x, y, z, hyp, sig2n, reg=False, want_alpha=True):
     return alpha, nll, info
 
 
+def _pairs_inputs(name, family, X, z, hyp, sig2n):
+    """The inputs of the wrappers for d canonical pairs per point: X (B, n_pts, 2d) or (n_pts, 2d) and z (B, n) or (n,) broadcast
+    over the rows of hyp, sig2n to (B,), the shapes checked (the ValueError names the wrapper), X in the library's layout.
+    -> lead (the arguments every d-pair entry starts with), the arrays behind its pointers, B, n, nhyp"""
+    X = np.asarray(X, dtype=np.float64)
+    z = np.asarray(z, dtype=np.float64)
+    hyp = np.asarray(hyp, dtype=np.float64)
+    if hyp.ndim != 2:
+        raise ValueError("%s: hyp (B, nhyp)" % name)
+    B = hyp.shape[0]
+    if X.ndim == 2:
+        X = np.broadcast_to(X, (B,) + X.shape)
+    if X.ndim != 3 or X.shape[0] != B or X.shape[2] % 2 or X.shape[2] == 0:
+        raise ValueError("%s: X (B, n_pts, 2d) or (n_pts, 2d), B the rows of hyp" % name)
+    n_pts, D = X.shape[1], X.shape[2]
+    n = D * n_pts
+    if z.ndim == 1:
+        z = np.broadcast_to(z, (B,) + z.shape)
+    if z.shape != (B, n):
+        raise ValueError("%s: z (B, n) or (n,), n = 2 d n_pts" % name)
+    if np.ndim(sig2n) > 1 or (np.ndim(sig2n) == 1 and np.shape(sig2n) != (B,)):
+        raise ValueError("%s: sig2n scalar or (B,)" % name)
+    # the library's layout: coordinate m of point i of problem b at (b 2d + m) n_pts + i
+    Xl = np.ascontiguousarray(np.swapaxes(X, 1, 2))
+    z = np.ascontiguousarray(z)
+    hyp = np.ascontiguousarray(hyp)
+    s2 = np.ascontiguousarray(np.broadcast_to(np.asarray(sig2n, dtype=np.float64), (B,)))
+    lead = (L.family_id(family), D // 2, B, n_pts, L.dptr(Xl), L.dptr(z), L.dptr(hyp), hyp.shape[1], L.dptr(s2), 0)
+    return lead, (Xl, z, hyp, s2), B, n, hyp.shape[1]
+
+
 def fit_batch_pairs(family, X, z, hyp, sig2n, want_alpha=True):
     """fit_batch for problems with d canonical pairs per point (SympFit.pairs' kernels and layouts), every order
     n = 2 d n_pts up to batch_max_order(): one launch up to order 256, the mid path above it.
@@ -444,33 +475,27 @@ def fit_batch_pairs(family, X, z, hyp, sig2n, want_alpha=True):
         a population of hyper-parameters;  z (B, n) or (n,), block by block like the rows of K;
         hyp (B, nhyp), rows as SympFit.pairs takes them;  sig2n (B,) or scalar.
     -> (alpha (B, n) or None, nll (B,), info (B,)): info[b] > 0 where Ky_b is not positive definite (nll[b] is NaN there)."""
-    X = np.asarray(X, dtype=np.float64)
-    z = np.asarray(z, dtype=np.float64)
-    hyp = np.asarray(hyp, dtype=np.float64)
-    if hyp.ndim != 2:
-        raise ValueError("fit_batch_pairs: hyp (B, nhyp)")
-    B = hyp.shape[0]
-    if X.ndim == 2:
-        X = np.broadcast_to(X, (B,) + X.shape)
-    if X.ndim != 3 or X.shape[0] != B or X.shape[2] % 2 or X.shape[2] == 0:
-        raise ValueError("fit_batch_pairs: X (B, n_pts, 2d) or (n_pts, 2d), B the rows of hyp")
-    n_pts, D = X.shape[1], X.shape[2]
-    n = D * n_pts
-    if z.ndim == 1:
-        z = np.broadcast_to(z, (B,) + z.shape)
-    if z.shape != (B, n):
-        raise ValueError("fit_batch_pairs: z (B, n) or (n,), n = 2 d n_pts")
-    if np.ndim(sig2n) > 1 or (np.ndim(sig2n) == 1 and np.shape(sig2n) != (B,)):
-        raise ValueError("fit_batch_pairs: sig2n scalar or (B,)")
-    # the library's layout: coordinate m of point i of problem b at (b 2d + m) n_pts + i
-    Xl = np.ascontiguousarray(np.swapaxes(X, 1, 2))
-    z = np.ascontiguousarray(z)
-    hyp = np.ascontiguousarray(hyp)
-    s2 = np.ascontiguousarray(np.broadcast_to(np.asarray(sig2n, dtype=np.float64), (B,)))
-    lead = (L.family_id(family), D // 2, B, n_pts, L.dptr(Xl), L.dptr(z), L.dptr(hyp), hyp.shape[1], L.dptr(s2), 0)
+    lead, _keep, B, n, _ = _pairs_inputs("fit_batch_pairs", family, X, z, hyp, sig2n)
     alpha, nll, info = _batch_run("sgpr_fit_batch_nd", lead, B, n, want_alpha)
     nll[info != 0] = np.nan
     return alpha, nll, info
+
+
+def fit_batch_pairs_grad(family, X, z, hyp, sig2n, want_alpha=False):
+    """fit_batch_pairs plus the exact gradient of every problem's nll in (hyp, sig2n), every order up to batch_max_order() on the
+    device (sgpr_fit_batch_nd_grad): one launch up to order 256, the mid path with its gradient phase above.  Shapes and
+    broadcasting as fit_batch_pairs.
+    -> (alpha (B, n) or None, nll (B,), grad (B, nhyp + 1), info (B,)).  Row b of grad is (d/dlq_1..d/dlq_d, d/dlP_1..d/dlP_d,
+    [d/dp_1..d/dp_d,] d/dsig, d/dsig2n), SympFit.pairs(...).nll_grad_full()'s order; Ky holds |sig2n[b]|, so the last entry carries
+    sign(sig2n[b]) (sign(0) = +1).  Rows with info > 0 are NaN (nll and the whole gradient row).  nll, alpha and info are the same
+    bits fit_batch_pairs returns; a row's gradient bits do not depend on the batch."""
+    lead, _keep, B, n, nhyp = _pairs_inputs("fit_batch_pairs_grad", family, X, z, hyp, sig2n)
+    grad = np.empty((B, nhyp + 1))
+    alpha, nll, info = _batch_run("sgpr_fit_batch_nd_grad", lead, B, n, want_alpha, (grad,))
+    bad = info != 0
+    nll[bad] = np.nan
+    grad[bad] = np.nan
+    return alpha, nll, grad, info
 
 
 def batch_grad_max_order():

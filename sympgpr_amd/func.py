@@ -155,6 +155,21 @@ def nll_chol_batch(hyps, x, y, N, reg=False):
     return nll
 
 
+def _pairs_check(name, hyps, X, z):
+    """hyps (B, nhyp + 1), X (n_pts, 2d), z (n,) as float64 arrays, the shapes checked -> hyps, X, z, n"""
+    hyps = np.atleast_2d(np.asarray(hyps, dtype=np.float64))
+    X = np.asarray(X, dtype=np.float64)
+    z = np.asarray(z, dtype=np.float64)
+    if X.ndim != 2 or X.shape[1] % 2 or X.shape[1] == 0:
+        raise ValueError("%s: X must be (n_pts, 2d)" % name)
+    n = X.shape[0] * X.shape[1]
+    if z.shape != (n,):
+        raise ValueError("%s: z must have length %d" % (name, n))
+    if hyps.ndim != 2 or hyps.shape[1] < 2:
+        raise ValueError("%s: rows (lq.., lP.., [p..,] sig, sig2_n)" % name)
+    return hyps, X, z, n
+
+
 def nll_chol_pairs_batch(hyps, X, z):
     """nll_chol_batch for a fit with d canonical pairs per point: the negative log-posterior of SympFit.pairs(family, X, z, ...)
     for a whole POPULATION of hyper-parameter vectors over one data set.  X (n_pts, 2d), columns (q_1..q_d, P_1..P_d); z the
@@ -163,16 +178,7 @@ def nll_chol_pairs_batch(hyps, X, z):
     above it a loop over ONE device-resident handle (set_hyp / run).  Rows whose Ky is not positive definite come back
     as +inf."""
     from .fit import batch_max_order, fit_batch_pairs
-    hyps = np.atleast_2d(np.asarray(hyps, dtype=np.float64))
-    X = np.asarray(X, dtype=np.float64)
-    z = np.asarray(z, dtype=np.float64)
-    if X.ndim != 2 or X.shape[1] % 2 or X.shape[1] == 0:
-        raise ValueError("nll_chol_pairs: X must be (n_pts, 2d)")
-    n = X.shape[0] * X.shape[1]
-    if z.shape != (n,):
-        raise ValueError("nll_chol_pairs: z must have length %d" % n)
-    if hyps.shape[1] < 2:
-        raise ValueError("nll_chol_pairs: rows (lq.., lP.., [p..,] sig, sig2_n)")
+    hyps, X, z, n = _pairs_check("nll_chol_pairs", hyps, X, z)
     if n <= batch_max_order():
         _, nll, info = fit_batch_pairs(get_family(), X, z, hyps[:, :-1], np.abs(hyps[:, -1]), want_alpha=False)
         nll[info != 0] = np.inf
@@ -197,6 +203,52 @@ def nll_chol_pairs(hyp, X, z):
     if hyp.ndim != 1:
         raise ValueError("nll_chol_pairs: hyp is one row (lq.., lP.., [p..,] sig, sig2_n)")
     return float(nll_chol_pairs_batch(hyp[None], X, z)[0])
+
+
+def nll_chol_pairs_grad_batch(hyps, X, z):
+    """nll_chol_pairs_batch with gradients: hyps (B, nhyp + 1), rows (lq_1..lq_d, lP_1..lP_d, [p_1..p_d,] sig, sig2_n) ->
+    (nlls (B,), grads (B, nhyp + 1)), grads[b, k] = d nll[b] / d hyps[b, k].  The noise enters as |hyps[b, -1]|, so the last column
+    carries its sign (sign(0) = +1).  Rows whose Ky is not positive definite give nll = +inf and a NaN gradient row.  Up to order
+    fit.batch_max_order() (2048) one batched call (fit.fit_batch_pairs_grad); above it a loop over ONE device-resident handle
+    (set_hyp / run / nll_grad_full)."""
+    from .fit import batch_max_order, fit_batch_pairs_grad
+    hyps, X, z, n = _pairs_check("nll_chol_pairs_grad", hyps, X, z)
+    sign = np.where(hyps[:, -1] < 0.0, -1.0, 1.0)
+    if n <= batch_max_order():
+        _, nll, grad, info = fit_batch_pairs_grad(get_family(), X, z, hyps[:, :-1], np.abs(hyps[:, -1]), want_alpha=False)
+        bad = info != 0
+        nll[bad] = np.inf
+        grad[bad] = np.nan
+        grad[:, -1] *= sign
+        return nll, grad
+    nll = np.empty(len(hyps))
+    grad = np.full(hyps.shape, np.nan)
+    if len(hyps) == 0:
+        return nll, grad
+    with SympFit.pairs(get_family(), X, z, hyps[0, :-1], np.abs(hyps[0, -1])) as f:
+        for b, h in enumerate(hyps):
+            try:
+                f.set_hyp(h[:-1], np.abs(h[-1]))
+                nll[b] = f.run().nll()
+                grad[b] = f.nll_grad_full()
+                grad[b, -1] *= sign[b]
+            except np.linalg.LinAlgError:
+                nll[b] = np.inf
+                grad[b] = np.nan
+    return nll, grad
+
+
+def nll_chol_pairs_grad(hyp, X, z):
+    """nll_chol_pairs and its exact gradient -> (nll, grad), grad[k] = d nll / d hyp[k] for every entry of hyp = (lq.., lP..,
+    [p..,] sig, sig2_n): the objective for scipy.optimize.minimize(..., jac=True) on a fit with d canonical pairs per point.
+    One row of nll_chol_pairs_grad_batch; raises LinAlgError where Ky is not positive definite, as nll_chol_grad does."""
+    hyp = np.asarray(hyp, dtype=np.float64)
+    if hyp.ndim != 1:
+        raise ValueError("nll_chol_pairs_grad: hyp is one row (lq.., lP.., [p..,] sig, sig2_n)")
+    nll, grad = nll_chol_pairs_grad_batch(hyp[None], X, z)
+    if nll[0] == np.inf:
+        raise np.linalg.LinAlgError("a leading minor of Ky is not positive definite")
+    return float(nll[0]), grad[0]
 
 
 def _batch_data(x, y, N, reg):
