@@ -171,6 +171,33 @@ int sgpr_probe_census(int na, int threads_a, int lds_a, int spin_a, const unsign
                       int nb, int threads_b, int lds_b, int spin_b, const unsigned *mask_b, int nwords_b,
                       unsigned long long *host_out);
 
+/* A third Strassen level on top of the front end, for the recursion's largest products (csrc/gemm_f64.hip: strassen_top_plan).
+ * Tunables, read at every factorisation: rec_strassen3_min (smallest half-size of m and n that takes it; 0: off),
+ * rec_strassen3_kslab / rec_strassen3_kslab_short (top k slab of a call whose k reaches the long one / of a shorter call; 0: none),
+ * rec_strassen3_overlap (1: the top passes run on a low-priority stream of their own under the next product; 0: on the caller's
+ * stream in list order), rec_strassen3_buffers (2: a second buffer set for that), rec_strassen3_noscratch (tests: the buffer's
+ * allocation is reported as failed -> the level is off).  With SGPR_GEMM_STRASSEN set in the environment the level is never taken.
+ * sgpr_probe_strassen_top_plan: the list of ONE call (m x n x k, lower), 16 words per record, [0] = kind:
+ *   6 top sum:    layout of kind 1; the result goes to the TOP scratch of that side
+ *   7 zero:       [1] rows [2] cols                       the temporary T = 0
+ *   8 top product [1] a_src (0: block of A at ([2], [3]), 1: the top A scratch) [4] b_src, ([5], [6]) likewise [7] m [8] n [9] k
+ *                 [10 .. 14] thresholds (smin, kslab, smin2, kslab2, smin_under) of the half-size call T += X Y^T, whose list is
+ *                 sgpr_probe_strassen_cfg_plan(m, n, k, 0, those)
+ *   9 accumulate  [1] rows [2] cols [3] [4] first destination (row, column of C) [5] its sign [6] [7] [8] the second (sign 0: none):
+ *                 C1 += alpha sign1 T, C2 += alpha sign2 T
+ *  10 pass-through: layout of kind 3 ([1] lower [2] ar [3] ac [4] br [5] bc [6] m [7] n [8] k [9] cr [10] cc), [11 .. 15] thresholds:
+ *                 that block through the front end as before (sgpr_probe_strassen_cfg_plan(m, n, k, lower, those)).  A call that
+ *                 does not qualify is this record alone.
+ * sgpr_probe_strassen_cfg_plan: the list (kinds 1 - 5) of one call under explicit thresholds.
+ * sgpr_probe_strassen_top_scratch: doubles of top-level scratch potrf() reserves at order n: out[0] one buffer set (T, A side,
+ * B side), out[1] with the second set.  sgpr_probe_gemm_strassen_top_dev: one product on device pointers as the recursion issues it.
+ * tools/strassen_top_plan.py replays the list. */
+int sgpr_probe_strassen_top_plan(int m, int n, int k, int lower, long scratch_doubles, long long *out, int max_records, int *count);
+int sgpr_probe_strassen_cfg_plan(int m, int n, int k, int lower, const long cfg[5], long long *out, int max_records, int *count);
+int sgpr_probe_strassen_top_scratch(int n, unsigned long long out[2]);
+int sgpr_probe_gemm_strassen_top_dev(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb,
+                                     double beta, double *C, size_t ldc, int lower, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -192,6 +192,13 @@ PROBE_SIGNATURES = {
                                                C.POINTER(C.c_longlong), C.c_int, C.POINTER(C.c_int)]),
     "sgpr_probe_gemm_strassen_rec_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                                    C.c_double, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
+    "sgpr_probe_strassen_top_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_long, C.POINTER(C.c_longlong), C.c_int,
+                                               C.POINTER(C.c_int)]),
+    "sgpr_probe_strassen_cfg_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_long), C.POINTER(C.c_longlong), C.c_int,
+                                               C.POINTER(C.c_int)]),
+    "sgpr_probe_strassen_top_scratch": (C.c_int, [C.c_int, C.POINTER(C.c_ulonglong)]),
+    "sgpr_probe_gemm_strassen_top_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                   C.c_double, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     "sgpr_probe_gemm_nt4_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_double, C.c_int,
                                           C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_double), C.c_void_p]),
     "sgpr_probe_batch_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -960,6 +960,7 @@ struct Ctx {
     void *qws = nullptr;    // the task-queue driver's part of the workspace (cholq.h), or null
     bool strassen = false;  // the deep products of the recursion go through gemm_nt_strassen (potrf() only: the solves' do not)
     StrassenRec rec;        // ... each with thresholds of its own, chosen per call from these (strassen_rec_cfg)
+    StrassenTop top;        // ... and the two largest with a third level on top (strassen_top_gemm)
 };
 
 int potrf_lookahead(int n, double *A, size_t lda, const Ctx &c, int nb, int off0);
@@ -978,7 +979,7 @@ int trsm_rec(int m, int n, const double *L, size_t ldl, double *B, size_t ldb, i
     int rc = trsm_rec(m, n1, L, ldl, B, ldb, off, c);
     if (rc) return rc;
     // B2 -= B1 L21^T
-    if (c.strassen) rc = gemm_nt_strassen_cfg(m, n2, n1, -1.0, B, ldb, L + n1, ldl, 1.0, B + (size_t)n1 * ldb, ldb, 0, strassen_rec_cfg(c.rec, n1, 0), c.st);
+    if (c.strassen) rc = strassen_top_gemm(m, n2, n1, -1.0, B, ldb, L + n1, ldl, 1.0, B + (size_t)n1 * ldb, ldb, 0, &c.rec, &c.top, c.st);
     else            rc = gemm_nt(m, n2, n1, -1.0, B, ldb, L + n1, ldl, 1.0, B + (size_t)n1 * ldb, ldb, 0, 0, c.st);
     if (rc) return rc;
     return trsm_rec(m, n2, L + n1 + (size_t)n1 * ldl, ldl, B + (size_t)n1 * ldb, ldb, off + n1, c);
@@ -1018,7 +1019,7 @@ int potrf_rec(int n, double *A, size_t lda, int off, const Ctx &c)
     rc = trsm_rec(n2, n1, A, lda, A21, lda, off, c);
     if (rc) return rc;
     // SYRK, lower (large ones: split around their square off-diagonal part, which takes the Strassen front end)
-    if (c.strassen) rc = gemm_nt_strassen_cfg(n2, n2, n1, -1.0, A21, lda, A21, lda, 1.0, A22, lda, 1, strassen_rec_cfg(c.rec, n1, 1), c.st);
+    if (c.strassen) rc = strassen_top_gemm(n2, n2, n1, -1.0, A21, lda, A21, lda, 1.0, A22, lda, 1, &c.rec, &c.top, c.st);
     else            rc = gemm_nt(n2, n2, n1, -1.0, A21, lda, A21, lda, 1.0, A22, lda, 1, 0, c.st);
     if (rc) return rc;
     return potrf_rec(n2, A22, lda, off + n1, c);
@@ -1214,7 +1215,7 @@ int side_stream(hipStream_t caller, hipStream_t *out, int *dev_out)
 
 // The streams of the Strassen front end's operand sums (gemm_f64.hip: run_schedule): two per device at the LOWEST priority --
 // the sums fill what the products leave free and must never hold one up.  Same life as the side stream above.
-hipStream_t g_sum[64][2] = {};
+hipStream_t g_sum[64][3] = {};      // [2]: the top level's passes (strassen_top_stream)
 }  // namespace
 
 int strassen_sum_streams(hipStream_t caller, int count, hipStream_t *out)
@@ -1240,6 +1241,33 @@ int strassen_sum_streams(hipStream_t caller, int count, hipStream_t *out)
         }
         out[t] = g_sum[dev][t];
     }
+    return 0;
+}
+
+// ... and a third one of the same kind for the passes of the top Strassen level (gemm_f64.hip: run_top): a stream of their own,
+// because run_schedule makes its side stream wait for the caller's at every entry -- a top pass queued there would sit in front
+// of the next half-size call's first inner sums.  Caller + panel + sums + this: four hardware queues.
+int strassen_top_stream(hipStream_t caller, hipStream_t *out)
+{
+    int dev = -1;
+    if (caller) {
+        SGPR_HIP(hipStreamGetDevice(caller, &dev));
+    } else {
+        SGPR_HIP(hipGetDevice(&dev));
+    }
+    if (dev < 0 || dev >= 64 || !out) { set_error("strassen_top_stream: bad device"); return SGPR_E_ARG; }
+    std::lock_guard<std::mutex> lock(g_side_mu);
+    if (!g_sum[dev][2]) {
+        int cur = -1, lo = 0, hi = 0;
+        SGPR_HIP(hipGetDevice(&cur));
+        if (cur != dev) SGPR_HIP(hipSetDevice(dev));
+        hipError_t e = hipDeviceGetStreamPriorityRange(&lo, &hi);
+        if (e == hipSuccess) e = hipStreamCreateWithPriority(&g_sum[dev][2], hipStreamNonBlocking, lo);
+        if (e == hipSuccess) register_exit_release();
+        if (cur != dev) (void)hipSetDevice(cur);
+        SGPR_HIP(e);
+    }
+    *out = g_sum[dev][2];
     return 0;
 }
 
@@ -1437,7 +1465,7 @@ void release_all_streams_at_exit()
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess) { (void)hipGetLastError(); return; }
     for (int dev = 0; dev < ndev && dev < 64; ++dev) {
-        hipStream_t drop[11] = {};
+        hipStream_t drop[12] = {};
         int nd = 0;
         {
             std::lock_guard<std::mutex> lock(g_side_mu);
@@ -1472,7 +1500,7 @@ int release_streams(int dev)
         bool any = false;
         {
             std::lock_guard<std::mutex> lock(g_side_mu);
-            any = g_side[dev] != nullptr || g_sum[dev][0] != nullptr || g_sum[dev][1] != nullptr;
+            any = g_side[dev] != nullptr || g_sum[dev][0] != nullptr || g_sum[dev][1] != nullptr || g_sum[dev][2] != nullptr;
         }
         QueueDevice &qd = g_qdev[dev];
         std::lock_guard<std::mutex> lock(qd.mu);
@@ -1496,6 +1524,7 @@ int release_streams(int dev)
         drop(g_side[dev]);
         drop(g_sum[dev][0]);
         drop(g_sum[dev][1]);
+        drop(g_sum[dev][2]);
     }
     {
         QueueDevice &qd = g_qdev[dev];
@@ -1802,7 +1831,35 @@ void need_potrf(int n, int la_max, const StrassenRec &v, int levels, size_t &nee
     need = std::max(need, strassen_scratch_doubles_cfg(n2, n2, n1, 1, levels, strassen_rec_cfg(v, n1, 1)));
     need_potrf(n2, la_max, v, levels, need);
 }
+// ... and the same walk for the top level's own buffer
+void need3_trsm(int m, int n, const StrassenRec &v, const StrassenTop &t, size_t &need)
+{
+    if (n <= LEAF || std::min(m, n) / 2 < t.smin3) return;
+    const int n1 = split(n), n2 = n - n1;
+    need3_trsm(m, n1, v, t, need);
+    need = std::max(need, strassen_top_scratch_doubles(m, n2, n1, 0, v, t));
+    need3_trsm(m, n2, v, t, need);
+}
+void need3_potrf(int n, int la_max, const StrassenRec &v, const StrassenTop &t, size_t &need)
+{
+    if (n <= LEAF || (n > 4 * LEAF && n <= la_max)) return;
+    const int n1 = split(n), n2 = n - n1;
+    need3_potrf(n1, la_max, v, t, need);
+    need3_trsm(n2, n1, v, t, need);
+    need = std::max(need, strassen_top_scratch_doubles(n2, n2, n1, 1, v, t));
+    need3_potrf(n2, la_max, v, t, need);
+}
 }  // namespace
+
+size_t potrf_strassen_top_need(int n)
+{
+    static const bool rec_mode = [] { const char *e = getenv("SGPR_POTRF"); return e && e[0] == 'r'; }();
+    const StrassenRec v = strassen_rec_values();
+    const StrassenTop t = strassen_top_values();
+    size_t need = 0;
+    if (v.on && t.smin3 > 0) need3_potrf(n, rec_mode ? 0 : la_max_value(), v, t, need);
+    return need;
+}
 
 void potrf_strassen_need(int n, size_t out[2])
 {
@@ -1832,11 +1889,13 @@ int potrf(int n, double *A, size_t lda, void *work, size_t lwork, int *dinfo, hi
     if (cholq::ws_bytes(n) > 0) c.qws = static_cast<char *>(work) + inv_bytes(n) + flag_bytes(n) + pub_bytes(n);
     c.strassen = true;
     c.rec = strassen_rec_values();
+    c.top = strassen_top_values();
     if (n > c.la_max && n > LEAF) {
         // size the operand-sum scratch once, before the first launch: the largest need over the plans of this order
         size_t need[2];
         potrf_strassen_need(n, need);
         strassen_reserve(need[0], need[1], st);   // both levels' operand sums, or the inner level's alone if that does not fit
+        strassen_top_reserve(potrf_strassen_top_need(n), st);     // the top level's buffer; without it that level is off
     }
     const bool dbg = PANEL_DBG && getenv("SGPR_PANEL_DBG") != nullptr;
     const int T = (n + LEAF - 1) / LEAF;

@@ -169,6 +169,26 @@ int strassen_sum_streams(hipStream_t caller, int count, hipStream_t *out);
 void potrf_strassen_need(int n, size_t out[2]);  // chol.hip: what potrf() reserves at order n (both levels, one level)
 void strassen_reserve(size_t both, size_t one, hipStream_t st);
 int strassen_trim();                             // release the scratch of the operand sums (every device)
+// A third level ON TOP of gemm_nt_strassen_cfg for the recursion's largest products (gemm_f64.hip: strassen_top_gemm): the same seven
+// formulas on the halves, each top product formed in a temporary by one half-size call of gemm_nt_strassen_cfg and added to its
+// blocks of C by a streaming pass.  Records (STRASSEN_REC words, layouts in gemm_f64.hip):
+enum { PLAN3_SUM = 6, PLAN3_ZERO = 7, PLAN3_PROD = 8, PLAN3_ACC = 9, PLAN3_PASS = 10 };
+// Tunables "rec_strassen3_min" (half-size of m and n; 0: off), "rec_strassen3_kslab" / "rec_strassen3_kslab_short" (top k slab of
+// a call whose k reaches the long one / of a shorter call; 0: none), read with the recursion's other values.
+struct StrassenTop { long smin3 = 0, kslab3 = 0, kslab3_short = 0; };
+StrassenTop strassen_top_values();
+// (v / t null: the values as the next factorisation would read them)
+int strassen_top_plan(int m, int n, int k, int lower, const StrassenRec *v, const StrassenTop *t, size_t scratch_doubles,
+                      std::vector<long long> &out);
+// the list of one call under explicit thresholds (what a PLAN3_PROD / PLAN3_PASS record's call turns into)
+int strassen_cfg_plan(int m, int n, int k, int lower, const long cfg[5], std::vector<long long> &out);
+size_t strassen_top_scratch_doubles(int m, int n, int k, int lower, const StrassenRec &v, const StrassenTop &t);
+// the recursion's entry (not named gemm_nt_strassen*: those are the front end's exported entries, csrc/exports.map)
+int strassen_top_gemm(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb, double beta,
+                      double *C, size_t ldc, int lower, const StrassenRec *v, const StrassenTop *t, hipStream_t st);
+size_t potrf_strassen_top_need(int n);           // chol.hip: doubles of top-level scratch at order n (one buffer per region)
+void strassen_top_reserve(size_t need, hipStream_t st);
+int strassen_top_stream(hipStream_t caller, hipStream_t *out);   // chol.hip: the low-priority stream of the top level's passes
 int gemm_profile_begin();
 int gemm_profile_end(double *out12);
 int gemm_profile_launches(double *buf, int max_records);

@@ -1145,8 +1145,11 @@ void strassen_reserve(size_t both, size_t one, hipStream_t st)
     if (one) (void)scratch_ensure(s, one);
 }
 
+namespace { void top_trim(); }
+
 int strassen_trim()
 {
+    top_trim();                                   // the top level's buffer (below)
     for (Scratch &s : g_scratch) {
         std::lock_guard<std::mutex> lock(s.mu);
         if (s.p) (void)hipFree(s.p);          // waits for whatever still uses it
@@ -1224,6 +1227,366 @@ int gemm_nt_strassen_cfg(int m, int n, int k, double alpha, const double *A, siz
     const Need2 nd = plan2_need(plan, c2);
     if (overlap) return enqueue(s, [&] { return run_schedule(plan, c2, nd, alpha, A, lda, B, ldb, beta, C, ldc, s, st); });
     return enqueue(s, [&] { return run_plan(plan, alpha, A, lda, B, ldb, beta, C, ldc, s.p, s.p + nd.v[0], st); });
+}
+
+// ---- a third level ON TOP of the front end, for the recursion's two largest products ----------------------------
+// The seven formulas once more on the halves of a product, per top k slab.  Unlike the two levels above, a top product M_i is not
+// accumulated into C by the product kernel (that would take eight destinations): it is formed in a temporary T (m/2 x n/2, zeroed
+// first) by ONE half-size call of gemm_nt_strassen_cfg -- which takes its two levels and its sum overlap exactly as today -- and
+// then added to its one or two blocks of C with alpha * sign by a streaming pass (block_acc_kernel).  Only kernels that exist
+// are launched, plus that pass.  Again host code emits records and the device path executes exactly that list:
+//   PLAN3_SUM   layout of PLAN_SUM; the result goes to the TOP scratch of that side
+//   PLAN3_ZERO  [1] rows [2] cols                                       T = 0
+//   PLAN3_PROD  [1] a_src (0: block of A at ([2], [3]), 1: the top A scratch) [4] b_src, ([5], [6]) likewise [7] m [8] n [9] k
+//               [10 .. 14] the thresholds of the half-size call (smin, kslab, smin2, kslab2, smin_under)
+//               T += X Y^T through gemm_nt_strassen_cfg(m, n, k, 1, X, Y, 1, T, ld m, not lower, those thresholds)
+//   PLAN3_ACC   [1] rows [2] cols [3] [4] first destination (row, column of C) [5] its sign [6] [7] [8] the second (sign 0: none)
+//               C1 += alpha sign1 T; C2 += alpha sign2 T
+//   PLAN3_PASS  layout of PLAN_CLASSIC ([1] lower [2] ar [3] ac [4] br [5] bc [6] m [7] n [8] k [9] cr [10] cc), [11 .. 15] thresholds:
+//               that block through gemm_nt_strassen_cfg as before.  A call that does not qualify is this record alone.
+// Qualifies: m % 2048 == 0, n % 1024 == 0 (the halves stay multiples of what the outer level asks), m / 2 and n / 2 >= smin3,
+// k holds a whole top slab (kslab3 if k reaches it, else kslab3_short); a remainder of k shorter than the slab is a PLAN3_PASS at
+// its k offset.  A lower update splits around its off-diagonal square as plan2_syrk does: lower(h), the square, lower(h).
+namespace {
+constexpr long REC_SMIN3 = 16384, REC_KSLAB3 = 65536, REC_KSLAB3_SHORT = 32768;
+
+// C1 += a1 T and, where C2 is given, C2 += a2 T: T (rows x cols, leading dimension rows) is read once.  The pattern of
+// block_sum_kernel: 16-byte accesses, 4 columns per thread in flight, grid-stride over pieces of 512 rows x 4 columns; rows even,
+// all bases 16-byte aligned, ldc even (checked by the caller).  A kernel of its own behind the others: they compile as without it.
+__global__ __launch_bounds__(256) void block_acc_kernel(int rows, int cols, const double *T, double *C1, double a1, double *C2, double a2,
+                                                        size_t ldc)
+{
+    const int nrc = (rows + 511) / 512, ncg = (cols + 3) / 4;
+    const long pieces = (long)nrc * ncg;
+    for (long p = blockIdx.x; p < pieces; p += gridDim.x) {
+        const int cg = (int)(p / nrc), rc = (int)(p - (long)cg * nrc);
+        const int r = rc * 512 + 2 * (int)threadIdx.x;
+        if (r >= rows) continue;
+        double2_t t[4], c1[4], c2[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int c = min(cg * 4 + u, cols - 1);
+            t[u] = *reinterpret_cast<const double2_t *>(T + (size_t)r + (size_t)c * (size_t)rows);
+            c1[u] = *reinterpret_cast<const double2_t *>(C1 + (size_t)r + (size_t)c * ldc);
+            if (C2) c2[u] = *reinterpret_cast<const double2_t *>(C2 + (size_t)r + (size_t)c * ldc);
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int c = cg * 4 + u;
+            if (c >= cols) continue;
+            *reinterpret_cast<double2_t *>(C1 + (size_t)r + (size_t)c * ldc) = c1[u] + a1 * t[u];
+            if (C2) *reinterpret_cast<double2_t *>(C2 + (size_t)r + (size_t)c * ldc) = c2[u] + a2 * t[u];
+        }
+    }
+}
+int block_acc(int rows, int cols, const double *T, double *C1, double a1, double *C2, double a2, size_t ldc, hipStream_t st, long wgs)
+{
+    const long pieces = (long)((rows + 511) / 512) * ((cols + 3) / 4);
+    hipLaunchKernelGGL(block_acc_kernel, dim3((unsigned)std::min(pieces, wgs)), dim3(256), 0, st, rows, cols, T, C1, a1, C2, a2, ldc);
+    SGPR_CHECK_LAUNCH();
+    return 0;
+}
+
+long top_slab(long k, const StrassenTop &t)
+{
+    const long s = (t.kslab3 > 0 && k >= t.kslab3) ? t.kslab3 : t.kslab3_short;
+    return (s >= 128 && s % 128 == 0 && k >= s) ? s : 0;
+}
+bool top_qualifies(long m, long n, long k, const StrassenRec &v, const StrassenTop &t, size_t scratch)
+{
+    if (!v.on || t.smin3 <= 0 || m <= 0 || n <= 0 || m % 2048 != 0 || n % 1024 != 0) return false;
+    if (m / 2 < t.smin3 || n / 2 < t.smin3) return false;
+    const long slab = top_slab(k, t);
+    return slab && (size_t)(m / 2) * (size_t)(n / 2) + (size_t)(m / 2 + n / 2) * (size_t)(slab / 2) <= scratch;
+}
+void put_cfg(std::vector<long long> &out, int at, const StrassenCfg &c)
+{
+    long long *r = &out[out.size() - STRASSEN_REC + at];
+    r[0] = c.smin; r[1] = c.kslab; r[2] = c.smin2; r[3] = c.kslab2; r[4] = c.smin_under;
+}
+// `kind`: the thresholds are those of a lower update's call (1) or of a product of trsm_rec (0), whatever the block itself is
+void top_pass(int lower, long ar, long ac, long br, long bc, long m, long n, long k, long cr, long cc, int kind, const StrassenRec &v,
+              std::vector<long long> &out)
+{
+    put(out, {PLAN3_PASS, lower, ar, ac, br, bc, m, n, k, cr, cc});
+    put_cfg(out, 11, strassen_rec_cfg(v, (int)k, kind));
+}
+void top_gemm(long m, long n, long k, long ar, long br, long cr, long cc, int kind, const StrassenRec &v, const StrassenTop &t,
+              size_t scratch, std::vector<long long> &out)
+{
+    if (!top_qualifies(m, n, k, v, t, scratch)) { top_pass(0, ar, 0, br, 0, m, n, k, cr, cc, kind, v, out); return; }
+    const long slab = top_slab(k, t), m2 = m / 2, n2 = n / 2, k2 = slab / 2;
+    std::vector<long long> seven_recs;
+    long k0 = 0;
+    for (; k0 + slab <= k; k0 += slab) {
+        seven_recs.clear();
+        seven(PLAN3_SUM, PLAN3_PROD, m2, n2, k2, k0, ar, br, cr, cc, seven_recs);
+        for (size_t i = 0; i + STRASSEN_REC <= seven_recs.size(); i += STRASSEN_REC) {
+            const long long *r = &seven_recs[i];
+            if (r[0] == PLAN3_SUM) { out.insert(out.end(), r, r + STRASSEN_REC); continue; }
+            put(out, {PLAN3_ZERO, m2, n2});
+            put(out, {PLAN3_PROD, r[1], r[2], r[3], r[4], r[5], r[6], r[7], r[8], r[9]});
+            put_cfg(out, 10, strassen_rec_cfg(v, (int)k2, kind));
+            put(out, {PLAN3_ACC, m2, n2, r[10], r[11], r[12], r[13], r[14], r[15]});
+        }
+    }
+    if (k0 < k) top_pass(0, ar, k0, br, k0, m, n, k - k0, cr, cc, kind, v, out);
+}
+void top_syrk(long n, long k, const StrassenRec &v, const StrassenTop &t, size_t scratch, std::vector<long long> &out)
+{
+    const long h = n / 2;
+    if (n % 2 != 0 || !top_qualifies(h, h, k, v, t, scratch)) { top_pass(1, 0, 0, 0, 0, n, n, k, 0, 0, 1, v, out); return; }
+    top_pass(1, 0, 0, 0, 0, h, h, k, 0, 0, 1, v, out);
+    top_gemm(h, h, k, h, 0, h, 0, 1, v, t, scratch, out);
+    top_pass(1, h, 0, h, 0, h, h, k, h, h, 1, v, out);
+}
+// doubles per region of the top scratch: T, the A side, the B side
+struct Need3 { size_t v[3] = {0, 0, 0}; size_t total() const { return v[0] + v[1] + v[2]; } };
+Need3 top_need(const std::vector<long long> &plan)
+{
+    Need3 nd;
+    for (size_t i = 0; i + STRASSEN_REC <= plan.size(); i += STRASSEN_REC) {
+        const long long *r = &plan[i];
+        if (r[0] == PLAN3_ZERO) nd.v[0] = std::max(nd.v[0], (size_t)r[1] * (size_t)r[2]);
+        else if (r[0] == PLAN3_SUM) nd.v[1 + r[1]] = std::max(nd.v[1 + r[1]], (size_t)r[2] * (size_t)r[3]);
+    }
+    return nd;
+}
+
+// The top scratch: a buffer of its own per device behind its own mutex -- the half-size calls take g_scratch's lock themselves.
+// Laid out as [T | A side | B side], a second set behind the first where there is room for it.
+struct TopScratch {
+    std::mutex mu;
+    double *p = nullptr;
+    size_t cap = 0, failed = 0;     // doubles; smallest request that could not be allocated (0: none)
+    hipEvent_t ev = nullptr;        // behind the last call that used the buffer
+    hipStream_t last = nullptr;
+    bool used = false;
+    std::vector<hipEvent_t> pool;   // events of the overlapped passes, timing disabled, created on demand
+};
+TopScratch g_top[64];
+
+// tunable "rec_strassen3_buffers": 2 (built in) = a second [T | A | B] set, so that the passes of one top product run under the
+// next; "rec_strassen3_overlap" = 0: all passes on the caller's stream in list order (and one set)
+int top_buffers_wanted() { return (tune("rec_strassen3_overlap", 1) != 0 && tune("rec_strassen3_buffers", 2) >= 2) ? 2 : 1; }
+// room for a call that needs `need` doubles per set: `sets` of them if that can be had, else one
+bool top_ensure(TopScratch &s, size_t need, int sets)
+{
+    if (tune("rec_strassen3_noscratch", 0) != 0) return false;     // tests: the allocation is reported as failed
+    if (s.cap >= need) return true;
+    if (s.failed && need >= s.failed) return false;
+    if (s.p) { (void)hipFree(s.p); s.p = nullptr; s.cap = 0; s.used = false; }   // hipFree waits for the device
+    for (int b = sets; b >= 1; --b) {
+        const size_t want = need * (size_t)b;
+        if (s.failed && want >= s.failed) continue;
+        if (hipMalloc((void **)&s.p, want * sizeof(double)) == hipSuccess) { s.cap = want; return true; }
+        (void)hipGetLastError();
+        s.p = nullptr;
+        s.failed = want;
+    }
+    return false;
+}
+void top_trim()
+{
+    for (TopScratch &s : g_top) {
+        std::lock_guard<std::mutex> lock(s.mu);
+        if (s.p) (void)hipFree(s.p);
+        if (s.ev) (void)hipEventDestroy(s.ev);
+        for (hipEvent_t e : s.pool) if (e) (void)hipEventDestroy(e);
+        s.pool.clear();
+        s.p = nullptr; s.ev = nullptr; s.cap = 0; s.failed = 0; s.used = false; s.last = nullptr;
+    }
+    (void)hipGetLastError();
+}
+
+// Execute a top list.  Serial form: every record on the caller's stream in list order.  Overlapped form: the sums, the zeroing
+// and the accumulations go to the library's low-priority top stream `sd` (one stream: they run in the order they are enqueued,
+// so the accumulations of a C block stay in list order); the half-size calls and the pass-through calls stay on the caller's.
+// With two buffer sets the accumulation of M_i is enqueued BEHIND the sums and the zeroing of M_i+1:
+//     sd:  S0 Z0 S1 Z1 | A0 S2 Z2 | A1 S3 Z3 | ...          caller:  P0 | P1 | P2 ...
+// P_i waits for the event behind Z_i, A_i for the event behind P_i; S_i+2 / Z_i+2 overwrite the set of M_i behind A_i, which has
+// waited for P_i.  So the passes of M_i and the preparation of M_i+2 run under P_i+1.  With one set the accumulation goes in front
+// of the next sums (list order): correct, and nothing overlaps.  sd waits for the caller's stream at entry (the operands may come
+// from the launches just before), the caller's stream waits for sd in front of every pass-through call and on EVERY return.
+int run_top(const std::vector<long long> &plan, const Need3 &nd, double alpha, const double *A, size_t lda, const double *B, size_t ldb,
+            double *C, size_t ldc, TopScratch &s, hipStream_t st)
+{
+    const size_t need = nd.total();
+    const bool overlap = tune("rec_strassen3_overlap", 1) != 0;
+    const int nbuf = (top_buffers_wanted() >= 2 && s.cap >= 2 * need) ? 2 : 1;
+    const long wgs = overlap ? std::min(65535L, std::max(1L, (long)tune("gemm_strassen_sum_wgs", (double)SUM_WGS_SIDE))) : SUM_WGS;
+    hipStream_t sd = st;
+    int rc = 0;
+    if (overlap && (rc = strassen_top_stream(st, &sd))) return rc;
+    auto at = [&](int region, int b) { return s.p + (size_t)b * need + (region == 0 ? 0 : (region == 1 ? nd.v[0] : nd.v[0] + nd.v[1])); };
+    // events: 0 entry, 1 exit / joins, 2 + 2 p behind the zeroing of product p, 3 + 2 p behind product p
+    auto event = [&](size_t i) {
+        if (s.pool.size() <= i) s.pool.resize(i + 1, nullptr);
+        if (!s.pool[i]) SGPR_HIP(hipEventCreateWithFlags(&s.pool[i], hipEventDisableTiming));
+        return 0;
+    };
+    auto join = [&]() {     // the caller's stream waits for everything on sd
+        if (!overlap) return 0;
+        SGPR_HIP(hipEventRecord(s.pool[1], sd));
+        SGPR_HIP(hipStreamWaitEvent(st, s.pool[1], 0));
+        return 0;
+    };
+    struct Join {
+        bool on; hipStream_t sd, st; hipEvent_t ev;
+        ~Join()
+        {
+            if (on && (hipEventRecord(ev, sd) != hipSuccess || hipStreamWaitEvent(st, ev, 0) != hipSuccess)) {
+                (void)hipGetLastError();
+                (void)hipStreamSynchronize(sd);
+            }
+        }
+    };
+    if ((rc = event(0)) || (rc = event(1))) return rc;
+    if (overlap) {
+        SGPR_HIP(hipEventRecord(s.pool[0], st));
+        SGPR_HIP(hipStreamWaitEvent(sd, s.pool[0], 0));
+    }
+    Join at_exit{overlap, sd, st, s.pool[1]};
+    struct Pend { const long long *r; int b; size_t p; };
+    std::vector<Pend> pending;
+    size_t p = 0;       // the top product the records belong to; its buffer set: p % nbuf
+    auto flush = [&]() {
+        for (const Pend &q : pending) {
+            const long long *r = q.r;
+            if (overlap) SGPR_HIP(hipStreamWaitEvent(sd, s.pool[3 + 2 * q.p], 0));
+            const int e = block_acc((int)r[1], (int)r[2], at(0, q.b), C + r[3] + (size_t)r[4] * ldc, alpha * (double)r[5],
+                                    r[8] ? C + r[6] + (size_t)r[7] * ldc : nullptr, alpha * (double)r[8], ldc, sd, wgs);
+            if (e) return e;
+        }
+        pending.clear();
+        return 0;
+    };
+    for (size_t i = 0; i + STRASSEN_REC <= plan.size(); i += STRASSEN_REC) {
+        const long long *r = &plan[i];
+        const int b = (int)(p % (size_t)nbuf);
+        if (r[0] == PLAN3_SUM) {
+            if (nbuf == 1 && (rc = flush())) return rc;
+            const double *P = r[1] ? B : A;
+            const size_t ld = r[1] ? ldb : lda;
+            rc = block_sum((int)r[2], (int)r[3], P + r[4] + (size_t)r[5] * ld, ld, P + r[6] + (size_t)r[7] * ld, ld, (double)r[8],
+                           at(1 + (int)r[1], b), sd, wgs);
+        } else if (r[0] == PLAN3_ZERO) {
+            if (nbuf == 1 && (rc = flush())) return rc;
+            SGPR_HIP(hipMemsetAsync(at(0, b), 0, (size_t)r[1] * (size_t)r[2] * sizeof(double), sd));
+        } else if (r[0] == PLAN3_PROD) {
+            const int m = (int)r[7], n = (int)r[8], k = (int)r[9];
+            if (overlap) {
+                if ((rc = event(2 + 2 * p)) || (rc = event(3 + 2 * p))) return rc;
+                SGPR_HIP(hipEventRecord(s.pool[2 + 2 * p], sd));
+                SGPR_HIP(hipStreamWaitEvent(st, s.pool[2 + 2 * p], 0));
+            }
+            const double *X = r[1] ? at(1, b) : A + r[2] + (size_t)r[3] * lda;
+            const double *Y = r[4] ? at(2, b) : B + r[5] + (size_t)r[6] * ldb;
+            StrassenCfg cfg;
+            cfg.smin = (long)r[10]; cfg.kslab = (long)r[11]; cfg.smin2 = (long)r[12]; cfg.kslab2 = (long)r[13]; cfg.smin_under = (long)r[14];
+            rc = gemm_nt_strassen_cfg(m, n, k, 1.0, X, r[1] ? (size_t)m : lda, Y, r[4] ? (size_t)n : ldb, 1.0, at(0, b), (size_t)m, 0, cfg, st);
+            if (rc) return rc;
+            if (overlap) SGPR_HIP(hipEventRecord(s.pool[3 + 2 * p], st));
+            rc = flush();       // the accumulations of the products before this one: behind its sums, under it
+        } else if (r[0] == PLAN3_ACC) {
+            pending.push_back(Pend{r, b, p});
+            ++p;
+        } else if (r[0] == PLAN3_PASS) {
+            if ((rc = flush()) || (rc = join())) return rc;
+            StrassenCfg cfg;
+            cfg.smin = (long)r[11]; cfg.kslab = (long)r[12]; cfg.smin2 = (long)r[13]; cfg.kslab2 = (long)r[14]; cfg.smin_under = (long)r[15];
+            rc = gemm_nt_strassen_cfg((int)r[6], (int)r[7], (int)r[8], alpha, A + r[2] + (size_t)r[3] * lda, lda, B + r[4] + (size_t)r[5] * ldb, ldb,
+                                      1.0, C + r[9] + (size_t)r[10] * ldc, ldc, (int)r[1], cfg, st);
+        } else {
+            set_error("run_top: unknown record");
+            rc = SGPR_E_ARG;
+        }
+        if (rc) return rc;
+    }
+    return flush();
+}
+}  // namespace
+
+StrassenTop strassen_top_values()
+{
+    StrassenTop t;
+    t.smin3 = std::max(0L, (long)tune("rec_strassen3_min", (double)REC_SMIN3));
+    t.kslab3 = std::max(0L, (long)tune("rec_strassen3_kslab", (double)REC_KSLAB3));
+    t.kslab3_short = std::max(0L, (long)tune("rec_strassen3_kslab_short", (double)REC_KSLAB3_SHORT));
+    return t;
+}
+
+// the top list of one call as the host decides it (no device)
+int strassen_top_plan(int m, int n, int k, int lower, const StrassenRec *vp, const StrassenTop *tp, size_t scratch_doubles,
+                      std::vector<long long> &out)
+{
+    const StrassenRec v = vp ? *vp : strassen_rec_values();
+    const StrassenTop t = tp ? *tp : strassen_top_values();
+    if (m < 0 || n < 0 || k < 0 || (lower && m != n)) { set_error("strassen_top_plan: bad extents"); return SGPR_E_ARG; }
+    out.clear();
+    if (lower) top_syrk(n, k, v, t, scratch_doubles, out);
+    else       top_gemm(m, n, k, 0, 0, 0, 0, 0, v, t, scratch_doubles, out);
+    return 0;
+}
+int strassen_cfg_plan(int m, int n, int k, int lower, const long cfg[5], std::vector<long long> &out)
+{
+    if (m < 0 || n < 0 || k < 0 || (lower && m != n) || !cfg) { set_error("strassen_cfg_plan: bad arguments"); return SGPR_E_ARG; }
+    StrassenCfg c;
+    c.smin = cfg[0]; c.kslab = cfg[1]; c.smin2 = cfg[2]; c.kslab2 = cfg[3]; c.smin_under = cfg[4];
+    outer_plan_of(m, n, k, lower, cfg2_of(c, ~(size_t)0), out);
+    return 0;
+}
+size_t strassen_top_scratch_doubles(int m, int n, int k, int lower, const StrassenRec &v, const StrassenTop &t)
+{
+    std::vector<long long> plan;
+    if (strassen_levels() < 2 || strassen_top_plan(m, n, k, lower, &v, &t, ~(size_t)0, plan)) return 0;
+    return top_need(plan).total();
+}
+// make room for the top level's calls of one factorisation (potrf: once, before the first launch): two buffer sets if they can
+// be had, else one; if not even that, the top level is off call by call and nothing else changes
+void strassen_top_reserve(size_t need, hipStream_t st)
+{
+    const int dev = device_of(st);
+    if (dev < 0 || !need) return;
+    TopScratch &s = g_top[dev];
+    std::lock_guard<std::mutex> lock(s.mu);
+    if (s.cap >= need * (size_t)top_buffers_wanted()) return;
+    if (s.cap >= need && s.failed && need * 2 >= s.failed) return;      // the second set has been refused before
+    if (s.p) { (void)hipFree(s.p); s.p = nullptr; s.cap = 0; s.used = false; }
+    (void)top_ensure(s, need, top_buffers_wanted());
+}
+
+// C += alpha A B^T as the recursion issues it, with the top level where it applies.  Whatever does not qualify is exactly the
+// call gemm_nt_strassen_cfg(..., strassen_rec_cfg(v, k, lower), st) that stood here before.
+int strassen_top_gemm(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb, double beta,
+                      double *C, size_t ldc, int lower, const StrassenRec *vp, const StrassenTop *tp, hipStream_t st)
+{
+    const StrassenRec v = vp ? *vp : strassen_rec_values();
+    const StrassenTop t = tp ? *tp : strassen_top_values();
+    const StrassenCfg cfg = strassen_rec_cfg(v, k, lower);
+    // (the size test first: the short products of the panel solves come through here by the thousand)
+    const bool aligned = ((((uintptr_t)A | (uintptr_t)B | (uintptr_t)C) & 15) == 0) && (((lda | ldb | ldc) & 1) == 0);
+    const int dev = (!v.on || t.smin3 <= 0 || std::min(lower ? m / 2 : m, lower ? n / 2 : n) / 2 < t.smin3) ? -1 : device_of(st);
+    if (dev < 0 || strassen_levels() < 2 || !aligned || beta != 1.0 || (lower && m != n))
+        return gemm_nt_strassen_cfg(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, lower, cfg, st);
+    std::vector<long long> plan;
+    int rc = strassen_top_plan(m, n, k, lower, &v, &t, ~(size_t)0, plan);
+    if (rc) return rc;
+    const Need3 nd = top_need(plan);
+    if (nd.total()) {
+        TopScratch &s = g_top[dev];
+        std::lock_guard<std::mutex> lock(s.mu);
+        if (top_ensure(s, nd.total(), top_buffers_wanted())) {
+            if (!s.ev) SGPR_HIP(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+            if (s.used && s.last != st) SGPR_HIP(hipStreamWaitEvent(st, s.ev, 0));
+            rc = run_top(plan, nd, alpha, A, lda, B, ldb, C, ldc, s, st);
+            SGPR_HIP(hipEventRecord(s.ev, st));
+            s.last = st;
+            s.used = true;
+            return rc;
+        }
+    }
+    return gemm_nt_strassen_cfg(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, lower, cfg, st);
 }
 
 }  // namespace sgpr

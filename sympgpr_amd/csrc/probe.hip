@@ -607,6 +607,41 @@ extern "C" int sgpr_probe_gemm_nt4_dev(int m, int n, int k, const double *A, siz
 {
     return gemm_nt_multi(m, n, k, A, lda, B, ldb, beta, count, C, ldc, alpha, static_cast<hipStream_t>(stream));
 }
+// ---- the top Strassen level of the recursion's largest products: the list of one call, the list of a call under explicit
+// thresholds (what the half-size and pass-through calls of that list turn into), the buffer potrf() reserves at an order, and
+// one product on device pointers as the recursion would issue it
+extern "C" int sgpr_probe_strassen_top_plan(int m, int n, int k, int lower, long scratch_doubles, long long *out, int max_records, int *count)
+{
+    if (!count || scratch_doubles < 0) { set_error("probe_strassen_top_plan: bad arguments"); return SGPR_E_ARG; }
+    std::vector<long long> plan;
+    const int rc = strassen_top_plan(m, n, k, lower, nullptr, nullptr, (size_t)scratch_doubles, plan);
+    if (rc) return rc;
+    *count = (int)(plan.size() / STRASSEN_REC);
+    for (size_t i = 0; out && i < plan.size() && (int)(i / STRASSEN_REC) < max_records; ++i) out[i] = plan[i];
+    return 0;
+}
+extern "C" int sgpr_probe_strassen_cfg_plan(int m, int n, int k, int lower, const long cfg[5], long long *out, int max_records, int *count)
+{
+    if (!count) { set_error("probe_strassen_cfg_plan: bad arguments"); return SGPR_E_ARG; }
+    std::vector<long long> plan;
+    const int rc = strassen_cfg_plan(m, n, k, lower, cfg, plan);
+    if (rc) return rc;
+    *count = (int)(plan.size() / STRASSEN_REC);
+    for (size_t i = 0; out && i < plan.size() && (int)(i / STRASSEN_REC) < max_records; ++i) out[i] = plan[i];
+    return 0;
+}
+extern "C" int sgpr_probe_strassen_top_scratch(int n, unsigned long long out[2])
+{
+    if (n < 0 || !out) { set_error("probe_strassen_top_scratch: bad arguments"); return SGPR_E_ARG; }
+    out[0] = potrf_strassen_top_need(n);
+    out[1] = 2 * out[0];
+    return 0;
+}
+extern "C" int sgpr_probe_gemm_strassen_top_dev(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb,
+                                                double beta, double *C, size_t ldc, int lower, void *stream)
+{
+    return strassen_top_gemm(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, lower, nullptr, nullptr, static_cast<hipStream_t>(stream));
+}
 // ---- the arena layout of a batched fit (batch.hip: batch_layout), host arithmetic only: no device call
 extern "C" int sgpr_probe_batch_layout(int path, int mode, int d, int reg, int nbatch, int n_pts, int nhyp, unsigned long long out[24])
 {
