@@ -77,7 +77,7 @@ int sgpr_probe_queue_force_giveup(int on);
  * Block solves: trsm_chain (workgroups of the chain class, 0 = built-in), trsm_piece (tiles per stream ticket, 0 = built-in: 16 up
  * to 128 strips, 128 above; read per call). */
 int sgpr_probe_tune(const char *name, double value);
-/* The Strassen front end of the fp64 NT product (csrc/gemm_f64.hip).  Host only: the list of operations one call
+/* The Strassen front end of the fp64 NT product (csrc/strassen.h: the record layouts; csrc/strassen_plan.hip: the planner; csrc/strassen.hip: the device path).  Host only: the list of operations one call
  * C -= A B^T (m x n x k; lower: the lower triangle of a square C) turns into, for a threshold `smin` (smallest half-size of m and n
  * that qualifies; k: half of it), a k slab `kslab` (< 0: the built-in values / tunables gemm_strassen_min, gemm_strassen_kslab)
  * and `scratch_doubles` of scratch.  16 words per record, word 0 = kind:
@@ -95,7 +95,7 @@ int sgpr_probe_gemm_strassen_dev(int m, int n, int k, double alpha, const double
                                  double beta, double *C, size_t ldc, int lower, void *stream);
 int sgpr_probe_gemm_nt2_dev(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb,
                             double beta, double *C, size_t ldc, double alpha2, double *C2, size_t ldc2, void *stream);
-/* The outer Strassen level (csrc/gemm_f64.hip).  Host only: the list of one call with both levels.  Records of the inner level
+/* The outer Strassen level (csrc/strassen_plan.hip).  Host only: the list of one call with both levels.  Records of the inner level
  * (kinds 1 - 3 above, unchanged: a call the outer level does not apply to gives exactly sgpr_probe_strassen_plan's list) and
  *   4 outer sum:     layout of kind 1; the result goes to the OUTER scratch of that side
  *   5 outer product: layout of kind 2; operands are raw blocks or the outer scratch, [7] [8] [9] the half-size extents.  Not a
@@ -171,7 +171,7 @@ int sgpr_probe_census(int na, int threads_a, int lds_a, int spin_a, const unsign
                       int nb, int threads_b, int lds_b, int spin_b, const unsigned *mask_b, int nwords_b,
                       unsigned long long *host_out);
 
-/* A third Strassen level on top of the front end, for the recursion's largest products (csrc/gemm_f64.hip: strassen_top_plan).
+/* A third Strassen level on top of the front end, for the recursion's largest products (csrc/strassen_plan.hip: strassen_top_plan).
  * Tunables, read at every factorisation: rec_strassen3_min (smallest half-size of m and n that takes it; 0: off),
  * rec_strassen3_kslab / rec_strassen3_kslab_short (top k slab of a call whose k reaches the long one / of a shorter call; 0: none),
  * rec_strassen3_overlap (1: the top passes run on a low-priority stream of their own under the next product; 0: on the caller's

@@ -20,6 +20,7 @@
 
 #include "cholq.h"
 #include "common.h"
+#include "strassen.h"
 #include "gemm_tile.h"
 #include "leaf.h"
 
@@ -1171,7 +1172,13 @@ struct StreamJoin {
 // whatever number of handles / threads are factoring.  The workgroups it waits for are its own (dispatched in block
 // order, each as soon as ONE CU drains); everything else on the device is an MFMA / Gram / solve launch whose
 // workgroups end by themselves.  tests/test_gpu_threads.py runs three handles at n = 16384 against this.
-hipStream_t g_side[64] = {};
+// The library's streams on one device, created on first use.  Slot 0: that side stream, at the HIGHEST priority.  Slots 1, 2: the
+// Strassen front end's operand sums (strassen.hip: run_schedule), at the LOWEST -- the sums fill what the products leave free and
+// must never hold one up.  Slot 3: the passes of the top Strassen level (run_top), lowest too and a stream of their own, because
+// run_schedule makes its side stream wait for the caller's at every entry -- a top pass queued there would sit in front of the
+// next half-size call's first inner sums.  Caller + panel + sums + top passes: four hardware queues.
+enum { SLOT_PANEL = 0, SLOT_SUM = 1, SLOT_TOP = 3, N_SLOT = 4 };
+hipStream_t g_streams[64][N_SLOT] = {};
 std::mutex g_side_mu;                                      // two fit handles may factor for the first time at once
 
 // The streams this library creates are handed back by an exit handler of the LIBRARY, registered when the first of them is
@@ -1187,89 +1194,40 @@ void register_exit_release()
     std::call_once(once, [] { (void)atexit(release_all_streams_at_exit); });
 }
 
-int side_stream(hipStream_t caller, hipStream_t *out, int *dev_out)
+// out[0 .. count): the streams of slots first .. first + count - 1 on the device that owns the caller's stream (the null stream
+// belongs to the current device); bad_device: the message for a device index out of range
+int lib_streams(hipStream_t caller, int first, int count, const char *bad_device, hipStream_t *out, int *dev_out = nullptr)
 {
-    hipStream_t *const side = g_side;
-    int dev = -1;
-    if (caller) {
-        SGPR_HIP(hipStreamGetDevice(caller, &dev));        // the device that owns the caller's stream
-    } else {
-        SGPR_HIP(hipGetDevice(&dev));                      // the null stream belongs to the current device
-    }
-    if (dev < 0 || dev >= 64) { set_error("potrf: device index out of range"); return SGPR_E_ARG; }
+    hipError_t e = hipSuccess;
+    const int dev = device_of(caller, &e);
+    SGPR_HIP(e);
+    if (dev < 0 || !out || count < 1) { set_error(bad_device); return SGPR_E_ARG; }
     std::lock_guard<std::mutex> lock(g_side_mu);
-    if (!side[dev]) {
-        int cur = -1, lo = 0, hi = 0;
-        SGPR_HIP(hipGetDevice(&cur));
-        if (cur != dev) SGPR_HIP(hipSetDevice(dev));
-        hipError_t e = hipDeviceGetStreamPriorityRange(&lo, &hi);
-        if (e == hipSuccess) e = hipStreamCreateWithPriority(&side[dev], hipStreamNonBlocking, hi);
-        if (e == hipSuccess) register_exit_release();
-        if (cur != dev) (void)hipSetDevice(cur);
-        SGPR_HIP(e);
-    }
-    *out = side[dev];
-    *dev_out = dev;
-    return 0;
-}
-
-// The streams of the Strassen front end's operand sums (gemm_f64.hip: run_schedule): two per device at the LOWEST priority --
-// the sums fill what the products leave free and must never hold one up.  Same life as the side stream above.
-hipStream_t g_sum[64][3] = {};      // [2]: the top level's passes (strassen_top_stream)
-}  // namespace
-
-int strassen_sum_streams(hipStream_t caller, int count, hipStream_t *out)
-{
-    int dev = -1;
-    if (caller) {
-        SGPR_HIP(hipStreamGetDevice(caller, &dev));
-    } else {
-        SGPR_HIP(hipGetDevice(&dev));
-    }
-    if (dev < 0 || dev >= 64 || count < 1 || count > 2) { set_error("strassen_sum_streams: bad device or count"); return SGPR_E_ARG; }
-    std::lock_guard<std::mutex> lock(g_side_mu);
-    for (int t = 0; t < count; ++t) {
-        if (!g_sum[dev][t]) {
+    for (int slot = first; slot < first + count; ++slot) {
+        hipStream_t &s = g_streams[dev][slot];
+        if (!s) {
             int cur = -1, lo = 0, hi = 0;
             SGPR_HIP(hipGetDevice(&cur));
             if (cur != dev) SGPR_HIP(hipSetDevice(dev));
-            hipError_t e = hipDeviceGetStreamPriorityRange(&lo, &hi);
-            if (e == hipSuccess) e = hipStreamCreateWithPriority(&g_sum[dev][t], hipStreamNonBlocking, lo);
+            e = hipDeviceGetStreamPriorityRange(&lo, &hi);
+            if (e == hipSuccess) e = hipStreamCreateWithPriority(&s, hipStreamNonBlocking, slot == SLOT_PANEL ? hi : lo);
             if (e == hipSuccess) register_exit_release();
             if (cur != dev) (void)hipSetDevice(cur);
             SGPR_HIP(e);
         }
-        out[t] = g_sum[dev][t];
+        out[slot - first] = s;
     }
+    if (dev_out) *dev_out = dev;
     return 0;
 }
+int side_stream(hipStream_t caller, hipStream_t *out, int *dev_out) { return lib_streams(caller, SLOT_PANEL, 1, "potrf: device index out of range", out, dev_out); }
+}  // namespace
 
-// ... and a third one of the same kind for the passes of the top Strassen level (gemm_f64.hip: run_top): a stream of their own,
-// because run_schedule makes its side stream wait for the caller's at every entry -- a top pass queued there would sit in front
-// of the next half-size call's first inner sums.  Caller + panel + sums + this: four hardware queues.
-int strassen_top_stream(hipStream_t caller, hipStream_t *out)
+int strassen_sum_streams(hipStream_t caller, int count, hipStream_t *out)
 {
-    int dev = -1;
-    if (caller) {
-        SGPR_HIP(hipStreamGetDevice(caller, &dev));
-    } else {
-        SGPR_HIP(hipGetDevice(&dev));
-    }
-    if (dev < 0 || dev >= 64 || !out) { set_error("strassen_top_stream: bad device"); return SGPR_E_ARG; }
-    std::lock_guard<std::mutex> lock(g_side_mu);
-    if (!g_sum[dev][2]) {
-        int cur = -1, lo = 0, hi = 0;
-        SGPR_HIP(hipGetDevice(&cur));
-        if (cur != dev) SGPR_HIP(hipSetDevice(dev));
-        hipError_t e = hipDeviceGetStreamPriorityRange(&lo, &hi);
-        if (e == hipSuccess) e = hipStreamCreateWithPriority(&g_sum[dev][2], hipStreamNonBlocking, lo);
-        if (e == hipSuccess) register_exit_release();
-        if (cur != dev) (void)hipSetDevice(cur);
-        SGPR_HIP(e);
-    }
-    *out = g_sum[dev][2];
-    return 0;
+    return lib_streams(caller, SLOT_SUM, (count == 1 || count == 2) ? count : 0, "strassen_sum_streams: bad device or count", out);
 }
+int strassen_top_stream(hipStream_t caller, hipStream_t *out) { return lib_streams(caller, SLOT_TOP, 1, "strassen_top_stream: bad device", out); }
 
 namespace {
 
@@ -1366,13 +1324,10 @@ thread_local bool t_last_potrf_used_queue = false;   // set by potrf_queue once 
 // returns 1 when the queue form cannot be used here (the caller falls back to the look-ahead driver), < 0 on errors
 int potrf_queue(int n, double *A, size_t lda, const Ctx &c, int off0)
 {
-    int dev = -1;
-    if (c.st) {
-        SGPR_HIP(hipStreamGetDevice(c.st, &dev));
-    } else {
-        SGPR_HIP(hipGetDevice(&dev));
-    }
-    if (dev < 0 || dev >= 64) { set_error("potrf: device index out of range"); return SGPR_E_ARG; }
+    hipError_t e = hipSuccess;
+    const int dev = device_of(c.st, &e);
+    SGPR_HIP(e);
+    if (dev < 0) { set_error("potrf: device index out of range"); return SGPR_E_ARG; }
     QueueDevice &qd = g_qdev[dev];
     std::lock_guard<std::mutex> lock(qd.mu);
     if (qd.failed) return 1;
@@ -1469,8 +1424,7 @@ void release_all_streams_at_exit()
         int nd = 0;
         {
             std::lock_guard<std::mutex> lock(g_side_mu);
-            if (g_side[dev]) { drop[nd++] = g_side[dev]; g_side[dev] = nullptr; }
-            for (hipStream_t &s : g_sum[dev]) if (s) { drop[nd++] = s; s = nullptr; }
+            for (hipStream_t &s : g_streams[dev]) if (s) { drop[nd++] = s; s = nullptr; }
         }
         {
             QueueDevice &qd = g_qdev[dev];
@@ -1500,7 +1454,7 @@ int release_streams(int dev)
         bool any = false;
         {
             std::lock_guard<std::mutex> lock(g_side_mu);
-            any = g_side[dev] != nullptr || g_sum[dev][0] != nullptr || g_sum[dev][1] != nullptr || g_sum[dev][2] != nullptr;
+            for (hipStream_t t : g_streams[dev]) any = any || t != nullptr;
         }
         QueueDevice &qd = g_qdev[dev];
         std::lock_guard<std::mutex> lock(qd.mu);
@@ -1521,10 +1475,7 @@ int release_streams(int dev)
     };
     {
         std::lock_guard<std::mutex> lock(g_side_mu);
-        drop(g_side[dev]);
-        drop(g_sum[dev][0]);
-        drop(g_sum[dev][1]);
-        drop(g_sum[dev][2]);
+        for (hipStream_t &t : g_streams[dev]) drop(t);
     }
     {
         QueueDevice &qd = g_qdev[dev];
@@ -1776,8 +1727,8 @@ bool potrf_queue_mark_failed(hipStream_t st)
     // handles that give up in the same moment must both get their retry, whoever marks the device first.)
     const bool used = t_last_potrf_used_queue;
     if (!used) return false;
-    int dev = -1;
-    if ((st ? hipStreamGetDevice(st, &dev) : hipGetDevice(&dev)) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); return false; }
+    const int dev = device_of(st);
+    if (dev < 0) return false;
     QueueDevice &qd = g_qdev[dev];
     std::lock_guard<std::mutex> lock(qd.mu);
     qd.failed = true;
@@ -1813,61 +1764,52 @@ int la_max_value()
     return v;
 }
 // The largest scratch over the products the recursion will issue (the same walk as potrf_rec / trsm_rec, sizes only): every
-// call plans with thresholds of its own, so the largest product need not be the one with the largest need.
-void need_trsm(int m, int n, const StrassenRec &v, int levels, size_t &need)
+// call plans with thresholds of its own, so the largest product need not be the one with the largest need.  need_of(m, n, k,
+// lower): the scratch of one product; cut: below this many rows or columns nothing qualifies.
+template <typename F>
+void need_trsm(int m, int n, long cut, F &need_of, size_t &need)
 {
-    if (n <= LEAF || std::min(m, n) < 256) return;      // below: nothing qualifies under any threshold (>= 128 per half)
+    if (n <= LEAF || std::min(m, n) < cut) return;
     const int n1 = split(n), n2 = n - n1;
-    need_trsm(m, n1, v, levels, need);
-    need = std::max(need, strassen_scratch_doubles_cfg(m, n2, n1, 0, levels, strassen_rec_cfg(v, n1, 0)));
-    need_trsm(m, n2, v, levels, need);
+    need_trsm(m, n1, cut, need_of, need);
+    need = std::max(need, need_of(m, n2, n1, 0));
+    need_trsm(m, n2, cut, need_of, need);
 }
-void need_potrf(int n, int la_max, const StrassenRec &v, int levels, size_t &need)
+template <typename F>
+void need_potrf(int n, int la_max, long cut, F &need_of, size_t &need)
 {
     if (n <= LEAF || (n > 4 * LEAF && n <= la_max)) return;
     const int n1 = split(n), n2 = n - n1;
-    need_potrf(n1, la_max, v, levels, need);
-    need_trsm(n2, n1, v, levels, need);
-    need = std::max(need, strassen_scratch_doubles_cfg(n2, n2, n1, 1, levels, strassen_rec_cfg(v, n1, 1)));
-    need_potrf(n2, la_max, v, levels, need);
+    need_potrf(n1, la_max, cut, need_of, need);
+    need_trsm(n2, n1, cut, need_of, need);
+    need = std::max(need, need_of(n2, n2, n1, 1));
+    need_potrf(n2, la_max, cut, need_of, need);
 }
-// ... and the same walk for the top level's own buffer
-void need3_trsm(int m, int n, const StrassenRec &v, const StrassenTop &t, size_t &need)
+int walk_la_max()
 {
-    if (n <= LEAF || std::min(m, n) / 2 < t.smin3) return;
-    const int n1 = split(n), n2 = n - n1;
-    need3_trsm(m, n1, v, t, need);
-    need = std::max(need, strassen_top_scratch_doubles(m, n2, n1, 0, v, t));
-    need3_trsm(m, n2, v, t, need);
-}
-void need3_potrf(int n, int la_max, const StrassenRec &v, const StrassenTop &t, size_t &need)
-{
-    if (n <= LEAF || (n > 4 * LEAF && n <= la_max)) return;
-    const int n1 = split(n), n2 = n - n1;
-    need3_potrf(n1, la_max, v, t, need);
-    need3_trsm(n2, n1, v, t, need);
-    need = std::max(need, strassen_top_scratch_doubles(n2, n2, n1, 1, v, t));
-    need3_potrf(n2, la_max, v, t, need);
+    static const bool rec_mode = [] { const char *e = getenv("SGPR_POTRF"); return e && e[0] == 'r'; }();
+    return rec_mode ? 0 : la_max_value();
 }
 }  // namespace
 
 size_t potrf_strassen_top_need(int n)
 {
-    static const bool rec_mode = [] { const char *e = getenv("SGPR_POTRF"); return e && e[0] == 'r'; }();
     const StrassenRec v = strassen_rec_values();
     const StrassenTop t = strassen_top_values();
     size_t need = 0;
-    if (v.on && t.smin3 > 0) need3_potrf(n, rec_mode ? 0 : la_max_value(), v, t, need);
+    auto need_of = [&](int m, int nn, int k, int lower) { return strassen_top_scratch_doubles(m, nn, k, lower, v, t); };
+    if (v.on && t.smin3 > 0) need_potrf(n, walk_la_max(), 2 * t.smin3, need_of, need);    // halves of at least smin3
     return need;
 }
 
 void potrf_strassen_need(int n, size_t out[2])
 {
-    static const bool rec_mode = [] { const char *e = getenv("SGPR_POTRF"); return e && e[0] == 'r'; }();
     const StrassenRec v = strassen_rec_values();
     out[0] = out[1] = 0;
-    need_potrf(n, rec_mode ? 0 : la_max_value(), v, 2, out[0]);
-    need_potrf(n, rec_mode ? 0 : la_max_value(), v, 1, out[1]);
+    for (int levels = 2; levels >= 1; --levels) {
+        auto need_of = [&](int m, int nn, int k, int lower) { return strassen_scratch_doubles_cfg(m, nn, k, lower, levels, strassen_rec_cfg(v, k, lower)); };
+        need_potrf(n, walk_la_max(), 256, need_of, out[2 - levels]);      // every threshold is at least 128 per half
+    }
 }
 
 int potrf(int n, double *A, size_t lda, void *work, size_t lwork, int *dinfo, hipStream_t st)

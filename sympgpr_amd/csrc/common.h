@@ -24,6 +24,18 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line);
     } while (0)
 
 #define SGPR_CHECK_LAUNCH() SGPR_HIP(hipGetLastError())
+#define SGPR_HIP_TYPES 1    // strassen.h: hipStream_t is declared
+
+// the device that owns a stream (the null stream: the current device) as an index of the per-device tables, 0 .. 63; -1: the
+// runtime refused (its error state is cleared; *err, where given, holds what it said) or the index is out of range
+inline int device_of(hipStream_t st, hipError_t *err = nullptr)
+{
+    int dev = -1;
+    const hipError_t e = st ? hipStreamGetDevice(st, &dev) : hipGetDevice(&dev);
+    if (err) *err = e;
+    if (e != hipSuccess) { (void)hipGetLastError(); return -1; }
+    return (dev >= 0 && dev < 64) ? dev : -1;
+}
 
 // Hyper-parameters split the way the reference does (`l = hyp[:-1]; sig = hyp[-1]`),
 // plus the derived constants every Gram kernel uses.
@@ -127,68 +139,9 @@ int gemm_nn(int m, int n, int k, double alpha, const double *A, size_t lda, cons
 // two destinations from one product: C = beta C + alpha A B^T, C2 += alpha2 A B^T
 int gemm_nt_two(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb, double beta,
              double *C, size_t ldc, double alpha2, double *C2, size_t ldc2, hipStream_t st);
-// one level of Strassen's algorithm in front of gemm_nt (gemm_f64.hip); lower: the SYRK decomposition around it
-constexpr int STRASSEN_REC = 16;                 // words per plan record
-enum { PLAN_SUM = 1, PLAN_PROD = 2, PLAN_CLASSIC = 3 };
-int gemm_nt_strassen(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb, double beta,
-                     double *C, size_t ldc, int lower, hipStream_t st);
-int strassen_plan(int m, int n, int k, int lower, long smin, long kslab, size_t scratch_doubles, std::vector<long long> &out);
-// a second level around it for the largest products: the outer list (records of the inner level + PLAN2_*, same layouts)
-enum { PLAN2_SUM = 4, PLAN2_PROD = 5 };
-int strassen_outer_plan(int m, int n, int k, int lower, long smin, long kslab, long smin2, long kslab2, size_t scratch_doubles,
-                   std::vector<long long> &out);
 // up to four destinations from one product (disjoint blocks): C[0] = beta C[0] + alpha[0] A B^T, C[d] += alpha[d] A B^T
 int gemm_nt_multi(int m, int n, int k, const double *A, size_t lda, const double *B, size_t ldb, double beta, int count,
                   double *const *C, const size_t *ldc, const double *alpha, hipStream_t st);
-size_t strassen_scratch_doubles(int m, int n, int k, int lower, int levels);
-// The thresholds of ONE call of the front end; a negative member: the library's value (gemm_strassen_* / gemm_strassen2_*).
-// smin_under: the inner threshold that holds under an outer product (negative: smin).
-struct StrassenCfg { long smin = -1, kslab = -1, smin2 = -1, kslab2 = -1, smin_under = -1; };
-int gemm_nt_strassen_cfg(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb, double beta,
-                         double *C, size_t ldc, int lower, const StrassenCfg &cfg, hipStream_t st);
-size_t strassen_scratch_doubles_cfg(int m, int n, int k, int lower, int levels, const StrassenCfg &cfg);
-// The recursive factorisation's own values (potrf_rec / trsm_rec; tunables "rec_strassen_*"): inner and outer
-// threshold for the products of trsm_rec and for the lower updates, and the outer k slab of a call whose k is shorter than
-// the long outer slab (0: such a call takes no outer level); the inner and the long outer k slab are the library's unless
-// tuned.  on = false (SGPR_GEMM_STRASSEN set): the library's values.
-struct StrassenRec { bool on = false; long smin_gemm = 0, smin_syrk = 0, smin2_gemm = 0, smin2_syrk = 0, kslab = 0, kslab2 = 0, kslab2_short = 0; };
-StrassenRec strassen_rec_values();
-StrassenCfg strassen_rec_cfg(const StrassenRec &v, int k, int lower);
-// the third probe entry: the list of one call as the recursion would plan it; cfg_out (may be null): the thresholds it resolved
-// to (smin, kslab, smin2, kslab2, smin_under); and the product itself on device pointers
-int strassen_rec_plan(int m, int n, int k, int lower, long cfg_out[5], size_t scratch_doubles, std::vector<long long> &out);
-int gemm_nt_strassen_rec(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb, double beta,
-                         double *C, size_t ldc, int lower, hipStream_t st);
-// the fourth probe entry: the schedule by which that list is executed with its operand sums on side streams (tunable
-// "gemm_strassen_overlap"; gemm_f64.hip: schedule_of) for a scratch buffer of cap_doubles (< 0: the call's need)
-constexpr int SCHED_REC = 32;                    // words per schedule record: the plan record + its annotations
-int strassen_schedule(int m, int n, int k, int lower, long long cap_doubles, long long info[12], std::vector<long long> &out);
-// chol.hip: the library's low-priority streams for those sums on the device of `caller` (count = 1 or 2; created on first use,
-// released with the look-ahead driver's side stream)
-int strassen_sum_streams(hipStream_t caller, int count, hipStream_t *out);
-void potrf_strassen_need(int n, size_t out[2]);  // chol.hip: what potrf() reserves at order n (both levels, one level)
-void strassen_reserve(size_t both, size_t one, hipStream_t st);
-int strassen_trim();                             // release the scratch of the operand sums (every device)
-// A third level ON TOP of gemm_nt_strassen_cfg for the recursion's largest products (gemm_f64.hip: strassen_top_gemm): the same seven
-// formulas on the halves, each top product formed in a temporary by one half-size call of gemm_nt_strassen_cfg and added to its
-// blocks of C by a streaming pass.  Records (STRASSEN_REC words, layouts in gemm_f64.hip):
-enum { PLAN3_SUM = 6, PLAN3_ZERO = 7, PLAN3_PROD = 8, PLAN3_ACC = 9, PLAN3_PASS = 10 };
-// Tunables "rec_strassen3_min" (half-size of m and n; 0: off), "rec_strassen3_kslab" / "rec_strassen3_kslab_short" (top k slab of
-// a call whose k reaches the long one / of a shorter call; 0: none), read with the recursion's other values.
-struct StrassenTop { long smin3 = 0, kslab3 = 0, kslab3_short = 0; };
-StrassenTop strassen_top_values();
-// (v / t null: the values as the next factorisation would read them)
-int strassen_top_plan(int m, int n, int k, int lower, const StrassenRec *v, const StrassenTop *t, size_t scratch_doubles,
-                      std::vector<long long> &out);
-// the list of one call under explicit thresholds (what a PLAN3_PROD / PLAN3_PASS record's call turns into)
-int strassen_cfg_plan(int m, int n, int k, int lower, const long cfg[5], std::vector<long long> &out);
-size_t strassen_top_scratch_doubles(int m, int n, int k, int lower, const StrassenRec &v, const StrassenTop &t);
-// the recursion's entry (not named gemm_nt_strassen*: those are the front end's exported entries, csrc/exports.map)
-int strassen_top_gemm(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb, double beta,
-                      double *C, size_t ldc, int lower, const StrassenRec *v, const StrassenTop *t, hipStream_t st);
-size_t potrf_strassen_top_need(int n);           // chol.hip: doubles of top-level scratch at order n (one buffer per region)
-void strassen_top_reserve(size_t need, hipStream_t st);
-int strassen_top_stream(hipStream_t caller, hipStream_t *out);   // chol.hip: the low-priority stream of the top level's passes
 int gemm_profile_begin();
 int gemm_profile_end(double *out12);
 int gemm_profile_launches(double *buf, int max_records);

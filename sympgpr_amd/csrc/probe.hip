@@ -7,6 +7,7 @@
 
 #include "cholq.h"
 #include "common.h"
+#include "strassen.h"
 #include "../../include/sympgpr_probe.h"
 #include "generated/pair_generated.h"
 #include "nd_eval.h"
@@ -528,7 +529,7 @@ extern "C" int sgpr_probe_tune(const char *name, double value)
     return 0;
 }
 
-// ---- the Strassen front end of the NT product (gemm_f64.hip)
+// ---- the Strassen front end of the NT product (strassen.h)
 extern "C" int sgpr_probe_strassen_plan(int m, int n, int k, int lower, long smin, long kslab, long scratch_doubles, long long *out,
                                         int max_records, int *count)
 {

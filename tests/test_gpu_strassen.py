@@ -1,4 +1,4 @@
-"""The Strassen front end of the fp64 NT product on the device (sympgpr_amd/csrc/gemm_f64.hip), with the threshold tunable
+"""The Strassen front end of the fp64 NT product on the device (sympgpr_amd/csrc/strassen.hip), with the threshold tunable
 `gemm_strassen_min` lowered so that orders of a few thousand qualify.  With the built-in threshold (half-sizes >= 8192) NO
 other GPU test of this suite reaches a qualifying product: they cover the classical path, this file covers the new one.
 

@@ -1,4 +1,4 @@
-"""The outer Strassen level of the fp64 NT product on the device (sympgpr_amd/csrc/gemm_f64.hip) and the product with up to four
+"""The outer Strassen level of the fp64 NT product on the device (sympgpr_amd/csrc/strassen.hip) and the product with up to four
 destinations it is built on, with both thresholds lowered (inner 256, outer 512, outer k slab 1024) so that orders of a few
 thousand take two levels.  With the built-in thresholds no other GPU test reaches the outer level.
 

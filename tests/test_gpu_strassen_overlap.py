@@ -1,4 +1,4 @@
-"""The Strassen front end with its operand sums on side streams beside the products (sympgpr_amd/csrc/gemm_f64.hip: run_schedule,
+"""The Strassen front end with its operand sums on side streams beside the products (sympgpr_amd/csrc/strassen.hip: run_schedule,
 tunable gemm_strassen_overlap), inside the recursive factorisation with the recursion's tunables and la_max scaled down by 32 as in
 tests/test_gpu_strassen_rec.py: at order 4096 trsm_rec's products and the lower update take both levels, at 4096 + 384 some products
 fall through to classical launches beside the ones that qualify.  potrf() reserves the scratch of the largest call, so the smaller

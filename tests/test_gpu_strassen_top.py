@@ -1,4 +1,4 @@
-"""The top Strassen level of the recursion's largest products on the device (sympgpr_amd/csrc/gemm_f64.hip: strassen_top_gemm),
+"""The top Strassen level of the recursion's largest products on the device (sympgpr_amd/csrc/strassen.hip: strassen_top_gemm),
 with everything scaled down by 32 as in tests/test_gpu_strassen_rec.py (library 256 / 512, slabs 512 / 1024; the recursion's own
 values 128 / 256, slabs 512 / 1024 / 512; la_max 1024) and the top level at a threshold of 512 with slabs of 2048 / 1024, so that
 4096 x 2048 x 2048 takes three levels and an order of 8192 runs the whole path: recursion -> top list -> operand sums, zeroing,

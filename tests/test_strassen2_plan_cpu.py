@@ -1,4 +1,4 @@
-"""The outer Strassen level of the fp64 NT product (sympgpr_amd/csrc/gemm_f64.hip, host code): the list one call C -= A B^T turns
+"""The outer Strassen level of the fp64 NT product (sympgpr_amd/csrc/strassen_plan.hip, host code): the list one call C -= A B^T turns
 into with both levels is fetched through the probe library and replayed in numpy (tools/strassen2_plan.py); the inner plans of
 its outer products come through the existing probe.  No GPU needed: the device path executes exactly this list (run_plan2).
 

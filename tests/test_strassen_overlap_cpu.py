@@ -1,4 +1,4 @@
-"""The schedule by which the Strassen front end runs its operand sums beside the products (sympgpr_amd/csrc/gemm_f64.hip:
+"""The schedule by which the Strassen front end runs its operand sums beside the products (sympgpr_amd/csrc/strassen_plan.hip:
 strassen_schedule, host code; the device path executes exactly its records): the call's list, inner plans expanded, every record
 annotated with its stream, its scratch buffers and the records it waits for.  Fetched through the fourth probe entry
 (sgpr_probe_strassen_schedule) with the recursion's tunables scaled down as in tests/test_strassen_rec_plan_cpu.py, and replayed in

@@ -1,4 +1,4 @@
-"""The Strassen front end of the fp64 NT product (sympgpr_amd/csrc/gemm_f64.hip, host code): the list of operations it emits
+"""The Strassen front end of the fp64 NT product (sympgpr_amd/csrc/strassen_plan.hip, host code): the list of operations it emits
 for one call C -= A B^T -- which operand sums, which seven half-size products, which destination blocks and signs, and what
 stays a classical launch -- is fetched through the probe library and replayed in numpy.  No GPU needed: the device path
 executes exactly this list (run_plan), one launch per record.

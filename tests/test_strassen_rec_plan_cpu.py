@@ -1,4 +1,4 @@
-"""The recursive factorisation's own Strassen thresholds (sympgpr_amd/csrc/gemm_f64.hip: strassen_rec_values / strassen_rec_cfg, host
+"""The recursive factorisation's own Strassen thresholds (sympgpr_amd/csrc/strassen_plan.hip: strassen_rec_values / strassen_rec_cfg, host
 code): potrf_rec / trsm_rec plan every product with thresholds chosen for that call.  The list of one call comes through the third
 probe entry (sgpr_probe_strassen_rec_plan) and is replayed in numpy (tools/strassen_rec_plan.py).  No GPU needed: the device path
 executes exactly this list.

@@ -1,4 +1,4 @@
-"""The top Strassen level of the recursion's largest products (sympgpr_amd/csrc/gemm_f64.hip: strassen_top_plan, host code): the list
+"""The top Strassen level of the recursion's largest products (sympgpr_amd/csrc/strassen_plan.hip: strassen_top_plan, host code): the list
 of one call comes through sgpr_probe_strassen_top_plan and is replayed in numpy (tools/strassen_top_plan.py), the half-size and
 pass-through calls of that list through the lists the front end gives them (sgpr_probe_strassen_cfg_plan).  No GPU needed: the
 device path executes exactly this list.

@@ -1,4 +1,4 @@
-"""Device checks of the outer Strassen level (csrc/gemm_f64.hip), one mode per process because the tunables are read once:
+"""Device checks of the outer Strassen level (csrc/strassen.hip), one mode per process because the tunables are read once:
     python tools/strassen2_check.py four   OUT.json   the product with 2 .. 4 destinations against separate classical launches
     python tools/strassen2_check.py front  OUT.json   the front end against the classical kernel on the same operands
     python tools/strassen2_check.py potrf  OUT.npz    factor + solve through the recursive driver (order 4096, la_max = 1024)

@@ -1,4 +1,4 @@
-"""The outer Strassen level's list (csrc/gemm_f64.hip: strassen_outer_plan) on the CPU: fetch what one call C -= A B^T turns into
+"""The outer Strassen level's list (csrc/strassen_plan.hip: strassen_outer_plan) on the CPU: fetch what one call C -= A B^T turns into
 with both levels (host code, no GPU needed) and replay it with NumPy.  Record layout: include/sympgpr_probe.h.  An outer
 product (kind 5) is replayed the way the device runs it: the inner plan of its half-size product is fetched through the
 existing probe (tools/strassen_plan.py) and every inner product is added to BOTH destination blocks.

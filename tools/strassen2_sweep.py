@@ -1,4 +1,4 @@
-"""Sweep of the outer Strassen level (csrc/gemm_f64.hip) on one MI355X: C -= A B^T through the front end with two levels, with
+"""Sweep of the outer Strassen level (csrc/strassen.hip) on one MI355X: C -= A B^T through the front end with two levels, with
 one level and through the classical launch, on the same seeded operands -- the products of the n = 131072 factorisation that
 take the outer level, and the candidates for a lower outer threshold.  SGPR_GEMM_STRASSEN and the tunables are read once per
 process, so every variant is a child process of its own (under a time limit); each prints best-of-REPS HIP-event times.

@@ -1,4 +1,4 @@
-"""Device checks of the Strassen front end (csrc/gemm_f64.hip), one mode per process because the tunables are read once:
+"""Device checks of the Strassen front end (csrc/strassen.hip), one mode per process because the tunables are read once:
     python tools/strassen_check.py front  OUT.json   front end against the classical kernel on the same operands
     python tools/strassen_check.py two    OUT.json   the two-destination product against two classical launches
     python tools/strassen_check.py potrf  OUT.npz    factor + solve through the recursive driver (order 4096, la_max = 1024)

@@ -1,4 +1,4 @@
-"""The Strassen front end's plan (csrc/gemm_f64.hip: strassen_plan) on the CPU: fetch the list of operations one call
+"""The Strassen front end's plan (csrc/strassen_plan.hip: strassen_plan) on the CPU: fetch the list of operations one call
 C -= A B^T turns into (host code, no GPU needed) and replay it with NumPy.  Record layout: include/sympgpr_probe.h.
 `python tools/strassen_plan.py M N K [lower] [smin] [kslab]` prints the plan's summary.
 Used by tests/test_strassen_plan_cpu.py."""

@@ -1,4 +1,4 @@
-"""Device check of the recursive factorisation's own Strassen thresholds (csrc/chol.hip, csrc/gemm_f64.hip): factor + solve of one
+"""Device check of the recursive factorisation's own Strassen thresholds (csrc/chol.hip, csrc/strassen.hip): factor + solve of one
 SPD matrix through potrf_rec, one process per configuration because the library's tunables are read once:
     python tools/strassen_rec_check.py OUT.npz
 Environment: REC_N (order, 4096); REC_TUNE="name=value,..." sets tunables through sgpr_probe_tune before the first call (the

@@ -1,4 +1,4 @@
-"""The list one product of the recursive factorisation turns into (csrc/gemm_f64.hip: strassen_rec_plan) on the CPU: potrf_rec /
+"""The list one product of the recursive factorisation turns into (csrc/strassen_plan.hip: strassen_rec_plan) on the CPU: potrf_rec /
 trsm_rec give every call thresholds of their own (tunables "rec_strassen_*", outer k slab chosen from the call's k), and the
 third probe entry returns the list of one call under that configuration together with the thresholds it resolved to.  Replay with
 NumPy goes through tools/strassen2_plan.py with the inner threshold that holds UNDER an outer product.  No GPU needed.
@@ -21,7 +21,7 @@ UNLIMITED = sp.UNLIMITED
 # the recursion's tunables and the values that make it plan like the library (sgpr_probe_strassen2_plan with defaults)
 LIBRARY = {"rec_strassen_min_gemm": 8192, "rec_strassen_min_syrk": 8192, "rec_strassen2_min_gemm": 16384,
            "rec_strassen2_min_syrk": 16384, "rec_strassen2_kslab_short": 0, "rec_strassen_kslab": 16384, "rec_strassen2_kslab": 32768}
-# ... and the shipped ones (csrc/gemm_f64.hip: REC_*)
+# ... and the shipped ones (csrc/strassen_plan.hip: REC_*)
 SHIPPED = {"rec_strassen_min_gemm": 4096, "rec_strassen_min_syrk": 8192, "rec_strassen2_min_gemm": 8192,
            "rec_strassen2_min_syrk": 8192, "rec_strassen2_kslab_short": 16384, "rec_strassen_kslab": 16384, "rec_strassen2_kslab": 32768}
 

@@ -1,4 +1,4 @@
-"""Sweep of the recursive factorisation's own Strassen thresholds (csrc/gemm_f64.hip: strassen_rec_values) on one MI355X: every
+"""Sweep of the recursive factorisation's own Strassen thresholds (csrc/strassen_plan.hip: strassen_rec_values) on one MI355X: every
 product class the n = 131072 factorisation issues, as the recursion would issue it (sgpr_probe_gemm_strassen_rec_dev), once with
 the recursion's tunables at the library's values ("current": what the tree did before) and once with the candidates, on the same
 seeded operands.  Tunables are read per call but the scratch is per process, so every variant is a child process of its own

@@ -1,5 +1,5 @@
 """The schedule one call of the Strassen front end is executed by when its operand sums run beside the products
-(csrc/gemm_f64.hip: strassen_schedule, tunable gemm_strassen_overlap) on the CPU: the call's list with the inner plans of its outer
+(csrc/strassen_plan.hip: strassen_schedule, tunable gemm_strassen_overlap) on the CPU: the call's list with the inner plans of its outer
 products expanded in place, every record annotated with its stream, the scratch buffers it writes / reads and the records it waits
 for (layout: include/sympgpr_probe.h).  Fetched through the fourth probe entry and replayed with NumPy in any order the
 annotations allow.  No GPU needed.

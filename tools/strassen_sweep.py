@@ -1,4 +1,4 @@
-"""Size sweep of the Strassen front end (csrc/gemm_f64.hip) against the classical launch on one MI355X: C -= A B^T for
+"""Size sweep of the Strassen front end (csrc/strassen.hip) against the classical launch on one MI355X: C -= A B^T for
 square and 2:1 products, both paths on the same operands, best of REPS runs each (HIP events on the launch stream).
 The threshold tunable is lowered so that every listed shape qualifies; `adds` is the front end's time outside its MFMA
 launches (the ten operand sums per k slab and the launch gaps), from the per-launch profile window of the same run.

@@ -1,4 +1,4 @@
-"""Device checks of the top Strassen level (csrc/gemm_f64.hip: strassen_top_gemm), one mode per process because the library's
+"""Device checks of the top Strassen level (csrc/strassen.hip: strassen_top_gemm), one mode per process because the library's
 tunables are read once:
     python tools/strassen_top_check.py front OUT.json   one product through the recursion's entry with the top level (twice), through
                                                         the entry it replaced (gemm_nt_strassen_rec) and through the classical kernel

@@ -1,4 +1,4 @@
-"""The top Strassen level of the recursion's largest products (csrc/gemm_f64.hip: strassen_top_plan) on the CPU: fetch the list one
+"""The top Strassen level of the recursion's largest products (csrc/strassen_plan.hip: strassen_top_plan) on the CPU: fetch the list one
 call of potrf_rec / trsm_rec turns into and replay it with NumPy.  Record layout: include/sympgpr_probe.h (kinds 6 - 10).  A top
 product (kind 8) is replayed the way the device runs it: its half-size call's list is fetched under the thresholds the record
 carries (sgpr_probe_strassen_cfg_plan) and replayed through tools/strassen2_plan.py into a zeroed temporary, which the
@@ -21,7 +21,7 @@ import strassen_rec_plan as srp  # noqa: E402
 REC = sp.REC
 SUM3, ZERO3, PROD3, ACC3, PASS3 = 6, 7, 8, 9, 10
 UNLIMITED = sp.UNLIMITED
-# the shipped values (csrc/gemm_f64.hip: REC_SMIN3, REC_KSLAB3, REC_KSLAB3_SHORT)
+# the shipped values (csrc/strassen_plan.hip: REC_SMIN3, REC_KSLAB3, REC_KSLAB3_SHORT)
 SHIPPED = {"rec_strassen3_min": 16384, "rec_strassen3_kslab": 65536, "rec_strassen3_kslab_short": 32768}
 set_tunables = srp.set_tunables
 

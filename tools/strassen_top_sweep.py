@@ -1,4 +1,4 @@
-"""The two product classes of the n = 131072 factorisation that take the top Strassen level (csrc/gemm_f64.hip:
+"""The two product classes of the n = 131072 factorisation that take the top Strassen level (csrc/strassen.hip:
 strassen_top_gemm), alone on one MI355X: as the recursion issues them (sgpr_probe_gemm_strassen_top_dev), with the level off,
 with its passes serial on the caller's stream, and with them on the low-priority stream (one and two buffer sets), on the same
 seeded operands.  The scratch is per process, so every variant is a child process of its own (under a time limit); each prints the
