@@ -368,7 +368,7 @@ int mid_build(hipStream_t st, const BatchCall &c, const BatchLayout &l, const Mi
     return 0;
 }
 
-// chol.hip's panel_batch_kernel: W = npad / 128 workgroups per problem run the leaf chain on their own matrix
+// panel.hip's panel_batch_kernel (through potrf_batch_panel, chol.hip): W = npad / 128 workgroups per problem run the leaf chain on their own matrix
 int mid_factor(hipStream_t st, const BatchLayout &l, const MidChunk &k)
 {
     const int npad = l.npad, W = l.W;

@@ -8,7 +8,7 @@ namespace {
 
 // ---- mid-size problems: 256 < n <= 2048 (a CMA-ES generation at N = 512 ... 1024 points) --------------------------
 // Three launches for the whole batch: (1) every Ky_b, lower triangle, into an npad x npad image (npad = n rounded up to
-// 128; the padding is an identity block: det 1, alpha 0 there); (2) chol.hip's panel_batch_kernel: W = npad / 128
+// 128; the padding is an identity block: det 1, alpha 0 there); (2) panel.hip's panel_batch_kernel: W = npad / 128
 // workgroups per problem run the leaf chain on their own matrix, problems side by side; (3) one workgroup per problem:
 // y = L^-1 z and alpha = L^-T y through the leaf inverses, and the negative log-likelihood.
 constexpr int MT = 256;                   // build: pair rows per tile (one per thread)

@@ -5,17 +5,19 @@
 // ONE persistent grid of workers pulls 256 x 128 tile tasks of the whole factorisation from an ordered list
 // (trailing updates U and the panel's rows-below solves T), each task waiting on device-side version counters
 // instead of kernel boundaries, while the chain of diagonal blocks runs beside it in the persistent panel
-// kernel (chol.hip) on a handful of CUs the worker grid leaves free.  No per-step fill / drain, no tile
+// kernel (panel.hip) on a handful of CUs the worker grid leaves free.  No per-step fill / drain, no tile
 // round-up per launch, and the panel stream is never starved of CUs.
 //
-// This header is shared by cholq.hip (plan builder, worker kernel) and chol.hip (the driver that launches the
-// panel kernels beside the workers).
+// cholq.hip holds all of it: plan builder, worker kernel and the driver (potrf_queue, chol.h) that launches the panel
+// kernel (through panel.h) beside the workers on a pair of CU-masked streams of its own.  The look-ahead driver of chol.hip
+// calls the driver and takes back the block it leaves ("q_tail"); streams.hip calls queue_release.
 #pragma once
 #include <vector>
 
 #include "common.h"
 
 namespace sgpr {
+struct StreamDrop;
 namespace cholq {
 
 constexpr int TM = 256, TN = 128;          // the workers' tile of the trailing matrix
@@ -95,6 +97,10 @@ Ws carve(void *base, int n);
 int prepare(const Plan &p, const Ws &w, hipStream_t st);
 int launch_workers(const Plan &p, const Ws &w, double *A, size_t lda, const double *inv, const int *flags, int *dinfo,
                    int pflag_stride, hipStream_t st);
+
+// the driver's masked stream pairs on `dev` go the way of the library's other streams (streams.h: release_streams), and its
+// per-device state with them
+void queue_release(int dev, StreamDrop &d);
 
 // diagnostics: the last queue workspace used by this process, and a dump of its state words (head, abort, the
 // first task / panel strip that gave up, tver, the ver map) to stderr; `always` = also when nothing gave up

@@ -1,4 +1,4 @@
-// cholq.hip -- plan builder and worker kernel of the task-queue Cholesky (see cholq.h).
+// cholq.hip -- plan builder, worker kernel and driver of the task-queue Cholesky (see cholq.h).
 //
 // The worker grid is persistent for the whole factorisation of one block: a workgroup draws a ticket, reads
 // the task behind it, waits until the task's inputs carry the version it expects, runs it on the fp64 matrix
@@ -6,7 +6,7 @@
 // and draws the next ticket.  Forward progress needs no co-residency of the workers: the list is ordered so
 // that every dependency of a task has a smaller ticket, a workgroup works its tickets in increasing order, so
 // the smallest unfinished ticket can always run.  What the workers DO rely on is the chain of diagonal blocks
-// making progress beside them (panel kernels on the CUs this grid leaves free, chol.hip); every spin is bounded
+// making progress beside them (the panel kernel of panel.hip on the CUs this grid leaves free); every spin is bounded
 // and an abort word stops the whole grid when one of them runs out.
 #include <algorithm>
 #include <atomic>
@@ -19,6 +19,9 @@
 
 #include "cholq.h"
 #include "gemm_tile.h"
+#include "chol.h"
+#include "panel.h"
+#include "streams.h"
 
 namespace sgpr {
 namespace cholq {
@@ -36,7 +39,7 @@ int q_max() { static const int v = std::min(env_int("SGPR_Q_MAX", 28672), MAX_OR
 // A persistent grid that fills every CU can lose workgroups for a while when the platform switches the queues out and in
 // (DESIGN.md section 3.9); the workers notice (nothing published anywhere for 3 ms), drain their kernel instance and the next
 // instance carries on (Q_INSTANCES).  Whether the worker grid and the panel kernel CAN run side by side on this process's
-// streams is not guessed from the environment any more (round 3 looked for a profiler's ROCPROF_COUNTER_COLLECTION): chol.hip
+// streams is not guessed from the environment any more (round 3 looked for a profiler's ROCPROF_COUNTER_COLLECTION): the driver below
 // tries it once per device with a pair of handshake kernels (queue_overlap_ok) -- counter collection, HIP_LAUNCH_BLOCKING,
 // AMD_SERIALIZE_KERNEL, a debugger: whatever serialises dispatches fails that test and the look-ahead driver is used.
 bool q_on()
@@ -739,4 +742,217 @@ int launch_workers(const Plan &p, const Ws &w, double *A, size_t lda, const doub
 }
 
 }  // namespace cholq
+
+namespace {
+
+// ---- the driver: host side ----------------------------------------------------------------------------------------
+// One persistent worker grid runs every trailing-update tile and every rows-below solve of the block from an ordered
+// task list; the chain of diagonal blocks runs as one panel kernel per panel (diagonal strips + the rows of the next
+// diagonal block) beside it, each strip starting as soon as its own tiles carry the updates of all earlier panels
+// (version counters, no kernel boundary).
+//
+// A panel workgroup (147 KiB of LDS) cannot share a CU with a worker (104 KiB), so the two kernels run on DISJOINT CU
+// SETS: two streams with CU masks (hipExtStreamCreateWithCUMask), R CUs of every XCD for the panel kernels, the rest for
+// the workers.  Merely launching fewer workers than CUs is not enough: the dispatcher binds a workgroup to an XCD and a
+// shader engine round-robin BEFORE it looks for a free CU, and a panel workgroup bound to an engine that the persistent
+// workers fill waits there for good, free CUs next door or not (tools/queue_fail_hunt.py caught it: one panel workgroup
+// started 1.09 s late, on the first CU a worker gave back).  With the masks an engine without a CU of the queue's set is
+// never chosen.  (Mask bit i is CU i / 8 of XCD i % 8: tools/probe_cumask.py.)
+// Queue factorisations of one device are serialised: they share these two streams and their CU sets.
+struct QueueDevice {
+    std::mutex mu;
+    hipEvent_t done = nullptr;                 // end of the last queue factorisation enqueued on this device
+    int ncu = 0;
+    hipStream_t workers[4] = {}, panels[4] = {};   // by R - 1 (CUs per XCD set aside for the panel kernels)
+    bool overlap_ok[4] = {};                   // ... and whether kernels on the pair have been SEEN to run side by side
+    bool failed = false;                       // masked streams cannot be had, kernels on them do not overlap, or a queue
+                                               // factorisation gave up: the look-ahead driver takes over (until the streams are released)
+};
+QueueDevice g_qdev[MAX_DEVICES];
+
+typedef __attribute__((address_space(1))) int gint;
+// Two one-thread kernels, one on each stream of the pair, that wait for each other (bounded: 50 ms).  The task-queue
+// factorisation is two persistent kernels that hand work to each other: where dispatches are serialised -- a profiler collecting
+// counters, HIP_LAUNCH_BLOCKING, AMD_SERIALIZE_KERNEL, a debugger -- the second never starts while the first waits, and the
+// factorisation would end in its time limit with A half overwritten.  Tried once per stream pair; w: 4 ints, zero.
+__global__ void overlap_probe_kernel(int *w, int me)
+{
+    __hip_atomic_store((gint *)(w + me), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+    int seen = 0;
+    while (!(seen = __hip_atomic_load((gint *)(w + 1 - me), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
+        __builtin_amdgcn_s_sleep(32);
+        if (__builtin_amdgcn_s_memrealtime() - t0 > 5000000ull) break;
+    }
+    w[2 + me] = seen ? 1 : 2;
+}
+static bool queue_overlap_ok(hipStream_t sw, hipStream_t sp)
+{
+    int *w = nullptr;
+    if (hipMalloc((void **)&w, 4 * sizeof(int)) != hipSuccess) { (void)hipGetLastError(); return false; }
+    int h[4] = {0, 0, 0, 0};
+    bool ok = hipMemset(w, 0, sizeof(h)) == hipSuccess;
+    if (ok) {
+        hipLaunchKernelGGL(overlap_probe_kernel, dim3(1), dim3(1), 0, sp, w, 0);
+        hipLaunchKernelGGL(overlap_probe_kernel, dim3(1), dim3(1), 0, sw, w, 1);
+        ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(sp) == hipSuccess && hipStreamSynchronize(sw) == hipSuccess &&
+             hipMemcpy(h, w, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess && h[2] == 1 && h[3] == 1;
+    }
+    (void)hipFree(w);
+    (void)hipGetLastError();
+    return ok;
+}
+
+int queue_streams(QueueDevice &qd, int dev, int R, hipStream_t *sw, hipStream_t *sp)
+{
+    if (!qd.workers[R - 1]) {
+        int cur = -1;
+        SGPR_HIP(hipGetDevice(&cur));
+        if (cur != dev) SGPR_HIP(hipSetDevice(dev));
+        const int words = qd.ncu / 32;
+        std::vector<uint32_t> mp((size_t)words, 0u), mw((size_t)words, 0xFFFFFFFFu);
+        for (int b = 0; b < 8 * R; ++b) { mp[b / 32] |= 1u << (b % 32); mw[b / 32] &= ~(1u << (b % 32)); }
+        hipError_t e = hipExtStreamCreateWithCUMask(&qd.panels[R - 1], (uint32_t)words, mp.data());
+        if (e == hipSuccess) e = hipExtStreamCreateWithCUMask(&qd.workers[R - 1], (uint32_t)words, mw.data());
+        if (e == hipSuccess) register_exit_release();
+        if (cur != dev) (void)hipSetDevice(cur);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            qd.failed = true;
+            return SGPR_E_HIP;
+        }
+    }
+    if (!qd.overlap_ok[R - 1]) {
+        if (!queue_overlap_ok(qd.workers[R - 1], qd.panels[R - 1])) {
+            qd.failed = true;
+            return SGPR_E_HIP;
+        }
+        qd.overlap_ok[R - 1] = true;
+    }
+    *sw = qd.workers[R - 1];
+    *sp = qd.panels[R - 1];
+    return 0;
+}
+
+thread_local bool t_last_potrf_used_queue = false;   // set by potrf_queue once its kernels are enqueued, cleared by every potrf()
+
+}  // namespace
+
+// returns 1 when the queue form cannot be used here (the caller falls back to the look-ahead driver), < 0 on errors
+int potrf_queue(int n, double *A, size_t lda, const Ctx &c, int off0)
+{
+    hipError_t e = hipSuccess;
+    const int dev = device_of(c.st, &e);
+    SGPR_HIP(e);
+    if (dev < 0) { set_error("potrf: device index out of range"); return SGPR_E_ARG; }
+    QueueDevice &qd = g_qdev[dev];
+    std::lock_guard<std::mutex> lock(qd.mu);
+    if (qd.failed) return 1;
+    if (!qd.ncu) {
+        SGPR_HIP(hipDeviceGetAttribute(&qd.ncu, hipDeviceAttributeMultiprocessorCount, dev));
+        SGPR_HIP(hipEventCreateWithFlags(&qd.done, hipEventDisableTiming));
+        SGPR_HIP(hipEventRecord(qd.done, c.st));
+    }
+    if (qd.ncu % 64 != 0 || qd.ncu < 64) { qd.failed = true; return 1; }      // 8 XCDs, whole mask words
+    const std::vector<int> starts = cholq::default_starts(n);
+    const cplan::QueueGeom qg = cplan::queue_geometry(starts);   // the panel grid of this schedule, R CUs per XCD for it
+    const int R = qg.R;
+    if (R > 4) return 1;
+    hipStream_t sw = nullptr, sp = nullptr;
+    if (queue_streams(qd, dev, R, &sw, &sp)) return 1;
+    // tunable "q_slack" = <CUs of the worker set left empty> (default 0; sgpr_probe_tune).  32 = one per shader engine: with that much room the
+    // workgroups of a preempted-and-restored grid all find a CU again (the stall) -- at 13 % of the throughput.
+    static const int qslack = (int)tune("q_slack", 0);
+    const int nworkers = qd.ncu - 8 * R - std::max(0, std::min(qslack, 64));
+    const cholq::Plan *plan = cholq::get_plan(n, nworkers);
+    if (!plan) return 1;
+    const cholq::Ws ws = cholq::carve(c.qws, n);
+    const hipStream_t su = c.st;
+    int rc;
+    SGPR_HIP(hipStreamWaitEvent(su, qd.done, 0));               // after the previous queue factorisation on this device
+    if ((rc = cholq::prepare(*plan, ws, su))) return rc;
+    if (cholq::forced_giveup()) {                                // tests only: the give-up word is up, and so is what a timed-out waiter leaves
+        static const int k_timeout = POTRF_HANDOFF_TIMEOUT;
+        SGPR_HIP(hipMemcpyAsync(c.dinfo, &k_timeout, sizeof(int), hipMemcpyHostToDevice, su));
+    }
+    EventSet es;
+    if ((rc = es.create(3))) return rc;
+    const int tn = n / cholq::TN;
+    double *inv_blk = c.inv + (size_t)(off0 / LEAF) * LEAF * LEAF;
+    int *flags_blk = c.flags + (size_t)(off0 / LEAF) * PFLAG_STRIDE;
+    {
+        SGPR_HIP(hipEventRecord(es.ev[0], su));                 // both queue streams join the caller's stream ...
+        SGPR_HIP(hipStreamWaitEvent(sp, es.ev[0], 0));
+        SGPR_HIP(hipStreamWaitEvent(sw, es.ev[0], 0));
+        StreamJoin join_p{sp, su, es.ev[1]};                    // ... and leave it again on every exit path
+        StreamJoin join_w{sw, su, es.ev[2]};
+        PanelSeq ps{};
+        ps.A = A; ps.lda = lda; ps.nblk = plan->nq; ps.nblk_all = plan->nblk; ps.pstart = ws.pstart;
+        ps.inv = inv_blk; ps.dinfo = c.dinfo; ps.goff = off0; ps.flags = flags_blk;
+        ps.ver = ws.ver; ps.ver_ld = tn; ps.tver = ws.tver; ps.abort = cholq::abort_word(ws);
+        ps.census = cholq::trace_panel_base((int)(plan->tasks.size() / 2));
+        ps.helpers = qg.helpers; ps.tiles = qg.tiles;
+        t_last_potrf_used_queue = true;
+        if ((rc = launch_panel_seq(ps, qg.pgrid, sp))) return rc;
+        if ((rc = cholq::launch_workers(*plan, ws, A, lda, inv_blk, flags_blk, c.dinfo, PFLAG_STRIDE, sw))) return rc;
+    }
+    SGPR_HIP(hipEventRecord(qd.done, su));
+    cholq::remember(ws, n, (int)(plan->tasks.size() / 2));
+    cholq::remember_plan(plan);          // for the post-mortem probe
+    static const bool qdebug = tune("q_debug", 0) != 0;
+    if (qdebug) {
+        SGPR_HIP(hipStreamSynchronize(su));
+        cholq::postmortem(false);
+    }
+    if (plan->nq < plan->nblk) {
+        // the block the queue left (every update of its panels applied, its rows of L final): the look-ahead driver
+        const int S = plan->starts[plan->nq];
+        Ctx ct = c;
+        ct.qws = nullptr;
+        // The host WAITS here.  With the look-ahead driver's ~100 launches enqueued behind the persistent kernels (on this
+        // stream and on the high-priority side stream, all of them blocked by the joins above) the stall of DESIGN 3.9 was no
+        // longer rare but came in the first factorisation, every time, ~4 ms in; with nothing enqueued behind them 400 in a
+        // row were clean (and 1 in ~300 - 1700 still stalls, as with the whole factorisation in the queue).
+        static const bool nosync = tune("q_nosync", 0) != 0;               // tests of the drain-and-relaunch recovery only
+        if (!nosync) SGPR_HIP(hipStreamSynchronize(su));
+        return potrf_lookahead(n - S, A + S + (size_t)S * lda, lda, ct, 0, off0 + S);
+    }
+    return 0;
+}
+
+// A queue factorisation on `st`'s device has given up (POTRF_HANDOFF_TIMEOUT read back by the caller): no further one is
+// started there until the streams are released.  Returns true when the queue was in use (a retry will take the other driver).
+bool potrf_queue_mark_failed(hipStream_t st)
+{
+    // Did THIS thread's last factorisation go through the queue?  (Not "was the queue still on for the device": a give-up of
+    // the look-ahead driver's panel kernel at an order the queue never takes must not trigger a pointless second run, and two
+    // handles that give up in the same moment must both get their retry, whoever marks the device first.)
+    const bool used = t_last_potrf_used_queue;
+    if (!used) return false;
+    const int dev = device_of(st);
+    if (dev < 0) return false;
+    QueueDevice &qd = g_qdev[dev];
+    std::lock_guard<std::mutex> lock(qd.mu);
+    qd.failed = true;
+    return true;
+}
+
+// The release routine of streams.hip comes by (under this device's mutex): the masked pairs are shown to it, and the driver's
+// own state follows what it did with them -- at exit nothing new is started on this device from here on; after a drain the
+// event goes too and the next queue factorisation starts from scratch (a device marked failed gets its chance again).
+void cholq::queue_release(int dev, StreamDrop &d)
+{
+    QueueDevice &qd = g_qdev[dev];
+    std::lock_guard<std::mutex> lock(qd.mu);
+    for (int r = 0; r < 4; ++r) { d.stream(qd.workers[r]); d.stream(qd.panels[r]); }
+    if (d.mode == StreamDrop::LOOK) { d.any = d.any || qd.done; return; }
+    if (d.mode == StreamDrop::AT_EXIT) { qd.failed = true; return; }
+    d.event(qd.done);
+    qd.ncu = 0;
+    qd.failed = false;
+    for (int r = 0; r < 4; ++r) qd.overlap_ok[r] = false;
+}
+
+void potrf_clear_queue_mark() { t_last_potrf_used_queue = false; }
+
 }  // namespace sgpr

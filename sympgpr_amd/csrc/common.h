@@ -26,7 +26,8 @@ int hip_fail(hipError_t e, const char *what, const char *file, int line);
 #define SGPR_CHECK_LAUNCH() SGPR_HIP(hipGetLastError())
 #define SGPR_HIP_TYPES 1    // strassen.h: hipStream_t is declared
 
-// the device that owns a stream (the null stream: the current device) as an index of the per-device tables, 0 .. 63; -1: the
+constexpr int MAX_DEVICES = 64;   // rows of every per-device table of the library (streams, events, queue state, Strassen scratch)
+// the device that owns a stream (the null stream: the current device) as an index of the per-device tables, 0 .. MAX_DEVICES - 1; -1: the
 // runtime refused (its error state is cleared; *err, where given, holds what it said) or the index is out of range
 inline int device_of(hipStream_t st, hipError_t *err = nullptr)
 {
@@ -34,7 +35,7 @@ inline int device_of(hipStream_t st, hipError_t *err = nullptr)
     const hipError_t e = st ? hipStreamGetDevice(st, &dev) : hipGetDevice(&dev);
     if (err) *err = e;
     if (e != hipSuccess) { (void)hipGetLastError(); return -1; }
-    return (dev >= 0 && dev < 64) ? dev : -1;
+    return (dev >= 0 && dev < MAX_DEVICES) ? dev : -1;
 }
 
 // Hyper-parameters split the way the reference does (`l = hyp[:-1]; sig = hyp[-1]`),
@@ -150,7 +151,7 @@ void gemm_set_overlap(int on);   // look-ahead driver: launches from here on sha
 int gemm_nt_diag(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B, size_t ldb,
                  double beta, double *C, size_t ldc, int lower, unsigned long long *stamps, int dbg, hipStream_t st);
 
-// ---- chol.hip : leaf factor / leaf inverse / recursion / solves
+// ---- chol.hip : recursion, look-ahead driver, potrf(), the batched panels (kernels: panel.hip; host arithmetic: chol_plan.hip)
 constexpr int LEAF = 128;  // order of the diagonal block factored in LDS by one workgroup
 // value left in *dinfo when a hand-off inside the persistent panel kernel timed out (a bug or a
 // device problem, never a property of the matrix); info_status() turns it into SGPR_E_HIP
@@ -168,13 +169,17 @@ int potrf(int n, double *A, size_t lda, void *work, size_t lwork, int *dinfo, hi
 // batch.hip's mid-size path: nbatch factorisations of order npad (multiple of 128, <= potrf_batch_max_order()) in one launch
 size_t potrf_batch_flag_bytes(int nbatch);
 int potrf_batch_max_order();
+int leaf_probe(double *A, size_t lda, double *inv, int *dinfo, unsigned long long *stamps, hipStream_t st);
 int potrf_batch(int nbatch, int npad, double *A, size_t stride_a, size_t lda, double *inv, size_t stride_inv, int *flags,
                 int *info, hipStream_t st);
 // one panel (columns k0 .. k0 + 128 Wd, rows down to npad) of every problem; flags: potrf_batch_flag_bytes(nbatch) bytes per call
 int potrf_batch_panel(int nbatch, int npad, int k0, int Wd, double *A, size_t stride_a, size_t lda, double *inv, size_t stride_inv,
                       int *flags, int *info, hipStream_t st);
+// ---- cholq.hip
 bool potrf_queue_mark_failed(hipStream_t st);   // a queue factorisation gave up: the look-ahead driver from now on (true: the queue was in use)
+// ---- streams.hip
 int release_device_streams(int dev);   // drain + destroy the streams potrf created on `dev` (they come back on demand)
+// ---- solve.hip : the triangular solves against a factor (its leaf inverses in `work`)
 int trsm_rlt(int m, int n, const double *L, size_t ldl, double *B, size_t ldb, const void *work,
              hipStream_t st);
 // One-right-hand-side solves keep their hand-off words (tickets, progress, the published segments) IN the workspace: one
@@ -194,7 +199,6 @@ bool potrs_mat_uses_strips(int n, int nrhs, const double *L, size_t ldl);   // t
 int trsv(int n, const double *L, size_t ldl, void *work, double *b, int trans, hipStream_t st);
 bool trsv_uses_strips(int n, const double *L, size_t ldl);      // potrs_vec / trsv take the one-launch strip kernels
 const int *trsv_state(int n, const void *work);                 // their 8 state words: [2], [6] != 0 = a hand-off timed out
-int leaf_probe(double *A, size_t lda, double *inv, int *dinfo, unsigned long long *stamps, hipStream_t st);
 int leaf_inverses(int n, const double *L, size_t ldl, void *work, int *dinfo, hipStream_t st);
 
 // ---- trsv.hip : one-right-hand-side triangular solve as one launch (strips + progress counter)

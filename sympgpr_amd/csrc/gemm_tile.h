@@ -1,5 +1,5 @@
 // gemm_tile.h -- device-side pieces of the fp64 MFMA product shared by gemm_f64.hip (the grid-wide
-// kernel) and chol.hip (the persistent panel kernel, whose workgroups run 128 x 128 x 128 products
+// kernel) and panel.hip (the persistent panel kernel, whose workgroups run 128 x 128 x 128 products
 // as tasks): argument block, workgroup -> tile map, operand staging, the two k-loop bodies.
 // See gemm_f64.hip for the design notes.
 #pragma once

@@ -1,5 +1,5 @@
 // leaf.h -- the 128 x 128 diagonal leaf of the Cholesky factorisation as a device function: factor and
-// invert one block entirely in LDS (one workgroup of 256 threads).  Shared by chol.hip (leaf_kernel and
+// invert one block entirely in LDS (one workgroup of 256 threads).  Shared by panel.hip (leaf_kernel and
 // the persistent panel kernel) and batch.hip (one small fit per workgroup).
 #pragma once
 #include "common.h"
@@ -57,7 +57,7 @@ __device__ __forceinline__ void leaf_body(double *s /* LEAF_LDS doubles: the blo
     };
 
     if (preloaded) {
-        // the caller has put the tile into s (strict upper triangle zero) behind a barrier: chol.hip, the chain
+        // the caller has put the tile into s (strict upper triangle zero) behind a barrier: panel.hip, the chain
     } else if (nb == LEAF && (lda & 1) == 0 && (((uintptr_t)A & 15) == 0)) {
         // full leaf: 32 independent 16-B loads per thread (the whole square is read, the strict
         // upper triangle -- whatever it holds -- is replaced by zeros on the way into LDS)
@@ -281,7 +281,7 @@ __device__ __forceinline__ void leaf_body(double *s /* LEAF_LDS doubles: the blo
     }
     if (early_flag) {
         // L (in A) and the inverses of its eight 16 x 16 diagonal blocks -- which ARE the diagonal blocks of
-        // inv(L) -- are all a blocked triangular solve against L needs (chol.hip, panel_trsm): hand them over
+        // inv(L) -- are all a blocked triangular solve against L needs (panel.hip, trsm_solve): hand them over
         // now, ~20 us before the full inverse (agent-scope release as in panel_publish)
         for (int idx = tid; idx < LEAF * PW; idx += LT) {
             const int i = idx % LEAF, c = (i / PW) * PW + idx / LEAF;     // row i, the 16 columns of its diagonal block

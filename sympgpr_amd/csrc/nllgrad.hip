@@ -2,7 +2,7 @@
 //     d nll / d theta = 1/2 sum_ij (Ky^-1 - alpha alpha^T)_ij dKy_ij / d theta.
 // Ky^-1 is formed by row panels, never all of it at once: for the panel of rows J .. J + nb,
 //     R = [I_nb | 0] (nb x (n - J)),  R := R L_tt^-T,  R := R L_tt^-1,  L_tt = L[J:, J:]
-// (the recursive panel solves of chol.hip on the trailing block, with the factor's own leaf inverses), after which
+// (the recursive panel solves of solve.hip on the trailing block, with the factor's own leaf inverses), after which
 // R = Ky^-1[J:J+nb, J:] -- 2 nb (n - J)^2 flop per panel, 2 n^3 / 3 in all, one nb x n block of scratch.  Then one launch
 // contracts the panel with the derivatives of K, evaluated pair by pair in registers, never stored:
 //   * every workgroup takes NG_T panel rows (one per thread) x NG_CJ column POINTS; a thread's row i is (part r, point

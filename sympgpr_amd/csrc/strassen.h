@@ -1,6 +1,6 @@
 // strassen.h -- the Strassen front end of the fp64 NT product: record layouts, thresholds and entry points.
 // strassen_plan.hip holds the planner (host C++ without a HIP header: which records, which thresholds, which schedule),
-// strassen.hip the scratch, the executors and the two streaming kernels, chol.hip the side streams and the sizing walk.
+// strassen.hip the scratch, the executors and the two streaming kernels, streams.hip the side streams, chol_plan.hip the sizing walk.
 // The part behind SGPR_HIP_TYPES needs common.h in front of it; the rest compiles with any C++17 compiler.
 #pragma once
 #include <algorithm>
@@ -130,8 +130,8 @@ int strassen_top_plan(int m, int n, int k, int lower, const StrassenRec *v, cons
 int strassen_cfg_plan(int m, int n, int k, int lower, const long cfg[5], std::vector<long long> &out);
 size_t strassen_top_scratch_doubles(int m, int n, int k, int lower, const StrassenRec &v, const StrassenTop &t);
 
-void potrf_strassen_need(int n, size_t out[2]);  // chol.hip: what potrf() reserves at order n (both levels, one level)
-size_t potrf_strassen_top_need(int n);           // chol.hip: doubles of top-level scratch at order n (one buffer per region)
+void potrf_strassen_need(int n, size_t out[2]);  // chol_plan.hip: what potrf() reserves at order n (both levels, one level)
+size_t potrf_strassen_top_need(int n);           // chol_plan.hip: doubles of top-level scratch at order n (one buffer per region)
 
 // ---- what the executors (strassen.hip) take from the planner (strassen_plan.hip)
 namespace splan {
@@ -184,7 +184,7 @@ int strassen_top_gemm(int m, int n, int k, double alpha, const double *A, size_t
 void strassen_reserve(size_t both, size_t one, hipStream_t st);
 void strassen_top_reserve(size_t need, hipStream_t st);
 int strassen_trim();                             // release the scratch of the operand sums and of the top level (every device)
-// chol.hip: the library's low-priority streams on the device of `caller`, created on first use and released with the look-ahead
+// streams.hip: the library's low-priority streams on the device of `caller`, created on first use and released with the look-ahead
 // driver's side stream -- for the operand sums (count = 1 or 2) and for the top level's passes
 int strassen_sum_streams(hipStream_t caller, int count, hipStream_t *out);
 int strassen_top_stream(hipStream_t caller, hipStream_t *out);

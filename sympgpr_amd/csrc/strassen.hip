@@ -138,7 +138,7 @@ struct Scratch {
         return 0;
     }
 };
-Scratch g_scratch[2][64];
+Scratch g_scratch[2][MAX_DEVICES];
 // tunables that report the allocation as failed (tests): the two lower ones are read once per process, the top one at every call
 bool lower_noscratch()
 {

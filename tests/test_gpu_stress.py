@@ -141,7 +141,7 @@ def test_wide_panels_with_helpers_and_tiles(nb, knobs):
 def test_three_threads_three_handles_order_16384(oracle):
     """Forward progress with concurrent handles at the size where the panels are wide (n = 16384: 1024- and 512-wide
     panels, up to 31 persistent workgroups each holding a CU): three threads factor three different problems at once,
-    twice.  Every panel kernel of the device runs on the one shared side stream (chol.hip, side_stream), so at most one
+    twice.  Every panel kernel of the device runs on the one shared side stream (streams.hip, side_stream), so at most one
     set of spinning strips is resident whatever the number of handles; each result must equal the same handle's
     single-threaded result bit for bit (no atomics anywhere on the path) and satisfy Ky alpha = z on sampled rows
     rebuilt by the oracle.  Then the per-device streams are released and come back on demand."""
