@@ -333,7 +333,8 @@ int sgpr_fit_batch(int family, int nbatch, int n_pts, const double *x, const dou
  * solve vectors.  All of it lives in the sgpr_fit_batch arena of the calling thread; sgpr_trim gives it back.
  * SGPR_E_ARG (before any device call) for d outside 1..3, an unknown family, a wrong nhyp, flags != 0 (there is no scalar-kernel
  * d-pair fit), nbatch < 0, n_pts <= 0, n above the maximum and a null pointer other than alpha; nbatch == 0 returns 0.  The
- * gradient is sgpr_fit_batch_nd_grad; there is no batched d-pair leave-one-out yet.  ABI 5 (an additional entry point). */
+ * gradient is sgpr_fit_batch_nd_grad, leave-one-point-out sgpr_fit_batch_nd_loo and its gradient sgpr_fit_batch_nd_loo_grad.  ABI 5
+ * (an additional entry point). */
 int sgpr_fit_batch_nd(int family, int d, int nbatch, int n_pts, const double *X, const double *z, const double *hyp,
                       int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, int *info);
 /* sgpr_fit_batch_nd plus d nll / d(hyp, sig2n) per problem, for every order n = 2 d n_pts <= sgpr_fit_batch_max_order() (2048) in
@@ -356,6 +357,37 @@ int sgpr_fit_batch_nd(int family, int d, int nbatch, int n_pts, const double *X,
  * point). */
 int sgpr_fit_batch_nd_grad(int family, int d, int nbatch, int n_pts, const double *X, const double *z, const double *hyp,
                            int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, double *grad, int *info);
+/* sgpr_fit_batch_nd plus leave-one-point-out cross-validation of every problem (see sgpr_fit_loo; a point owns its D = 2d rows
+ * {c n_pts + i}), for every order n = 2 d n_pts <= sgpr_fit_batch_max_order() (2048) in one entry.  X, z, hyp, nhyp, sig2n, flags
+ * (must be 0), alpha (may be NULL), nll and info exactly as sgpr_fit_batch_nd.  loo: nbatch x 2, row-major; row b = {loo, press} by
+ * sgpr_fit_loo's definitions.  nll, alpha and info are bit-identical to sgpr_fit_batch_nd's; info[b] > 0: nll[b] and the row loo[b]
+ * are NaN, the other problems are untouched and the call returns 0.  A problem's loo bits do not depend on its place in the batch,
+ * the batch size, the chunk or a repetition (no atomics).  n <= 256: one launch, one workgroup per problem, which after the fit
+ * forms Ky^-1 = L^-T L^-1 over L as sgpr_fit_batch_nd_grad does; then thread i gathers point i's D x D block of Ky^-1 from the lower
+ * triangle and takes it through the block algebra of sgpr_fit_loo in registers; the sums fold in a fixed order.  Scratch as
+ * sgpr_fit_batch_nd_grad.  Above: the chunks, images and Ky^-1 stage of sgpr_fit_batch_nd_grad's mid path, then one thread per point
+ * and a fold per problem in place of the contraction (sgpr_fit_batch_loo's kernels at block size D).  SGPR_E_ARG (before any device
+ * call) for d outside 1..3, an unknown family, a wrong nhyp, flags != 0, nbatch < 0, n_pts <= 0, n above the maximum and a null
+ * pointer other than alpha (loo is required); nbatch == 0 returns 0.  ABI 5 (an additional entry point). */
+int sgpr_fit_batch_nd_loo(int family, int d, int nbatch, int n_pts, const double *X, const double *z, const double *hyp,
+                          int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, double *loo, int *info);
+/* sgpr_fit_batch_nd plus one leave-one-point-out objective and its gradient per problem, for orders n = 2 d n_pts <= 256.  which:
+ * SGPR_LOO_LPD (value = loo) or SGPR_LOO_PRESS (value = press), the same for the whole batch; value: nbatch; grad: nbatch x
+ * (nhyp + 1), row-major, in sgpr_fit_batch_nd_grad's order, the last entry d/dsig2n with sign(sig2n[b]) (sign(0) = +1); the formulas
+ * are sgpr_fit_loo_grad's with D = 2d.  Everything else as sgpr_fit_batch_nd.  nll, alpha and info are bit-identical to
+ * sgpr_fit_batch_nd's and value to column `which` of sgpr_fit_batch_nd_loo's (the same code up to the sums).  info[b] > 0: nll[b],
+ * value[b] and the whole row grad[b] are NaN, the other problems are untouched and the call returns 0.  A problem's bits do not
+ * depend on its place in the batch, the batch size or a repetition.  One launch, one workgroup per problem: behind
+ * sgpr_fit_batch_nd_loo's steps each point's weight block W~_i (D (D + 1) / 2 doubles) and v[B_i] go to LDS, Ky^-1 is mirrored to
+ * full storage, beta = Ky^-1 v and Y = W~ Ky^-1 (D rows of Ky^-1 per row of Y) follow, then W' = Ky^-1 Y - beta alpha^T - alpha beta^T
+ * (n^3 flop, sgpr_fit_batch_loo_grad's code) and its contraction with dK over D x D blocks of point pairs
+ * (sgpr_fit_batch_nd_grad's code).  Scratch per workgroup as sgpr_fit_batch_loo_grad: ~1.8 MiB, at most 1024 workgroups (~1.8 GiB),
+ * in the sgpr_fit_batch arena, kept until sgpr_trim.  SGPR_E_ARG (before any device call) for d outside 1..3, an unknown family, a
+ * wrong nhyp, flags != 0, an unknown which, nbatch < 0, n_pts <= 0, an order above 256 and a null pointer other than alpha;
+ * nbatch == 0 returns 0.  ABI 5 (an additional entry point). */
+int sgpr_fit_batch_nd_loo_grad(int family, int d, int nbatch, int n_pts, const double *X, const double *z, const double *hyp,
+                               int nhyp, const double *sig2n, unsigned flags, int which, double *alpha, double *nll,
+                               double *value, double *grad, int *info);
 /* sgpr_fit_batch plus d nll / d(hyp, sig2n) per problem.  Order per problem n = 2 n_pts (n_pts with SGPR_FIT_REG) <= 256.
  * grad: nbatch x (nhyp + 1), row-major; row b = (d/dhyp_0 .. d/dhyp_{nhyp-1}, d/dsig2n).  hyp layout and nhyp as
  * sgpr_fit_batch: (lx, ly, sig), or (lx, ly, p, sig) for families with a period.  Ky holds |sig2n[b]|, so the last entry is

@@ -155,6 +155,9 @@ int sgpr_probe_strassen_schedule(int m, int n, int k, int lower, long capacity_d
  * [20] the scratch size; [21] sizeof KConst, [22] sizeof NdConst, [23] the flag bytes of one panel for a chunk (0 on path 0).
  * tests/test_batch_layout_cpu.py checks it against the formulas. */
 int sgpr_probe_batch_layout(int path, int mode, int d, int reg, int nbatch, int n_pts, int nhyp, unsigned long long out[24]);
+/* The same for sgpr_fit_batch_nd_loo (mode 2, both paths) and sgpr_fit_batch_nd_loo_grad (mode 3, path 0 only), d = 1 .. 3: the modes
+ * sgpr_probe_batch_layout refuses for d > 0.  out as above.  tests/test_batch_pairs_loo_cpu.py checks it against the formulas. */
+int sgpr_probe_batch_layout_nd_loo(int path, int mode, int d, int nbatch, int n_pts, int nhyp, unsigned long long out[24]);
 unsigned sgpr_probe_map_calls(void);
 int sgpr_probe_map_team(int ntest, int n0);
 

@@ -141,6 +141,10 @@ SIGNATURES = {
                                     C.POINTER(C.c_int)]),
     "sgpr_fit_batch_nd_grad": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_uint, _dp, _dp, _dp,
                                          C.POINTER(C.c_int)]),
+    "sgpr_fit_batch_nd_loo": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_uint, _dp, _dp, _dp,
+                                        C.POINTER(C.c_int)]),
+    "sgpr_fit_batch_nd_loo_grad": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_uint, C.c_int, _dp,
+                                             _dp, _dp, _dp, C.POINTER(C.c_int)]),
     "sgpr_fit_batch_grad": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_uint, _dp, _dp, _dp,
                                       C.POINTER(C.c_int)]),
     "sgpr_fit_batch_grad_mid": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_uint, _dp, _dp, _dp,
@@ -203,6 +207,7 @@ PROBE_SIGNATURES = {
                                           C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_double), C.c_void_p]),
     "sgpr_probe_batch_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.POINTER(C.c_ulonglong)]),
+    "sgpr_probe_batch_layout_nd_loo": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]),
     "sgpr_probe_census": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint), C.c_int,
                                     C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint), C.c_int,
                                     C.POINTER(C.c_ulonglong)]),

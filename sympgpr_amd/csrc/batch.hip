@@ -15,6 +15,9 @@
 // Problems with d canonical pairs per point (sgpr_fit_batch_nd) take the same path behind a Gram stage of their own: the entry
 // formulas of nd_eval.h, fit_batch_nd_kernel / mid_build_nd_kernel.  Their nll gradient (sgpr_fit_batch_nd_grad) is that path with the
 // Ky^-1 stage of the d = 1 gradient and a contraction over D x D blocks of point pairs: contract_rows_nd / mid_grad_nd_kernel.
+// Their leave-one-point-out sums (sgpr_fit_batch_nd_loo) take one thread per point behind the same Ky^-1 stage, with D x D blocks
+// (loo_point_nd; mid_loo_kernel<D> above order 256), and the gradient of one of them (sgpr_fit_batch_nd_loo_grad, orders up to 256)
+// the phases (L1) - (L4) of the d = 1 loo gradient over those blocks (grad_problem_nd).
 // The device code is in batch_small.h (n <= 256) and batch_mid.h (256 < n <= 2048), included here and only here: one translation
 // unit.  This file holds the arena, its one layout function, the staging of a call and the two host drivers.
 #include <cmath>
@@ -266,13 +269,18 @@ int fit_batch_small(const BatchCall &c)
     if (c.d) {
         const BatchNdArgs a{c.nbatch, c.npts, c.n, at<double>(m.din, l.o_x), at<double>(m.din, l.o_z), at<nd::NdConst>(m.din, l.o_kc),
                             at<double>(m.din, l.o_no), at<double>(m.dscr, 0), c.alpha ? at<double>(m.dout, l.o_al) : nullptr,
-                            at<double>(m.dout, l.o_nll), at<int>(m.dout, l.o_info)};
+                            at<double>(m.dout, l.o_nll), at<int>(m.dout, l.o_info), c.which};
         if ((rc = nd::dispatch_nd(c.family, c.d, [&](auto fam, auto dd) {
-                if (mode == MODE_GRAD)
-                    hipLaunchKernelGGL((fit_batch_nd_kernel<decltype(fam)::value, decltype(dd)::value, MODE_GRAD>), g, t, 0, st, a);
-                else
-                    hipLaunchKernelGGL((fit_batch_nd_kernel<decltype(fam)::value, decltype(dd)::value, MODE_FIT>), g, t, 0, st, a);
-                return 0;
+                auto launch = [&](auto md) {
+                    hipLaunchKernelGGL((fit_batch_nd_kernel<decltype(fam)::value, decltype(dd)::value, decltype(md)::value>), g, t, 0, st, a);
+                    return 0;
+                };
+                switch (mode) {
+                case MODE_LOOGRAD: return launch(std::integral_constant<int, MODE_LOOGRAD>());
+                case MODE_GRAD:    return launch(std::integral_constant<int, MODE_GRAD>());
+                case MODE_LOO:     return launch(std::integral_constant<int, MODE_LOO>());
+                default:           return launch(std::integral_constant<int, MODE_FIT>());
+                }
             })))
             return rc;
     } else {
@@ -302,7 +310,8 @@ int fit_batch_small(const BatchCall &c)
 // ---- problems of order 256 < n <= 2048 (batch_mid.h): chunks of problems share the scratch images; every chunk runs the stages
 // below on the stream, in this order.  With grad or loo (the Ky^-1 phase) a second image per problem (U = L^-T) stands behind the L
 // images, and the sums come back behind nll in the chunk's one device-to-host copy.  d > 0: X in place of x | y, one NdConst per
-// problem, mid_build_nd_kernel in place of mid_build_kernel and mid_grad_nd_kernel in place of mid_grad_kernel; no loo phase.
+// problem, mid_build_nd_kernel in place of mid_build_kernel and mid_grad_nd_kernel in place of mid_grad_kernel; the loo phase is
+// mid_loo_kernel at 2 d rows per point.  The mid path has no loo gradient, for any d.
 
 // the device pointers of one chunk of nb problems
 struct MidChunk {
@@ -433,8 +442,14 @@ int mid_kinv(hipStream_t st, const BatchLayout &l, const MidChunk &k)
 // {loo, press} of every problem from Ky^-1 and alpha, behind nll
 int mid_loo(hipStream_t st, const BatchCall &c, const BatchLayout &l, const MidChunk &k)
 {
-    const MidLoo ml{c.npts, c.reg, l.lnwg, (size_t)l.npad, k.A, k.r, k.part, k.info, k.sums};
-    hipLaunchKernelGGL(mid_loo_kernel, dim3((unsigned)l.lnwg, 1, (unsigned)k.nb), dim3(GT), 0, st, ml);
+    const MidLoo ml{c.npts, l.lnwg, (size_t)l.npad, k.A, k.r, k.part, k.info, k.sums};
+    const dim3 g((unsigned)l.lnwg, 1, (unsigned)k.nb);
+    switch (c.d ? 2 * c.d : c.reg ? 1 : 2) {              // the rows per point
+    case 1:  hipLaunchKernelGGL(mid_loo_kernel<1>, g, dim3(GT), 0, st, ml); break;
+    case 2:  hipLaunchKernelGGL(mid_loo_kernel<2>, g, dim3(GT), 0, st, ml); break;
+    case 4:  hipLaunchKernelGGL(mid_loo_kernel<4>, g, dim3(GT), 0, st, ml); break;
+    default: hipLaunchKernelGGL(mid_loo_kernel<6>, g, dim3(GT), 0, st, ml); break;
+    }
     SGPR_CHECK_LAUNCH();
     hipLaunchKernelGGL(mid_loo_fold_kernel, dim3(k.nb), dim3(64), 0, st, ml);
     SGPR_CHECK_LAUNCH();
@@ -535,6 +550,24 @@ int fit_batch_nd_grad(int family, int d, int nbatch, int npts, const double *X, 
     const BatchCall c{family, d, 0, nbatch, npts, 2 * d * npts, nhyp, X, nullptr, z, hyp, sig2n, alpha, nll, info,
                       grad, nullptr, nullptr, SGPR_LOO_LPD};
     return c.n > BMAX ? fit_batch_mid(c) : fit_batch_small(c);
+}
+
+// sgpr_fit_batch_nd_loo: n = 2 d npts <= fit_batch_max_order()
+int fit_batch_nd_loo(int family, int d, int nbatch, int npts, const double *X, const double *z, const double *hyp, int nhyp,
+                     const double *sig2n, double *alpha, double *nll, double *loo, int *info)
+{
+    const BatchCall c{family, d, 0, nbatch, npts, 2 * d * npts, nhyp, X, nullptr, z, hyp, sig2n, alpha, nll, info,
+                      nullptr, loo, nullptr, SGPR_LOO_LPD};
+    return c.n > BMAX ? fit_batch_mid(c) : fit_batch_small(c);
+}
+
+// sgpr_fit_batch_nd_loo_grad: n = 2 d npts <= BMAX
+int fit_batch_nd_loo_grad(int family, int d, int nbatch, int npts, const double *X, const double *z, const double *hyp, int nhyp,
+                          const double *sig2n, int which, double *alpha, double *nll, double *value, double *grad, int *info)
+{
+    const BatchCall c{family, d, 0, nbatch, npts, 2 * d * npts, nhyp, X, nullptr, z, hyp, sig2n, alpha, nll, info,
+                      grad, nullptr, value, which};
+    return fit_batch_small(c);
 }
 
 // sgpr_fit_batch_grad_mid: BMAX < n <= fit_batch_max_order()

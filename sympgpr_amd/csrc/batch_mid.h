@@ -445,7 +445,7 @@ __global__ __launch_bounds__(64) void mid_grad_fold_kernel(const MidGrad a)
 
 // ---- leave-one-point-out sums of the mid-size problems (sgpr_fit_batch_loo): behind step (b) above, in place of (c) ----------
 struct MidLoo {
-    int npts, reg, nwg;
+    int npts, nwg;
     size_t ld;                            // npad: Ky^-1 (lower) of problem b at K + b ld^2, its alpha at alpha + b ld
     const double *K, *alpha;
     double *part;                         // sum k of workgroup w of problem b at part[(b nwg + w) 2 + k]: k = 0 lpd, 1 |r|^2
@@ -453,7 +453,9 @@ struct MidLoo {
     double *out;                          // problem b's {loo, press} at out + 2 b
 };
 
-// points blockIdx.x GT .. + GT (one per thread) of problem blockIdx.z: the point's block from the lower triangle of Ky^-1
+// points blockIdx.x GT .. + GT (one per thread) of problem blockIdx.z: the point's D x D block from the lower triangle of Ky^-1
+// (loo_point_nd, batch_small.h).  D = 1: reg fits, D = 2: pairs (d = 1 or one canonical pair), D = 4, 6: d-pair fits; no family enters.
+template <int D>
 __global__ __launch_bounds__(GT) void mid_loo_kernel(const MidLoo a)
 {
     __shared__ double red[GT / 64][2];
@@ -461,18 +463,8 @@ __global__ __launch_bounds__(GT) void mid_loo_kernel(const MidLoo a)
     const double *K = a.K + (size_t)b * a.ld * a.ld, *al = a.alpha + (size_t)b * a.ld;
     double lv[2] = {0.0, 0.0};
     if (i < N) {
-        double lpd, rr;
-        if (a.reg) {
-            const double C[1] = {K[i + i * a.ld]}, ai[1] = {al[i]};
-            double r[1], S[1];
-            loo::block<1>(C, ai, r, S, lpd);
-            rr = r[0] * r[0];
-        } else {
-            const double C[3] = {K[i + i * a.ld], K[(N + i) + i * a.ld], K[(N + i) + (N + i) * a.ld]}, ai[2] = {al[i], al[N + i]};
-            double r[2], S[3];
-            loo::block<2>(C, ai, r, S, lpd);
-            rr = __builtin_fma(r[1], r[1], r[0] * r[0]);
-        }
+        double r[D], S[D * (D + 1) / 2], lpd, rr;
+        loo_point_nd<D>(K, a.ld, al, i, N, r, S, lpd, rr);
         lv[0] = lpd; lv[1] = rr;
     }
 #pragma unroll

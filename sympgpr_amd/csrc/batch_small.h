@@ -198,10 +198,13 @@ struct BatchNdArgs {
     const double *X, *z;                  // nbatch x D x npts (coordinate m of point i of problem b at (b D + m) npts + i), nbatch x n
     const nd::NdConst *nc;                // per problem
     const double *noise;                  // per problem, >= 0
-    double *scratch;                      // per workgroup: PER_WG doubles [+ BMAX*BMAX (U = L^-T) for the gradient], as fit_batch_kernel
+    double *scratch;                      // per workgroup: PER_WG doubles [+ BMAX*BMAX (U = L^-T) for the gradient and loo]
+                                          // [+ BMAX*BMAX (W') for the loo gradient], as fit_batch_kernel
     double *alpha, *nll;                  // outputs (alpha may be null); the gradient kernel writes problem b's raw sums at
-                                          // nll + nbatch + b * grad_nacc_nd<FAM, D>()
+                                          // nll + nbatch + b * grad_nacc_nd<FAM, D>(), the loo kernel {loo, press} at nll + nbatch + 2 b,
+                                          // the loo gradient kernel {loo, press, raw sums} at nll + nbatch + b * (2 + grad_nacc_nd<FAM, D>())
     int *info;                            // per problem, zero on entry
+    int which;                            // the loo gradient's objective (SGPR_LOO_LPD / SGPR_LOO_PRESS), the same for the launch
 };
 
 // entry (i, j) of the blocks (ca, 0 .. ca) of one evaluated pair into the lower triangle at P = A + i + j ld (ld: the leading
@@ -219,21 +222,23 @@ __device__ __forceinline__ void store_pair_lower(double *P, size_t ld, int N, bo
     }
 }
 
-template <int FAM, int D>
+template <int FAM, int D, int MODE>
 __device__ void grad_problem_nd(const BatchNdArgs &a, int b, const nd::NdConst &nc, double *s, double *A, const double *inv, double *U,
                                 const double *al);
 
-// MODE_GRAD: after the fit, the gradient of problem b's nll (grad_problem_nd below); scratch then PER_WG + BMAX^2 doubles per
-// workgroup, as fit_batch_kernel<FAM, MODE_GRAD>.  There is no d-pair MODE_LOO or MODE_LOOGRAD.
+// The modes of fit_batch_kernel (grad_problem_nd below).  MODE_GRAD: after the fit, the gradient of problem b's nll; MODE_LOO: its
+// leave-one-point-out sums over D x D point blocks; scratch then PER_WG + BMAX^2 doubles per workgroup.  MODE_LOOGRAD: the sums and
+// the gradient of one of them, with a third block: PER_WG + 2 BMAX^2 doubles per workgroup, as fit_batch_kernel<FAM, MODE_LOOGRAD>.
 template <int FAM, int D, int MODE = MODE_FIT>
 __global__ __launch_bounds__(LT) void fit_batch_nd_kernel(const BatchNdArgs a)
 {
-    static_assert(MODE == MODE_FIT || MODE == MODE_GRAD, "the d-pair kernel has the fit and the nll gradient");
+    static_assert(MODE >= MODE_FIT && MODE <= MODE_LOOGRAD, "fit, nll gradient, loo or loo gradient");
     __shared__ double s[LEAF_LDS];
     __shared__ double red[LT / 64];
     const int tid = threadIdx.x;
     const int n = a.n, N = a.npts;
-    const size_t per_wg = PER_WG + (MODE != MODE_FIT ? (size_t)BMAX * BMAX : 0);               // PER_WG [+ U]
+    const size_t per_wg = PER_WG + (MODE != MODE_FIT ? (size_t)BMAX * BMAX : 0) +
+                          (MODE == MODE_LOOGRAD ? (size_t)BMAX * BMAX : 0);                    // PER_WG [+ U] [+ W']
     double *A = a.scratch + (size_t)blockIdx.x * per_wg;      // column-major, ld = BMAX
     double *inv = A + (size_t)BMAX * BMAX;
     double *v = inv + 2 * (size_t)LEAF * LEAF;                // y, then alpha
@@ -256,7 +261,7 @@ __global__ __launch_bounds__(LT) void fit_batch_nd_kernel(const BatchNdArgs a)
             store_pair_lower<FAM, D>(A + i + j * ld, ld, N, i >= j, i == j, noise, E, g, nh);
         }
         fit_solve_body(s, red, A, inv, v, v + BMAX, z, n, n1, n2, a.alpha ? a.alpha + (size_t)b * n : nullptr, a.nll + b, a.info + b);
-        if constexpr (MODE == MODE_GRAD) grad_problem_nd<FAM, D>(a, b, nc, s, A, inv, v + 2 * BMAX, v + BMAX);
+        if constexpr (MODE != MODE_FIT) grad_problem_nd<FAM, D, MODE>(a, b, nc, s, A, inv, v + 2 * BMAX, v + BMAX);
     }
 }
 
@@ -278,6 +283,25 @@ __device__ __forceinline__ void loo_point(const double *A, const double *al, int
         loo::block<2>(C, ai, r, S, lpd);
         rr = __builtin_fma(r[1], r[1], r[0] * r[0]);
     }
+}
+
+// The same for a point with D rows {c N + i} (d-pair fits: D = 2 d; the mid path's d = 1 fits: D = 1 for reg, 2 for pairs): the block's
+// entries (e N + i, c N + i), e >= c, from the lower triangle of Ky^-1 (K, leading dimension ld), packed with loo::pk.
+template <int D>
+__device__ __forceinline__ void loo_point_nd(const double *K, size_t ld, const double *al, int i, int N, double (&r)[D],
+                                             double (&S)[D * (D + 1) / 2], double &lpd, double &rr)
+{
+    double C[D * (D + 1) / 2], ai[D];
+#pragma unroll
+    for (int e = 0; e < D; ++e) {
+#pragma unroll
+        for (int c = 0; c <= e; ++c) C[loo::pk(e, c)] = K[((size_t)e * N + i) + ((size_t)c * N + i) * ld];
+        ai[e] = al[e * N + i];
+    }
+    loo::block<D>(C, ai, r, S, lpd);
+    rr = r[0] * r[0];
+#pragma unroll
+    for (int k = 1; k < D; ++k) rr = __builtin_fma(r[k], r[k], rr);
 }
 
 // The per-thread {lpd, |r|^2} fold wave by wave in a fixed order (through s[0 .. 7]) into out = {loo, press}.  Ends on a barrier.
@@ -544,21 +568,21 @@ __device__ void grad_problem(const BatchArgs &a, int b, double *s, double *A, co
 // ---- the nll gradient for d canonical pairs per point (D = 2 d): lq_1..lq_d, lP_1..lP_d, [p_1..p_d,] sig, sig2n
 template <int FAM, int D> constexpr int grad_nacc_nd() { return D + (grad_has_p<FAM>() ? D / 2 : 0) + 2; }
 
-// Step (3) for D x D blocks of point pairs: thread i < n owns row i of W = Ky^-1 - alpha alpha^T (Ky^-1: the lower triangle in A),
-// which is part r = i / N of point pi = i % N, and walks the column points pj = 0 .. N - 1.  Each pair is evaluated once
+// Step (3) for D x D blocks of point pairs, for any symmetric weight: thread i < n owns row i of W, given as wf(i, alpha_i, col) for
+// col <= i (the nll gradient: Ky^-1 - alpha alpha^T from the lower triangle of Ky^-1; the loo gradient: a load of W'), which is
+// part r = i / N of point pi = i % N, and walks the column points pj = 0 .. N - 1.  Each pair is evaluated once
 // (nllg::pair_grad, dK from the generated forms) and feeds the D entries (i, c N + pj): W_ii on the diagonal (also the noise sum),
 // 2 W_ij below it, 0 above it; the walk stops at the first pj with no entry on or below the diagonal (pj > i).  The points (D N <=
 // BMAX doubles, coordinate m of point p at s[m N + p]) and alpha (at s + 2 BMAX) go to LDS first, the wave partials behind them.
 // Lengths and periods as nllgrad.hip fills GradArgs::l / pp, from the problem's NdConst.  The per-thread sums fold wave by wave in a
 // fixed order into out[0 .. NACC), unscaled.
-template <int FAM, int D>
-__device__ __forceinline__ void contract_rows_nd(const double *X, const nd::NdConst &nc, int N, int n, double *s, const double *A,
-                                                 const double *al, double *out)
+template <int FAM, int D, class WF>
+__device__ __forceinline__ void contract_rows_nd(const double *X, const nd::NdConst &nc, int N, int n, double *s, const double *al,
+                                                 double *out, WF wf)
 {
     constexpr bool HASP = grad_has_p<FAM>();
     constexpr int NACC = grad_nacc_nd<FAM, D>(), d = D / 2;
     static_assert(3 * BMAX + 4 * NACC <= (int)LEAF_LDS, "points | alpha | wave partials fit in the leaf's LDS");
-    constexpr size_t ld = BMAX;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, i = tid;
     double *sx = s, *sal = s + 2 * BMAX, *red = s + 3 * BMAX;
     for (int e = tid; e < n; e += LT) { sx[e] = X[e]; sal[e] = al[e]; }      // D N = n
@@ -575,7 +599,6 @@ __device__ __forceinline__ void contract_rows_nd(const double *X, const nd::NdCo
     if (i < n) {
         const int r = i / N, pi = i - r * N;
         const double ai = sal[i];
-        const double *Arow = A + i;
         double xi[D];
 #pragma unroll
         for (int m = 0; m < D; ++m) xi[m] = sx[m * N + pi];
@@ -587,7 +610,7 @@ __device__ __forceinline__ void contract_rows_nd(const double *X, const nd::NdCo
                 const int col = c * N + pj;
                 w[c] = 0.0;
                 if (col <= i) {
-                    const double W = Arow[col * ld] - ai * sal[col];
+                    const double W = wf(i, ai, col);
                     if (col == i) { w[c] = W; acc[NACC - 1] += W; }
                     else w[c] = 2.0 * W;
                 }
@@ -609,23 +632,140 @@ __device__ __forceinline__ void contract_rows_nd(const double *X, const nd::NdCo
     __syncthreads();                                      // A, U and s are the next problem's
 }
 
-// grad_problem's MODE_GRAD for the d-pair kernel: the NaN row of a problem that is not positive definite, kinv_problem (steps (1)
-// and (2), the text the d = 1 kernel runs), then contract_rows_nd.  The sums leave unscaled: the host applies sig / 2 (sig from the
-// staged NdConst), 1/2 and sign(sig2n) / 2.
-template <int FAM, int D>
+// Step (L3) of the d-pair loo gradient: grad_problem's (L3), statement by statement (neither the points nor the block size enter;
+// the d = 1 kernel keeps its inline text, and with it its compiled code): W'[i, j] from M[i, j] = sum_k Ky^-1[i, k] Y[k, j], i >= j,
+// with Ky^-1 full in A and Y in Y (ld = BMAX): thread i its row, columns j0 .. j0 + 3 from one pass over the row (a column past
+// n - 1 is clamped: computed again, not stored), k = 0 .. n - 1 in order.  Stored in M: W' = M - beta alpha^T - alpha beta^T (al:
+// global, sbeta: LDS).  No barrier: thread i reads back its own row.
+__device__ __forceinline__ void wprime_rows(const double *A, const double *Y, double *M, const double *al, const double *sbeta, int n)
+{
+    constexpr size_t ld = BMAX;
+    const int i = threadIdx.x;
+    for (int j0 = 0; j0 < n; j0 += 4) {
+        if (i < n && i >= j0) {
+            const double *y0 = Y + j0 * ld, *y1 = Y + min(j0 + 1, n - 1) * ld, *y2 = Y + min(j0 + 2, n - 1) * ld,
+                         *y3 = Y + min(j0 + 3, n - 1) * ld;
+            double m0 = 0.0, m1 = 0.0, m2 = 0.0, m3 = 0.0;
+            for (int k = 0; k < n; ++k) {
+                const double kik = A[i + k * ld];
+                m0 = __builtin_fma(kik, y0[k], m0);
+                m1 = __builtin_fma(kik, y1[k], m1);
+                m2 = __builtin_fma(kik, y2[k], m2);
+                m3 = __builtin_fma(kik, y3[k], m3);
+            }
+            const double bi = sbeta[i], ali = al[i];
+            auto wp = [=](double m, int j) { return m - bi * al[j] - ali * sbeta[j]; };
+            M[i + j0 * ld] = wp(m0, j0);
+            if (j0 + 1 <= i) M[i + (j0 + 1) * ld] = wp(m1, j0 + 1);
+            if (j0 + 2 <= i) M[i + (j0 + 2) * ld] = wp(m2, j0 + 2);
+            if (j0 + 3 <= i) M[i + (j0 + 3) * ld] = wp(m3, j0 + 3);
+        }
+    }
+}
+
+// grad_problem for the d-pair kernel: the NaN row of a problem that is not positive definite, kinv_problem (steps (1) and (2), the
+// text the d = 1 kernel runs), then by mode
+//   MODE_GRAD     contract_rows_nd on Ky^-1 - alpha alpha^T.  The sums leave unscaled: the host applies sig / 2 (sig from the staged
+//                 NdConst), 1/2 and sign(sig2n) / 2;
+//   MODE_LOO      thread i < N takes point i's D x D block of Ky^-1 (loo_point_nd) through loo_block.h; lpd and |r|^2 fold wave by
+//                 wave in the fixed order (loo_fold) into {loo, press};
+//   MODE_LOOGRAD  MODE_LOO's steps and sums by the same code (the same bits), then grad_problem's phases (L1) - (L4) over D x D
+//                 blocks: (L1) W~_i (packed lower, T = D (D + 1) / 2 doubles per point, entry t of point i at sW[t N + i]: T N =
+//                 (D + 1) n / 2 <= 3.5 BMAX doubles at D = 6) and v[B_i] into LDS, with v and beta behind W~, and the mirror of
+//                 Ky^-1; (L2) beta = Ky^-1 v and Y = W~ Ky^-1 over U, row c N + i of Y from the point's D rows of Ky^-1; (L3)
+//                 wprime_rows into the third block; (L4) contract_rows_nd with a plain load of W'.
+// Output: MODE_GRAD the NACC raw sums, MODE_LOO {loo, press}, MODE_LOOGRAD {loo, press, the NACC raw sums}.
+template <int FAM, int D, int MODE>
 __device__ void grad_problem_nd(const BatchNdArgs &a, int b, const nd::NdConst &nc, double *s, double *A, const double *inv, double *U,
                                 const double *al)
 {
-    constexpr int NACC = grad_nacc_nd<FAM, D>();
+    constexpr int NACC = grad_nacc_nd<FAM, D>(), NOUT = MODE == MODE_LOO ? 2 : MODE == MODE_LOOGRAD ? 2 + NACC : NACC;
+    constexpr int T = D * (D + 1) / 2;
+    // LDS: contract_rows_nd's points | alpha | partials in [0, 4 BMAX), then W~ (T N <= (D + 1) BMAX / 2), v, beta
+    static_assert((D + 1) * BMAX / 2 <= 4 * BMAX && 10 * BMAX <= (int)LEAF_LDS, "W~, v and beta fit in the leaf's LDS behind the contraction's part");
+    constexpr size_t ld = BMAX;
     const int tid = threadIdx.x;
     const int n = a.n, N = a.npts, n1 = min(n, (int)LEAF), n2 = n - n1;
-    double *out = a.nll + a.nbatch + (size_t)b * NACC;
+    const double *X = a.X + (size_t)b * D * N;
+    double *out = a.nll + a.nbatch + (size_t)b * NOUT;
     if (__hip_atomic_load(a.info + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-        if (tid < NACC) out[tid] = __builtin_nan("");
+        if (tid < NOUT) out[tid] = __builtin_nan("");
         return;
     }
     kinv_problem(s, A, inv, U, n, n1, n2);
-    contract_rows_nd<FAM, D>(a.X + (size_t)b * D * N, nc, N, n, s, A, al, out);
+    [[maybe_unused]] double *sal = s + 2 * BMAX;          // contract_rows_nd's alpha
+    if constexpr (MODE == MODE_GRAD) {
+        contract_rows_nd<FAM, D>(X, nc, N, n, s, al, out, [=](int row, double ai, int col) { return A[row + col * ld] - ai * sal[col]; });
+        return;
+    }
+    const int i = tid;
+    [[maybe_unused]] double *sW = s + 4 * BMAX, *sv = s + 8 * BMAX, *sbeta = s + 9 * BMAX;
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();                                      // point i's block has entries written by the threads c N + i; T is dead
+    double lv[2] = {0.0, 0.0};
+    if (i < N) {
+        double r[D], S[T], lpd, rr;
+        loo_point_nd<D>(A, ld, al, i, N, r, S, lpd, rr);
+        lv[0] = lpd; lv[1] = rr;
+        if constexpr (MODE == MODE_LOOGRAD) {
+            // (L1) W~_i and v[B_i]
+            if (a.which == SGPR_LOO_PRESS) {
+                double sr[D];                             // s = S r
+#pragma unroll
+                for (int e = 0; e < D; ++e) {
+                    double acc = S[loo::pk(e, 0)] * r[0];
+#pragma unroll
+                    for (int c = 1; c < D; ++c) acc = __builtin_fma(S[c <= e ? loo::pk(e, c) : loo::pk(c, e)], r[c], acc);
+                    sr[e] = acc;
+                }
+#pragma unroll
+                for (int e = 0; e < D; ++e) {
+#pragma unroll
+                    for (int c = 0; c <= e; ++c) sW[loo::pk(e, c) * N + i] = 2.0 * __builtin_fma(r[e], sr[c], sr[e] * r[c]);
+                    sv[e * N + i] = 2.0 * sr[e];
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < D; ++e) {
+#pragma unroll
+                    for (int c = 0; c <= e; ++c) sW[loo::pk(e, c) * N + i] = __builtin_fma(r[e], r[c], S[loo::pk(e, c)]);
+                    sv[e * N + i] = r[e];
+                }
+            }
+        }
+    }
+    if constexpr (MODE == MODE_LOOGRAD) {
+        // the mirror: strictly above the diagonal, which no thread reads in this phase
+        if (i < n)
+            for (int j = 0; j < i; ++j) A[j + i * ld] = A[i + j * ld];
+    }
+    loo_fold(lv, s, out);                                 // ends on the fence: the mirror and the LDS vectors are visible
+    if constexpr (MODE == MODE_LOOGRAD) {
+        // ---- (L2) beta and Y
+        if (i < n) {
+            double acc = 0.0;
+            for (int j = 0; j < n; ++j) acc = __builtin_fma(A[i + j * ld], sv[j], acc);
+            sbeta[i] = acc;
+            // row i = c N + pi of Y from the point's rows e N + pi of Ky^-1, weights W~_pi[c, e]
+            const int c = i / N, pi = i - c * N;
+            double w[D];
+#pragma unroll
+            for (int e = 0; e < D; ++e) w[e] = sW[(e >= c ? loo::pk(e, c) : loo::pk(c, e)) * N + pi];
+            const double *Ap = A + pi;
+            for (int k = 0; k < n; ++k) {
+                double y = w[D - 1] * Ap[(size_t)(D - 1) * N + k * ld];
+#pragma unroll
+                for (int e = D - 2; e >= 0; --e) y = __builtin_fma(w[e], Ap[(size_t)e * N + k * ld], y);
+                U[i + k * ld] = y;
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        // ---- (L3) W' into the third block, (L4) thread i reads the row of W' it wrote
+        double *M = U + (size_t)BMAX * BMAX;
+        wprime_rows(A, U, M, al, sbeta, n);
+        contract_rows_nd<FAM, D>(X, nc, N, n, s, al, out + 2, [=](int row, double, int col) { return M[row + col * ld]; });
+    }
 }
 
 }  // namespace

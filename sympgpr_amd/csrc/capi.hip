@@ -365,6 +365,31 @@ int sgpr_fit_batch_nd_grad(int family, int d, int nbatch, int n_pts, const doubl
     return fit_batch_nd_grad(family, d, nbatch, n_pts, X, z, hyp, nhyp, sig2n, alpha, nll, grad, info);
 }
 
+/* sgpr_fit_batch_nd plus leave-one-point-out cross-validation per problem over 2d x 2d point blocks, every order up to the maximum
+ * (batch.hip: the loo mode of fit_batch_nd_kernel up to order 256, the mid path with mid_loo_kernel<2d> above). */
+int sgpr_fit_batch_nd_loo(int family, int d, int nbatch, int n_pts, const double *X, const double *z, const double *hyp, int nhyp,
+                          const double *sig2n, unsigned flags, double *alpha, double *nll, double *loo, int *info)
+{
+    int rc = check_batch_args("fit_batch_nd_loo", family, &d, nhyp, flags, nullptr, nbatch, n_pts, 0, fit_batch_max_order(),
+                              "nll, loo or info", nll && loo && info, X && z && hyp && sig2n);
+    if (rc || nbatch == 0) return rc;
+    if ((rc = need_device())) return rc;
+    return fit_batch_nd_loo(family, d, nbatch, n_pts, X, z, hyp, nhyp, sig2n, alpha, nll, loo, info);
+}
+
+/* sgpr_fit_batch_nd plus one leave-one-point-out objective and its gradient per problem, orders up to 256 (batch.hip: the loograd
+ * mode of fit_batch_nd_kernel). */
+int sgpr_fit_batch_nd_loo_grad(int family, int d, int nbatch, int n_pts, const double *X, const double *z, const double *hyp,
+                               int nhyp, const double *sig2n, unsigned flags, int which, double *alpha, double *nll,
+                               double *value, double *grad, int *info)
+{
+    int rc = check_batch_args("fit_batch_nd_loo_grad", family, &d, nhyp, flags, &which, nbatch, n_pts, 0, fit_batch_grad_max_order(),
+                              "nll, value, grad or info", nll && value && grad && info, X && z && hyp && sig2n);
+    if (rc || nbatch == 0) return rc;
+    if ((rc = need_device())) return rc;
+    return fit_batch_nd_loo_grad(family, d, nbatch, n_pts, X, z, hyp, nhyp, sig2n, which, alpha, nll, value, grad, info);
+}
+
 /* sgpr_fit_batch plus the gradient of every problem's nll (batch.hip: the gradient mode of fit_batch_kernel). */
 int sgpr_fit_batch_grad(int family, int nbatch, int n_pts, const double *x, const double *y, const double *z,
                         const double *hyp, int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll,

@@ -293,6 +293,13 @@ int fit_batch_nd(int family, int d, int nbatch, int npts, const double *X, const
 // d-pair fit; both paths (the one-launch kernel in its gradient mode, the mid path with mid_grad_nd_kernel)
 int fit_batch_nd_grad(int family, int d, int nbatch, int npts, const double *X, const double *z, const double *hyp, int nhyp,
                       const double *sig2n, double *alpha, double *nll, double *grad, int *info);
+// the same plus leave-one-point-out cross-validation over 2d x 2d point blocks: loo is nbatch x 2, row b = {loo, press}; both paths
+int fit_batch_nd_loo(int family, int d, int nbatch, int npts, const double *X, const double *z, const double *hyp, int nhyp,
+                     const double *sig2n, double *alpha, double *nll, double *loo, int *info);
+// one of the two objectives (which: SGPR_LOO_LPD / SGPR_LOO_PRESS) and its gradient, n = 2 d npts <= fit_batch_grad_max_order(): value
+// is nbatch doubles, grad nbatch x (nhyp + 1) in fit_batch_nd_grad's order
+int fit_batch_nd_loo_grad(int family, int d, int nbatch, int npts, const double *X, const double *z, const double *hyp, int nhyp,
+                          const double *sig2n, int which, double *alpha, double *nll, double *value, double *grad, int *info);
 int fit_batch_grad_max_order();                  // 256: one workgroup holds the whole problem
 int fit_batch_grad(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
                    int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, double *grad, int *info);

@@ -643,13 +643,15 @@ extern "C" int sgpr_probe_gemm_strassen_top_dev(int m, int n, int k, double alph
 {
     return strassen_top_gemm(m, n, k, alpha, A, lda, B, ldb, beta, C, ldc, lower, nullptr, nullptr, static_cast<hipStream_t>(stream));
 }
-// ---- the arena layout of a batched fit (batch.hip: batch_layout), host arithmetic only: no device call
-extern "C" int sgpr_probe_batch_layout(int path, int mode, int d, int reg, int nbatch, int n_pts, int nhyp, unsigned long long out[24])
+// ---- the arena layout of a batched fit (batch.hip: batch_layout), host arithmetic only: no device call.  nd_loo: the d-pair loo
+// modes are allowed (sgpr_probe_batch_layout_nd_loo); sgpr_probe_batch_layout keeps refusing them, as its tests pin it
+static int probe_batch_layout(const char *entry, bool nd_loo, int path, int mode, int d, int reg, int nbatch, int n_pts, int nhyp,
+                              unsigned long long out[24])
 {
     const long n = d ? 2L * d * n_pts : reg ? (long)n_pts : 2L * n_pts;
-    if (path < 0 || path > 1 || mode < 0 || mode > 3 || (path && mode == 3) || d < 0 || d > 3 || (d && (reg || mode > 1)) || nbatch < 1 ||
-        n_pts < 1 || nhyp < 1 || (path ? n <= 256 || n > 2048 : n > 256) || !out) {
-        set_error("probe_batch_layout: bad arguments");
+    if (path < 0 || path > 1 || mode < 0 || mode > 3 || (path && mode == 3) || d < 0 || d > 3 || (d && (reg || (mode > 1 && !nd_loo))) ||
+        nbatch < 1 || n_pts < 1 || nhyp < 1 || (path ? n <= 256 || n > 2048 : n > 256) || !out) {
+        set_error(std::string(entry) + ": bad arguments");
         return SGPR_E_ARG;
     }
     const BatchLayout l = batch_layout(path, mode, d, reg, nbatch, n_pts, nhyp);
@@ -658,6 +660,18 @@ extern "C" int sgpr_probe_batch_layout(int path, int mode, int d, int reg, int n
                           sizeof(KConst), sizeof(nd::NdConst), l.flag_bytes};
     for (int i = 0; i < 24; ++i) out[i] = v[i];
     return 0;
+}
+extern "C" int sgpr_probe_batch_layout(int path, int mode, int d, int reg, int nbatch, int n_pts, int nhyp, unsigned long long out[24])
+{
+    return probe_batch_layout("probe_batch_layout", false, path, mode, d, reg, nbatch, n_pts, nhyp, out);
+}
+extern "C" int sgpr_probe_batch_layout_nd_loo(int path, int mode, int d, int nbatch, int n_pts, int nhyp, unsigned long long out[24])
+{
+    if (d < 1 || (mode != 2 && mode != 3)) {
+        set_error("probe_batch_layout_nd_loo: d is 1 .. 3 and mode 2 (loo) or 3 (loo gradient)");
+        return SGPR_E_ARG;
+    }
+    return probe_batch_layout("probe_batch_layout_nd_loo", true, path, mode, d, 0, nbatch, n_pts, nhyp, out);
 }
 extern "C" unsigned sgpr_probe_map_calls(void) { return applymap_last_calls(); }
 extern "C" int sgpr_probe_map_team(int ntest, int n0) { return applymap_team(ntest, n0); }

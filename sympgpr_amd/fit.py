@@ -498,6 +498,54 @@ def fit_batch_pairs_grad(family, X, z, hyp, sig2n, want_alpha=False):
     return alpha, nll, grad, info
 
 
+def fit_batch_pairs_loo(family, X, z, hyp, sig2n, want_alpha=False):
+    """fit_batch_pairs plus leave-one-point-out cross-validation of every problem (SympFit.pairs(...).loo()'s definitions: a point
+    owns its 2d rows), every order up to batch_max_order() on the device (sgpr_fit_batch_nd_loo): one launch up to order 256, the
+    mid path with its loo phase above.  Shapes and broadcasting as fit_batch_pairs.
+    -> (alpha (B, n) or None, nll (B,), loo (B, 2), info (B,)).  Row b of loo is (loo, press).  Rows with info > 0 are NaN (nll and
+    the loo row).  nll, alpha and info are the same bits fit_batch_pairs returns; a row's loo bits do not depend on the batch."""
+    lead, _keep, B, n, _ = _pairs_inputs("fit_batch_pairs_loo", family, X, z, hyp, sig2n)
+    loo = np.empty((B, 2))
+    alpha, nll, info = _batch_run("sgpr_fit_batch_nd_loo", lead, B, n, want_alpha, (loo,))
+    bad = info != 0
+    nll[bad] = np.nan
+    loo[bad] = np.nan
+    return alpha, nll, loo, info
+
+
+def fit_batch_pairs_loo_grad(family, X, z, hyp, sig2n, objective="loo", want_alpha=False):
+    """fit_batch_pairs plus one leave-one-point-out objective of every problem and its exact gradient in (hyp, sig2n):
+    objective="loo" (minus the summed log predictive densities) or "press" (the summed squared residuals),
+    SympFit.pairs(...).loo_grad's definitions.  Shapes and broadcasting as fit_batch_pairs.
+    -> (alpha (B, n) or None, nll (B,), value (B,), grad (B, nhyp + 1), info (B,)).  Row b of grad is in fit_batch_pairs_grad's
+    order; Ky holds |sig2n[b]|, so the last entry carries sign(sig2n[b]) (sign(0) = +1).  Rows with info > 0 are NaN (nll, value and
+    the whole gradient row).  nll, alpha and info are the same bits fit_batch_pairs returns, value the bits of
+    fit_batch_pairs_loo's column.
+    n <= 256: ONE launch (sgpr_fit_batch_nd_loo_grad), one workgroup per problem.
+    256 < n <= 2048 (the slow path): nll, alpha, info and value from one fit_batch_pairs_loo call, and the gradient of every
+    positive-definite row from SympFit.pairs(...).run().loo_grad(objective), one device-resident fit per row."""
+    if objective not in ("loo", "press"):
+        raise ValueError('fit_batch_pairs_loo_grad: objective is "loo" or "press"')
+    which = L.LOO_PRESS if objective == "press" else L.LOO_LPD
+    lead, keep, B, n, nhyp = _pairs_inputs("fit_batch_pairs_loo_grad", family, X, z, hyp, sig2n)
+    if n > batch_grad_max_order():
+        Xl, zl, hl, s2 = keep
+        alpha, nll, loo, info = fit_batch_pairs_loo(family, np.swapaxes(Xl, 1, 2), zl, hl, s2, want_alpha=want_alpha)
+        grad = np.full((B, nhyp + 1), np.nan)
+        for b in np.flatnonzero(info == 0):
+            with SympFit.pairs(family, Xl[b].T, zl[b], hl[b], s2[b]) as f:
+                grad[b] = f.run().loo_grad(objective)[1]
+        return alpha, nll, loo[:, which].copy(), grad, info
+    value = np.empty(B)
+    grad = np.empty((B, nhyp + 1))
+    alpha, nll, info = _batch_run("sgpr_fit_batch_nd_loo_grad", lead, B, n, want_alpha, (value, grad), which)
+    bad = info != 0
+    nll[bad] = np.nan
+    value[bad] = np.nan
+    grad[bad] = np.nan
+    return alpha, nll, value, grad, info
+
+
 def batch_grad_max_order():
     """largest matrix order per problem sgpr_fit_batch_grad takes on the device (256)"""
     return 256

@@ -251,6 +251,108 @@ def nll_chol_pairs_grad(hyp, X, z):
     return float(nll[0]), grad[0]
 
 
+def loo_chol_pairs_batch(hyps, X, z):
+    """loo_chol_batch for a fit with d canonical pairs per point: the leave-one-point-out objective (minus the summed log predictive
+    densities of each point's 2d rows given all other points, SympFit.pairs(...).loo()) for a whole population of hyper-parameter
+    vectors over one data set.  Arguments as nll_chol_pairs_batch.  Rows whose Ky is not positive definite come back as NaN, as in
+    loo_chol_batch.  Up to order fit.batch_max_order() (2048) one batched call (fit.fit_batch_pairs_loo); above it a loop over ONE
+    device-resident handle (set_hyp / run / loo)."""
+    from .fit import batch_max_order, fit_batch_pairs_loo
+    hyps, X, z, n = _pairs_check("loo_chol_pairs", hyps, X, z)
+    if n <= batch_max_order():
+        _, _, loo, info = fit_batch_pairs_loo(get_family(), X, z, hyps[:, :-1], np.abs(hyps[:, -1]))
+        out = loo[:, 0].copy()
+        out[info != 0] = np.nan
+        return out
+    out = np.empty(len(hyps))
+    if len(hyps) == 0:
+        return out
+    with SympFit.pairs(get_family(), X, z, hyps[0, :-1], np.abs(hyps[0, -1])) as f:
+        for b, h in enumerate(hyps):
+            try:
+                f.set_hyp(h[:-1], np.abs(h[-1]))
+                out[b] = f.run().loo(resid=False, lpd=False)["loo"]
+            except np.linalg.LinAlgError:
+                out[b] = np.nan
+    return out
+
+
+def loo_chol_pairs(hyp, X, z):
+    """loo_chol for a fit with d canonical pairs per point: one row of loo_chol_pairs_batch -- the cross-validation objective of
+    an optimiser over (lq.., lP.., [p..,] sig, sig2_n).  Raises LinAlgError where Ky is not positive definite, as loo_chol does."""
+    from .fit import batch_max_order, fit_batch_pairs_loo
+    hyp = np.asarray(hyp, dtype=np.float64)
+    if hyp.ndim != 1:
+        raise ValueError("loo_chol_pairs: hyp is one row (lq.., lP.., [p..,] sig, sig2_n)")
+    hyps, X, z, n = _pairs_check("loo_chol_pairs", hyp[None], X, z)
+    if n <= batch_max_order():
+        _, _, loo, info = fit_batch_pairs_loo(get_family(), X, z, hyps[:, :-1], np.abs(hyps[:, -1]))
+        if info[0]:
+            raise np.linalg.LinAlgError("%d-th leading minor of the array is not positive definite" % int(info[0]))
+        return float(loo[0, 0])
+    with SympFit.pairs(get_family(), X, z, hyp[:-1], np.abs(hyp[-1])) as f:
+        return f.run().loo(resid=False, lpd=False)["loo"]
+
+
+def loo_chol_pairs_grad_batch(hyps, X, z, objective="loo"):
+    """loo_chol_pairs_batch with gradients: hyps (B, nhyp + 1), rows (lq_1..lq_d, lP_1..lP_d, [p_1..p_d,] sig, sig2_n) -> (value
+    (B,), grad (B, nhyp + 1)), grad[b, k] = d value[b] / d hyps[b, k].  objective="press": the sum of squared leave-one-point-out
+    residuals instead.  The noise enters as |hyps[b, -1]|, so the last column carries its sign (sign(0) = +1).  Rows whose Ky is not
+    positive definite give NaN in the value and the whole gradient row, as in loo_chol_grad_batch.  Up to order 256 one launch
+    (fit.fit_batch_pairs_loo_grad); up to fit.batch_max_order() (2048) the values from one batched call and the gradients row by
+    row (that wrapper's slow path); above it a loop over ONE device-resident handle (set_hyp / run / loo_grad)."""
+    from .fit import batch_max_order, fit_batch_pairs_loo_grad
+    if objective not in ("loo", "press"):
+        raise ValueError('loo_chol_pairs_grad: objective is "loo" or "press"')
+    hyps, X, z, n = _pairs_check("loo_chol_pairs_grad", hyps, X, z)
+    sign = np.where(hyps[:, -1] < 0.0, -1.0, 1.0)
+    if n <= batch_max_order():
+        _, _, value, grad, info = fit_batch_pairs_loo_grad(get_family(), X, z, hyps[:, :-1], np.abs(hyps[:, -1]), objective=objective)
+        bad = info != 0
+        value[bad] = np.nan
+        grad[bad] = np.nan
+        grad[:, -1] *= sign
+        return value, grad
+    value = np.full(len(hyps), np.nan)
+    grad = np.full(hyps.shape, np.nan)
+    if len(hyps) == 0:
+        return value, grad
+    with SympFit.pairs(get_family(), X, z, hyps[0, :-1], np.abs(hyps[0, -1])) as f:
+        for b, h in enumerate(hyps):
+            try:
+                f.set_hyp(h[:-1], np.abs(h[-1]))
+                value[b], grad[b] = f.run().loo_grad(objective)
+                grad[b, -1] *= sign[b]
+            except np.linalg.LinAlgError:
+                value[b] = np.nan
+                grad[b] = np.nan
+    return value, grad
+
+
+def loo_chol_pairs_grad(hyp, X, z, objective="loo"):
+    """loo_chol_pairs and its exact gradient -> (value, grad), grad[k] = d value / d hyp[k] for every entry of hyp = (lq.., lP..,
+    [p..,] sig, sig2_n): the objective for scipy.optimize.minimize(..., jac=True) on the cross-validation objective of a fit with
+    d canonical pairs per point.  One row of loo_chol_pairs_grad_batch; raises LinAlgError where Ky is not positive definite."""
+    from .fit import batch_max_order, fit_batch_pairs_loo_grad
+    if objective not in ("loo", "press"):
+        raise ValueError('loo_chol_pairs_grad: objective is "loo" or "press"')
+    hyp = np.asarray(hyp, dtype=np.float64)
+    if hyp.ndim != 1:
+        raise ValueError("loo_chol_pairs_grad: hyp is one row (lq.., lP.., [p..,] sig, sig2_n)")
+    hyps, X, z, n = _pairs_check("loo_chol_pairs_grad", hyp[None], X, z)
+    sign = -1.0 if hyp[-1] < 0.0 else 1.0
+    if n <= batch_max_order():
+        _, _, value, grad, info = fit_batch_pairs_loo_grad(get_family(), X, z, hyps[:, :-1], np.abs(hyps[:, -1]), objective=objective)
+        if info[0]:
+            raise np.linalg.LinAlgError("%d-th leading minor of the array is not positive definite" % int(info[0]))
+        grad[0, -1] *= sign
+        return float(value[0]), grad[0]
+    with SympFit.pairs(get_family(), X, z, hyp[:-1], np.abs(hyp[-1])) as f:
+        value, grad = f.run().loo_grad(objective)
+        grad[-1] *= sign
+        return value, grad
+
+
 def _batch_data(x, y, N, reg):
     npts = N if reg else N // 2
     return x[0:npts], x[npts:2 * npts], y[:N if reg else 2 * npts]
