@@ -451,6 +451,28 @@ int sgpr_fit_batch_loo(int family, int nbatch, int n_pts, const double *x, const
 int sgpr_fit_batch_loo_grad(int family, int nbatch, int n_pts, const double *x, const double *y, const double *z,
                             const double *hyp, int nhyp, const double *sig2n, unsigned flags, int which, double *alpha,
                             double *nll, double *value, double *grad, int *info);
+/* sgpr_fit_batch_loo_grad for orders 256 < n <= sgpr_fit_batch_max_order() (2048): arguments, outputs, the sign of the last entry
+ * and the NaN rows exactly as there.  nll, alpha and info are bit-identical to sgpr_fit_batch's and value[b] to the `which` column of
+ * sgpr_fit_batch_loo's row b (the same code up to the sums); a problem's bits do not depend on its place in the batch, the batch
+ * size, the chunking or a repetition (no atomics, no waiting between workgroups).  Per chunk of problems, behind sgpr_fit_batch's mid
+ * path and the Ky^-1 stage of sgpr_fit_batch_grad_mid: one thread per point (sgpr_fit_batch_loo's pass, which also keeps the weight
+ * block W~_i and v), the mirror of Ky^-1 to full storage, beta = Ky^-1 v, Z = Ky^-1 W~ over the L^-T image, M = Ky^-1 Z^T (lower
+ * 128 x 128 tiles, n^3 flop per problem on the fp64 matrix cores) into a third npad x npad image, and sgpr_fit_batch_grad_mid's
+ * contraction with the weight M - beta alpha^T - alpha beta^T.  Scratch per chunk: three images per problem, at most ~2 GiB (21
+ * problems of order 2048), plus W~, v, beta and the partials, in the sgpr_fit_batch arena, kept until sgpr_trim.  SGPR_E_ARG (before any
+ * device call) for an order <= 256 or above the maximum (the message names the order and the limit), an unknown family, a wrong nhyp,
+ * an unknown flag, an unknown which, nbatch < 0, n_pts <= 0 and a null pointer other than alpha; nbatch == 0 returns 0.  ABI 5 (an
+ * additional entry point). */
+int sgpr_fit_batch_loo_grad_mid(int family, int nbatch, int n_pts, const double *x, const double *y, const double *z,
+                                const double *hyp, int nhyp, const double *sig2n, unsigned flags, int which, double *alpha,
+                                double *nll, double *value, double *grad, int *info);
+/* The same for problems with d canonical pairs per point: sgpr_fit_batch_nd_loo_grad for orders 256 < n = 2 d n_pts <=
+ * sgpr_fit_batch_max_order(), arguments and outputs as there, over 2d x 2d point blocks; nll, alpha and info are bit-identical to
+ * sgpr_fit_batch_nd's and value to column `which` of sgpr_fit_batch_nd_loo's.  SGPR_E_ARG as above, and for d outside 1..3 and
+ * flags != 0.  ABI 5 (an additional entry point). */
+int sgpr_fit_batch_nd_loo_grad_mid(int family, int d, int nbatch, int n_pts, const double *X, const double *z, const double *hyp,
+                                   int nhyp, const double *sig2n, unsigned flags, int which, double *alpha, double *nll,
+                                   double *value, double *grad, int *info);
 
 /* Gives back what the CALLING thread's earlier calls keep for re-use: the device arena and page-locked staging block of
  * sgpr_fit_batch and sgpr_fit_batch_grad (up to ~2 GiB after a large batch of order-2048 problems, ~1.3 GiB after a gradient batch

@@ -158,6 +158,11 @@ int sgpr_probe_batch_layout(int path, int mode, int d, int reg, int nbatch, int 
 /* The same for sgpr_fit_batch_nd_loo (mode 2, both paths) and sgpr_fit_batch_nd_loo_grad (mode 3, path 0 only), d = 1 .. 3: the modes
  * sgpr_probe_batch_layout refuses for d > 0.  out as above.  tests/test_batch_pairs_loo_cpu.py checks it against the formulas. */
 int sgpr_probe_batch_layout_nd_loo(int path, int mode, int d, int nbatch, int n_pts, int nhyp, unsigned long long out[24]);
+/* The mid path's layout for the loo gradient (sgpr_fit_batch_loo_grad_mid: d = 0, reg 0 or 1; sgpr_fit_batch_nd_loo_grad_mid: d = 1 .. 3,
+ * reg 0), which the two probes above refuse; 256 < order <= 2048.  out[0 .. 23] as above ([12] the L / U / M images); [24 .. 27] the
+ * regions behind the contraction's partials: the point pass's partials, W~, v, beta, and [28] the contraction's vector of zeros; [29] the padded order, [30] images per problem;
+ * [31] zero.  tests/test_batch_loo_grad_mid_cpu.py checks it against the formulas. */
+int sgpr_probe_batch_layout_loograd_mid(int d, int reg, int nbatch, int n_pts, int nhyp, unsigned long long out[32]);
 unsigned sgpr_probe_map_calls(void);
 int sgpr_probe_map_team(int ntest, int n0);
 

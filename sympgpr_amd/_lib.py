@@ -153,6 +153,10 @@ SIGNATURES = {
                                      C.POINTER(C.c_int)]),
     "sgpr_fit_batch_loo_grad": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_uint, C.c_int, _dp,
                                           _dp, _dp, _dp, C.POINTER(C.c_int)]),
+    "sgpr_fit_batch_loo_grad_mid": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, C.c_int, _dp, C.c_uint, C.c_int, _dp,
+                                              _dp, _dp, _dp, C.POINTER(C.c_int)]),
+    "sgpr_fit_batch_nd_loo_grad_mid": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, C.c_int, _dp, C.c_uint, C.c_int,
+                                                 _dp, _dp, _dp, _dp, C.POINTER(C.c_int)]),
 }
 
 # include/sympgpr_probe.h: measurement aids in their own library (never loaded by a product path)
@@ -208,6 +212,7 @@ PROBE_SIGNATURES = {
     "sgpr_probe_batch_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.POINTER(C.c_ulonglong)]),
     "sgpr_probe_batch_layout_nd_loo": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]),
+    "sgpr_probe_batch_layout_loograd_mid": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]),
     "sgpr_probe_census": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint), C.c_int,
                                     C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint), C.c_int,
                                     C.POINTER(C.c_ulonglong)]),

@@ -17,7 +17,8 @@
 // Ky^-1 stage of the d = 1 gradient and a contraction over D x D blocks of point pairs: contract_rows_nd / mid_grad_nd_kernel.
 // Their leave-one-point-out sums (sgpr_fit_batch_nd_loo) take one thread per point behind the same Ky^-1 stage, with D x D blocks
 // (loo_point_nd; mid_loo_kernel<D> above order 256), and the gradient of one of them (sgpr_fit_batch_nd_loo_grad, orders up to 256)
-// the phases (L1) - (L4) of the d = 1 loo gradient over those blocks (grad_problem_nd).
+// the phases (L1) - (L4) of the d = 1 loo gradient over those blocks (grad_problem_nd); above order 256 both layouts take the mid
+// path's loo gradient stage (sgpr_fit_batch_loo_grad_mid, sgpr_fit_batch_nd_loo_grad_mid: mid_loograd).
 // The device code is in batch_small.h (n <= 256) and batch_mid.h (256 < n <= 2048), included here and only here: one translation
 // unit.  This file holds the arena, its one layout function, the staging of a call and the two host drivers.
 #include <cmath>
@@ -206,9 +207,9 @@ BatchLayout batch_layout(int mid, int mode, int d, int reg, int nbatch, int npts
         l.ggy = (npts + GCJ - 1) / GCJ;
         l.lnwg = (npts + GT - 1) / GT;
         img = (size_t)l.npad * l.npad * 8;
-        nimg = kinv ? 2 : 1;
-        // at most ~2 GiB of images per chunk (64 problems of order 2048, 32 with the gradient's second image: 2 x 32 MiB each; round 3:
-        // 6 GiB), at least one chip-full of strips (256 workgroups)
+        nimg = mode == MODE_LOOGRAD ? 3 : kinv ? 2 : 1;
+        // at most ~2 GiB of images per chunk (64 problems of order 2048, 32 with the gradient's second image: 2 x 32 MiB each, 21 with
+        // the loo gradient's third; round 3: 6 GiB), at least one chip-full of strips (256 workgroups)
         l.chunk = (int)std::min<size_t>((size_t)nbatch, std::max<size_t>((256 + l.W - 1) / l.W, (2ull << 30) / (nimg * img)));
         if (l.chunk > 16384) l.chunk = 16384;      // grid.z of the build launch
         if (kinv) {                                // tunable "batch_gradmid_chunk" > 0 caps it (tests: several chunks of few problems)
@@ -247,7 +248,19 @@ BatchLayout batch_layout(int mid, int mode, int d, int reg, int nbatch, int npts
     l.o_st = l.o_pub + up256(2 * C * l.npad * 8);
     l.o_part = l.o_st + up256(C * 8 * sizeof(int));
     // (GPART doubles per partial; GPART_ND for d > 0, whose sums number up to 11)
-    l.scr_bytes = l.o_part + (mode == MODE_GRAD ? up256(C * l.ggx * l.ggy * (d ? GPART_ND : GPART) * 8) : mode == MODE_LOO ? up256(C * l.lnwg * 2 * 8) : 0);
+    const size_t gpart_bytes = up256(C * l.ggx * l.ggy * (d ? GPART_ND : GPART) * 8), lpart_bytes = up256(C * l.lnwg * 2 * 8);
+    l.scr_bytes = l.o_part + (mode == MODE_GRAD ? gpart_bytes : mode == MODE_LOO ? lpart_bytes : 0);
+    if (mode == MODE_LOOGRAD) {
+        // the loo gradient: both sets of partials, then per problem W~ (T = D (D + 1) / 2 doubles per point, D the rows per point),
+        // v, beta and a vector of zeros (npad doubles each)
+        const size_t D = d ? 2 * (size_t)d : reg ? 1 : 2;
+        l.o_lpart = l.o_part + gpart_bytes;
+        l.o_wt = l.o_lpart + lpart_bytes;
+        l.o_v = l.o_wt + up256(C * (D * (D + 1) / 2) * npts * 8);
+        l.o_beta = l.o_v + up256(C * l.npad * 8);
+        l.o_zero = l.o_beta + up256(C * l.npad * 8);
+        l.scr_bytes = l.o_zero + up256(C * l.npad * 8);
+    }
     return l;
 }
 
@@ -311,17 +324,19 @@ int fit_batch_small(const BatchCall &c)
 // below on the stream, in this order.  With grad or loo (the Ky^-1 phase) a second image per problem (U = L^-T) stands behind the L
 // images, and the sums come back behind nll in the chunk's one device-to-host copy.  d > 0: X in place of x | y, one NdConst per
 // problem, mid_build_nd_kernel in place of mid_build_kernel and mid_grad_nd_kernel in place of mid_grad_kernel; the loo phase is
-// mid_loo_kernel at 2 d rows per point.  The mid path has no loo gradient, for any d.
+// mid_loo_kernel at 2 d rows per point.  The loo gradient (value and grad) takes a third image per problem behind the U images and
+// the stage mid_loograd in place of the two before it.
 
 // the device pointers of one chunk of nb problems
 struct MidChunk {
     int nb;
     MidArgs a;                            // the solves' kernels (and the d = 0 build)
-    double *A, *U, *inv;                  // L images, U images, leaf inverses
+    double *A, *U, *M, *inv;              // L images, U images, the loo gradient's M images, leaf inverses
     int *fl, *fl2;                        // the flags of the first and the second panel
     double *r, *pub;                      // right-hand sides / solutions, publication buffers
     int *state;
     double *part, *sums;                  // the partials; the sums behind nll
+    double *lpart, *wt, *v, *beta, *zero; // the loo gradient: the point pass's partials, W~, v, beta, zeros
     int *info;
     size_t stride, stride_inv;            // doubles per image, per problem's leaf inverses
 };
@@ -335,6 +350,7 @@ MidChunk mid_chunk(const BatchCall &c, const BatchLayout &l, const Blocks &m, in
     k.stride_inv = (size_t)l.W * LEAF * LEAF;
     k.A = at<double>(m.dscr, l.o_A);
     k.U = k.A + C * k.stride;
+    k.M = k.U + C * k.stride;
     k.inv = at<double>(m.dscr, l.o_inv);
     k.fl = at<int>(m.dscr, l.o_fl);
     k.fl2 = at<int>(m.dscr, l.o_fl2);
@@ -342,6 +358,11 @@ MidChunk mid_chunk(const BatchCall &c, const BatchLayout &l, const Blocks &m, in
     k.pub = at<double>(m.dscr, l.o_pub);
     k.state = at<int>(m.dscr, l.o_st);
     k.part = at<double>(m.dscr, l.o_part);
+    k.lpart = at<double>(m.dscr, l.o_lpart);
+    k.wt = at<double>(m.dscr, l.o_wt);
+    k.v = at<double>(m.dscr, l.o_v);
+    k.beta = at<double>(m.dscr, l.o_beta);
+    k.zero = at<double>(m.dscr, l.o_zero);
     k.sums = at<double>(m.dout, l.o_nll) + C;
     k.info = at<int>(m.dout, l.o_info);
     k.a = MidArgs{nb, c.npts, c.n, l.npad, c.reg, at<double>(m.din, l.o_x), at<double>(m.din, l.o_y), at<double>(m.din, l.o_z),
@@ -355,9 +376,10 @@ int mid_build(hipStream_t st, const BatchCall &c, const BatchLayout &l, const Mi
 {
     const size_t B = (size_t)k.nb, img = k.stride * 8;
     if (c.grad || c.loo) {
-        // both images, unconditionally: the zeros the gradient phase reads above L's diagonal, below U's and in the images of
-        // a problem whose factorisation stops early come from here (and the leaf inverses of such a problem are defined)
-        SGPR_HIP(hipMemsetAsync(k.A, 0, ((size_t)l.chunk + B) * img, st));
+        // both images (all three of the loo gradient), unconditionally: the zeros the gradient phase reads above L's diagonal, below
+        // U's and in the images of a problem whose factorisation stops early come from here (and the leaf inverses of such a
+        // problem are defined)
+        SGPR_HIP(hipMemsetAsync(k.A, 0, ((c.value ? 2 : 1) * (size_t)l.chunk + B) * img, st));
         SGPR_HIP(hipMemsetAsync(k.inv, 0, B * k.stride_inv * 8, st));
     } else if (l.npad != c.n) SGPR_HIP(hipMemsetAsync(k.A, 0, B * img, st));
     const dim3 grid((c.npts + MT - 1) / MT, (c.npts + MJ - 1) / MJ, k.nb);
@@ -480,6 +502,70 @@ int mid_grad(hipStream_t st, const BatchCall &c, const BatchLayout &l, const Mid
     return 0;
 }
 
+// The loo gradient behind Ky^-1, steps (p) - (c) of batch_mid.h: {loo, press} and the raw gradient sums of the objective c.which
+// behind nll
+int mid_loograd(hipStream_t st, const BatchCall &c, const BatchLayout &l, const MidChunk &k)
+{
+    const int D = c.d ? 2 * c.d : c.reg ? 1 : 2, W = l.W, npad = l.npad;
+    const size_t ld = (size_t)npad;
+    const unsigned nb = (unsigned)k.nb, rowb = (unsigned)((npad + GT - 1) / GT);
+    // (p) the point pass
+    const MidLooW lw{c.npts, c.n, l.lnwg, c.which, ld, k.A, k.r, k.lpart, k.wt, k.v};
+    const dim3 gp((unsigned)l.lnwg, 1, nb);
+    // (z) beta and Z: ZP points per workgroup, the padding columns behind them
+    const MidZ mz{c.npts, c.n, ld, k.A, k.wt, k.v, k.beta, k.U};
+    const dim3 gz(rowb, (unsigned)((c.npts + ZP - 1) / ZP + 1), nb);
+    auto point_pass = [&](auto dd) { hipLaunchKernelGGL(mid_loow_kernel<decltype(dd)::value>, gp, dim3(GT), 0, st, lw); };
+    auto z_pass = [&](auto dd) { hipLaunchKernelGGL(mid_z_kernel<decltype(dd)::value>, gz, dim3(GT), 0, st, mz); };
+    auto by_rows = [&](auto f) {
+        switch (D) {
+        case 1:  f(std::integral_constant<int, 1>()); break;
+        case 2:  f(std::integral_constant<int, 2>()); break;
+        case 4:  f(std::integral_constant<int, 4>()); break;
+        default: f(std::integral_constant<int, 6>()); break;
+        }
+    };
+    by_rows(point_pass);
+    SGPR_CHECK_LAUNCH();
+    // (m) the mirror
+    const int T64 = npad / MB;
+    hipLaunchKernelGGL(mid_mirror_kernel, dim3((unsigned)(T64 * (T64 + 1) / 2), nb), dim3(256), 0, st,
+                       MidInv{k.A, k.U, k.inv, k.stride, ld, k.stride_inv, W, 1});
+    SGPR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(mid_beta_kernel, dim3(rowb, nb), dim3(GT), 0, st, mz);
+    SGPR_CHECK_LAUNCH();
+    by_rows(z_pass);
+    SGPR_CHECK_LAUNCH();
+    // (M) M = Ky^-1 Z^T, lower tiles, into the third image
+    hipLaunchKernelGGL(mid_m_kernel, dim3((unsigned)(W * (W + 1) / 2), nb), dim3(256), 0, st, MidM{k.A, k.U, k.M, k.stride, ld, npad});
+    SGPR_CHECK_LAUNCH();
+    // (w) W' over M's lower triangle
+    hipLaunchKernelGGL(mid_wprime_kernel, dim3(rowb, (unsigned)((c.n + WC - 1) / WC), nb), dim3(GT), 0, st, MidWp{c.n, ld, k.r, k.beta, k.M});
+    SGPR_CHECK_LAUNCH();
+    // (c) the contraction of W' with dK -- the nll gradient's kernels on the M image with zeros for alpha -- and the fold of both sets
+    // of partials
+    SGPR_HIP(hipMemsetAsync(k.zero, 0, (size_t)k.nb * ld * 8, st));
+    const MidGrad mg{c.npts, c.n, c.reg, l.ggx * l.ggy, (int)l.nacc, c.d ? GPART_ND : GPART, ld, k.a.x, k.a.y, k.a.kc, k.M, k.zero,
+                     k.part, k.info, k.sums};
+    const dim3 gg((unsigned)l.ggx, (unsigned)l.ggy, nb);
+    if (c.d) {
+        const MidGradNd mn{c.npts, c.n, mg.nwg, ld, k.a.x, reinterpret_cast<const nd::NdConst *>(k.a.kc), k.M, k.zero, k.part};
+        const int rc = nd::dispatch_nd(c.family, c.d, [&](auto fam, auto dd) {
+            hipLaunchKernelGGL((mid_grad_nd_kernel<decltype(fam)::value, decltype(dd)::value>), gg, dim3(GT), 0, st, mn);
+            return 0;
+        });
+        if (rc) return rc;
+    } else
+        (void)dispatch_family(c.family, [&](auto fam) {         // the family has been checked
+            hipLaunchKernelGGL(mid_grad_kernel<decltype(fam)::value>, gg, dim3(GT), 0, st, mg);
+            return 0;
+        });
+    SGPR_CHECK_LAUNCH();
+    hipLaunchKernelGGL(mid_loograd_fold_kernel, dim3(nb), dim3(64), 0, st, mg, (const double *)k.lpart, l.lnwg);
+    SGPR_CHECK_LAUNCH();
+    return 0;
+}
+
 int fit_batch_mid(const BatchCall &c)
 {
     const bool kinv = c.grad || c.loo;
@@ -497,7 +583,8 @@ int fit_batch_mid(const BatchCall &c)
         if ((rc = mid_solve(st, l, k))) return rc;
         if (kinv && (rc = mid_kinv(st, l, k))) return rc;
         if (c.loo && (rc = mid_loo(st, c, l, k))) return rc;
-        if (c.grad && (rc = mid_grad(st, c, l, k))) return rc;
+        if (c.value) { if ((rc = mid_loograd(st, c, l, k))) return rc; }
+        else if (c.grad && (rc = mid_grad(st, c, l, k))) return rc;
         if ((rc = fetch_out(c, l, m, b0, nb, st))) return rc;
         for (int b = 0; b < nb; ++b)
             if (c.info[b0 + b] < 0) return info_status(c.info[b0 + b]);     // a hand-off timed out: an error of the call
@@ -607,6 +694,27 @@ int fit_batch_loo_grad(int family, int nbatch, int npts, const double *x, const 
     c.value = value;
     c.which = which;
     return fit_batch_small(c);
+}
+
+// sgpr_fit_batch_loo_grad_mid: BMAX < n <= fit_batch_max_order()
+int fit_batch_loo_grad_mid(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
+                           int nhyp, const double *sig2n, unsigned flags, int which, double *alpha, double *nll, double *value,
+                           double *grad, int *info)
+{
+    BatchCall c = call_xy(family, nbatch, npts, x, y, z, hyp, nhyp, sig2n, flags, alpha, nll, info);
+    c.grad = grad;
+    c.value = value;
+    c.which = which;
+    return fit_batch_mid(c);
+}
+
+// sgpr_fit_batch_nd_loo_grad_mid: BMAX < n = 2 d npts <= fit_batch_max_order()
+int fit_batch_nd_loo_grad_mid(int family, int d, int nbatch, int npts, const double *X, const double *z, const double *hyp, int nhyp,
+                              const double *sig2n, int which, double *alpha, double *nll, double *value, double *grad, int *info)
+{
+    const BatchCall c{family, d, 0, nbatch, npts, 2 * d * npts, nhyp, X, nullptr, z, hyp, sig2n, alpha, nll, info,
+                      grad, nullptr, value, which};
+    return fit_batch_mid(c);
 }
 
 }  // namespace sgpr

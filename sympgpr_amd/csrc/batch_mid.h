@@ -1,5 +1,5 @@
 // batch_mid.h -- device code of the batched fits of order 256 < n <= 2048: build, the rank-k update between two panels, the
-// solves' ends, and the Ky^-1, gradient and leave-one-point-out phases.  Included only by batch.hip, behind batch_small.h.
+// solves' ends, and the Ky^-1, gradient, leave-one-point-out and loo gradient phases.  Included only by batch.hip, behind batch_small.h.
 #pragma once
 
 namespace sgpr {
@@ -490,6 +490,228 @@ __global__ __launch_bounds__(64) void mid_loo_fold_kernel(const MidLoo a)
     double v = 0.0;
     for (int w = 0; w < a.nwg; ++w) v += p[(size_t)w * 2];
     a.out[(size_t)b * 2 + k] = a.info[b] != 0 ? __builtin_nan("") : (k == 0 ? -v : v);
+}
+
+// ---- the gradient of one leave-one-point-out objective of the mid-size problems (sgpr_fit_batch_loo_grad_mid): behind step (b) -----
+// The formulas of loograd.hip and of grad_problem's phases (L1) - (L4), every step a grid over all problems of the chunk, ordered
+// by the stream alone; a third npad x npad image per problem (M) stands behind the U images.
+//   (p) the point pass (mid_loow_kernel): mid_loo_kernel's statements, so {loo, press} have its bits, and per point the weight block
+//       W~_i (packed lower, T = D (D + 1) / 2 doubles, entry t of point i at wt[t N + i]) and v[B_i] (npad doubles, zero in the padding):
+//       loo  W~_i = r r^T + S, v = r;   press  W~_i = 2 (r s^T + s r^T), v = 2 s, s = S r;
+//   (m) the mirror (mid_mirror_kernel): Ky^-1's lower triangle into the strict upper one of its image, 64 x 64 blocks through LDS;
+//   (z) beta = Ky^-1 v (mid_beta_kernel, n^2 flop) and Z = Ky^-1 W~ over the U image, dead after (b) (mid_z_kernel): column c N + i of
+//       Z is sum_e W~_i[e, c] (column e N + i of Ky^-1); the whole npad x npad image is written, zeros in the padding rows and columns;
+//   (M) M = Ky^-1 Z^T, lower 128 x 128 tiles, k over npad (mid_m_kernel): n^3 flop per problem on the matrix cores;
+//   (w) W' = M - beta alpha^T - alpha beta^T over M's lower triangle (mid_wprime_kernel, the expression of grad_problem's (L3));
+//   (c) the contraction of W' with dK by the nll gradient's own instances, mid_grad_kernel / mid_grad_nd_kernel, handed the M image
+//       for Ky^-1 and a vector of zeros for alpha (their weight K[i, j] - alpha_i alpha_j is then W'[i, j] - 0, exactly): no second
+//       set of contraction instances, and the existing ones keep their code; then one fold of both sets of partials
+//       (mid_loograd_fold_kernel): {loo, press, raw sums}.
+// A point whose block has a pivot that is not positive and finite has NaN in W~_i: D columns of Z, so all of M, so every sum.
+struct MidLooW {
+    int npts, n, nwg, which;              // which: SGPR_LOO_LPD / SGPR_LOO_PRESS, the same for the launch
+    size_t ld;                            // npad: Ky^-1 (lower) of problem b at K + b ld^2, its alpha at alpha + b ld
+    const double *K, *alpha;
+    double *part;                         // as MidLoo::part
+    double *wt, *v;                       // problem b's W~ at wt + b T npts, its v at v + b ld
+};
+
+template <int D>
+__global__ __launch_bounds__(GT) void mid_loow_kernel(const MidLooW a)
+{
+    constexpr int T = D * (D + 1) / 2;
+    __shared__ double red[GT / 64][2];
+    const int b = blockIdx.z, N = a.npts, tid = threadIdx.x, i = blockIdx.x * GT + tid;
+    const double *K = a.K + (size_t)b * a.ld * a.ld, *al = a.alpha + (size_t)b * a.ld;
+    double *wt = a.wt + (size_t)b * T * N, *v = a.v + (size_t)b * a.ld;
+    if (blockIdx.x == 0)
+        for (int r = a.n + tid; r < (int)a.ld; r += GT) v[r] = 0.0;
+    double lv[2] = {0.0, 0.0};
+    if (i < N) {
+        double r[D], S[T], lpd, rr;
+        loo_point_nd<D>(K, a.ld, al, i, N, r, S, lpd, rr);
+        lv[0] = lpd; lv[1] = rr;
+        if (a.which == SGPR_LOO_PRESS) {
+            double sr[D];                                 // s = S r
+#pragma unroll
+            for (int e = 0; e < D; ++e) {
+                double acc = S[loo::pk(e, 0)] * r[0];
+#pragma unroll
+                for (int c = 1; c < D; ++c) acc = __builtin_fma(S[c <= e ? loo::pk(e, c) : loo::pk(c, e)], r[c], acc);
+                sr[e] = acc;
+            }
+#pragma unroll
+            for (int e = 0; e < D; ++e) {
+#pragma unroll
+                for (int c = 0; c <= e; ++c) wt[(size_t)loo::pk(e, c) * N + i] = 2.0 * __builtin_fma(r[e], sr[c], sr[e] * r[c]);
+                v[e * N + i] = 2.0 * sr[e];
+            }
+        } else {
+#pragma unroll
+            for (int e = 0; e < D; ++e) {
+#pragma unroll
+                for (int c = 0; c <= e; ++c) wt[(size_t)loo::pk(e, c) * N + i] = __builtin_fma(r[e], r[c], S[loo::pk(e, c)]);
+                v[e * N + i] = r[e];
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const double s = wave_sum(lv[k]);
+        if ((tid & 63) == 0) red[tid >> 6][k] = s;
+    }
+    __syncthreads();
+    if (tid < 2) {
+        double s = red[0][tid];
+#pragma unroll
+        for (int w = 1; w < GT / 64; ++w) s += red[w][tid];
+        a.part[((size_t)b * a.nwg + blockIdx.x) * 2 + tid] = s;
+    }
+}
+
+constexpr int MB = 64;                    // mirror: block side
+
+// 64 x 64 block (r, t), r >= t, of problem blockIdx.y's Ky^-1 into block (t, r), transposed; a diagonal block: its strict upper part
+__global__ __launch_bounds__(256) void mid_mirror_kernel(const MidInv a)
+{
+    __shared__ double s[MB][MB + 1];
+    int t = (int)blockIdx.x, r = 0;            // lower blocks row by row, as mid_syrk_kernel
+    while (t > r) { t -= r + 1; ++r; }
+    double *K = a.L + (size_t)blockIdx.y * a.stride;
+    const size_t ld = a.ld, r0 = (size_t)r * MB, c0 = (size_t)t * MB;
+    for (int e = threadIdx.x; e < MB * MB; e += 256) {
+        const int i = e % MB, j = e / MB;
+        s[j][i] = K[(r0 + i) + (c0 + j) * ld];
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < MB * MB; e += 256) {
+        const int i = e % MB, j = e / MB;                 // entry (c0 + i, r0 + j) = entry (r0 + j, c0 + i)
+        if (r != t || i < j) K[(c0 + i) + (r0 + j) * ld] = s[i][j];
+    }
+}
+
+constexpr int ZP = 32;                    // Z: points per workgroup
+
+struct MidZ {
+    int npts, n;
+    size_t ld;                            // npad: Ky^-1 (full) of problem b at K + b ld^2, Z at Z + b ld^2, v and beta at + b ld
+    const double *K, *wt, *v;
+    double *beta, *Z;
+};
+
+// row blockIdx.x GT + tid of beta = Ky^-1 v of problem blockIdx.y, the columns in order; zero in the padding
+__global__ __launch_bounds__(GT) void mid_beta_kernel(const MidZ a)
+{
+    const int b = blockIdx.y, r = blockIdx.x * GT + threadIdx.x;
+    if (r >= (int)a.ld) return;
+    const double *K = a.K + (size_t)b * a.ld * a.ld + r, *v = a.v + (size_t)b * a.ld;
+    double acc = 0.0;
+    for (int k = 0; k < a.n; ++k) acc = __builtin_fma(K[(size_t)k * a.ld], v[k], acc);
+    a.beta[(size_t)b * a.ld + r] = r < a.n ? acc : 0.0;
+}
+
+// rows blockIdx.x GT .. + GT (one per thread) x the D columns of each of the points blockIdx.y ZP .. + ZP of problem blockIdx.z's Z; the
+// last blockIdx.y: the padding columns.  Rows below n only; the padding rows are zeros.
+template <int D>
+__global__ __launch_bounds__(GT) void mid_z_kernel(const MidZ a)
+{
+    constexpr int T = D * (D + 1) / 2;
+    __shared__ double sw[T][ZP];
+    const int b = blockIdx.z, N = a.npts, n = a.n, tid = threadIdx.x, r = blockIdx.x * GT + tid;
+    const size_t ld = a.ld;
+    const double *K = a.K + (size_t)b * ld * ld;
+    double *Z = a.Z + (size_t)b * ld * ld;
+    if (blockIdx.y == gridDim.y - 1) {
+        if (r < (int)ld)
+            for (int col = n; col < (int)ld; ++col) Z[r + (size_t)col * ld] = 0.0;
+        return;
+    }
+    const int p0 = blockIdx.y * ZP, np = min(ZP, N - p0);
+    for (int e = tid; e < T * np; e += GT) sw[e / np][e % np] = a.wt[(size_t)b * T * N + (size_t)(e / np) * N + p0 + e % np];
+    __syncthreads();
+    if (r >= (int)ld) return;
+    for (int jj = 0; jj < np; ++jj) {
+        const int i = p0 + jj;
+        double kc[D];
+#pragma unroll
+        for (int e = 0; e < D; ++e) kc[e] = K[r + ((size_t)e * N + i) * ld];
+#pragma unroll
+        for (int c = 0; c < D; ++c) {
+            double z = sw[loo::pk(D - 1, c)][jj] * kc[D - 1];
+#pragma unroll
+            for (int e = D - 2; e >= 0; --e) z = __builtin_fma(sw[e >= c ? loo::pk(e, c) : loo::pk(c, e)][jj], kc[e], z);
+            Z[r + ((size_t)c * N + i) * ld] = r < n ? z : 0.0;
+        }
+    }
+}
+
+struct MidM {
+    const double *K, *Z;  // problem b's Ky^-1 (full) and Z at + b * stride (column-major, ld)
+    double *M;
+    size_t stride, ld;
+    int k;                // npad
+};
+
+__global__ __launch_bounds__(256, 2) void mid_m_kernel(const MidM a)
+{
+    __shared__ double smem[2 * tile::BK * (2 * (128 + tile::PAD))];
+    int t = (int)blockIdx.x, r = 0;            // lower tiles row by row, as mid_syrk_kernel
+    while (t > r) { t -= r + 1; ++r; }
+    const size_t off = (size_t)blockIdx.y * a.stride, ld = a.ld, ri = (size_t)r * LEAF, cj = (size_t)t * LEAF;
+    tile::GemmArgs g{};
+    g.m = 128; g.n = 128; g.k = a.k;
+    g.alpha = 1.0; g.beta = 0.0;
+    g.A = a.K + off + ri; g.lda = ld;          // M[i, j] = sum_k Ky^-1[i, k] Z[j, k]
+    g.B = a.Z + off + cj; g.ldb = ld;
+    g.C = a.M + off + ri + cj * ld; g.ldc = ld;
+    tile::gemm_body_dma<128, 128, 2>(g, smem, 0, 0);
+}
+
+constexpr int WC = 64;                    // W': columns per workgroup
+
+struct MidWp {
+    int n;
+    size_t ld;                            // npad: M of problem b at M + b ld^2, alpha and beta at + b ld
+    const double *alpha, *beta;
+    double *M;
+};
+
+// rows blockIdx.x GT .. + GT (one per thread) x columns blockIdx.y WC .. + WC of problem blockIdx.z, on and below the diagonal, below n
+__global__ __launch_bounds__(GT) void mid_wprime_kernel(const MidWp a)
+{
+    __shared__ double sal[WC], sbe[WC];
+    const int b = blockIdx.z, tid = threadIdx.x, i = blockIdx.x * GT + tid, j0 = blockIdx.y * WC, nj = min(WC, a.n - j0);
+    if ((int)(blockIdx.x * GT + GT - 1) < j0) return;     // the whole tile is above the diagonal
+    const double *al = a.alpha + (size_t)b * a.ld, *be = a.beta + (size_t)b * a.ld;
+    if (tid < nj) { sal[tid] = al[j0 + tid]; sbe[tid] = be[j0 + tid]; }
+    __syncthreads();
+    if (i >= a.n) return;
+    double *Mrow = a.M + (size_t)b * a.ld * a.ld + i;
+    const double bi = be[i], ali = al[i];
+    for (int jj = 0; jj < nj; ++jj) {
+        const int j = j0 + jj;
+        if (j > i) break;
+        Mrow[(size_t)j * a.ld] = Mrow[(size_t)j * a.ld] - bi * sal[jj] - ali * sbe[jj];
+    }
+}
+
+// problem blockIdx.x: {loo, press} from the point pass's partials (mid_loo_fold_kernel's order and signs) and, behind them, the raw
+// gradient sums from the contraction's (mid_grad_fold_kernel's order), nacc = 2 + the number of sums apart; NaN where the
+// factorisation failed
+__global__ __launch_bounds__(64) void mid_loograd_fold_kernel(const MidGrad a, const double *lpart, int lnwg)
+{
+    const int b = blockIdx.x, k = threadIdx.x;
+    if (k >= a.nacc) return;
+    double v = 0.0;
+    if (k < 2) {
+        const double *p = lpart + (size_t)b * lnwg * 2 + k;
+        for (int w = 0; w < lnwg; ++w) v += p[(size_t)w * 2];
+        if (k == 0) v = -v;
+    } else {
+        const double *p = a.part + (size_t)b * a.nwg * a.gpart + (k - 2);
+        for (int w = 0; w < a.nwg; ++w) v += p[(size_t)w * a.gpart];
+    }
+    a.out[(size_t)b * a.nacc + k] = a.info[b] != 0 ? __builtin_nan("") : v;
 }
 
 }  // namespace

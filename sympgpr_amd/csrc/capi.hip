@@ -334,7 +334,7 @@ static int check_batch_args(const char *entry, int family, const int *d, int nhy
     if (nbatch < 0) return E("nbatch < 0");
     if (n_pts <= 0) return E("n_pts <= 0");
     const long n = d ? 2L * *d * n_pts : (flags & SGPR_FIT_REG) ? (long)n_pts : 2L * n_pts;
-    if (n <= nmin) return E("order per problem " + std::to_string(n) + " is at most " + std::to_string(nmin) + ": sgpr_fit_batch_grad's range");
+    if (n <= nmin) return E("order per problem " + std::to_string(n) + " is at most " + std::to_string(nmin) + ": the one-launch entry's range");
     if (n > nmax) return E("order per problem " + std::to_string(n) + " exceeds " + std::to_string(nmax));
     if (!outs_ok) return E(std::string("null ") + outs);
     if (!ins_ok) return E("null input");
@@ -438,6 +438,30 @@ int sgpr_fit_batch_loo_grad(int family, int nbatch, int n_pts, const double *x, 
     if (rc || nbatch == 0) return rc;
     if ((rc = need_device())) return rc;
     return fit_batch_loo_grad(family, nbatch, n_pts, x, y, z, hyp, nhyp, sig2n, flags, which, alpha, nll, value, grad, info);
+}
+
+/* The same above order 256, up to sgpr_fit_batch_max_order() (batch.hip: the mid path with its loo gradient stage). */
+int sgpr_fit_batch_loo_grad_mid(int family, int nbatch, int n_pts, const double *x, const double *y, const double *z,
+                                const double *hyp, int nhyp, const double *sig2n, unsigned flags, int which, double *alpha,
+                                double *nll, double *value, double *grad, int *info)
+{
+    int rc = check_batch_args("fit_batch_loo_grad_mid", family, nullptr, nhyp, flags, &which, nbatch, n_pts, fit_batch_grad_max_order(),
+                              fit_batch_max_order(), "nll, value, grad or info", nll && value && grad && info, x && y && z && hyp && sig2n);
+    if (rc || nbatch == 0) return rc;
+    if ((rc = need_device())) return rc;
+    return fit_batch_loo_grad_mid(family, nbatch, n_pts, x, y, z, hyp, nhyp, sig2n, flags, which, alpha, nll, value, grad, info);
+}
+
+/* sgpr_fit_batch_nd_loo_grad above order 256, up to sgpr_fit_batch_max_order() (batch.hip: the same stage over 2d x 2d point blocks). */
+int sgpr_fit_batch_nd_loo_grad_mid(int family, int d, int nbatch, int n_pts, const double *X, const double *z, const double *hyp,
+                                   int nhyp, const double *sig2n, unsigned flags, int which, double *alpha, double *nll,
+                                   double *value, double *grad, int *info)
+{
+    int rc = check_batch_args("fit_batch_nd_loo_grad_mid", family, &d, nhyp, flags, &which, nbatch, n_pts, fit_batch_grad_max_order(),
+                              fit_batch_max_order(), "nll, value, grad or info", nll && value && grad && info, X && z && hyp && sig2n);
+    if (rc || nbatch == 0) return rc;
+    if ((rc = need_device())) return rc;
+    return fit_batch_nd_loo_grad_mid(family, d, nbatch, n_pts, X, z, hyp, nhyp, sig2n, which, alpha, nll, value, grad, info);
 }
 
 /* applymap / applymap_henon (functions/func.py:216-260) and the per-example variants for all Ntest

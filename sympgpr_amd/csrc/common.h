@@ -281,6 +281,7 @@ struct BatchLayout {
     size_t o_x, o_y, o_z, o_kc, o_no, in_bytes;      // x | y | z | consts | noise
     size_t o_al, o_nll, o_info, out_bytes;           // alpha | nll [+ sums] | info
     size_t o_A, o_inv, o_fl, o_fl2, o_r, o_pub, o_st, o_part, scr_bytes;     // mid path's scratch regions; the total of either path
+    size_t o_lpart, o_wt, o_v, o_beta, o_zero;       // mid path's loo gradient: the point pass's partials, W~, v, beta, zeros (behind o_part)
 };
 BatchLayout batch_layout(int mid, int mode, int d, int reg, int nbatch, int npts, int nhyp);
 int fit_batch(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
@@ -315,6 +316,13 @@ int fit_batch_loo(int family, int nbatch, int npts, const double *x, const doubl
 int fit_batch_loo_grad(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
                        int nhyp, const double *sig2n, unsigned flags, int which, double *alpha, double *nll, double *value,
                        double *grad, int *info);
+// the same for 256 < order <= fit_batch_max_order(), x | y points and d canonical pairs per point: the mid path with its Ky^-1 phase,
+// then M = Ky^-1 W~ Ky^-1 per problem on the matrix cores in a third image (batch_mid.h)
+int fit_batch_loo_grad_mid(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
+                           int nhyp, const double *sig2n, unsigned flags, int which, double *alpha, double *nll, double *value,
+                           double *grad, int *info);
+int fit_batch_nd_loo_grad_mid(int family, int d, int nbatch, int npts, const double *X, const double *z, const double *hyp, int nhyp,
+                              const double *sig2n, int which, double *alpha, double *nll, double *value, double *grad, int *info);
 
 // ---- blas_small.hip
 int zero_strict_upper(int n, double *A, size_t lda, hipStream_t st);

@@ -673,6 +673,20 @@ extern "C" int sgpr_probe_batch_layout_nd_loo(int path, int mode, int d, int nba
     }
     return probe_batch_layout("probe_batch_layout_nd_loo", true, path, mode, d, 0, nbatch, n_pts, nhyp, out);
 }
+extern "C" int sgpr_probe_batch_layout_loograd_mid(int d, int reg, int nbatch, int n_pts, int nhyp, unsigned long long out[32])
+{
+    const long n = d ? 2L * d * n_pts : reg ? (long)n_pts : 2L * n_pts;
+    if (d < 0 || d > 3 || reg < 0 || reg > 1 || (d && reg) || nbatch < 1 || n_pts < 1 || nhyp < 1 || n <= 256 || n > 2048 || !out) {
+        set_error("probe_batch_layout_loograd_mid: bad arguments (256 < order <= 2048)");
+        return SGPR_E_ARG;
+    }
+    const BatchLayout l = batch_layout(1, 3, d, reg, nbatch, n_pts, nhyp);
+    const size_t v[32] = {(size_t)l.chunk, l.nacc, l.o_x, l.o_y, l.o_z, l.o_kc, l.o_no, l.in_bytes, l.o_al, l.o_nll, l.o_info, l.out_bytes,
+                          l.o_A, l.o_inv, l.o_fl, l.o_fl2, l.o_r, l.o_pub, l.o_st, l.o_part, l.scr_bytes,
+                          sizeof(KConst), sizeof(nd::NdConst), l.flag_bytes, l.o_lpart, l.o_wt, l.o_v, l.o_beta, l.o_zero, (size_t)l.npad, 3, 0};
+    for (int i = 0; i < 32; ++i) out[i] = v[i];
+    return 0;
+}
 extern "C" unsigned sgpr_probe_map_calls(void) { return applymap_last_calls(); }
 extern "C" int sgpr_probe_map_team(int ntest, int n0) { return applymap_team(ntest, n0); }
 extern "C" int sgpr_probe_trsm_piece(int ticket, int cap, int strips, int out[5]) { if (ticket < 0 || cap < 1 || strips < 0 || !out) return SGPR_E_ARG; trsm_piece_of(ticket, cap, strips, out); return 0; }

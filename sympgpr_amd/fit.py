@@ -523,7 +523,8 @@ def fit_batch_pairs_loo_grad(family, X, z, hyp, sig2n, objective="loo", want_alp
     fit_batch_pairs_loo's column.
     n <= 256: ONE launch (sgpr_fit_batch_nd_loo_grad), one workgroup per problem.
     256 < n <= 2048 (the slow path): nll, alpha, info and value from one fit_batch_pairs_loo call, and the gradient of every
-    positive-definite row from SympFit.pairs(...).run().loo_grad(objective), one device-resident fit per row."""
+    positive-definite row from SympFit.pairs(...).run().loo_grad(objective), one device-resident fit per row.  Every gradient of
+    that range on the device: fit_batch_pairs_loo_grad_mid."""
     if objective not in ("loo", "press"):
         raise ValueError('fit_batch_pairs_loo_grad: objective is "loo" or "press"')
     which = L.LOO_PRESS if objective == "press" else L.LOO_LPD
@@ -539,6 +540,28 @@ def fit_batch_pairs_loo_grad(family, X, z, hyp, sig2n, objective="loo", want_alp
     value = np.empty(B)
     grad = np.empty((B, nhyp + 1))
     alpha, nll, info = _batch_run("sgpr_fit_batch_nd_loo_grad", lead, B, n, want_alpha, (value, grad), which)
+    bad = info != 0
+    nll[bad] = np.nan
+    value[bad] = np.nan
+    grad[bad] = np.nan
+    return alpha, nll, value, grad, info
+
+
+def fit_batch_pairs_loo_grad_mid(family, X, z, hyp, sig2n, objective="loo", want_alpha=False):
+    """fit_batch_pairs_loo_grad for 256 < n <= batch_max_order(), every gradient on the device (sgpr_fit_batch_nd_loo_grad_mid): shapes,
+    broadcasting, the returned (alpha or None, nll, value, grad, info) and the NaN rows for info > 0 as fit_batch_pairs_loo_grad; nll,
+    alpha and info are the bits fit_batch_pairs returns, value the bits of fit_batch_pairs_loo's column.  Per chunk of problems, behind
+    the mid path's Ky^-1 stage: one thread per point, M = Ky^-1 W~ Ky^-1 on the matrix cores, one contraction launch.  ValueError for
+    n <= 256: fit_batch_pairs_loo_grad serves that range in one launch."""
+    if objective not in ("loo", "press"):
+        raise ValueError('fit_batch_pairs_loo_grad_mid: objective is "loo" or "press"')
+    which = L.LOO_PRESS if objective == "press" else L.LOO_LPD
+    lead, _keep, B, n, nhyp = _pairs_inputs("fit_batch_pairs_loo_grad_mid", family, X, z, hyp, sig2n)
+    if n <= batch_grad_max_order():
+        raise ValueError("fit_batch_pairs_loo_grad_mid: order %d <= %d is fit_batch_pairs_loo_grad's range" % (n, batch_grad_max_order()))
+    value = np.empty(B)
+    grad = np.empty((B, nhyp + 1))
+    alpha, nll, info = _batch_run("sgpr_fit_batch_nd_loo_grad_mid", lead, B, n, want_alpha, (value, grad), which)
     bad = info != 0
     nll[bad] = np.nan
     value[bad] = np.nan
@@ -615,7 +638,8 @@ def fit_batch_loo_grad(family, x, y, z, hyp, sig2n, reg=False, objective="loo", 
     value the bits of fit_batch_loo's column.
     n <= 256: ONE launch (sgpr_fit_batch_loo_grad), one workgroup per problem.
     256 < n <= 2048 (the slow path): nll, alpha, info and value from one fit_batch_loo call, and the gradient of every
-    positive-definite row from SympFit(...).run().loo_grad(objective), one device-resident fit per row."""
+    positive-definite row from SympFit(...).run().loo_grad(objective), one device-resident fit per row.  Every gradient of that
+    range on the device: fit_batch_loo_grad_mid."""
     if objective not in ("loo", "press"):
         raise ValueError('fit_batch_loo_grad: objective is "loo" or "press"')
     which = L.LOO_PRESS if objective == "press" else L.LOO_LPD
@@ -631,5 +655,24 @@ def fit_batch_loo_grad(family, x, y, z, hyp, sig2n, reg=False, objective="loo", 
     value = np.empty(B)
     grad = np.empty((B, nhyp + 1))
     alpha, nll, info = _batch_run("sgpr_fit_batch_loo_grad", _batch_lead(family, arrays, B, n_pts, reg), B, n, want_alpha,
+                                  (value, grad), which)
+    return alpha, nll, value, grad, info
+
+
+def fit_batch_loo_grad_mid(family, x, y, z, hyp, sig2n, reg=False, objective="loo", want_alpha=False):
+    """fit_batch_loo_grad for 256 < n <= batch_grad_mid_max_order(), every gradient on the device (sgpr_fit_batch_loo_grad_mid): shapes,
+    the returned (alpha or None, nll, value, grad, info) and the NaN rows for info > 0 as fit_batch_loo_grad; nll, alpha and info are
+    the bits fit_batch returns, value the bits of fit_batch_loo's column.  Per chunk of problems, behind fit_batch_grad_mid's Ky^-1
+    stage: one thread per point, M = Ky^-1 W~ Ky^-1 on the matrix cores, one contraction launch.  ValueError for n <= 256:
+    fit_batch_loo_grad serves that range in one launch."""
+    if objective not in ("loo", "press"):
+        raise ValueError('fit_batch_loo_grad_mid: objective is "loo" or "press"')
+    which = L.LOO_PRESS if objective == "press" else L.LOO_LPD
+    arrays, B, n_pts, n, nhyp = _batch_inputs("fit_batch_loo_grad_mid", x, y, z, hyp, sig2n, reg)
+    if n <= batch_grad_max_order():
+        raise ValueError("fit_batch_loo_grad_mid: order %d <= %d is fit_batch_loo_grad's range" % (n, batch_grad_max_order()))
+    value = np.empty(B)
+    grad = np.empty((B, nhyp + 1))
+    alpha, nll, info = _batch_run("sgpr_fit_batch_loo_grad_mid", _batch_lead(family, arrays, B, n_pts, reg), B, n, want_alpha,
                                   (value, grad), which)
     return alpha, nll, value, grad, info

@@ -294,20 +294,26 @@ def loo_chol_pairs(hyp, X, z):
         return f.run().loo(resid=False, lpd=False)["loo"]
 
 
-def loo_chol_pairs_grad_batch(hyps, X, z, objective="loo"):
+def loo_chol_pairs_grad_batch(hyps, X, z, objective="loo", mid=None):
     """loo_chol_pairs_batch with gradients: hyps (B, nhyp + 1), rows (lq_1..lq_d, lP_1..lP_d, [p_1..p_d,] sig, sig2_n) -> (value
     (B,), grad (B, nhyp + 1)), grad[b, k] = d value[b] / d hyps[b, k].  objective="press": the sum of squared leave-one-point-out
     residuals instead.  The noise enters as |hyps[b, -1]|, so the last column carries its sign (sign(0) = +1).  Rows whose Ky is not
     positive definite give NaN in the value and the whole gradient row, as in loo_chol_grad_batch.  Up to order 256 one launch
     (fit.fit_batch_pairs_loo_grad); up to fit.batch_max_order() (2048) the values from one batched call and the gradients row by
-    row (that wrapper's slow path); above it a loop over ONE device-resident handle (set_hyp / run / loo_grad)."""
-    from .fit import batch_max_order, fit_batch_pairs_loo_grad
+    row (that wrapper's slow path); above it a loop over ONE device-resident handle (set_hyp / run / loo_grad).
+    mid="device": orders 256 < n <= 2048 go through fit.fit_batch_pairs_loo_grad_mid instead, every gradient on the device in a few
+    launches per chunk, with the same conventions (the gradients agree with the slow path to rounding, not bit for bit).  mid=None
+    (the default) is the behaviour described first."""
+    from .fit import batch_grad_max_order, batch_max_order, fit_batch_pairs_loo_grad, fit_batch_pairs_loo_grad_mid
     if objective not in ("loo", "press"):
         raise ValueError('loo_chol_pairs_grad: objective is "loo" or "press"')
+    if mid not in (None, "device"):
+        raise ValueError('loo_chol_pairs_grad_batch: mid is None or "device"')
     hyps, X, z, n = _pairs_check("loo_chol_pairs_grad", hyps, X, z)
     sign = np.where(hyps[:, -1] < 0.0, -1.0, 1.0)
     if n <= batch_max_order():
-        _, _, value, grad, info = fit_batch_pairs_loo_grad(get_family(), X, z, hyps[:, :-1], np.abs(hyps[:, -1]), objective=objective)
+        fn = fit_batch_pairs_loo_grad_mid if mid == "device" and n > batch_grad_max_order() else fit_batch_pairs_loo_grad
+        _, _, value, grad, info = fn(get_family(), X, z, hyps[:, :-1], np.abs(hyps[:, -1]), objective=objective)
         bad = info != 0
         value[bad] = np.nan
         grad[bad] = np.nan
@@ -490,15 +496,20 @@ def loo_chol_batch(hyps, x, y, N, reg=False):
     return loo[:, 0].copy()
 
 
-def loo_chol_grad_batch(hyps, x, y, N, reg=False, objective="loo"):
+def loo_chol_grad_batch(hyps, x, y, N, reg=False, objective="loo", mid=None):
     """loo_chol_batch with gradients: hyps (B, nhyp + 1) rows like loo_chol's hyp -> (value (B,), grad (B, nhyp + 1)), grad[b, k]
     = d value[b] / d hyps[b, k]; the last column is sig2_n, which enters as |hyps[b, -1]| and gives that entry its sign.
     objective="press": the sum of squared leave-one-point-out residuals instead.  Sliced and checked like nll_chol_grad_batch.
     Rows whose Ky is not positive definite give NaN in the value and the whole gradient row, as in loo_chol_batch.  Up to order
-    256 one launch (fit.fit_batch_loo_grad); above it the values from one fit_batch_loo call and the gradients row by row."""
-    from .fit import fit_batch_loo_grad
+    256 one launch (fit.fit_batch_loo_grad); above it the values from one fit_batch_loo call and the gradients row by row.
+    mid="device": orders 256 < N <= 2048 go through fit.fit_batch_loo_grad_mid instead, every gradient on the device in a few
+    launches per chunk, with the same conventions (the gradients agree with the slow path to rounding, not bit for bit).  mid=None
+    (the default) is the behaviour described first."""
+    from .fit import batch_grad_max_order, batch_grad_mid_max_order, fit_batch_loo_grad, fit_batch_loo_grad_mid
     if objective not in ("loo", "press"):
         raise ValueError('loo_chol_grad_batch: objective is "loo" or "press"')
+    if mid not in (None, "device"):
+        raise ValueError('loo_chol_grad_batch: mid is None or "device"')
     hyps = np.atleast_2d(np.asarray(hyps, dtype=np.float64))
     x = np.asarray(x, dtype=np.float64)
     y = np.asarray(y, dtype=np.float64)
@@ -510,9 +521,11 @@ def loo_chol_grad_batch(hyps, x, y, N, reg=False, objective="loo"):
     if len(X) != (N if reg else N // 2) or len(Y) != len(X) or len(Z) != (N if reg else 2 * len(X)):
         raise ValueError("loo_chol_grad_batch: x holds 2 * n_pts coordinates and y the n targets of order N")
     B = len(hyps)
-    _, _, value, grad, _ = fit_batch_loo_grad(get_family(), np.broadcast_to(X, (B, len(X))), np.broadcast_to(Y, (B, len(Y))),
-                                              np.broadcast_to(Z, (B, len(Z))), hyps[:, :-1], hyps[:, -1], reg=reg,
-                                              objective=objective)
+    fn = fit_batch_loo_grad
+    if mid == "device" and batch_grad_max_order() < N <= batch_grad_mid_max_order():
+        fn = fit_batch_loo_grad_mid
+    _, _, value, grad, _ = fn(get_family(), np.broadcast_to(X, (B, len(X))), np.broadcast_to(Y, (B, len(Y))),
+                              np.broadcast_to(Z, (B, len(Z))), hyps[:, :-1], hyps[:, -1], reg=reg, objective=objective)
     return value, grad
 
 
