@@ -368,8 +368,9 @@ __global__ __launch_bounds__(TT) void applymap_sections_kernel(const MapSecArgs 
 // workgroup per orbit.  Two members of DIFFERENT orbits per CU is the point: a residual is ~3.5 us of VALU work per CU and ~5 us
 // of reduction + exchange with the rest of the team, and with one 512-thread member per CU (the first form: 81 G pair
 // evaluations per second at N0 = 16 384, Ntest = 37) the CU idles through the exchange; with two the other orbit computes.
-// Every member of a team has to be resident at once (they wait for each other): 512 workgroups of 4 waves fit the chip at
-// <= 170 VGPRs (3 waves per SIMD; family A, the largest, has 136).
+// Every member of a team has to be resident at once (they wait for each other), so two workgroups must fit one CU: 2 waves per
+// SIMD (<= 256 VGPRs; families A and D, the largest, have 142) and twice the kernel's LDS within the CU's 160 KB (2 x 72 328 B
+// with MAP_STAGE 5; a sixth staged round would not fit).  tests/test_applymap_team_cpu.py holds every instance to this.
 int applymap_team(int ntest, int n0)
 {
     // resident workgroups the device can hold: two of these per CU (queried once per device; 256 CUs -> 512)
