@@ -629,6 +629,35 @@ int sgpr_applymap_sections_host(int family, int mode, int nsec, int first, int n
                                 const double *alpha, const double *hypp, int nhypp, int n0p, const double *xtrainp,
                                 const double *ytrainp, const double *alphap, const double *Q0, const double *P0,
                                 double *qmap, double *pmap, double *pdiff);
+/* The sectioned map WITH ITS TANGENT MAP: the same orbits -- qmap, pmap and pdiff are bit-identical to
+ * sgpr_applymap_sections_host, whose arguments, layout and checks this entry shares -- and the derivative of every step.  After
+ * each accepted step (new P finite) one more pass over the section's training points sums the Hessian of its generating function
+ * at (q, P): A = H_qq, B = H_qP, C = H_PP, three sums in one reduction.  With T = 1 / (1 + B) the Jacobian of the step
+ * (q, p) -> (Q, P) is
+ *     M = [ 1 + B - C T A    C T ]      rows (Q, P), columns (q, p),
+ *         [     - T A         T  ]
+ * of determinant 1 for any A, B, C; wrapping q does not change it.  The outputs have the layout of
+ * sgpr_applymap_nd_tangent_host at d = 1:
+ * jac  (may be NULL): [nm-1][ntest][2][2] doubles, C order: M of every step (step i belongs to section (first + i) mod nsec).
+ * mono (may be NULL): [ntest][2][2] = M_{nm-1} ... M_1, the identity for nm = 1 (Greene's residue (2 - tr mono) / 4 of a
+ *      periodic field line).
+ * lyap (may be NULL): [ntest][2] finite-time Lyapunov exponents by Benettin's method (Z = M Qmat, modified Gram-Schmidt in column
+ *      order, log |r_cc| summed per column, divided by nm - 1).  The orthonormal basis lives inside one call: a run split into
+ *      several calls takes its exponents from the calls' jac (maps.tangent_from_jac).
+ * From the step at which an orbit is lost its jac rows are NaN, and so are its mono and lyap; so is the jac row of a step whose
+ * 1 + B is 0 or not finite, with mono and lyap (the orbit itself goes on).  An orbit's outputs depend on nothing but its own
+ * start point, `first` and the sections.
+ * On top of the plain entry's checks (SGPR_E_ARG before any device call): SGPR_MAP_WRAP_P (the implicit half and the q half
+ * would sit at different points and need two Hessians; no driver of the sectioned map wraps P); SGPR_MAP_EXPLICIT with a
+ * product family (accepted for the sum kernels -- family B, or a USER sum kernel -- where B = 0, A depends on q and C on P
+ * only); lyap != NULL with nm < 2.  Then SGPR_E_NODEVICE without a device; ntest == 0 returns 0; nm == 1 writes the start row
+ * and mono = identity.
+ * Added in ABI 5 (additional entry point). */
+int sgpr_applymap_sections_tangent_host(int family, int mode, int nsec, int first, int nm, int ntest,
+                                        const double *hyp, int nhyp, int n0, const double *xtrain, const double *ytrain,
+                                        const double *alpha, const double *hypp, int nhypp, int n0p, const double *xtrainp,
+                                        const double *ytrainp, const double *alphap, const double *Q0, const double *P0,
+                                        double *qmap, double *pmap, double *pdiff, double *jac, double *mono, double *lyap);
 /* The symplectic map of a fit with d canonical pairs (d = 1, 2, 3), nm - 1 steps for ntest orbits with every step on the
  * device: one workgroup per orbit, no workgroup waits on another.  With x = (q_1..q_d, P_1..P_d) and G(x) = K*(x) alpha (what
  * sgpr_fit_predict_nd returns: G_q = dF/dq = p - P, G_P = dF/dP = Q - q) a step solves

@@ -114,6 +114,72 @@ static int applymap_nd_host(const char *me, int family, int d, int mode, int nm,
                           qmap, pmap, iters, st, tan);
 }
 
+// sgpr_applymap_sections_host (tan null) and sgpr_applymap_sections_tangent_host: every argument is checked before any device call
+static int applymap_sections_host(const char *me, int family, int mode, int nsec, int first, int nm, int ntest, const double *hyp,
+                                  int nhyp, int n0, const double *xtrain, const double *ytrain, const double *alpha,
+                                  const double *hypp, int nhypp, int n0p, const double *xtrainp, const double *ytrainp,
+                                  const double *alphap, const double *Q0, const double *P0, double *qmap, double *pmap, double *pdiff,
+                                  const MapTangentOut *tan)
+{
+    auto E = [&](const char *what) { set_error(std::string(me) + ": " + what); return SGPR_E_ARG; };
+    const bool expl = (mode & SGPR_MAP_EXPLICIT) != 0;
+    if (expl) n0p = 0;                       /* no first-guess GPs in the explicit map */
+    if (mode & ~(SGPR_MAP_WRAP_Q | SGPR_MAP_WRAP_P | SGPR_MAP_EXPLICIT | SGPR_MAP_LOSS_NEGP)) return E("unknown mode bit");
+    if (expl && (mode & SGPR_MAP_LOSS_NEGP)) return E("SGPR_MAP_LOSS_NEGP belongs to the implicit map");
+    if (nsec < 1) return E("nsec < 1");
+    if (first < 0 || first >= nsec) return E("first outside [0, nsec)");
+    if (nm < 1) return E("nm < 1");
+    if (ntest < 0 || n0 < 0 || n0p < 0) return E("negative ntest, n0 or n0p");
+    if (!hyp || (!expl && !hypp) || !Q0 || !P0 || !qmap || !pmap) return E("null hyp, hypp, Q0, P0, qmap or pmap");
+    if ((n0 > 0 && (!xtrain || !ytrain || !alpha)) || (n0p > 0 && (!xtrainp || !ytrainp || !alphap)))
+        return E("null training points or alpha");
+    if (tan) {
+        if (mode & SGPR_MAP_WRAP_P) return E("SGPR_MAP_WRAP_P has no tangent map here (it would need two Hessians per step)");
+        if (expl && !family_is_sum(family))
+            return E("SGPR_MAP_EXPLICIT has a tangent map for the sum kernels only (family B, or a USER sum kernel)");
+        if (tan->lyap && nm < 2) return E("lyap needs nm >= 2");
+    }
+    int rc;
+    std::vector<KConst> kc(2 * (size_t)nsec);           /* the sections' constants: nsec for the map, nsec for the guess */
+    for (int s = 0; s < nsec; ++s) {
+        if ((rc = make_kconst(family, hyp + (size_t)s * nhyp, nhyp, &kc[s]))) return rc;
+        if (!expl && (rc = make_kconst(family, hypp + (size_t)s * nhypp, nhypp, &kc[nsec + s]))) return rc;
+    }
+    if ((rc = need_device())) return rc;
+    if (ntest == 0) return 0;
+    DevBuf x, y, al, xp, yp, alp, dk, q0, p0, dj, dm, dl;
+    hipStream_t st = nullptr;
+    const size_t ns = (size_t)nsec;
+    static_assert(sizeof(KConst) % sizeof(double) == 0, "KConst is uploaded as doubles");
+    if ((rc = upload(x, xtrain, ns * n0, st)) || (rc = upload(y, ytrain, ns * n0, st)) || (rc = upload(al, alpha, 2 * ns * n0, st)) ||
+        (rc = upload(xp, xtrainp, ns * n0p, st)) || (rc = upload(yp, ytrainp, ns * n0p, st)) || (rc = upload(alp, alphap, ns * n0p, st)) ||
+        (rc = upload(dk, reinterpret_cast<const double *>(kc.data()), kc.size() * (sizeof(KConst) / sizeof(double)), st)) ||
+        (rc = upload(q0, Q0, ntest, st)) || (rc = upload(p0, P0, ntest, st)))
+        return rc;
+    if (!tan)
+        return map_outputs(nm, ntest, qmap, pmap, pdiff, st, [&](double *qm, double *pm, double *pd) {
+            return applymap_sections(family, mode, nsec, first, nm, ntest, n0, x.as<double>(), y.as<double>(), al.as<double>(),
+                                     dk.as<KConst>(), n0p, xp.as<double>(), yp.as<double>(), alp.as<double>(), dk.as<KConst>() + nsec,
+                                     q0.as<double>(), p0.as<double>(), qm, pm, pd, st);
+        });
+    const size_t mono_bytes = (size_t)ntest * 4 * sizeof(double), jac_bytes = (size_t)(nm - 1) * mono_bytes;
+    const size_t lyap_bytes = (size_t)ntest * 2 * sizeof(double);
+    if ((tan->jac && (rc = dj.alloc(jac_bytes))) || (tan->mono && (rc = dm.alloc(mono_bytes))) || (tan->lyap && (rc = dl.alloc(lyap_bytes))))
+        return rc;
+    rc = map_outputs(nm, ntest, qmap, pmap, pdiff, st, [&](double *qm, double *pm, double *pd) {
+        return applymap_sections_tangent(family, mode, nsec, first, nm, ntest, n0, x.as<double>(), y.as<double>(), al.as<double>(),
+                                         dk.as<KConst>(), n0p, xp.as<double>(), yp.as<double>(), alp.as<double>(),
+                                         dk.as<KConst>() + nsec, q0.as<double>(), p0.as<double>(), qm, pm, pd, dj.as<double>(),
+                                         dm.as<double>(), dl.as<double>(), st);
+    });
+    if (rc) return rc;
+    if (tan->jac && jac_bytes) SGPR_HIP(hipMemcpyAsync(tan->jac, dj.p, jac_bytes, hipMemcpyDeviceToHost, st));
+    if (tan->mono) SGPR_HIP(hipMemcpyAsync(tan->mono, dm.p, mono_bytes, hipMemcpyDeviceToHost, st));
+    if (tan->lyap) SGPR_HIP(hipMemcpyAsync(tan->lyap, dl.p, lyap_bytes, hipMemcpyDeviceToHost, st));
+    SGPR_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
 extern "C" {
 
 int sgpr_abi_version(void) { return SGPR_ABI_VERSION; }
@@ -510,40 +576,20 @@ int sgpr_applymap_sections_host(int family, int mode, int nsec, int first, int n
                                 int n0p, const double *xtrainp, const double *ytrainp, const double *alphap, const double *Q0,
                                 const double *P0, double *qmap, double *pmap, double *pdiff)
 {
-    auto E = [](const char *what) { set_error(std::string("applymap_sections_host: ") + what); return SGPR_E_ARG; };
-    const bool expl = (mode & SGPR_MAP_EXPLICIT) != 0;
-    if (expl) n0p = 0;                       /* no first-guess GPs in the explicit map */
-    if (mode & ~(SGPR_MAP_WRAP_Q | SGPR_MAP_WRAP_P | SGPR_MAP_EXPLICIT | SGPR_MAP_LOSS_NEGP)) return E("unknown mode bit");
-    if (expl && (mode & SGPR_MAP_LOSS_NEGP)) return E("SGPR_MAP_LOSS_NEGP belongs to the implicit map");
-    if (nsec < 1) return E("nsec < 1");
-    if (first < 0 || first >= nsec) return E("first outside [0, nsec)");
-    if (nm < 1) return E("nm < 1");
-    if (ntest < 0 || n0 < 0 || n0p < 0) return E("negative ntest, n0 or n0p");
-    if (!hyp || (!expl && !hypp) || !Q0 || !P0 || !qmap || !pmap) return E("null hyp, hypp, Q0, P0, qmap or pmap");
-    if ((n0 > 0 && (!xtrain || !ytrain || !alpha)) || (n0p > 0 && (!xtrainp || !ytrainp || !alphap)))
-        return E("null training points or alpha");
-    int rc;
-    std::vector<KConst> kc(2 * (size_t)nsec);           /* the sections' constants: nsec for the map, nsec for the guess */
-    for (int s = 0; s < nsec; ++s) {
-        if ((rc = make_kconst(family, hyp + (size_t)s * nhyp, nhyp, &kc[s]))) return rc;
-        if (!expl && (rc = make_kconst(family, hypp + (size_t)s * nhypp, nhypp, &kc[nsec + s]))) return rc;
-    }
-    if ((rc = need_device())) return rc;
-    if (ntest == 0) return 0;
-    DevBuf x, y, al, xp, yp, alp, dk, q0, p0;
-    hipStream_t st = nullptr;
-    const size_t ns = (size_t)nsec;
-    static_assert(sizeof(KConst) % sizeof(double) == 0, "KConst is uploaded as doubles");
-    if ((rc = upload(x, xtrain, ns * n0, st)) || (rc = upload(y, ytrain, ns * n0, st)) || (rc = upload(al, alpha, 2 * ns * n0, st)) ||
-        (rc = upload(xp, xtrainp, ns * n0p, st)) || (rc = upload(yp, ytrainp, ns * n0p, st)) || (rc = upload(alp, alphap, ns * n0p, st)) ||
-        (rc = upload(dk, reinterpret_cast<const double *>(kc.data()), kc.size() * (sizeof(KConst) / sizeof(double)), st)) ||
-        (rc = upload(q0, Q0, ntest, st)) || (rc = upload(p0, P0, ntest, st)))
-        return rc;
-    return map_outputs(nm, ntest, qmap, pmap, pdiff, st, [&](double *qm, double *pm, double *pd) {
-        return applymap_sections(family, mode, nsec, first, nm, ntest, n0, x.as<double>(), y.as<double>(), al.as<double>(),
-                                 dk.as<KConst>(), n0p, xp.as<double>(), yp.as<double>(), alp.as<double>(), dk.as<KConst>() + nsec,
-                                 q0.as<double>(), p0.as<double>(), qm, pm, pd, st);
-    });
+    return applymap_sections_host("applymap_sections_host", family, mode, nsec, first, nm, ntest, hyp, nhyp, n0, xtrain, ytrain, alpha,
+                                  hypp, nhypp, n0p, xtrainp, ytrainp, alphap, Q0, P0, qmap, pmap, pdiff, nullptr);
+}
+
+/* The same with the tangent map (mapsec_tan.h): the orbit outputs have the bits of sgpr_applymap_sections_host. */
+int sgpr_applymap_sections_tangent_host(int family, int mode, int nsec, int first, int nm, int ntest, const double *hyp, int nhyp,
+                                        int n0, const double *xtrain, const double *ytrain, const double *alpha, const double *hypp,
+                                        int nhypp, int n0p, const double *xtrainp, const double *ytrainp, const double *alphap,
+                                        const double *Q0, const double *P0, double *qmap, double *pmap, double *pdiff, double *jac,
+                                        double *mono, double *lyap)
+{
+    const MapTangentOut tan = {jac, mono, lyap};
+    return applymap_sections_host("applymap_sections_tangent_host", family, mode, nsec, first, nm, ntest, hyp, nhyp, n0, xtrain, ytrain,
+                                  alpha, hypp, nhypp, n0p, xtrainp, ytrainp, alphap, Q0, P0, qmap, pmap, pdiff, &tan);
 }
 
 /* The d-pair map from caller-supplied training points and alpha (the counterpart of sgpr_applymap_host for d canonical pairs). */

@@ -101,6 +101,11 @@ int applymap_sections(int family, int mode, int nsec, int first, int nm, int nte
                       const double *alpha, const KConst *kcs, int n0p, const double *xtrp, const double *ytrp,
                       const double *alphap, const KConst *kcps, const double *Q0, const double *P0, double *qmap, double *pmap,
                       double *pdiff, hipStream_t st);
+// the same with the tangent map (mapsec_tan.h): jac [nm - 1][ntest][2][2], mono [ntest][2][2], lyap [ntest][2], each or null
+int applymap_sections_tangent(int family, int mode, int nsec, int first, int nm, int ntest, int n0, const double *xtr,
+                              const double *ytr, const double *alpha, const KConst *kcs, int n0p, const double *xtrp,
+                              const double *ytrp, const double *alphap, const KConst *kcps, const double *Q0, const double *P0,
+                              double *qmap, double *pmap, double *pdiff, double *jac, double *mono, double *lyap, hipStream_t st);
 
 // ---- gram_nd.hip : d canonical pairs per point (X: points x 2d, column-major)
 int gram_nd(int family, int d, int mi, int mj, const double *Xb, size_t ldxb, const double *Xa, size_t ldxa,

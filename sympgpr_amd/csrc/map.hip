@@ -1,7 +1,9 @@
 // map.hip -- the symplectic map of a one-pair (d = 1) fit for gfx950 (MI355X): every time step of every orbit on the device,
 // for one GP pair (applymap_kernel) and for one GP pair per toroidal section (applymap_sections_kernel).  The two kernels
-// share one time step (map_step) and one copy of the per-thread sums (rows_part, guess_part).
+// share one time step (map_step) and one copy of the per-thread sums (rows_part, guess_part).  The sectioned kernel has a TAN
+// instance (mapsec_tan.h): the step's Jacobian, the monodromy matrix and the finite-time Lyapunov exponents of every orbit.
 #include <atomic>
+#include <type_traits>
 #include "common.h"
 #include "devmath.h"
 #include "pair_eval.h"
@@ -290,14 +292,20 @@ struct MapSecArgs {
     double *qmap, *pmap, *pdiff;          // [nm][ntest], C order; pdiff may be null
 };
 
+#include "mapsec_tan.h"   // the tangent map: what TAN = true adds to the kernel below
+
+// TAN: after every accepted step (new p finite: block-uniform) one more pass over section m's points sums the Hessian of the
+// generating function at (q_old, P_new); the step's Jacobian M, the product of the M's and the Benettin sums follow from it.
+// The orbit itself makes the same rows / guess calls in the same order as without TAN and has the same bits.  A lost orbit's M
+// is NaN from that step on, and with it mono and the exponents.
 // kcs, kcps: the sections' constants (make_kconst) in device memory, nsec each; a step reads its pair with block-uniform loads
 // (__restrict__: nothing the kernel writes can alias them, so the compiler fetches them with scalar loads, into SGPRs, where
 // applymap_kernel has its kernel arguments)
-template <int FAM, int TT>
-__global__ __launch_bounds__(TT) void applymap_sections_kernel(const MapSecArgs a, const KConst *__restrict__ kcs,
-                                                               const KConst *__restrict__ kcps)
+template <int FAM, int TT, bool TAN = false>
+__global__ __launch_bounds__(TT) void applymap_sections_kernel(const std::conditional_t<TAN, MapSecTanArgs, MapSecArgs> a,
+                                                               const KConst *__restrict__ kcs, const KConst *__restrict__ kcps)
 {
-    __shared__ double sh[2][2 * (TT / 64)];
+    __shared__ double sh[2][(TAN ? 3 : 2) * (TT / 64)];
     extern __shared__ double sec_st[];                  // [section]{x, y, alpha (two halves): n0 each; guess x, y, alpha: n0p each}
     const int k = blockIdx.x, tid = threadIdx.x, n0 = a.n0, n0p = a.n0p;
     const int per = 4 * n0 + 3 * n0p;                   // (staged only: nsec * per <= MAPSEC_STAGE)
@@ -329,8 +337,10 @@ __global__ __launch_bounds__(TT) void applymap_sections_kernel(const MapSecArgs 
         if (a.pdiff) a.pdiff[k] = pd;
     }
     int m = a.first;
+    if constexpr (TAN) sec_tan_init();
     for (int i = 0; i + 1 < a.nm; ++i) {
         const KConst kc = kcs[m];
+        const double q_old = q;
         auto rows = [&](double q, double P, double &r1, double &r2) {   // section m's Kstar(1,:).alpha, Kstar(2,:).alpha
             if (staged) {
                 const double *d = sec_st + m * per;
@@ -352,6 +362,27 @@ __global__ __launch_bounds__(TT) void applymap_sections_kernel(const MapSecArgs 
             return r;
         };
         map_step(a.mode, a.maxiter, a.tol, q, p, pd, rows, guess);
+        if constexpr (TAN) {                                // section m's Hessian at (q_old, P_new) of the accepted step
+            double M[4];
+            bool tan_ok = false;
+            if (sec_finite(p)) {
+                double hA, hB, hC;
+                if (staged) {
+                    const double *d = sec_st + m * per;
+                    sec_hess_part<FAM>(d, d + n0, d + 2 * n0, d + 3 * n0, tid, TT, tid, TT, n0, q_old, p, kc, hA, hB, hC);
+                } else {
+                    const double *al = a.alpha + (size_t)m * 2 * n0;
+                    sec_hess_part<FAM>(a.xtr + (size_t)m * n0, a.ytr + (size_t)m * n0, al, al + n0, tid, TT, tid, TT, n0, q_old, p,
+                                       kc, hA, hB, hC);
+                }
+                ++seq;
+                block_sum3<TT>(hA, hB, hC, sh[seq & 1u]);
+                tan_ok = sec_tan_matrix(hA, hB, hC, M);
+            }
+            if (!tan_ok) M[0] = M[1] = M[2] = M[3] = __builtin_nan("");
+            sec_tan_publish(M, a.jac ? a.jac + ((size_t)i * a.ntest + k) * 4 : nullptr);
+            sec_tan_advance();
+        }
         if (++m == a.nsec) m = 0;
         if (tid == 0) {
             a.qmap[(size_t)(i + 1) * a.ntest + k] = q;
@@ -359,6 +390,7 @@ __global__ __launch_bounds__(TT) void applymap_sections_kernel(const MapSecArgs 
             if (a.pdiff) a.pdiff[(size_t)(i + 1) * a.ntest + k] = pd;
         }
     }
+    if constexpr (TAN) sec_tan_finish(a, k);
 }
 
 }  // namespace
@@ -428,6 +460,20 @@ int applymap_status(const void *team_ws, int ntest, int n0)
 
 // The sectioned map: one launch, one 256-thread workgroup per orbit.  Dynamic LDS: the drivers' size (4 sections of 70 points)
 // reserves 15.7 KB, not the 70 KB of the limit, so several orbits share a CU.
+template <bool TAN, typename Args>
+static int applymap_sections_launch(int family, const Args &a, size_t lds, const KConst *kcs, const KConst *kcps, hipStream_t st)
+{
+    return dispatch_family(family, [&](auto fam) {
+        constexpr int F = decltype(fam)::value;
+        auto kern = applymap_sections_kernel<F, MAP_T, TAN>;
+        if (lds > 48 * 1024)
+            SGPR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(kern, dim3(a.ntest), dim3(MAP_T), lds, st, a, kcs, kcps);
+        SGPR_CHECK_LAUNCH();
+        return 0;
+    });
+}
+
 int applymap_sections(int family, int mode, int nsec, int first, int nm, int ntest, int n0, const double *xtr, const double *ytr,
                       const double *alpha, const KConst *kcs, int n0p, const double *xtrp, const double *ytrp,
                       const double *alphap, const KConst *kcps, const double *Q0, const double *P0, double *qmap, double *pmap,
@@ -439,15 +485,23 @@ int applymap_sections(int family, int mode, int nsec, int first, int nm, int nte
     const size_t lds = staged ? (size_t)need * sizeof(double) : 0;
     MapSecArgs a{nm, ntest, n0, n0p, mode, 60, nsec, first, staged ? 1 : 0, 1e-13, xtr, ytr, alpha, xtrp, ytrp, alphap, Q0, P0,
                  qmap, pmap, pdiff};
-    return dispatch_family(family, [&](auto fam) {
-        constexpr int F = decltype(fam)::value;
-        auto kern = applymap_sections_kernel<F, MAP_T>;
-        if (lds > 48 * 1024)
-            SGPR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(ntest), dim3(MAP_T), lds, st, a, kcs, kcps);
-        SGPR_CHECK_LAUNCH();
-        return 0;
-    });
+    return applymap_sections_launch<false>(family, a, lds, kcs, kcps, st);
+}
+
+// The same with the tangent map (mapsec_tan.h): jac [nm - 1][ntest][2][2], mono [ntest][2][2], lyap [ntest][2], each or null.
+// Same staging rule, same LDS, same orbit bits.
+int applymap_sections_tangent(int family, int mode, int nsec, int first, int nm, int ntest, int n0, const double *xtr,
+                              const double *ytr, const double *alpha, const KConst *kcs, int n0p, const double *xtrp,
+                              const double *ytrp, const double *alphap, const KConst *kcps, const double *Q0, const double *P0,
+                              double *qmap, double *pmap, double *pdiff, double *jac, double *mono, double *lyap, hipStream_t st)
+{
+    if (nm <= 0 || ntest <= 0) return 0;
+    const long need = (long)nsec * (4L * n0 + 3L * n0p);
+    const bool staged = need <= MAPSEC_STAGE;
+    const size_t lds = staged ? (size_t)need * sizeof(double) : 0;
+    MapSecTanArgs a{{nm, ntest, n0, n0p, mode, 60, nsec, first, staged ? 1 : 0, 1e-13, xtr, ytr, alpha, xtrp, ytrp, alphap, Q0, P0,
+                     qmap, pmap, pdiff}, jac, mono, lyap};
+    return applymap_sections_launch<true>(family, a, lds, kcs, kcps, st);
 }
 
 }  // namespace sgpr

@@ -27,19 +27,27 @@ def nll_chol(hyp, x, y, N):
     return _c.nll_fit(FAMILY, hyp, x, y, N, neig=len(x) // 2)
 
 
-def map_in_chunks(run, nphmap, nm, Ntest, Q0map, P0map, compute_r=None, steps_per_launch=None):
+def map_steps(nphmap, nm):
+    """the steps applymap_tok runs: the reference's while loop advances nphmap steps at a time (func.py:196-197)"""
+    return -(-(nm - nphmap) // nphmap) * nphmap if nm > nphmap else 0
+
+
+def map_in_chunks(run, nphmap, nm, Ntest, Q0map, P0map, compute_r=None, steps_per_launch=None, jac_out=None):
     """The bookkeeping of applymap_tok around a stepper `run(first, steps, Q0, P0) -> (q, p)`, each [steps + 1, len(Q0)] with
     row 0 the start points and NaN from the step at which an orbit is lost: `steps` steps of the sectioned map whose first
     step uses section `first`.  The reference's loop quirk is kept (func.py:196-197: the while loop advances nphmap steps at
     a time): ceil((nm - nphmap) / nphmap) nphmap steps are run and the rows beyond them stay 0.  Without a callback the
     whole map is one call of `run`; with one, `steps_per_launch` steps per call, each continued with first = i mod nphmap from
     the orbits still alive, and compute_r is applied to the new rows step by step and orbit by orbit in the reference's
-    order (func.py:212-217).  What a chunk computed for an orbit beyond the step that lost it is dropped."""
+    order (func.py:212-217).  What a chunk computed for an orbit beyond the step that lost it is dropped.
+    jac_out (map_steps(nphmap, nm), Ntest, 2, 2), filled with NaN by the caller: `run` then returns (q, p, jac) with jac
+    [steps, len(Q0), 2, 2] the step matrices, and row i of jac_out receives the matrix of step i -> i + 1 of every orbit whose
+    row i + 1 is kept."""
     pmap = np.zeros([nm, Ntest])
     qmap = np.zeros([nm, Ntest])
     pmap[0, :] = P0map
     qmap[0, :] = Q0map
-    steps = -(-(nm - nphmap) // nphmap) * nphmap if nm > nphmap else 0
+    steps = map_steps(nphmap, nm)
     if steps == 0:
         return qmap, pmap
     k = steps if compute_r is None else max(1, int(steps_per_launch or 1))
@@ -50,9 +58,13 @@ def map_in_chunks(run, nphmap, nm, Ntest, Q0map, P0map, compute_r=None, steps_pe
         kk = min(k, steps - i)
         idx = np.nonzero(~np.isnan(pmap[i, :]))[0]
         if len(idx):
-            qq, pp = run(i % nphmap, kk, qmap[i, idx], pmap[i, idx])
+            out = run(i % nphmap, kk, qmap[i, idx], pmap[i, idx])
+            qq, pp = out[0], out[1]
+            jj = out[2] if jac_out is not None else None
             if compute_r is None:
                 pmap[i + 1:i + kk + 1, idx], qmap[i + 1:i + kk + 1, idx] = pp[1:], qq[1:]
+                if jj is not None:
+                    jac_out[i:i + kk, idx] = jj
             else:
                 alive = np.ones(len(idx), dtype=bool)
                 for s in range(1, kk + 1):
@@ -67,6 +79,8 @@ def map_in_chunks(run, nphmap, nm, Ntest, Q0map, P0map, compute_r=None, steps_pe
                             alive[j] = False
                             continue
                         pmap[i + s, orbit], qmap[i + s, orbit] = pp[s, j], qq[s, j]
+                        if jj is not None:
+                            jac_out[i + s - 1, orbit] = jj[s - 1, j]
         i += kk
     return qmap, pmap
 
@@ -84,6 +98,14 @@ def applymap_tok(nphmap, nm, Ntest, Q0map, P0map, xtrainp, ztrainp, Kyinvp, hypp
     if compute_r is not None and steps_per_launch is None:
         return _applymap_tok_host(nphmap, nm, Ntest, Q0map, P0map, xtrainp, ztrainp, Kyinvp, hypp, xtrain, ztrain, Kyinv, hyp,
                                   compute_r)
+    run = _sections_stepper(nphmap, xtrainp, ztrainp, Kyinvp, hypp, xtrain, ztrain, Kyinv, hyp)
+    return map_in_chunks(run, nphmap, nm, Ntest, np.broadcast_to(Q0map, (Ntest,)), np.broadcast_to(P0map, (Ntest,)), compute_r,
+                         steps_per_launch)
+
+
+def _sections_stepper(nphmap, xtrainp, ztrainp, Kyinvp, hypp, xtrain, ztrain, Kyinv, hyp, tangent=None):
+    """map_in_chunks's `run` for the drivers' arrays: maps.run_map_sections, or with `tangent` (a dict of
+    maps.run_map_sections_tangent's jac / mono / lyap switches) that entry; its last result's dict is kept in tangent["last"]"""
     from .. import maps
     f = lambda a: np.asarray(a, dtype=np.float64)
     xtrain, ztrain, xtrainp, ztrainp, hyp, hypp = (f(a) for a in (xtrain, ztrain, xtrainp, ztrainp, hyp, hypp))
@@ -92,11 +114,46 @@ def applymap_tok(nphmap, nm, Ntest, Q0map, P0map, xtrainp, ztrainp, Kyinvp, hypp
     alpha = np.stack([f(Kyinv[m]) @ ztrain[:, m] for m in sec], axis=1)           # once per section, not per step
     alphap = np.stack([f(Kyinvp[m]) @ ztrainp[:, m] for m in sec], axis=1)
     mode = maps.WRAP_Q | maps.LOSS_NEGP
-    run = lambda first, steps, Q0, P0: maps.run_map_sections(
-        mode, steps + 1, len(Q0), hyp[:nphmap], xtrain[:N, :nphmap], xtrain[N:2 * N, :nphmap], alpha, Q0, P0, hypp[:nphmap],
-        xtrainp[:Np, :nphmap], xtrainp[Np:2 * Np, :nphmap], alphap, first=first, family=FAMILY)
-    return map_in_chunks(run, nphmap, nm, Ntest, np.broadcast_to(Q0map, (Ntest,)), np.broadcast_to(P0map, (Ntest,)), compute_r,
-                         steps_per_launch)
+
+    def run(first, steps, Q0, P0):
+        args = (mode, steps + 1, len(Q0), hyp[:nphmap], xtrain[:N, :nphmap], xtrain[N:2 * N, :nphmap], alpha, Q0, P0, hypp[:nphmap],
+                xtrainp[:Np, :nphmap], xtrainp[Np:2 * Np, :nphmap], alphap)
+        if tangent is None:
+            return maps.run_map_sections(*args, first=first, family=FAMILY)
+        q, p, t = maps.run_map_sections_tangent(*args, first=first, family=FAMILY, jac=tangent["jac"], mono=tangent["mono"],
+                                                lyap=tangent["lyap"])
+        tangent["last"] = t
+        return q, p, t.get("jac")
+    return run
+
+
+def applymap_tok_tangent(nphmap, nm, Ntest, Q0map, P0map, xtrainp, ztrainp, Kyinvp, hypp, xtrain, ztrain, Kyinv, hyp,
+                         compute_r=None, steps_per_launch=None):
+    """applymap_tok with the tangent map (maps.run_map_sections_tangent): -> (qmap, pmap, t), the orbits as applymap_tok returns
+    them from the device and t["jac"] (steps, Ntest, 2, 2), t["mono"] (Ntest, 2, 2), t["lyap"] (Ntest, 2) over the
+    steps = map_steps(nphmap, nm) steps that are run; NaN from the step at which an orbit is lost.  Without a callback ONE
+    launch, mono and lyap from the device.  With compute_r, steps_per_launch = k steps per launch (1 if not given: every step
+    runs on the device here), the chunks' jac collected by map_in_chunks's bookkeeping and mono, lyap taken from them on the
+    host (maps.tangent_from_jac): Benettin's basis does not survive a relaunch."""
+    from .. import maps
+    steps = map_steps(nphmap, nm)
+    Q0, P0 = np.broadcast_to(Q0map, (Ntest,)), np.broadcast_to(P0map, (Ntest,))
+    t = {"jac": np.full((steps, Ntest, 2, 2), np.nan), "mono": np.broadcast_to(np.eye(2), (Ntest, 2, 2)).copy(),
+         "lyap": np.full((Ntest, 2), np.nan)}
+    if steps == 0:
+        qmap, pmap = map_in_chunks(None, nphmap, nm, Ntest, Q0, P0)
+        return qmap, pmap, t
+    one = compute_r is None
+    sw = {"jac": True, "mono": one, "lyap": one}
+    run = _sections_stepper(nphmap, xtrainp, ztrainp, Kyinvp, hypp, xtrain, ztrain, Kyinv, hyp, tangent=sw)
+    qmap, pmap = map_in_chunks(run, nphmap, nm, Ntest, Q0, P0, compute_r, steps_per_launch, jac_out=t["jac"])
+    if one and "last" in sw:                  # one launch over all Ntest orbits (a NaN start is an orbit like any other there)
+        alive = ~np.isnan(P0)
+        t["mono"][:], t["lyap"][:] = np.nan, np.nan
+        t["mono"][alive], t["lyap"][alive] = sw["last"]["mono"], sw["last"]["lyap"]
+    else:
+        t["mono"], t["lyap"] = maps.tangent_from_jac(t["jac"])
+    return qmap, pmap, t
 
 
 def _applymap_tok_host(nphmap, nm, Ntest, Q0map, P0map, xtrainp, ztrainp, Kyinvp, hypp, xtrain, ztrain, Kyinv, hyp, compute_r):

@@ -9,7 +9,10 @@ One recurrence, the variants the reference's drivers carry in their own func.py 
     applymap          01_pendulum/explicit/func_expl.py:113-128   explicit, q mod 2 pi
     applymap_tok      05_tokamak/SympGPR/func.py:182-211  implicit, q mod 2 pi, an orbit with P < 0 is lost (LOSS_NEGP)
     applymap_tok      05_tokamak/Split_SympGPR/func.py:184-219   the same with one GP pair per toroidal section, applied in
-                                                                 turn: run_map_sections (sgpr_applymap_sections_host)
+                                                                 turn: run_map_sections (sgpr_applymap_sections_host);
+                                                                 run_map_sections_tangent adds the step matrices, their
+                                                                 product and Lyapunov exponents, tangent_from_jac rebuilds the
+                                                                 last two on the host from the jac of a run split into chunks
 
 For fits with d canonical pairs (d = 1, 2, 3) the map is run_map_nd / SympFit.applymap_pairs: Newton with the analytic
 Jacobian on the d unknowns P, one workgroup per orbit (include/sympgpr_hip.h: sgpr_applymap_nd_host).
@@ -79,18 +82,9 @@ def _section_columns(name, a, rows, nsec):
     return np.asfortranarray(a)
 
 
-def run_map_sections(mode, nm, Ntest, hyp, xt, yt, alpha, Q0, P0, hypp=None, xp=None, yp=None, alphap=None, first=0,
-                     want_pdiff=False, family=None):
-    """The sectioned map of 05_tokamak/Split_SympGPR/func.py:184-219 in ONE launch: nsec independent GP pairs of one size,
-    applied in turn -- step i -> i + 1 uses section (first + i) mod nsec (sgpr_applymap_sections_host).
-
-    hyp (nsec, nhyp), row s = section s's (lx, ly, sig) -- (lx, ly, p, sig) for family D; xt, yt (N0, nsec) and alpha
-    (2 N0, nsec), one column per section; hypp (nsec, nhyp), xp, yp, alphap (N0p, nsec) the regular GPs of the first guess
-    (not needed with EXPLICIT).  alpha and alphap are the posterior weights Ky^-1 z of the sections' fits: what fit.fit_batch
-    returns for them or sections.gather_sections collects, stacked as columns (np.stack(alphas, axis=1)).
-    -> (qmap, pmap) or (qmap, pmap, pdiff), each [nm, Ntest]; NaN from the step at which an orbit is lost.  A map continued
-    from row i with first = (first + i) mod nsec has the bits of the uninterrupted one.  Shape errors are ValueError before
-    any device call."""
+def _sections_call(mode, nm, Ntest, hyp, xt, yt, alpha, Q0, P0, hypp, xp, yp, alphap, first, want_pdiff, family):
+    """What run_map_sections and run_map_sections_tangent share: the checked, laid-out arguments of the two C entries up to and
+    including pdiff, as a list, and the output arrays (qmap, pmap, pdiff or None).  Shape errors are ValueError."""
     family = get_family() if family is None else family
     mode, nm, Ntest, first = int(mode), int(nm), int(Ntest), int(first)
     hyp = np.asarray(hyp, dtype=np.float64)
@@ -122,12 +116,83 @@ def run_map_sections(mode, nm, Ntest, hyp, xt, yt, alpha, Q0, P0, hypp=None, xp=
     Q0, P0 = L.f64(np.broadcast_to(Q0, (Ntest,))), L.f64(np.broadcast_to(P0, (Ntest,)))
     qmap, pmap = np.zeros([nm, Ntest]), np.zeros([nm, Ntest])
     pdiff = np.zeros([nm, Ntest]) if want_pdiff else None
+    keep = (hyp, hp, xt, yt, alpha, xp, yp, alphap, Q0, P0)        # the arrays the pointers below point into
+    args = [L.family_id(family), mode, nsec, first, nm, Ntest, L.dptr(hyp), hyp.shape[1], N0, L.dptr(xt), L.dptr(yt), L.dptr(alpha),
+            L.dptr(hp), hp.shape[1], N0p, L.dptr(xp), L.dptr(yp), L.dptr(alphap), L.dptr(Q0), L.dptr(P0), L.dptr(qmap), L.dptr(pmap),
+            L.dptr(pdiff) if want_pdiff else None]
+    return args, keep, (qmap, pmap, pdiff)
+
+
+def run_map_sections(mode, nm, Ntest, hyp, xt, yt, alpha, Q0, P0, hypp=None, xp=None, yp=None, alphap=None, first=0,
+                     want_pdiff=False, family=None):
+    """The sectioned map of 05_tokamak/Split_SympGPR/func.py:184-219 in ONE launch: nsec independent GP pairs of one size,
+    applied in turn -- step i -> i + 1 uses section (first + i) mod nsec (sgpr_applymap_sections_host).
+
+    hyp (nsec, nhyp), row s = section s's (lx, ly, sig) -- (lx, ly, p, sig) for family D; xt, yt (N0, nsec) and alpha
+    (2 N0, nsec), one column per section; hypp (nsec, nhyp), xp, yp, alphap (N0p, nsec) the regular GPs of the first guess
+    (not needed with EXPLICIT).  alpha and alphap are the posterior weights Ky^-1 z of the sections' fits: what fit.fit_batch
+    returns for them or sections.gather_sections collects, stacked as columns (np.stack(alphas, axis=1)).
+    -> (qmap, pmap) or (qmap, pmap, pdiff), each [nm, Ntest]; NaN from the step at which an orbit is lost.  A map continued
+    from row i with first = (first + i) mod nsec has the bits of the uninterrupted one.  Shape errors are ValueError before
+    any device call."""
+    args, keep, (qmap, pmap, pdiff) = _sections_call(mode, nm, Ntest, hyp, xt, yt, alpha, Q0, P0, hypp, xp, yp, alphap, first,
+                                                     want_pdiff, family)
     lib = L.load_library()
-    L.check(lib.sgpr_applymap_sections_host(L.family_id(family), mode, nsec, first, nm, Ntest, L.dptr(hyp), hyp.shape[1], N0,
-                                            L.dptr(xt), L.dptr(yt), L.dptr(alpha), L.dptr(hp), hp.shape[1], N0p, L.dptr(xp),
-                                            L.dptr(yp), L.dptr(alphap), L.dptr(Q0), L.dptr(P0), L.dptr(qmap), L.dptr(pmap),
-                                            L.dptr(pdiff) if want_pdiff else None), "sgpr_applymap_sections_host")
+    L.check(lib.sgpr_applymap_sections_host(*args), "sgpr_applymap_sections_host")
     return (qmap, pmap, pdiff) if want_pdiff else (qmap, pmap)
+
+
+def run_map_sections_tangent(mode, nm, Ntest, hyp, xt, yt, alpha, Q0, P0, hypp=None, xp=None, yp=None, alphap=None, first=0,
+                             want_pdiff=False, family=None, jac=True, mono=True, lyap=True):
+    """run_map_sections with the tangent map (sgpr_applymap_sections_tangent_host): -> (qmap, pmap[, pdiff], t).  The orbits
+    have the bits of run_map_sections; `t` is a dict of the requested arrays: t["jac"] (nm - 1, Ntest, 2, 2), the Jacobian M of
+    every step with rows (Q, P) and columns (q, p) -- step i belongs to section (first + i) mod nsec; t["mono"] (Ntest, 2, 2) =
+    M_{nm-1} ... M_1 (greene_residue reads it); t["lyap"] (Ntest, 2), finite-time Lyapunov exponents per step of the map by
+    Benettin's method.  All NaN from the step at which an orbit is lost.  WRAP_P has no tangent map; EXPLICIT only with the sum
+    kernels (family B); lyap needs nm >= 2: ValueError before any device call, like the shape errors.  A run split into several
+    calls keeps the calls' jac and takes mono and lyap from tangent_from_jac."""
+    if int(mode) & WRAP_P:
+        raise ValueError("the sectioned map's tangent knows no WRAP_P (it would need two Hessians per step)")
+    fam = get_family() if family is None else family
+    if int(mode) & EXPLICIT and not L.family_id(fam) == L.family_id("B"):
+        raise ValueError("EXPLICIT has a tangent map for the sum kernels only (family B)")
+    args, keep, (qmap, pmap, pdiff) = _sections_call(mode, nm, Ntest, hyp, xt, yt, alpha, Q0, P0, hypp, xp, yp, alphap, first,
+                                                     want_pdiff, family)
+    t = tangent_outputs_nd(int(nm), int(Ntest), 1, jac, mono, lyap)
+    lib = L.load_library()
+    L.check(lib.sgpr_applymap_sections_tangent_host(*args, _optr(t, "jac"), _optr(t, "mono"), _optr(t, "lyap")),
+            "sgpr_applymap_sections_tangent_host")
+    return (qmap, pmap, pdiff, t) if want_pdiff else (qmap, pmap, t)
+
+
+def tangent_from_jac(jac):
+    """mono, lyap on the host from the step matrices jac (steps, Ntest, D, D) of one or several calls, concatenated in step order:
+    mono (Ntest, D, D) = M_steps ... M_1 and lyap (Ntest, D) by Benettin's method with the kernels' Gram-Schmidt order (modified,
+    in column order, log |r_cc| summed per column, divided by the number of steps).  An orbit with a NaN step has NaN mono and
+    lyap.  For runs split into several launches: Benettin's basis does not survive a relaunch, the step matrices do."""
+    jac = np.asarray(jac, dtype=np.float64)
+    if jac.ndim != 4 or jac.shape[2] != jac.shape[3] or jac.shape[0] < 1:
+        raise ValueError("jac must be (steps >= 1, Ntest, D, D)")
+    steps, Ntest, D = jac.shape[:3]
+    mono = np.broadcast_to(np.eye(D), (Ntest, D, D)).copy()
+    Q = mono.copy()
+    s = np.zeros((Ntest, D))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for M in jac:
+            mono = M @ mono
+            Z = M @ Q
+            for c in range(D):
+                r = np.sqrt(np.einsum("kr,kr->k", Z[:, :, c], Z[:, :, c]))
+                Z[:, :, c] /= r[:, None]
+                for e in range(c + 1, D):
+                    Z[:, :, e] -= np.einsum("kr,kr->k", Z[:, :, c], Z[:, :, e])[:, None] * Z[:, :, c]
+                s[:, c] += np.log(np.abs(r))
+            Q = Z
+    bad = ~np.isfinite(jac).all(axis=(0, 2, 3))
+    mono[bad] = np.nan
+    lyap = s / steps
+    lyap[bad] = np.nan
+    return mono, lyap
 
 
 def start_points_nd(Q0, P0, d):
