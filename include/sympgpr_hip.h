@@ -143,11 +143,11 @@ typedef struct sgpr_fit *sgpr_fit_t;
  *   needs built:    factor;  get_matrix takes built or factored
  *   needs factored: solve, ldiag, solve_rhs, solve_rhs_dev, inverse, cond_estimate
  *   needs solved:   alpha, nll, predict_rows, predict_nd, predict_cov, predict_genfun, nll_grad, nll_grad_terms,
- *                   nll_grad_full, loo, applymap_nd, applymap_nd_tangent
+ *                   nll_grad_full, loo, applymap_nd, applymap_nd_tangent, applymap_nd_inverse
  *                   loo_grad (as nll_grad_full: SGPR_FIT_BLOCK_QQ / _PP fits refused; grows the fit's scratch block)
  * An entry called without what it needs returns SGPR_E_STATE.  So does one called on a kind of fit it is not defined for:
  *   SGPR_FIT_BLOCK_QQ / _PP fits: every "needs solved" entry except alpha and nll, and cond_estimate;
- *   SGPR_FIT_REG fits: predict_nd, applymap_nd, applymap_nd_tangent (predict_genfun: SGPR_E_ARG, see there);
+ *   SGPR_FIT_REG fits: predict_nd, applymap_nd, applymap_nd_tangent, applymap_nd_inverse (predict_genfun: SGPR_E_ARG, see there);
  *   create_nd fits with d > 1: predict_rows, nll_grad, nll_grad_terms.
  * Argument errors (SGPR_E_ARG) are reported first.  Every refusal happens before any device call and leaves the handle, the
  * device buffers and the scratch as they were; its message (sgpr_last_error) begins with the entry's name without "sgpr_"
@@ -713,6 +713,31 @@ int sgpr_applymap_nd_tangent_host(int family, int d, int mode, int nm, int ntest
                                   const double *X, size_t ldx, const double *alpha, const double *Q0, size_t ldq,
                                   const double *P0, size_t ldp, double *qmap, double *pmap, int *iters,
                                   double *jac, double *mono, double *lyap);
+/* The d-pair map BACKWARDS: row 0 of qmap / pmap is a point (Q, P), row i its i-th preimage under the map of sgpr_fit_applymap_nd /
+ * sgpr_applymap_nd_host (mode without SGPR_MAP_EXPLICIT).  The forward step passes through x = (q, P); so does the backward
+ * one, with P known and q unknown: it solves
+ *     f(q) = q + G_P(q, P) - Q = 0   for q in R^d,   then   p = P + G_q(q, P),
+ * by Newton from q = Q with the analytic Jacobian I + dG_P/dq.  G is the gradient of the generating function, so dG_P/dq is the
+ * TRANSPOSE of the dG_q/dP block the forward solve uses: the same pass over the training points, the same 2d + d^2 sums, the same
+ * closed-form d x d solve on the transposed block.  It stops when max|dq| <= 1e-13 max(1, max|q|) or after 60 iterations; one
+ * more pass at the final q gives G_q and the residual, and the step is accepted when max|f| <= 1e-8 max(1, max|Q|) (the forward
+ * rule with the roles swapped).  Otherwise -- also on a non-finite value or a singular Jacobian -- the orbit is lost: NaN from
+ * that step on; an orbit that starts NaN stays NaN.  The sum kernels' G_P does not depend on q: one exact Newton step.
+ * mode: SGPR_MAP_WRAP_Q (every solved q_i mod 2 pi: the preimage of a wrapped orbit, as the forward map wraps Q) or 0.
+ * SGPR_MAP_EXPLICIT is SGPR_E_ARG for every family: the explicit product-family map P = p - G_q(q, p) evaluates G at (q, p),
+ * not at (q, P), so its inverse needs a second solve (in p) that is not built; the sum kernels' explicit and implicit maps
+ * coincide, so mode 0 inverts them already.  Any other bit is SGPR_E_ARG as well.
+ * Arguments, shapes, checks, states and thread counts as the forward pair: Q0, P0 ntest x d column-major (ldq, ldp >= ntest);
+ * qmap, pmap [nm][ntest][d]; iters (may be NULL) [nm-1][ntest], -1 for a lost orbit; ntest == 0 returns 0, nm == 1 writes the
+ * start row only; an orbit's bits depend on nothing but its own start point.  There is no tangent form: the Jacobian of a
+ * backward step is the symplectic inverse -J M^T J of the forward step matrix M at the same (q, P), which
+ * sgpr_*_applymap_nd_tangent returns for one step from the preimage.
+ * Added in ABI 5 (additional entry points). */
+int sgpr_fit_applymap_nd_inverse(sgpr_fit_t f, int mode, int nm, int ntest, const double *Q0, size_t ldq,
+                                 const double *P0, size_t ldp, double *qmap, double *pmap, int *iters);
+int sgpr_applymap_nd_inverse_host(int family, int d, int mode, int nm, int ntest, const double *hyp, int nhyp, int n0,
+                                  const double *X, size_t ldx, const double *alpha, const double *Q0, size_t ldq,
+                                  const double *P0, size_t ldp, double *qmap, double *pmap, int *iters);
 /* alpha-solve on device with the factor and its leaf inverses: b (n) := L^-T L^-1 b */
 int sgpr_potrs_vec_dev(int n, const double *L, size_t ldl, void *work, double *b,
                        void *stream);

@@ -135,6 +135,10 @@ SIGNATURES = {
     "sgpr_applymap_nd_tangent_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _dp,
                                                 C.c_size_t, _dp, _dp, C.c_size_t, _dp, C.c_size_t, _dp, _dp, C.POINTER(C.c_int),
                                                 _dp, _dp, _dp]),
+    "sgpr_fit_applymap_nd_inverse": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, C.c_size_t, _dp, C.c_size_t, _dp, _dp,
+                                               C.POINTER(C.c_int)]),
+    "sgpr_applymap_nd_inverse_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _dp,
+                                                C.c_size_t, _dp, _dp, C.c_size_t, _dp, C.c_size_t, _dp, _dp, C.POINTER(C.c_int)]),
     "sgpr_potrs_vec_dev": (C.c_int, [C.c_int, _vp, C.c_size_t, _vp, _vp, _vp]),
     "sgpr_solve_status_dev": (C.c_int, [C.c_int, _vp, C.c_size_t, _vp, _vp]),
     "sgpr_fit_batch_max_order": (C.c_int, []),

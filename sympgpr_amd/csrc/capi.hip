@@ -90,14 +90,17 @@ static int map_outputs(int nm, int ntest, double *qmap, double *pmap, double *pd
     return 0;
 }
 
-// sgpr_applymap_nd_host (tan null) and sgpr_applymap_nd_tangent_host: every argument is checked before any device call
+// sgpr_applymap_nd_host (tan null), sgpr_applymap_nd_tangent_host and sgpr_applymap_nd_inverse_host (MAP_BACKWARD, tan null):
+// every argument is checked before any device call
 static int applymap_nd_host(const char *me, int family, int d, int mode, int nm, int ntest, const double *hyp, int nhyp, int n0,
                             const double *X, size_t ldx, const double *alpha, const double *Q0, size_t ldq, const double *P0,
-                            size_t ldp, double *qmap, double *pmap, int *iters, const MapTangentOut *tan)
+                            size_t ldp, double *qmap, double *pmap, int *iters, const MapTangentOut *tan,
+                            MapDirection dir = MAP_FORWARD)
 {
     int rc = applymap_nd_kernel_check(me, family, d, hyp, nhyp);
     if (rc || (rc = applymap_nd_call_check(me, mode, nm, ntest, Q0, ldq, P0, ldp, qmap, pmap)) ||
-        (tan && (rc = applymap_nd_tangent_check(me, family, mode, nm, tan->lyap))))
+        (tan && (rc = applymap_nd_tangent_check(me, family, mode, nm, tan->lyap))) ||
+        (dir == MAP_BACKWARD && (rc = applymap_nd_inverse_check(me, mode))))
         return rc;
     if (n0 < 0 || (n0 > 0 && (!X || !alpha || ldx < (size_t)n0))) {
         set_error(std::string(me) + ": n0 < 0, null X or alpha, or ldx < n0");
@@ -111,7 +114,7 @@ static int applymap_nd_host(const char *me, int family, int d, int mode, int nm,
     if ((rc = dX.alloc((size_t)n0 * D * sizeof(double))) || (rc = upload(dal, alpha, (size_t)D * n0, st))) return rc;
     if (n0 > 0 && (rc = copy_in(dX.p, (size_t)n0, X, ldx, (size_t)n0, D, st))) return rc;
     return applymap_nd_io(family, d, mode, nm, ntest, n0, dX.as<double>(), (size_t)n0, hyp, nhyp, dal.as<double>(), Q0, ldq, P0, ldp,
-                          qmap, pmap, iters, st, tan);
+                          qmap, pmap, iters, st, tan, dir);
 }
 
 // sgpr_applymap_sections_host (tan null) and sgpr_applymap_sections_tangent_host: every argument is checked before any device call
@@ -609,6 +612,15 @@ int sgpr_applymap_nd_tangent_host(int family, int d, int mode, int nm, int ntest
     const MapTangentOut tan = {jac, mono, lyap};
     return applymap_nd_host("applymap_nd_tangent_host", family, d, mode, nm, ntest, hyp, nhyp, n0, X, ldx, alpha, Q0, ldq, P0, ldp,
                             qmap, pmap, iters, &tan);
+}
+
+/* The backward orbit: Q0 / P0 hold the images (Q, P), row i of qmap / pmap is the i-th preimage. */
+int sgpr_applymap_nd_inverse_host(int family, int d, int mode, int nm, int ntest, const double *hyp, int nhyp, int n0,
+                                  const double *X, size_t ldx, const double *alpha, const double *Q0, size_t ldq, const double *P0,
+                                  size_t ldp, double *qmap, double *pmap, int *iters)
+{
+    return applymap_nd_host("applymap_nd_inverse_host", family, d, mode, nm, ntest, hyp, nhyp, n0, X, ldx, alpha, Q0, ldq, P0, ldp,
+                            qmap, pmap, iters, nullptr, MAP_BACKWARD);
 }
 
 int sgpr_release_device_streams(int device)

@@ -823,6 +823,26 @@ int sgpr_fit_applymap_nd_tangent(sgpr_fit_t f, int mode, int nm, int ntest, cons
     return check_solve(me, f);
 }
 
+/* The backward orbit of the same map (gram_nd.hip: applymap_nd_inverse_kernel): Q0 / P0 hold the images, row i the i-th preimage. */
+int sgpr_fit_applymap_nd_inverse(sgpr_fit_t f, int mode, int nm, int ntest, const double *Q0, size_t ldq, const double *P0,
+                                 size_t ldp, double *qmap, double *pmap, int *iters)
+{
+    const char *me = "fit_applymap_nd_inverse";
+    int rc = guard(me, f, true);
+    if (rc) return rc;
+    if ((rc = applymap_nd_call_check(me, mode, nm, ntest, Q0, ldq, P0, ldp, qmap, pmap))) return rc;
+    if ((rc = applymap_nd_inverse_check(me, mode))) return rc;
+    if ((rc = guard(me, f, true, NEED_SOLVED | NEED_ALL_BLOCKS | NEED_PAIR_KERNEL))) return rc;
+    if (ntest == 0) return 0;
+    double hyp1[4];
+    int nhyp;
+    const double *hyp = fit_hyp_nd(f, hyp1, &nhyp);
+    if ((rc = applymap_nd_io(f->family, f->d, mode, nm, ntest, f->npts, f->dX, (size_t)f->npts, hyp, nhyp, f->dalpha, Q0, ldq, P0,
+                             ldp, qmap, pmap, iters, f->st, nullptr, MAP_BACKWARD)))
+        return rc;
+    return check_solve(me, f);
+}
+
 // cond_2(Ky) from below: lambda_max by power iteration on Ky v (the rows of K are re-evaluated from the training points by the
 // prediction kernel -- the matrix itself has been overwritten by its factor -- plus |sig2n| v), lambda_min by inverse iteration
 // with the cached factor (two strip solves per step).  Both are Rayleigh quotients of unit vectors, so lambda_max is a lower

@@ -113,16 +113,31 @@ inline int applymap_nd_tangent_check(const char *entry, int family, int mode, in
     return 0;
 }
 
+// ... and what the two backward entries (sgpr_fit_applymap_nd_inverse, sgpr_applymap_nd_inverse_host) ask on top of it: the
+// explicit product-family map P = p - G_q(q, p) has another inverse (a second solve, in p), and the sum kernels' explicit and
+// implicit maps coincide, so mode 0 inverts them already -- the bit is refused for every family
+inline int applymap_nd_inverse_check(const char *entry, int mode)
+{
+    if (mode & SGPR_MAP_EXPLICIT) {
+        set_error(std::string(entry) + ": SGPR_MAP_EXPLICIT has no backward step (only the implicit map is inverted; for the sum kernels "
+                                       "the two coincide)");
+        return SGPR_E_ARG;
+    }
+    return 0;
+}
+
 // the host arrays a tangent entry fills, each or null: jac [nm - 1][ntest][2d][2d], mono [ntest][2d][2d], lyap [ntest][2d]
 struct MapTangentOut {
     double *jac, *mono, *lyap;
 };
 
 // uploads the start points, runs applymap_nd on device-resident training points and alpha, brings the orbits back and waits;
-// with `tan` the launch is applymap_nd_tangent and its outputs come back too
+// with `tan` the launch is applymap_nd_tangent and its outputs come back too; MAP_BACKWARD runs applymap_nd_inverse (no tangent)
+enum MapDirection { MAP_FORWARD, MAP_BACKWARD };
 inline int applymap_nd_io(int family, int d, int mode, int nm, int ntest, int n0, const double *dXtr, size_t ldxtr,
                           const double *hyp, int nhyp, const double *dalpha, const double *Q0, size_t ldq, const double *P0,
-                          size_t ldp, double *qmap, double *pmap, int *iters, hipStream_t st, const MapTangentOut *tan = nullptr)
+                          size_t ldp, double *qmap, double *pmap, int *iters, hipStream_t st, const MapTangentOut *tan = nullptr,
+                          MapDirection dir = MAP_FORWARD)
 {
     int rc;
     DevBuf q0, p0, qm, pm, it, dj, dm, dl;
@@ -136,7 +151,10 @@ inline int applymap_nd_io(int family, int d, int mode, int nm, int ntest, int n0
                 (tan->lyap && (rc = dl.alloc(lyap_bytes)))))
         return rc;
     if ((rc = copy_in(q0.p, nt, Q0, ldq, nt, d, st)) || (rc = copy_in(p0.p, nt, P0, ldp, nt, d, st))) return rc;
-    if (!tan)
+    if (dir == MAP_BACKWARD)
+        rc = applymap_nd_inverse(family, d, mode, nm, ntest, n0, dXtr, ldxtr, hyp, nhyp, dalpha, q0.as<double>(), p0.as<double>(),
+                                 qm.as<double>(), pm.as<double>(), iters ? it.as<int>() : nullptr, st);
+    else if (!tan)
         rc = applymap_nd(family, d, mode, nm, ntest, n0, dXtr, ldxtr, hyp, nhyp, dalpha, q0.as<double>(), p0.as<double>(),
                          qm.as<double>(), pm.as<double>(), iters ? it.as<int>() : nullptr, st);
     else

@@ -120,6 +120,10 @@ int predict_nd(int family, int d, int m, const double *Xt, size_t ldxt, int n0, 
 int applymap_nd(int family, int d, int mode, int nm, int ntest, int n0, const double *Xtr, size_t ldxtr, const double *hyp,
                 int nhyp, const double *alpha, const double *Q0, const double *P0, double *qmap, double *pmap, int *iters,
                 hipStream_t st);
+// the backward orbit with the same buffers: Q0 / P0 hold the images (Q, P), row i of qmap / pmap is the i-th preimage
+int applymap_nd_inverse(int family, int d, int mode, int nm, int ntest, int n0, const double *Xtr, size_t ldxtr, const double *hyp,
+                        int nhyp, const double *alpha, const double *Q0, const double *P0, double *qmap, double *pmap, int *iters,
+                        hipStream_t st);
 // the same with the tangent map (maptan.h): jac [nm - 1][ntest][2d][2d], mono [ntest][2d][2d], lyap [ntest][2d], each or null
 int applymap_nd_tangent(int family, int d, int mode, int nm, int ntest, int n0, const double *Xtr, size_t ldxtr, const double *hyp,
                         int nhyp, const double *alpha, const double *Q0, const double *P0, double *qmap, double *pmap, int *iters,

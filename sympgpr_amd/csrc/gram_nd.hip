@@ -411,6 +411,109 @@ __global__ __launch_bounds__(TT) void applymap_nd_kernel(const std::conditional_
     if constexpr (TAN) maptan_finish<D>(a, k);
 }
 
+// The backward step: rows qmap[0], pmap[0] hold (Q, P), and one step returns the (q, p) that the kernel above takes there.  The
+// point of the passes is the same x = (q, P); now P is known and q is not: Newton on f(q) = q + G_P(q, P) - Q = 0 from q = Q,
+// then p = P + G_q(q, P).  The Jacobian is I + dG_P/dq, and G is a gradient (of the generating function), so dG_P/dq is the
+// transpose of the dG_q/dP that mapnd_pass<.., true> sums: the same pass, the same 2d + d^2 sums, newton_step on the transposed
+// block.  The closing pass and the acceptance rule are the forward ones with the roles swapped (|f| <= 1e-8 max(1, max|Q|));
+// SGPR_MAP_WRAP_Q wraps the q that was solved for.  The sum kernels' G_P does not depend on q: the first step is exact.
+// SGPR_MAP_EXPLICIT never arrives here (the C entries refuse it).  Staging, TT, the seq alternation and the lost-orbit rule (NaN
+// from that step on, iters = -1) are those of applymap_nd_kernel; there is no TAN instance -- the backward step's Jacobian is
+// the symplectic inverse of the forward step matrix at the same (q, P).
+template <int FAM, int D, int TT>
+__global__ __launch_bounds__(TT) void applymap_nd_inverse_kernel(const MapNdArgs a)
+{
+    constexpr int d = D / 2, W = TT / 64, NSMAX = D + d * d;
+    constexpr bool HAS_STAGE = TT == MAPND_T_SMALL;
+    __shared__ double part[2][W * NSMAX];
+    __shared__ double res[2][NSMAX];
+    __shared__ double stage[HAS_STAGE ? 2 * D * MAPND_STAGE_PTS : 1];
+    const int k = blockIdx.x, n0 = a.k.mj;
+    const double *stg = nullptr;
+    if (HAS_STAGE && n0 <= MAPND_STAGE_PTS) {               // as applymap_nd_kernel: every thread reads back what it wrote itself
+        for (int j = threadIdx.x; j < n0; j += TT) {
+#pragma unroll
+            for (int c = 0; c < D; ++c) {
+                stage[c * MAPND_STAGE_PTS + j] = a.k.Xa[(size_t)j + (size_t)c * a.k.ldxa];
+                stage[(D + c) * MAPND_STAGE_PTS + j] = a.alpha[(size_t)c * n0 + j];
+            }
+        }
+        stg = stage;
+    }
+    unsigned seq = 0;
+    double Q[d], P[d];                                      // the point the next step starts from: the image (Q, P)
+#pragma unroll
+    for (int c = 0; c < d; ++c) {
+        Q[c] = a.Q0[(size_t)k + (size_t)c * a.ntest];
+        P[c] = a.P0[(size_t)k + (size_t)c * a.ntest];
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int c = 0; c < d; ++c) { a.qmap[(size_t)k * d + c] = Q[c]; a.pmap[(size_t)k * d + c] = P[c]; }
+    }
+    const double nan = __builtin_nan("");
+    const double twopi = 6.283185307179586477;
+    for (int i = 0; i + 1 < a.nm; ++i) {
+        bool good = true;                                   // block-uniform, like everything below
+#pragma unroll
+        for (int c = 0; c < d; ++c) good = good && finite_d(Q[c]) && finite_d(P[c]);   // a lost (NaN) orbit stays lost
+        int its = 0;
+        double x[D], G[D], J[d * d], q[d], p[d];
+#pragma unroll
+        for (int c = 0; c < d; ++c) { x[c] = Q[c]; x[d + c] = P[c]; q[c] = nan; p[c] = nan; }
+        if (good) {                                         // Newton on f(q) = q + G_P(q, P) - Q from q = Q
+            for (int it = 0; it < a.maxiter; ++it) {
+                ++seq;
+                mapnd_pass<FAM, D, TT, true>(a, x, stg, G, J, part[seq & 1u], res[seq & 1u]);
+                double f[d], Jt[d * d], dq[d], step = 0.0, size = 1.0;
+#pragma unroll
+                for (int c = 0; c < d; ++c) {
+                    f[c] = x[c] + G[d + c] - Q[c];
+#pragma unroll
+                    for (int e = 0; e < d; ++e) Jt[c * d + e] = J[e * d + c];   // dG_P,c / dq_e = dG_q,e / dP_c
+                }
+                if (!newton_step<d>(Jt, f, dq)) { good = false; break; }
+#pragma unroll
+                for (int c = 0; c < d; ++c) {
+                    x[c] += dq[c];
+                    step = fmax(step, fabs(dq[c]));
+                    size = fmax(size, fabs(x[c]));
+                }
+                ++its;
+                if (step <= a.tol * size) break;
+            }
+        }
+        if (good) {                                         // one pass without the Jacobian at the final q: the residual and G_q
+            ++seq;
+            mapnd_pass<FAM, D, TT, false>(a, x, stg, G, J, part[seq & 1u], res[seq & 1u]);
+            double r = 0.0, qmax = 1.0;
+#pragma unroll
+            for (int c = 0; c < d; ++c) {
+                const double fc = x[c] + G[d + c] - Q[c];
+                good = good && finite_d(fc);
+                r = fmax(r, fabs(fc));
+                qmax = fmax(qmax, fabs(Q[c]));
+            }
+            good = good && r <= 1e-8 * qmax;                // the forward rule with the roles swapped
+#pragma unroll
+            for (int c = 0; c < d; ++c) {
+                p[c] = P[c] + G[c];
+                good = good && finite_d(p[c]);
+                q[c] = x[c];
+                if (a.mode & SGPR_MAP_WRAP_Q) q[c] -= twopi * floor(q[c] / twopi);
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < d; ++c) { Q[c] = good ? q[c] : nan; P[c] = good ? p[c] : nan; }
+        if (threadIdx.x == 0) {
+            const size_t o = ((size_t)(i + 1) * a.ntest + k) * d;
+#pragma unroll
+            for (int c = 0; c < d; ++c) { a.qmap[o + c] = Q[c]; a.pmap[o + c] = P[c]; }
+            if (a.iters) a.iters[(size_t)i * a.ntest + k] = good ? its : -1;
+        }
+    }
+}
+
 // ---- genfun: the generating function F itself, of which every entry above returns derivatives ------------------------------
 // The observations are (dF/dq, dF/dP), so cov(F(x*), observation c of training point j) = d(sig k)/dx_train,c = E_c g_c with
 // dx = x_train - x* (E, g as above), and
@@ -616,6 +719,29 @@ int applymap_nd(int family, int d, int mode, int nm, int ntest, int n0, const do
         constexpr int F = decltype(fam)::value, D = decltype(dd)::value;
         if (small) hipLaunchKernelGGL((applymap_nd_kernel<F, D, MAPND_T_SMALL>), dim3(ntest), dim3(MAPND_T_SMALL), 0, st, a);
         else       hipLaunchKernelGGL((applymap_nd_kernel<F, D, MAPND_T_LARGE>), dim3(ntest), dim3(MAPND_T_LARGE), 0, st, a);
+        SGPR_CHECK_LAUNCH();
+        return 0;
+    });
+}
+
+// the backward orbit: Q0 / P0 hold the images (Q, P), row i of qmap / pmap is the i-th preimage.  Arguments and shapes as
+// applymap_nd; mode: SGPR_MAP_WRAP_Q only (the C entries refuse SGPR_MAP_EXPLICIT)
+int applymap_nd_inverse(int family, int d, int mode, int nm, int ntest, int n0, const double *Xtr, size_t ldxtr, const double *hyp,
+                        int nhyp, const double *alpha, const double *Q0, const double *P0, double *qmap, double *pmap, int *iters,
+                        hipStream_t st)
+{
+    MapNdArgs a{};
+    int rc = fill_args(family, d, hyp, nhyp, a.k);
+    if (rc) return rc;
+    if (nm <= 0 || ntest <= 0) return 0;
+    a.k.mj = n0; a.k.Xa = Xtr; a.k.ldxa = ldxtr;
+    a.nm = nm; a.ntest = ntest; a.mode = mode; a.maxiter = 60; a.tol = 1e-13;   // as applymap_nd
+    a.alpha = alpha; a.Q0 = Q0; a.P0 = P0; a.qmap = qmap; a.pmap = pmap; a.iters = iters;
+    const bool small = applymap_nd_threads(n0) == MAPND_T_SMALL;
+    return dispatch_nd(family, d, [&](auto fam, auto dd) {
+        constexpr int F = decltype(fam)::value, D = decltype(dd)::value;
+        if (small) hipLaunchKernelGGL((applymap_nd_inverse_kernel<F, D, MAPND_T_SMALL>), dim3(ntest), dim3(MAPND_T_SMALL), 0, st, a);
+        else       hipLaunchKernelGGL((applymap_nd_inverse_kernel<F, D, MAPND_T_LARGE>), dim3(ntest), dim3(MAPND_T_LARGE), 0, st, a);
         SGPR_CHECK_LAUNCH();
         return 0;
     });

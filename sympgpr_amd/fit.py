@@ -180,6 +180,24 @@ class SympFit:
                                                        opt("lyap")), "sgpr_fit_applymap_nd_tangent")
         return qmap, pmap, iters, out
 
+    def applymap_pairs_inverse(self, nm, Q0, P0, wrap_q=False, return_iters=False):
+        """applymap_pairs backwards: Q0, P0 (Ntest, d) -- for d = 1 also (Ntest,) -- are points (Q, P), and row i of qmap, pmap
+        (nm, Ntest, d) is their i-th preimage under the fit's (implicit) map, row 0 the start points: per step
+        q + G_P(q, P) - Q = 0 is solved for q by Newton from q = Q with the transposed Jacobian block of the forward solve, then
+        p = P + G_q(q, P).  wrap_q: every solved q_i mod 2 pi.  There is no explicit mode: the explicit product-family map has
+        another inverse, and for the sum kernels the two maps coincide.  NaN from the step at which an orbit is lost; with
+        return_iters also iters (nm - 1, Ntest), -1 for a lost orbit.  The tangent map of a backward orbit:
+        maps.symplectic_inverse.  Needs a solved fit (run()); not defined for reg=True and block="qq" / "PP" fits."""
+        from . import maps
+        Q0, P0 = maps.start_points_nd(Q0, P0, self.d)
+        Ntest = Q0.shape[0]
+        nm, qmap, pmap, iters = maps.map_outputs_nd(nm, Ntest, self.d)
+        mode = maps.WRAP_Q if wrap_q else 0
+        L.check(self._lib.sgpr_fit_applymap_nd_inverse(self._h, mode, nm, Ntest, L.dptr(Q0), max(Ntest, 1), L.dptr(P0),
+                                                       max(Ntest, 1), L.dptr(qmap), L.dptr(pmap),
+                                                       iters.ctypes.data_as(C.POINTER(C.c_int))), "sgpr_fit_applymap_nd_inverse")
+        return (qmap, pmap, iters) if return_iters else (qmap, pmap)
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             self._lib.sgpr_fit_destroy(self._h)

@@ -18,6 +18,8 @@ For fits with d canonical pairs (d = 1, 2, 3) the map is run_map_nd / SympFit.ap
 Jacobian on the d unknowns P, one workgroup per orbit (include/sympgpr_hip.h: sgpr_applymap_nd_host).
 run_map_nd_tangent / SympFit.applymap_pairs_tangent return the same orbits with the Jacobian of every step, their product and
 finite-time Lyapunov exponents (sgpr_applymap_nd_tangent_host); symplectic_defect and greene_residue read them.
+run_map_nd_inverse / SympFit.applymap_pairs_inverse iterate the same map backwards (sgpr_applymap_nd_inverse_host): Newton on the
+d unknowns q with the transposed Jacobian; symplectic_inverse turns a forward step matrix into the backward step's.
 genfun_along evaluates the learned generating function itself along computed orbits (sgpr_fit_predict_genfun).
 
 alpha = Kyinv ztrain is formed once (the reference re-multiplies Kyinv inside every calcP / calcQ
@@ -297,6 +299,35 @@ def run_map_nd_tangent(family, d, mode, nm, hyp, X, alpha, Q0, P0, jac=True, mon
     return qmap, pmap, iters, out
 
 
+def map_mode_nd_inverse(mode):
+    mode = map_mode_nd(mode)
+    if mode & EXPLICIT:
+        raise ValueError("the backward d-pair map inverts the implicit map only: EXPLICIT has no backward step "
+                         "(for the sum kernels the two maps coincide, use mode 0)")
+    return mode
+
+
+def run_map_nd_inverse(family, d, mode, nm, hyp, X, alpha, Q0, P0, return_iters=False):
+    """run_map_nd backwards: Q0, P0 (Ntest, d) are points (Q, P) and row i of qmap, pmap (nm, Ntest, d) is their i-th preimage
+    under the map of run_map_nd with the same X, alpha, hyp (row 0 the start points).  A step solves q + G_P(q, P) - Q = 0 for q
+    by Newton from q = Q with the transposed Jacobian block of the forward solve, then p = P + G_q(q, P); mode = WRAP_Q (the
+    solved q mod 2 pi) or 0 -- EXPLICIT raises ValueError (the explicit product-family map has another inverse).  NaN from the
+    step at which an orbit is lost; with return_iters also iters (nm - 1, Ntest): Newton iterations, -1 for a lost orbit.  Every
+    step runs on the device, one workgroup per orbit (sgpr_applymap_nd_inverse_host)."""
+    lib = L.load_library()
+    d, X, alpha, hyp = _nd_inputs(d, X, alpha, hyp)
+    N0 = X.shape[0]
+    mode = map_mode_nd_inverse(mode)
+    Q0, P0 = start_points_nd(Q0, P0, d)
+    Ntest = Q0.shape[0]
+    nm, qmap, pmap, iters = map_outputs_nd(nm, Ntest, d)
+    L.check(lib.sgpr_applymap_nd_inverse_host(L.family_id(family), d, mode, nm, Ntest, L.dptr(hyp), len(hyp), N0, L.dptr(X),
+                                              max(N0, 1), L.dptr(alpha), L.dptr(Q0), max(Ntest, 1), L.dptr(P0), max(Ntest, 1),
+                                              L.dptr(qmap), L.dptr(pmap), iters.ctypes.data_as(C.POINTER(C.c_int))),
+            "sgpr_applymap_nd_inverse_host")
+    return (qmap, pmap, iters) if return_iters else (qmap, pmap)
+
+
 def genfun_along(fit, qmap, pmap, ref=None):
     """The fit's learned generating function along computed orbits: F(q_k, P_{k+1}) for k = 0 .. nm-2 -> (nm - 1, Ntest), an
     energy-like diagnostic that needs no analytic H.  qmap, pmap: (nm, Ntest) or (nm, Ntest, d) as applymap / applymap_pairs
@@ -323,6 +354,23 @@ def symplectic_defect(M):
     J = np.zeros((2 * d, 2 * d))
     J[:d, d:], J[d:, :d] = np.eye(d), -np.eye(d)
     return np.abs(np.swapaxes(M, -1, -2) @ J @ M - J).max(axis=(-2, -1))
+
+
+def symplectic_inverse(M):
+    """-J M^T J over the last two axes of M (..., D, D), J as in symplectic_defect: the inverse of a symplectic M, exact (the
+    blocks [[a, b], [c, e]] are rearranged to [[e^T, -b^T], [-c^T, a^T]], no arithmetic).
+    This is how the tangent map of a BACKWARD orbit is obtained without a kernel of its own: the Jacobian of backward step i,
+    (Q, P) -> (q, p), is the symplectic inverse of the forward step matrix at the same (q, P).  Run run_map_nd_tangent /
+    SympFit.applymap_pairs_tangent for one step (nm = 2) from each row i + 1 of the backward orbit and apply this to jac[0]."""
+    M = np.asarray(M, dtype=np.float64)
+    if M.ndim < 2 or M.shape[-1] != M.shape[-2] or M.shape[-1] % 2:
+        raise ValueError("M must be (..., D, D) with D even")
+    d = M.shape[-1] // 2
+    T = np.swapaxes(M, -1, -2)
+    out = np.empty_like(T)
+    out[..., :d, :d], out[..., :d, d:] = T[..., d:, d:], -T[..., d:, :d]      # T = M^T holds [[a^T, c^T], [b^T, e^T]]
+    out[..., d:, :d], out[..., d:, d:] = -T[..., :d, d:], T[..., :d, :d]
+    return out
 
 
 def greene_residue(mono):
