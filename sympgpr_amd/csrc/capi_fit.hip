@@ -718,7 +718,7 @@ int sgpr_fit_predict_cov(sgpr_fit_t f, int m, const double *Xt, size_t ldxt, dou
     return 0;
 }
 
-/* The generating function F itself at m test points (gram_nd.hip: genfun_nd_kernel), relative to `ref` if one is given, and
+/* The generating function F itself at m test points (genfun_nd.hip: genfun_nd_kernel), relative to `ref` if one is given, and
  * with `var` its latent posterior variance, in chunks of mc = 256 points:
  *   per chunk  V = the cross-covariance columns v_t - v_0 (n x mc, genfun_cross_kernel) and the prior of F(x_t) - F(x_0),
  *              V := L^-1 V (potrs_mat_fwd, as sgpr_fit_predict_cov), var_t = prior_t - |V_t|^2 (postcov.hip with D = 1: the
@@ -783,7 +783,7 @@ int sgpr_fit_predict_genfun(sgpr_fit_t f, int m, const double *Xt, size_t ldxt, 
     return 0;
 }
 
-/* nm steps of the fit's symplectic map (gram_nd.hip: applymap_nd_kernel) for ntest orbits, with the fit's own device-resident
+/* nm steps of the fit's symplectic map (map_nd.hip: applymap_nd_kernel) for ntest orbits, with the fit's own device-resident
  * training points and alpha; d = 1 fits run the D = 2 instance of the d-pair kernel. */
 int sgpr_fit_applymap_nd(sgpr_fit_t f, int mode, int nm, int ntest, const double *Q0, size_t ldq, const double *P0, size_t ldp,
                          double *qmap, double *pmap, int *iters)
@@ -823,7 +823,7 @@ int sgpr_fit_applymap_nd_tangent(sgpr_fit_t f, int mode, int nm, int ntest, cons
     return check_solve(me, f);
 }
 
-/* The backward orbit of the same map (gram_nd.hip: applymap_nd_inverse_kernel): Q0 / P0 hold the images, row i the i-th preimage. */
+/* The backward orbit of the same map (map_nd.hip: applymap_nd_inverse_kernel): Q0 / P0 hold the images, row i the i-th preimage. */
 int sgpr_fit_applymap_nd_inverse(sgpr_fit_t f, int mode, int nm, int ntest, const double *Q0, size_t ldq, const double *P0,
                                  size_t ldp, double *qmap, double *pmap, int *iters)
 {

@@ -115,6 +115,9 @@ int gram_nd_sel(int family, int d, int mi, int mj, const double *Xb, size_t ldxb
                 const double *hyp, int nhyp, double *K, size_t ld, const long *roff, const long *coff, hipStream_t st);
 int predict_nd(int family, int d, int m, const double *Xt, size_t ldxt, int n0, const double *Xtr, size_t ldxtr,
                const double *hyp, int nhyp, const double *alpha, double *out, hipStream_t st);
+bool family_is_sum(int family);   // k = sum of the factors (family B, or a USER sum kernel): the explicit maps
+
+// ---- map_nd.hip : the symplectic map of those fits, forwards, with its tangent map and backwards
 // nm steps of the d-pair symplectic map for ntest orbits, one workgroup per orbit (device buffers: Xtr n0 x 2d, alpha 2 d n0,
 // Q0 / P0 ntest x d with leading dimension ntest, qmap / pmap [nm][ntest][d], iters [nm - 1][ntest] or null)
 int applymap_nd(int family, int d, int mode, int nm, int ntest, int n0, const double *Xtr, size_t ldxtr, const double *hyp,
@@ -128,6 +131,8 @@ int applymap_nd_inverse(int family, int d, int mode, int nm, int ntest, int n0, 
 int applymap_nd_tangent(int family, int d, int mode, int nm, int ntest, int n0, const double *Xtr, size_t ldxtr, const double *hyp,
                         int nhyp, const double *alpha, const double *Q0, const double *P0, double *qmap, double *pmap, int *iters,
                         double *jac, double *mono, double *lyap, hipStream_t st);
+
+// ---- genfun_nd.hip : the generating function of those fits
 // the generating function F itself at m device-resident test points (has_ref: row m of Xt is a reference point, F has m + 1
 // entries and F[t] := F(x_t) - F(x_0)); one chunk of its variance: the cross-covariance columns V (2 d n0 x mc) and the prior
 int genfun_nd(int family, int d, int m, const double *Xt, size_t ldxt, bool has_ref, int n0, const double *Xtr, size_t ldxtr,
@@ -135,7 +140,6 @@ int genfun_nd(int family, int d, int m, const double *Xt, size_t ldxt, bool has_
 int genfun_cross_nd(int family, int d, int mc, const double *Xt, size_t ldxt, const double *x0, size_t ldx0, int n0,
                     const double *Xtr, size_t ldxtr, const double *hyp, int nhyp, double *V, size_t ldv, double *prior,
                     size_t prior_stride, hipStream_t st);
-bool family_is_sum(int family);   // k = sum of the factors (family B, or a USER sum kernel): the explicit maps
 
 // ---- gemm_f64.hip : C = beta C + alpha A B^T on fp64 MFMA tiles
 int gemm_nt(int m, int n, int k, double alpha, const double *A, size_t lda, const double *B,

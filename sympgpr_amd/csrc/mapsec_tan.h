@@ -1,7 +1,7 @@
 // mapsec_tan.h -- the tangent map of the sectioned d = 1 map: the TAN = true half of applymap_sections_kernel.
 //
 // Included by map.hip INSIDE its anonymous namespace, after block_sum2 and MapSecArgs, which it uses as they are; nothing else
-// includes it.  maptan.h (the d-pair map's tangent, gram_nd.hip) has the derivation; this is its D = 2 case restated on the
+// includes it.  maptan.h (the d-pair map's tangent, map_nd.hip) has the derivation; this is its D = 2 case restated on the
 // d = 1 kernels' constants (KConst) and data layout, with the operation order of maptan.h at D = 2.
 //
 // One step (q, p) -> (Q, P) of section m solves P = p - G_q(q, P), then Q = q + G_P(q, P).  After an accepted step one more pass

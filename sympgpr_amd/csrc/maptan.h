@@ -1,7 +1,7 @@
 // maptan.h -- the tangent map of the d-pair symplectic map: the TAN = true half of applymap_nd_kernel.
 //
-// Included by gram_nd.hip INSIDE its anonymous namespace, after the map's own pieces (NdArgs, MapNdArgs, all_coords, weights,
-// block_sum_n, finite_d), which it uses as they are; nothing else includes it.
+// Included by map_nd.hip INSIDE its anonymous namespace, after the map's own pieces (NdArgs, MapNdArgs, all_coords, weights,
+// block_sum_n, finite_d), which it uses as they are; map_nd.hip is its only includer.
 //
 // One step (q, p) -> (Q, P) of the map solves P = p - G_q(q, P), then Q = q + G_P(q, P), with G(x) = K*(x) alpha the gradient of
 // the learned generating function.  Its Jacobian needs the Hessian H = dG/dx (D x D, symmetric) at the accepted (q, P): with

@@ -1,7 +1,7 @@
 // nd_eval.h -- the entry formulas of the d-pair kernels (gram_nd.hip has the derivation), shared by gram_nd.hip (Gram build,
-// prediction, map, generating function) and batch.hip (the batched d-pair fits).  Per-problem constants live in NdConst: the
-// single-problem kernels carry one inside their argument block (NdArgs::c), the batched kernels read one per problem, as
-// they read one KConst per problem for d = 1.
+// prediction), map_nd.hip (the symplectic map), genfun_nd.hip (the generating function) and batch.hip (the batched d-pair
+// fits).  Per-problem constants live in NdConst: the single-problem kernels carry one inside their argument block
+// (NdArgs::c, nd_args.h), the batched kernels read one per problem, as they read one KConst per problem for d = 1.
 #pragma once
 #include <type_traits>
 #include "common.h"

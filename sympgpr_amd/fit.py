@@ -154,13 +154,8 @@ class SympFit:
         return_iters also iters (nm - 1, Ntest): Newton iterations per solve, 0 in explicit mode, -1 for a lost orbit.
         Needs a solved fit (run()); not defined for reg=True and block="qq" / "PP" fits."""
         from . import maps
-        Q0, P0 = maps.start_points_nd(Q0, P0, self.d)
-        Ntest = Q0.shape[0]
-        nm, qmap, pmap, iters = maps.map_outputs_nd(nm, Ntest, self.d)
         mode = (maps.WRAP_Q if wrap_q else 0) | (maps.EXPLICIT if explicit else 0)
-        L.check(self._lib.sgpr_fit_applymap_nd(self._h, mode, nm, Ntest, L.dptr(Q0), max(Ntest, 1), L.dptr(P0), max(Ntest, 1),
-                                               L.dptr(qmap), L.dptr(pmap), iters.ctypes.data_as(C.POINTER(C.c_int))),
-                "sgpr_fit_applymap_nd")
+        qmap, pmap, iters, _ = maps._map_call_nd("sgpr_fit_applymap_nd", (self._h,), self.d, mode, nm, Q0, P0)
         return (qmap, pmap, iters) if return_iters else (qmap, pmap)
 
     def applymap_pairs_tangent(self, nm, Q0, P0, wrap_q=False, explicit=False, jac=True, mono=True, lyap=True):
@@ -168,17 +163,8 @@ class SympFit:
         the requested arrays jac (nm - 1, Ntest, D, D), mono (Ntest, D, D), lyap (Ntest, D) with D = 2 d -- see
         maps.run_map_nd_tangent; maps.symplectic_defect and maps.greene_residue (d = 1) read them.  explicit: sum kernels only."""
         from . import maps
-        Q0, P0 = maps.start_points_nd(Q0, P0, self.d)
-        Ntest = Q0.shape[0]
-        nm, qmap, pmap, iters = maps.map_outputs_nd(nm, Ntest, self.d)
-        out = maps.tangent_outputs_nd(nm, Ntest, self.d, jac, mono, lyap)
         mode = (maps.WRAP_Q if wrap_q else 0) | (maps.EXPLICIT if explicit else 0)
-        opt = lambda name: L.dptr(out[name]) if name in out else None
-        L.check(self._lib.sgpr_fit_applymap_nd_tangent(self._h, mode, nm, Ntest, L.dptr(Q0), max(Ntest, 1), L.dptr(P0),
-                                                       max(Ntest, 1), L.dptr(qmap), L.dptr(pmap),
-                                                       iters.ctypes.data_as(C.POINTER(C.c_int)), opt("jac"), opt("mono"),
-                                                       opt("lyap")), "sgpr_fit_applymap_nd_tangent")
-        return qmap, pmap, iters, out
+        return maps._map_call_nd("sgpr_fit_applymap_nd_tangent", (self._h,), self.d, mode, nm, Q0, P0, tangent=(jac, mono, lyap))
 
     def applymap_pairs_inverse(self, nm, Q0, P0, wrap_q=False, return_iters=False):
         """applymap_pairs backwards: Q0, P0 (Ntest, d) -- for d = 1 also (Ntest,) -- are points (Q, P), and row i of qmap, pmap
@@ -189,13 +175,8 @@ class SympFit:
         return_iters also iters (nm - 1, Ntest), -1 for a lost orbit.  The tangent map of a backward orbit:
         maps.symplectic_inverse.  Needs a solved fit (run()); not defined for reg=True and block="qq" / "PP" fits."""
         from . import maps
-        Q0, P0 = maps.start_points_nd(Q0, P0, self.d)
-        Ntest = Q0.shape[0]
-        nm, qmap, pmap, iters = maps.map_outputs_nd(nm, Ntest, self.d)
         mode = maps.WRAP_Q if wrap_q else 0
-        L.check(self._lib.sgpr_fit_applymap_nd_inverse(self._h, mode, nm, Ntest, L.dptr(Q0), max(Ntest, 1), L.dptr(P0),
-                                                       max(Ntest, 1), L.dptr(qmap), L.dptr(pmap),
-                                                       iters.ctypes.data_as(C.POINTER(C.c_int))), "sgpr_fit_applymap_nd_inverse")
+        qmap, pmap, iters, _ = maps._map_call_nd("sgpr_fit_applymap_nd_inverse", (self._h,), self.d, mode, nm, Q0, P0)
         return (qmap, pmap, iters) if return_iters else (qmap, pmap)
 
     def close(self):

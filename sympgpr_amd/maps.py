@@ -232,16 +232,7 @@ def run_map_nd(family, d, mode, nm, hyp, X, alpha, Q0, P0, return_iters=False):
     Q0, P0 (Ntest, d) start points; mode = WRAP_Q | EXPLICIT bits.  -> qmap, pmap of shape (nm, Ntest, d), row 0 the start
     points, NaN from the step at which an orbit is lost; with return_iters also iters (nm - 1, Ntest): Newton iterations of
     each solve, 0 in explicit mode, -1 for a lost orbit.  Every step runs on the device, one workgroup per orbit."""
-    lib = L.load_library()
-    d, X, alpha, hyp = _nd_inputs(d, X, alpha, hyp)
-    N0 = X.shape[0]
-    mode = map_mode_nd(mode)
-    Q0, P0 = start_points_nd(Q0, P0, d)
-    Ntest = Q0.shape[0]
-    nm, qmap, pmap, iters = map_outputs_nd(nm, Ntest, d)
-    L.check(lib.sgpr_applymap_nd_host(L.family_id(family), d, mode, nm, Ntest, L.dptr(hyp), len(hyp), N0, L.dptr(X), max(N0, 1),
-                                      L.dptr(alpha), L.dptr(Q0), max(Ntest, 1), L.dptr(P0), max(Ntest, 1), L.dptr(qmap),
-                                      L.dptr(pmap), iters.ctypes.data_as(C.POINTER(C.c_int))), "sgpr_applymap_nd_host")
+    qmap, pmap, iters, _ = _run_map_nd("sgpr_applymap_nd_host", family, d, map_mode_nd, mode, nm, hyp, X, alpha, Q0, P0)
     return (qmap, pmap, iters) if return_iters else (qmap, pmap)
 
 
@@ -277,26 +268,40 @@ def _optr(out, name):
     return L.dptr(out[name]) if name in out else None
 
 
+def _map_call_nd(entry_name, lead_args, d, mode, nm, Q0, P0, model_args=(), tangent=None):
+    """The one call behind the six d-pair map wrappers: the C entry `entry_name` with the arguments
+    (*lead_args, mode, nm, Ntest, *model_args, Q0, ldq, P0, ldp, qmap, pmap, iters[, jac, mono, lyap]) -- a fit's entries lead
+    with the handle, the _host entries with (family, d) and carry the model (hyp .. alpha) in model_args.
+    tangent = (jac, mono, lyap): which tangent arrays are wanted.  -> (qmap, pmap, iters, out or None).  Shape errors are
+    ValueError before the library is loaded."""
+    Q0, P0 = start_points_nd(Q0, P0, d)
+    Ntest = Q0.shape[0]
+    nm, qmap, pmap, iters = map_outputs_nd(nm, Ntest, d)
+    out = None if tangent is None else tangent_outputs_nd(nm, Ntest, d, *tangent)
+    opt = () if tangent is None else (_optr(out, "jac"), _optr(out, "mono"), _optr(out, "lyap"))
+    entry = getattr(L.load_library(), entry_name)
+    L.check(entry(*lead_args, mode, nm, Ntest, *model_args, L.dptr(Q0), max(Ntest, 1), L.dptr(P0), max(Ntest, 1), L.dptr(qmap),
+                  L.dptr(pmap), iters.ctypes.data_as(C.POINTER(C.c_int)), *opt), entry_name)
+    return qmap, pmap, iters, out
+
+
+def _run_map_nd(entry_name, family, d, check_mode, mode, nm, hyp, X, alpha, Q0, P0, tangent=None):
+    """run_map_nd, run_map_nd_tangent and run_map_nd_inverse: the model's checks, then the mode's, then _map_call_nd"""
+    d, X, alpha, hyp = _nd_inputs(d, X, alpha, hyp)
+    N0 = X.shape[0]
+    mode = check_mode(mode)
+    model = (L.dptr(hyp), len(hyp), N0, L.dptr(X), max(N0, 1), L.dptr(alpha))
+    return _map_call_nd(entry_name, (L.family_id(family), d), d, mode, nm, Q0, P0, model, tangent)
+
+
 def run_map_nd_tangent(family, d, mode, nm, hyp, X, alpha, Q0, P0, jac=True, mono=True, lyap=True):
     """run_map_nd with the tangent map: -> (qmap, pmap, iters, out).  qmap, pmap, iters have the bits of run_map_nd; `out` is a
     dict of the requested arrays: jac (nm - 1, Ntest, D, D), the Jacobian M of every step with rows (Q_1..Q_d, P_1..P_d) and
     columns (q_1..q_d, p_1..p_d), D = 2 d; mono (Ntest, D, D) = M_{nm-1} ... M_1; lyap (Ntest, D), finite-time Lyapunov exponents
     per step of the map by Benettin's method, in Gram-Schmidt column order.  All NaN from the step at which an orbit is lost.
     EXPLICIT is accepted for the sum kernels only (family B)."""
-    lib = L.load_library()
-    d, X, alpha, hyp = _nd_inputs(d, X, alpha, hyp)
-    N0 = X.shape[0]
-    mode = map_mode_nd(mode)
-    Q0, P0 = start_points_nd(Q0, P0, d)
-    Ntest = Q0.shape[0]
-    nm, qmap, pmap, iters = map_outputs_nd(nm, Ntest, d)
-    out = tangent_outputs_nd(nm, Ntest, d, jac, mono, lyap)
-    L.check(lib.sgpr_applymap_nd_tangent_host(L.family_id(family), d, mode, nm, Ntest, L.dptr(hyp), len(hyp), N0, L.dptr(X),
-                                              max(N0, 1), L.dptr(alpha), L.dptr(Q0), max(Ntest, 1), L.dptr(P0), max(Ntest, 1),
-                                              L.dptr(qmap), L.dptr(pmap), iters.ctypes.data_as(C.POINTER(C.c_int)),
-                                              _optr(out, "jac"), _optr(out, "mono"), _optr(out, "lyap")),
-            "sgpr_applymap_nd_tangent_host")
-    return qmap, pmap, iters, out
+    return _run_map_nd("sgpr_applymap_nd_tangent_host", family, d, map_mode_nd, mode, nm, hyp, X, alpha, Q0, P0,
+                       (jac, mono, lyap))
 
 
 def map_mode_nd_inverse(mode):
@@ -314,17 +319,8 @@ def run_map_nd_inverse(family, d, mode, nm, hyp, X, alpha, Q0, P0, return_iters=
     solved q mod 2 pi) or 0 -- EXPLICIT raises ValueError (the explicit product-family map has another inverse).  NaN from the
     step at which an orbit is lost; with return_iters also iters (nm - 1, Ntest): Newton iterations, -1 for a lost orbit.  Every
     step runs on the device, one workgroup per orbit (sgpr_applymap_nd_inverse_host)."""
-    lib = L.load_library()
-    d, X, alpha, hyp = _nd_inputs(d, X, alpha, hyp)
-    N0 = X.shape[0]
-    mode = map_mode_nd_inverse(mode)
-    Q0, P0 = start_points_nd(Q0, P0, d)
-    Ntest = Q0.shape[0]
-    nm, qmap, pmap, iters = map_outputs_nd(nm, Ntest, d)
-    L.check(lib.sgpr_applymap_nd_inverse_host(L.family_id(family), d, mode, nm, Ntest, L.dptr(hyp), len(hyp), N0, L.dptr(X),
-                                              max(N0, 1), L.dptr(alpha), L.dptr(Q0), max(Ntest, 1), L.dptr(P0), max(Ntest, 1),
-                                              L.dptr(qmap), L.dptr(pmap), iters.ctypes.data_as(C.POINTER(C.c_int))),
-            "sgpr_applymap_nd_inverse_host")
+    qmap, pmap, iters, _ = _run_map_nd("sgpr_applymap_nd_inverse_host", family, d, map_mode_nd_inverse, mode, nm, hyp, X, alpha,
+                                       Q0, P0)
     return (qmap, pmap, iters) if return_iters else (qmap, pmap)
 
 

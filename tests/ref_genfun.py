@@ -3,7 +3,7 @@
 The observations of a fit are (dF/dq, dF/dP), so with alpha = Ky^-1 z
     F(x*) = sig sum_j [dk/dx(x_j; x*) alpha_j + dk/dy(x_j; x*) alpha_{N+j}],
 the derivatives taken in the TRAINING point: dkdx_num / dkdy_num of the reference's kernels*.f90 (Oracle.scalar_x, ids 16 and
-17).  d = 1 goes through those; d pairs through the per-coordinate forms of gram_nd.hip (dx = x_train - x_test, g = f'/f,
+17).  d = 1 goes through those; d pairs through the per-coordinate forms of genfun_nd.hip (dx = x_train - x_test, g = f'/f,
 E = sig k for the product families and sig f_c per coordinate for the sum family B).  Both return a dict:
     F (m,), T (m,) = sum_j sum_c |term| (the scale of F's rounding error), v (m, n) the cross vectors (F = v alpha),
     kappa (m, m) the prior sig k between the test points.

@@ -1,4 +1,4 @@
-"""NumPy restatement of the backward step of the d-pair symplectic map (csrc/gram_nd.hip: applymap_nd_inverse_kernel), on top of
+"""NumPy restatement of the backward step of the d-pair symplectic map (csrc/map_nd.hip: applymap_nd_inverse_kernel), on top of
 tests/ref_tangent.py (gradient, hessian).  Written from the mathematics: G = K*(x) alpha is the gradient of the generating function
 F(q, P), G_q = p - P and G_P = Q - q, H = dG/dx symmetric with blocks A = H_qq, B = H_qP, C = H_PP.
 

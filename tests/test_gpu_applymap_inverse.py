@@ -1,4 +1,4 @@
-"""GPU tests of the backward step of the d-pair symplectic map (csrc/gram_nd.hip: applymap_nd_inverse_kernel;
+"""GPU tests of the backward step of the d-pair symplectic map (csrc/map_nd.hip: applymap_nd_inverse_kernel;
 sgpr_fit_applymap_nd_inverse, sgpr_applymap_nd_inverse_host; SympFit.applymap_pairs_inverse, maps.run_map_nd_inverse) on the data of
 tests/test_gpu_applymap_nd.py: NT = 40, NTEST = 5, NM = 6, families A, C, D at d = 2, 3.
 

@@ -1,4 +1,4 @@
-"""GPU tests of the d-pair symplectic map (csrc/gram_nd.hip: applymap_nd_kernel; sgpr_fit_applymap_nd, sgpr_applymap_nd_host;
+"""GPU tests of the d-pair symplectic map (csrc/map_nd.hip: applymap_nd_kernel; sgpr_fit_applymap_nd, sgpr_applymap_nd_host;
 SympFit.applymap_pairs, maps.run_map_nd) against the implicit equation solved on the CPU: K* rows from the oracle's build_K_nd,
 MINPACK hybrd (scipy.optimize.fsolve, xtol 1e-13) from P = p -- the solver and tolerance of _ref_map in test_gpu_examples.py --,
 then the Q update.  Tolerance: rtol = atol = 1e-8, the reference's own map tolerance (test_sympgpr.py:92-93).  Every output is
@@ -196,7 +196,7 @@ def test_lost_orbits(refs):
 
 @pytest.mark.parametrize("n0", [1, 63, 255, 257, 1025])
 def test_kernel_edges(oracle, n0):
-    """training-set sizes around the wave, the workgroup and the staging capacity of the D = 6 instance (csrc/gram_nd.hip,
+    """training-set sizes around the wave, the workgroup and the staging capacity of the D = 6 instance (csrc/map_nd.hip,
     MAPND_STAGE_PTS = 1024 points in LDS; 1025 runs the 512-thread instance from memory), random X and alpha through the
     stateless entry.
     atol scales with max |G|: the sums are larger than on the fitted data."""
