@@ -658,6 +658,38 @@ int sgpr_applymap_sections_tangent_host(int family, int mode, int nsec, int firs
                                         const double *alpha, const double *hypp, int nhypp, int n0p, const double *xtrainp,
                                         const double *ytrainp, const double *alphap, const double *Q0, const double *P0,
                                         double *qmap, double *pmap, double *pdiff, double *jac, double *mono, double *lyap);
+/* The sectioned map BACKWARDS (with nsec == 1: the one-pair map of sgpr_applymap_host backwards): row 0 of qmap / pmap is a point
+ * (Q, P), row i its i-th preimage, all nm - 1 backward steps of all ntest orbits in ONE launch.  The forward step of a section
+ * passes through the point (q, P): with r1, r2 = Kstar(1,:).alpha, Kstar(2,:).alpha at (q, P) it solves p = P + r1 for P and sets
+ * Q = q + r2.  The backward step passes through the same point with the roles swapped: P is known, it solves
+ *     g(q) = q + r2(q, P) - Q = 0   for q,   then   p = P + r1(q, P),
+ * by the forward map's secant without a first-guess GP: q0 = Q, q1 = q0 - g(q0), at most 60 updates, stopped when
+ * |q1 - q0| <= 1e-13 max(1, |q1|), when g(q1) is not finite or when g(q1) == g(q0).  The step is accepted when g(q1) is finite
+ * and |g(q1)| <= 1e-8 max(1, |Q|) (the forward rule with the roles swapped); the r1 of the last residual gives p.  Otherwise the
+ * orbit is lost: NaN in q and p from that row on.  A NaN or infinite start value loses that orbit and no other.
+ * Section order: step i (row i -> row i + 1) undoes section (first - i) mod nsec; `first` is the section whose forward step
+ * produced row 0 -- from the last row of a forward call of nm rows that began with `first_f`, first = (first_f + nm - 2) mod nsec.
+ * A run continued from row i with first' = (first - i) mod nsec repeats the bits of the uninterrupted one.
+ * mode: SGPR_MAP_WRAP_Q (the solved q mod 2 pi: the preimage of a wrapped orbit) | SGPR_MAP_LOSS_NEGP (a step whose solved p < 0
+ * loses the orbit: the backward twin of the forward "new momentum < 0"; row 0 is not tested).
+ * Layout as sgpr_applymap_sections_host without the guess GPs and without pdiff (SGPR_MAP_WRAP_P is refused, so the unwrapped
+ * momentum is pmap itself): hyp nhyp x nsec, xtrain / ytrain n0 x nsec, alpha 2 n0 x nsec, column-major and tight; Q0, P0 ntest;
+ * qmap, pmap [nm][ntest] C-ordered, row 0 = the start points.  iters (may be NULL): [nm-1][ntest] ints, the secant updates of each
+ * step (the residual evaluations beyond the two starting ones), -1 for a lost step.
+ * One 256-thread workgroup per orbit at every n0; no workgroup waits for another.  The sections are staged in LDS when
+ * nsec * 4 n0 <= 8960 doubles and read from memory otherwise, with the same bits either way.  An orbit's bits depend on nothing
+ * but its own start point, `first` and the sections.
+ * Checked before any device call (SGPR_E_ARG): nsec < 1, first outside [0, nsec), nm < 1, negative ntest / n0, an unknown mode
+ * bit, SGPR_MAP_WRAP_P (the two halves of a wrapped step sit at different P), SGPR_MAP_EXPLICIT (as for the d-pair inverse), a
+ * null required pointer, an unknown family, a wrong nhyp for the family.  Then SGPR_E_NODEVICE without a device; ntest == 0
+ * returns 0; nm == 1 writes the start row only.  There is no tangent form: the Jacobian of a backward step is the symplectic
+ * inverse of the forward step matrix at the same (q, P), which sgpr_applymap_sections_tangent_host returns for one step from the
+ * preimage.
+ * Added in ABI 5 (additional entry point). */
+int sgpr_applymap_sections_inverse_host(int family, int mode, int nsec, int first, int nm, int ntest,
+                                        const double *hyp, int nhyp, int n0, const double *xtrain, const double *ytrain,
+                                        const double *alpha, const double *Q0, const double *P0, double *qmap, double *pmap,
+                                        int *iters);
 /* The symplectic map of a fit with d canonical pairs (d = 1, 2, 3), nm - 1 steps for ntest orbits with every step on the
  * device: one workgroup per orbit, no workgroup waits on another.  With x = (q_1..q_d, P_1..P_d) and G(x) = K*(x) alpha (what
  * sgpr_fit_predict_nd returns: G_q = dF/dq = p - P, G_P = dF/dP = Q - q) a step solves

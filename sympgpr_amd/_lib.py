@@ -126,6 +126,8 @@ SIGNATURES = {
     "sgpr_applymap_sections_tangent_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int,
                                                       _dp, _dp, _dp, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
                                                       _dp, _dp, _dp]),
+    "sgpr_applymap_sections_inverse_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int,
+                                                      _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.POINTER(C.c_int)]),
     "sgpr_fit_applymap_nd": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, C.c_size_t, _dp, C.c_size_t, _dp, _dp,
                                        C.POINTER(C.c_int)]),
     "sgpr_applymap_nd_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_size_t,

@@ -595,6 +595,45 @@ int sgpr_applymap_sections_tangent_host(int family, int mode, int nsec, int firs
                                   alpha, hypp, nhypp, n0p, xtrainp, ytrainp, alphap, Q0, P0, qmap, pmap, pdiff, &tan);
 }
 
+/* The sectioned map BACKWARDS (map.hip: applymap_sections_inverse_kernel): Q0 / P0 hold the images, row i the i-th preimage, step
+ * i undoes section (first - i) mod nsec.  Every argument is checked before any device call. */
+int sgpr_applymap_sections_inverse_host(int family, int mode, int nsec, int first, int nm, int ntest, const double *hyp, int nhyp,
+                                        int n0, const double *xtrain, const double *ytrain, const double *alpha, const double *Q0,
+                                        const double *P0, double *qmap, double *pmap, int *iters)
+{
+    auto E = [&](const char *what) { set_error(std::string("applymap_sections_inverse_host: ") + what); return SGPR_E_ARG; };
+    if (mode & ~(SGPR_MAP_WRAP_Q | SGPR_MAP_WRAP_P | SGPR_MAP_EXPLICIT | SGPR_MAP_LOSS_NEGP)) return E("unknown mode bit");
+    if (mode & SGPR_MAP_WRAP_P) return E("SGPR_MAP_WRAP_P has no backward step (the two halves of a wrapped step sit at different P)");
+    if (mode & SGPR_MAP_EXPLICIT) return E("SGPR_MAP_EXPLICIT has no backward step (for the sum kernels the two maps coincide: use the implicit mode)");
+    if (nsec < 1) return E("nsec < 1");
+    if (first < 0 || first >= nsec) return E("first outside [0, nsec)");
+    if (nm < 1) return E("nm < 1");
+    if (ntest < 0 || n0 < 0) return E("negative ntest or n0");
+    if (!hyp || !Q0 || !P0 || !qmap || !pmap) return E("null hyp, Q0, P0, qmap or pmap");
+    if (n0 > 0 && (!xtrain || !ytrain || !alpha)) return E("null training points or alpha");
+    int rc;
+    std::vector<KConst> kc((size_t)nsec);
+    for (int s = 0; s < nsec; ++s)
+        if ((rc = make_kconst(family, hyp + (size_t)s * nhyp, nhyp, &kc[s]))) return rc;
+    if ((rc = need_device())) return rc;
+    if (ntest == 0) return 0;
+    DevBuf x, y, al, dk, q0, p0, di;
+    hipStream_t st = nullptr;
+    const size_t ns = (size_t)nsec, it_bytes = (size_t)(nm - 1) * ntest * sizeof(int);
+    const bool want_it = iters && it_bytes;
+    if ((rc = upload(x, xtrain, ns * n0, st)) || (rc = upload(y, ytrain, ns * n0, st)) || (rc = upload(al, alpha, 2 * ns * n0, st)) ||
+        (rc = upload(dk, reinterpret_cast<const double *>(kc.data()), kc.size() * (sizeof(KConst) / sizeof(double)), st)) ||
+        (rc = upload(q0, Q0, ntest, st)) || (rc = upload(p0, P0, ntest, st)) || (want_it && (rc = di.alloc(it_bytes))))
+        return rc;
+    return map_outputs(nm, ntest, qmap, pmap, nullptr, st, [&](double *qm, double *pm, double *) {
+        int r = applymap_sections_inverse(family, mode, nsec, first, nm, ntest, n0, x.as<double>(), y.as<double>(), al.as<double>(),
+                                          dk.as<KConst>(), q0.as<double>(), p0.as<double>(), qm, pm, want_it ? di.as<int>() : nullptr, st);
+        if (r) return r;
+        if (want_it) SGPR_HIP(hipMemcpyAsync(iters, di.p, it_bytes, hipMemcpyDeviceToHost, st));    // (map_outputs waits for the stream)
+        return 0;
+    });
+}
+
 /* The d-pair map from caller-supplied training points and alpha (the counterpart of sgpr_applymap_host for d canonical pairs). */
 int sgpr_applymap_nd_host(int family, int d, int mode, int nm, int ntest, const double *hyp, int nhyp, int n0, const double *X,
                           size_t ldx, const double *alpha, const double *Q0, size_t ldq, const double *P0, size_t ldp,

@@ -106,6 +106,11 @@ int applymap_sections_tangent(int family, int mode, int nsec, int first, int nm,
                               const double *ytr, const double *alpha, const KConst *kcs, int n0p, const double *xtrp,
                               const double *ytrp, const double *alphap, const KConst *kcps, const double *Q0, const double *P0,
                               double *qmap, double *pmap, double *pdiff, double *jac, double *mono, double *lyap, hipStream_t st);
+// the sectioned map backwards: Q0 / P0 hold the images (Q, P), row i of qmap / pmap is the i-th preimage, step i undoes section
+// (first - i) mod nsec; no guess GPs; iters [nm - 1][ntest] or null
+int applymap_sections_inverse(int family, int mode, int nsec, int first, int nm, int ntest, int n0, const double *xtr,
+                              const double *ytr, const double *alpha, const KConst *kcs, const double *Q0, const double *P0,
+                              double *qmap, double *pmap, int *iters, hipStream_t st);
 
 // ---- gram_nd.hip : d canonical pairs per point (X: points x 2d, column-major)
 int gram_nd(int family, int d, int mi, int mj, const double *Xb, size_t ldxb, const double *Xa, size_t ldxa,

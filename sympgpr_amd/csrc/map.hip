@@ -2,6 +2,7 @@
 // for one GP pair (applymap_kernel) and for one GP pair per toroidal section (applymap_sections_kernel).  The two kernels
 // share one time step (map_step) and one copy of the per-thread sums (rows_part, guess_part).  The sectioned kernel has a TAN
 // instance (mapsec_tan.h): the step's Jacobian, the monodromy matrix and the finite-time Lyapunov exponents of every orbit.
+// applymap_sections_inverse_kernel iterates the sectioned map (one section: the one-pair map) backwards, with map_step_inverse.
 #include <atomic>
 #include <type_traits>
 #include "common.h"
@@ -393,6 +394,125 @@ __global__ __launch_bounds__(TT) void applymap_sections_kernel(const std::condit
     if constexpr (TAN) sec_tan_finish(a, k);
 }
 
+// ---- the sectioned map BACKWARDS.  The forward step passes through the point (q, P): it solves p = P + r1(q, P) for P and sets
+// Q = q + r2(q, P).  The backward step passes through the same point with the roles swapped: P is known, it solves
+// g(q) = q + r2(q, P) - Q = 0 for q and sets p = P + r1(q, P).
+// One backward step (Q, P) -> (q, p) of one orbit, map_step's twin; NaN in both from the step at which the orbit is lost, `iters`
+// the secant updates (the rows calls beyond the two starting residuals), -1 for a lost step.  The same two rules hold as for
+// map_step: every value that decides a branch is the block-uniform result of the sums (or a kernel argument), so all threads
+// make the same rows calls in the same order -- two starting residuals, then one per secant update --, and nothing here adds
+// across threads.  The r1 of the last rows call belongs to (q1, P): no further pass for p.  No first-guess GP: the secant starts
+// from q = Q, the identity map's answer.
+template <typename Rows>
+__device__ __forceinline__ void map_step_inverse(int mode, int maxiter, double tol, double &q, double &p, int &iters, Rows &&rows)
+{
+    const double nan = __builtin_nan("");
+    const double twopi = 6.283185307179586477;
+    const double Q = q, P = p;
+    double qn = nan, pn = nan;
+    int itn = -1;
+    if (sec_finite(Q) && sec_finite(P)) {              // NaN = lost orbit stays lost; an infinite start value is lost as well
+        double r1, r2;
+        double q0 = Q;
+        rows(q0, P, r1, r2);
+        double f0 = r2;                                 // g(q0) = q0 + r2 - Q at q0 = Q
+        double q1 = q0 - f0;                            // g'(q) ~ 1 near the identity map
+        rows(q1, P, r1, r2);
+        double f1 = q1 + r2 - Q;
+        int it = 0;
+        for (; it < maxiter; ++it) {                    // secant; every quantity is block-uniform
+            if (!(fabs(q1 - q0) > tol * fmax(1.0, fabs(q1))) || !sec_finite(f1)) break;
+            const double d = f1 - f0;
+            if (d == 0.0) break;
+            const double qs = q1 - f1 * (q1 - q0) / d;
+            q0 = q1; f0 = f1; q1 = qs;
+            rows(q1, P, r1, r2);
+            f1 = q1 + r2 - Q;
+        }
+        if (sec_finite(f1) && fabs(f1) <= 1e-8 * fmax(1.0, fabs(Q))) {   // the forward rule with the roles swapped
+            const double pp = P + r1;                   // r1 belongs to (q1, P)
+            // the backward twin of the forward "new momentum < 0": the preimage has left the plasma
+            const bool negp = (mode & SGPR_MAP_LOSS_NEGP) && pp < 0.0;
+            if (sec_finite(pp) && !negp) {
+                pn = pp;
+                qn = q1;
+                if (mode & SGPR_MAP_WRAP_Q) qn -= twopi * floor(qn / twopi);
+                itn = it;
+            }
+        }
+    }
+    q = qn; p = pn; iters = itn;
+}
+
+struct MapSecInvArgs {
+    int nm, ntest, n0, mode, maxiter;
+    int nsec, first;
+    int staged;                           // all sections' points and weights (4 n0 doubles each) fit into MAPSEC_STAGE doubles of LDS
+    double tol;
+    const double *xtr, *ytr, *alpha;      // n0 x nsec, n0 x nsec, 2 n0 x nsec, column-major, tight
+    const double *Q0, *P0;                // the images (Q, P)
+    double *qmap, *pmap;                  // [nm][ntest], C order: row i the i-th preimage
+    int *iters;                           // [nm - 1][ntest] or null
+};
+
+// All nm - 1 backward steps of all orbits in one launch: step i (row i -> row i + 1) undoes section (first - i) mod nsec,
+// `first` the section whose forward step produced row 0.  applymap_sections_kernel's shape: one workgroup per orbit, the
+// sections staged in dynamic LDS when they fit (no guess GP: 4 n0 doubles per section), the same per-thread point order
+// (j = tid, tid + TT, ...) staged or not, rows_part + block_sum2 on alternating LDS halves, the sections' constants by
+// block-uniform scalar loads.  No workgroup waits for another.
+template <int FAM, int TT>
+__global__ __launch_bounds__(TT) void applymap_sections_inverse_kernel(const MapSecInvArgs a, const KConst *__restrict__ kcs)
+{
+    __shared__ double sh[2][2 * (TT / 64)];
+    extern __shared__ double sec_st[];                  // [section]{x, y, alpha (two halves): n0 each}
+    const int k = blockIdx.x, tid = threadIdx.x, n0 = a.n0;
+    const int per = 4 * n0;                             // (staged only: nsec * per <= MAPSEC_STAGE)
+    const bool staged = a.staged != 0;
+    if (staged) {
+        for (int s = 0; s < a.nsec; ++s) {
+            double *d = sec_st + s * per;
+            const double *x = a.xtr + (size_t)s * n0, *y = a.ytr + (size_t)s * n0, *al = a.alpha + (size_t)s * 2 * n0;
+            for (int j = tid; j < n0; j += TT) {
+                d[j] = x[j]; d[n0 + j] = y[j];
+                d[2 * n0 + j] = al[j]; d[3 * n0 + j] = al[n0 + j];
+            }
+        }
+        // (every thread reads back what it wrote itself: no barrier needed)
+    }
+    unsigned seq = 0;
+    auto sum2 = [&](double &x, double &y) {
+        ++seq;
+        block_sum2<TT>(x, y, sh[seq & 1u]);
+    };
+    double q = a.Q0[k], p = a.P0[k];
+    if (tid == 0) {
+        a.qmap[k] = q;
+        a.pmap[k] = p;
+    }
+    int m = a.first;
+    for (int i = 0; i + 1 < a.nm; ++i) {
+        const KConst kc = kcs[m];
+        auto rows = [&](double q, double P, double &r1, double &r2) {   // section m's Kstar(1,:).alpha, Kstar(2,:).alpha
+            if (staged) {
+                const double *d = sec_st + m * per;
+                rows_part<FAM>(d, d + n0, d + 2 * n0, d + 3 * n0, tid, TT, tid, TT, n0, q, P, kc, r1, r2);
+            } else {
+                const double *al = a.alpha + (size_t)m * 2 * n0;
+                rows_part<FAM>(a.xtr + (size_t)m * n0, a.ytr + (size_t)m * n0, al, al + n0, tid, TT, tid, TT, n0, q, P, kc, r1, r2);
+            }
+            sum2(r1, r2);
+        };
+        int it;
+        map_step_inverse(a.mode, a.maxiter, a.tol, q, p, it, rows);
+        if (--m < 0) m = a.nsec - 1;
+        if (tid == 0) {
+            a.qmap[(size_t)(i + 1) * a.ntest + k] = q;
+            a.pmap[(size_t)(i + 1) * a.ntest + k] = p;
+            if (a.iters) a.iters[(size_t)i * a.ntest + k] = it;
+        }
+    }
+}
+
 }  // namespace
 
 // Workgroups per orbit: TWO 256-thread members per CU (512 slots) shared out among the ntest orbits, at most 16 per orbit, and no
@@ -502,6 +622,28 @@ int applymap_sections_tangent(int family, int mode, int nsec, int first, int nm,
     MapSecTanArgs a{{nm, ntest, n0, n0p, mode, 60, nsec, first, staged ? 1 : 0, 1e-13, xtr, ytr, alpha, xtrp, ytrp, alphap, Q0, P0,
                      qmap, pmap, pdiff}, jac, mono, lyap};
     return applymap_sections_launch<true>(family, a, lds, kcs, kcps, st);
+}
+
+// The sectioned map backwards: one launch, one 256-thread workgroup per orbit.  No guess GPs, so a section takes 4 n0 doubles of
+// the same MAPSEC_STAGE limit, and exactly what is staged is reserved.
+int applymap_sections_inverse(int family, int mode, int nsec, int first, int nm, int ntest, int n0, const double *xtr,
+                              const double *ytr, const double *alpha, const KConst *kcs, const double *Q0, const double *P0,
+                              double *qmap, double *pmap, int *iters, hipStream_t st)
+{
+    if (nm <= 0 || ntest <= 0) return 0;
+    const long need = (long)nsec * 4L * n0;
+    const bool staged = need <= MAPSEC_STAGE;
+    const size_t lds = staged ? (size_t)need * sizeof(double) : 0;
+    MapSecInvArgs a{nm, ntest, n0, mode, 60, nsec, first, staged ? 1 : 0, 1e-13, xtr, ytr, alpha, Q0, P0, qmap, pmap, iters};
+    return dispatch_family(family, [&](auto fam) {
+        constexpr int F = decltype(fam)::value;
+        auto kern = applymap_sections_inverse_kernel<F, MAP_T>;
+        if (lds > 48 * 1024)
+            SGPR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(kern, dim3(ntest), dim3(MAP_T), lds, st, a, kcs);
+        SGPR_CHECK_LAUNCH();
+        return 0;
+    });
 }
 
 }  // namespace sgpr

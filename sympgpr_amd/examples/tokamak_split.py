@@ -156,6 +156,75 @@ def applymap_tok_tangent(nphmap, nm, Ntest, Q0map, P0map, xtrainp, ztrainp, Kyin
     return qmap, pmap, t
 
 
+def map_in_chunks_inverse(run, nphmap, nm, Ntest, Q0map, P0map, start=0, compute_r=None, steps_per_launch=None):
+    """map_in_chunks's backward twin, around a stepper `run(first, steps, Q0, P0) -> (q, p)`, each [steps + 1, len(Q0)] with row
+    0 the start points and NaN from the step at which an orbit is lost: `steps` BACKWARD steps of the sectioned map whose first
+    step undoes section `first`.  The start points sit at toroidal section index `start`; row j sits at index (start - j) mod
+    nphmap and step j -> j + 1 undoes GP pair (start - j - 1) mod nphmap.  All nm - 1 steps are run (the forward loop's quirk of
+    whole turns belongs to the reference's forward loop only).  Without a callback one call of `run`; with one,
+    `steps_per_launch` steps per call, each continued at its section from the orbits still alive, and compute_r is applied to the
+    new rows step by step and orbit by orbit at the row's own angle.  What a chunk computed for an orbit beyond the step that
+    lost it is dropped."""
+    pmap = np.zeros([nm, Ntest])
+    qmap = np.zeros([nm, Ntest])
+    pmap[0, :] = P0map
+    qmap[0, :] = Q0map
+    steps = nm - 1
+    if steps <= 0:
+        return qmap, pmap
+    k = steps if compute_r is None else max(1, int(steps_per_launch or 1))
+    pmap[1:, :] = np.nan
+    qmap[1:, :] = np.nan
+    i = 0
+    while i < steps:
+        kk = min(k, steps - i)
+        idx = np.nonzero(~np.isnan(pmap[i, :]))[0]
+        if len(idx):
+            qq, pp = run((start - i - 1) % nphmap, kk, qmap[i, idx], pmap[i, idx])[:2]
+            if compute_r is None:
+                pmap[i + 1:i + kk + 1, idx], qmap[i + 1:i + kk + 1, idx] = pp[1:], qq[1:]
+            else:
+                alive = np.ones(len(idx), dtype=bool)
+                for s in range(1, kk + 1):
+                    ph = (2 * np.pi) / nphmap * np.mod(start - (i + s), nphmap)
+                    for j, orbit in enumerate(idx):
+                        if not alive[j]:
+                            continue
+                        if np.isnan(pp[s, j]):                  # the solve failed or p < 0: lost inside the kernel
+                            alive[j] = False
+                            continue
+                        if compute_r(np.array([pp[s, j] * 1e-2, qq[s, j], ph]), 0.3) > 0.5:
+                            alive[j] = False
+                            continue
+                        pmap[i + s, orbit], qmap[i + s, orbit] = pp[s, j], qq[s, j]
+        i += kk
+    return qmap, pmap
+
+
+def applymap_tok_inverse(nphmap, nm, Ntest, Q0map, P0map, xtrain, ztrain, Kyinv, hyp, start=0, compute_r=None,
+                         steps_per_launch=None):
+    """applymap_tok BACKWARDS (maps.run_map_sections_inverse): Q0map, P0map are points at toroidal section index `start`, row j
+    of (qmap, pmap) [nm, Ntest] their j-th preimage, at section index (start - j) mod nphmap; step j uses GP pair
+    (start - j - 1) mod nphmap.  From the last row i of a forward applymap_tok run, start = i mod nphmap.  xtrain (2N x nphmap),
+    ztrain (2N x nphmap), Kyinv (nphmap x 2N x 2N), hyp (nphmap x 3): the symplectic GPs alone, the backward solve needs no
+    guess.  An orbit whose preimage has p < 0 -- or compute_r > 0.5, with a callback -- is lost: NaN from that row on.  All nm - 1
+    steps run on the device: without a callback in ONE launch; with compute_r, steps_per_launch = k steps per launch (1 if not
+    given) with the callback applied on the host to each new row at that row's own angle (map_in_chunks_inverse)."""
+    from .. import maps
+    f = lambda a: np.asarray(a, dtype=np.float64)
+    xtrain, ztrain, hyp = f(xtrain), f(ztrain), f(hyp)
+    nphmap, start = int(nphmap), int(start)
+    N = xtrain.shape[0] // 2
+    alpha = np.stack([f(Kyinv[m]) @ ztrain[:, m] for m in range(nphmap)], axis=1)           # once per section, not per step
+    mode = maps.WRAP_Q | maps.LOSS_NEGP
+
+    def run(first, steps, Q0, P0):
+        return maps.run_map_sections_inverse(mode, steps + 1, len(Q0), hyp[:nphmap], xtrain[:N, :nphmap], xtrain[N:2 * N, :nphmap],
+                                             alpha, Q0, P0, first=first, family=FAMILY)
+    return map_in_chunks_inverse(run, nphmap, nm, Ntest, np.broadcast_to(Q0map, (Ntest,)), np.broadcast_to(P0map, (Ntest,)),
+                                 start % nphmap, compute_r, steps_per_launch)
+
+
 def _applymap_tok_host(nphmap, nm, Ntest, Q0map, P0map, xtrainp, ztrainp, Kyinvp, hypp, xtrain, ztrain, Kyinv, hyp, compute_r):
     """the host-driven form of applymap_tok: a Python loop over the time steps"""
     preds = [_c.predictor_pair(FAMILY, hyp[m, :], hypp[m, :], xtrainp[:, m], ztrainp[:, m], Kyinvp[m], xtrain[:, m],

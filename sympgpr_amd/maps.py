@@ -12,7 +12,10 @@ One recurrence, the variants the reference's drivers carry in their own func.py 
                                                                  turn: run_map_sections (sgpr_applymap_sections_host);
                                                                  run_map_sections_tangent adds the step matrices, their
                                                                  product and Lyapunov exponents, tangent_from_jac rebuilds the
-                                                                 last two on the host from the jac of a run split into chunks
+                                                                 last two on the host from the jac of a run split into chunks;
+                                                                 run_map_sections_inverse iterates it BACKWARDS
+                                                                 (sgpr_applymap_sections_inverse_host), run_map_inverse the
+                                                                 one-pair map of run_map_alpha: one section of the same entry
 
 For fits with d canonical pairs (d = 1, 2, 3) the map is run_map_nd / SympFit.applymap_pairs: Newton with the analytic
 Jacobian on the d unknowns P, one workgroup per orbit (include/sympgpr_hip.h: sgpr_applymap_nd_host).
@@ -84,9 +87,9 @@ def _section_columns(name, a, rows, nsec):
     return np.asfortranarray(a)
 
 
-def _sections_call(mode, nm, Ntest, hyp, xt, yt, alpha, Q0, P0, hypp, xp, yp, alphap, first, want_pdiff, family):
-    """What run_map_sections and run_map_sections_tangent share: the checked, laid-out arguments of the two C entries up to and
-    including pdiff, as a list, and the output arrays (qmap, pmap, pdiff or None).  Shape errors are ValueError."""
+def _sections_model(mode, nm, Ntest, hyp, xt, yt, alpha, first, family):
+    """What every sectioned entry, forwards and backwards, asks of the symplectic GPs and the call's sizes: -> (family, mode, nm,
+    Ntest, first, nsec, N0, hyp (nsec, nhyp), xt, yt, alpha as tight columns).  Shape errors are ValueError."""
     family = get_family() if family is None else family
     mode, nm, Ntest, first = int(mode), int(nm), int(Ntest), int(first)
     hyp = np.asarray(hyp, dtype=np.float64)
@@ -101,6 +104,13 @@ def _sections_call(mode, nm, Ntest, hyp, xt, yt, alpha, Q0, P0, hypp, xp, yp, al
     N0 = xt.shape[0]
     yt = _section_columns("yt", yt, N0, nsec)
     alpha = _section_columns("alpha", alpha, 2 * N0, nsec)
+    return family, mode, nm, Ntest, first, nsec, N0, hyp, xt, yt, alpha
+
+
+def _sections_call(mode, nm, Ntest, hyp, xt, yt, alpha, Q0, P0, hypp, xp, yp, alphap, first, want_pdiff, family):
+    """What run_map_sections and run_map_sections_tangent share: the checked, laid-out arguments of the two C entries up to and
+    including pdiff, as a list, and the output arrays (qmap, pmap, pdiff or None).  Shape errors are ValueError."""
+    family, mode, nm, Ntest, first, nsec, N0, hyp, xt, yt, alpha = _sections_model(mode, nm, Ntest, hyp, xt, yt, alpha, first, family)
     if mode & EXPLICIT:
         N0p, hp = 0, np.zeros((nsec, 0))
         xp = yp = alphap = np.zeros((0, nsec), order="F")
@@ -165,6 +175,66 @@ def run_map_sections_tangent(mode, nm, Ntest, hyp, xt, yt, alpha, Q0, P0, hypp=N
     L.check(lib.sgpr_applymap_sections_tangent_host(*args, _optr(t, "jac"), _optr(t, "mono"), _optr(t, "lyap")),
             "sgpr_applymap_sections_tangent_host")
     return (qmap, pmap, pdiff, t) if want_pdiff else (qmap, pmap, t)
+
+
+def last_section(first, nm, nsec):
+    """The section whose step produced the LAST row of a forward run of nm rows that began with section `first`:
+    (first + nm - 2) mod nsec -- the `first` to hand to run_map_sections_inverse with that row as start points.  (nm = 1, a run
+    of no step: the section before `first`, whose step a longer run would have ended with.)"""
+    first, nm, nsec = int(first), int(nm), int(nsec)
+    if nsec < 1 or nm < 1 or not 0 <= first < nsec:
+        raise ValueError("last_section needs nsec >= 1, nm >= 1 and first in [0, nsec)")
+    return (first + nm - 2) % nsec
+
+
+def map_mode_sections_inverse(mode):
+    mode = int(mode)
+    if mode & ~(WRAP_Q | WRAP_P | EXPLICIT | LOSS_NEGP):
+        raise ValueError("unknown mode bit")
+    if mode & WRAP_P:
+        raise ValueError("the backward sectioned map knows no WRAP_P (the two halves of a wrapped step sit at different P)")
+    if mode & EXPLICIT:
+        raise ValueError("the backward sectioned map inverts the implicit map only: EXPLICIT has no backward step "
+                         "(for the sum kernels the two maps coincide, use the implicit mode)")
+    return mode
+
+
+def run_map_sections_inverse(mode, nm, Ntest, hyp, xt, yt, alpha, Q0, P0, first=0, family=None, return_iters=False):
+    """run_map_sections BACKWARDS in one launch (sgpr_applymap_sections_inverse_host): Q0, P0 are points (Q, P) and row i of
+    qmap, pmap [nm, Ntest] is their i-th preimage (row 0 the start points).  Step i undoes section (first - i) mod nsec: `first`
+    is the section whose forward step produced the start points -- last_section(first_forward, nm, nsec) from the last row of a
+    forward run.  A step solves q + r2(q, P) - Q = 0 for q by the forward map's secant from q = Q (no guess GPs are needed),
+    then p = P + r1(q, P).  hyp, xt, yt, alpha as run_map_sections takes them; mode = WRAP_Q (the solved q mod 2 pi) |
+    LOSS_NEGP (a step whose solved p < 0 loses the orbit); WRAP_P and EXPLICIT have no backward step.
+    -> (qmap, pmap) or with return_iters (qmap, pmap, iters): iters (nm - 1, Ntest) int32, the secant updates of each step, -1
+    for a lost one.  NaN from the step at which an orbit is lost.  A run continued from row i with first = (first - i) mod nsec
+    has the bits of the uninterrupted one.  Shape and mode errors are ValueError before any device call."""
+    mode = map_mode_sections_inverse(mode)
+    family, mode, nm, Ntest, first, nsec, N0, hyp, xt, yt, alpha = _sections_model(mode, nm, Ntest, hyp, xt, yt, alpha, first, family)
+    hyp = L.f64(hyp)                                    # C order: section s at hyp + s * nhyp
+    Q0, P0 = L.f64(np.broadcast_to(Q0, (Ntest,))), L.f64(np.broadcast_to(P0, (Ntest,)))
+    qmap, pmap = np.zeros([nm, Ntest]), np.zeros([nm, Ntest])
+    iters = np.zeros((nm - 1, Ntest), dtype=np.int32)
+    lib = L.load_library()
+    L.check(lib.sgpr_applymap_sections_inverse_host(L.family_id(family), mode, nsec, first, nm, Ntest, L.dptr(hyp), hyp.shape[1], N0,
+                                                    L.dptr(xt), L.dptr(yt), L.dptr(alpha), L.dptr(Q0), L.dptr(P0), L.dptr(qmap),
+                                                    L.dptr(pmap), iters.ctypes.data_as(C.POINTER(C.c_int))),
+            "sgpr_applymap_sections_inverse_host")
+    return (qmap, pmap, iters) if return_iters else (qmap, pmap)
+
+
+def run_map_inverse(mode, nm, Ntest, l, Q0, P0, xt, yt, alpha, family=None, return_iters=False):
+    """The one-pair (d = 1) map of run_map_alpha BACKWARDS: Q0, P0 are points (Q, P), row i of qmap, pmap [nm, Ntest] their i-th
+    preimage under the map with the same l = (lx, ly, sig), xt, yt (N0) and alpha (2 N0).  The sectioned backward map with one
+    section (run_map_sections_inverse): mode = WRAP_Q | LOSS_NEGP bits, no guess GP.  -> (qmap, pmap[, iters])."""
+    def vec(name, a):
+        a = np.asarray(a, dtype=np.float64)
+        if a.ndim != 1:
+            raise ValueError("%s must be a vector" % name)
+        return a
+    xt, yt, alpha, l = vec("xt", xt), vec("yt", yt), vec("alpha", alpha), vec("l", l)
+    return run_map_sections_inverse(mode, nm, Ntest, l[None, :], xt[:, None], yt[:, None], alpha[:, None], Q0, P0, first=0,
+                                    family=family, return_iters=return_iters)
 
 
 def tangent_from_jac(jac):
