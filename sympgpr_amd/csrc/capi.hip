@@ -117,23 +117,29 @@ static int applymap_nd_host(const char *me, int family, int d, int mode, int nm,
                           qmap, pmap, iters, st, tan, dir);
 }
 
-// sgpr_applymap_sections_host (tan null) and sgpr_applymap_sections_tangent_host: every argument is checked before any device call
+// sgpr_applymap_sections_host (tan null), sgpr_applymap_sections_tangent_host and sgpr_applymap_sections_inverse_host (MAP_BACKWARD:
+// no guess GPs, no pdiff, no tangent; iters [nm - 1][ntest] or null is its own output): every argument is checked before any
+// device call
 static int applymap_sections_host(const char *me, int family, int mode, int nsec, int first, int nm, int ntest, const double *hyp,
                                   int nhyp, int n0, const double *xtrain, const double *ytrain, const double *alpha,
                                   const double *hypp, int nhypp, int n0p, const double *xtrainp, const double *ytrainp,
                                   const double *alphap, const double *Q0, const double *P0, double *qmap, double *pmap, double *pdiff,
-                                  const MapTangentOut *tan)
+                                  const MapTangentOut *tan, MapDirection dir = MAP_FORWARD, int *iters = nullptr)
 {
     auto E = [&](const char *what) { set_error(std::string(me) + ": " + what); return SGPR_E_ARG; };
-    const bool expl = (mode & SGPR_MAP_EXPLICIT) != 0;
-    if (expl) n0p = 0;                       /* no first-guess GPs in the explicit map */
+    const bool back = dir == MAP_BACKWARD, expl = (mode & SGPR_MAP_EXPLICIT) != 0;
+    const bool guess = !back && !expl;       /* no first-guess GPs in the explicit map, nor backwards */
+    if (!guess) n0p = 0;
     if (mode & ~(SGPR_MAP_WRAP_Q | SGPR_MAP_WRAP_P | SGPR_MAP_EXPLICIT | SGPR_MAP_LOSS_NEGP)) return E("unknown mode bit");
+    if (back && (mode & SGPR_MAP_WRAP_P)) return E("SGPR_MAP_WRAP_P has no backward step (the two halves of a wrapped step sit at different P)");
+    if (back && expl) return E("SGPR_MAP_EXPLICIT has no backward step (for the sum kernels the two maps coincide: use the implicit mode)");
     if (expl && (mode & SGPR_MAP_LOSS_NEGP)) return E("SGPR_MAP_LOSS_NEGP belongs to the implicit map");
     if (nsec < 1) return E("nsec < 1");
     if (first < 0 || first >= nsec) return E("first outside [0, nsec)");
     if (nm < 1) return E("nm < 1");
-    if (ntest < 0 || n0 < 0 || n0p < 0) return E("negative ntest, n0 or n0p");
-    if (!hyp || (!expl && !hypp) || !Q0 || !P0 || !qmap || !pmap) return E("null hyp, hypp, Q0, P0, qmap or pmap");
+    if (ntest < 0 || n0 < 0 || n0p < 0) return E(back ? "negative ntest or n0" : "negative ntest, n0 or n0p");
+    if (!hyp || (guess && !hypp) || !Q0 || !P0 || !qmap || !pmap)
+        return E(back ? "null hyp, Q0, P0, qmap or pmap" : "null hyp, hypp, Q0, P0, qmap or pmap");
     if ((n0 > 0 && (!xtrain || !ytrain || !alpha)) || (n0p > 0 && (!xtrainp || !ytrainp || !alphap)))
         return E("null training points or alpha");
     if (tan) {
@@ -143,42 +149,42 @@ static int applymap_sections_host(const char *me, int family, int mode, int nsec
         if (tan->lyap && nm < 2) return E("lyap needs nm >= 2");
     }
     int rc;
-    std::vector<KConst> kc(2 * (size_t)nsec);           /* the sections' constants: nsec for the map, nsec for the guess */
+    const size_t ns = (size_t)nsec;
+    std::vector<KConst> kc((back ? 1 : 2) * ns);        /* the sections' constants: nsec for the map, forwards nsec for the guess */
     for (int s = 0; s < nsec; ++s) {
         if ((rc = make_kconst(family, hyp + (size_t)s * nhyp, nhyp, &kc[s]))) return rc;
-        if (!expl && (rc = make_kconst(family, hypp + (size_t)s * nhypp, nhypp, &kc[nsec + s]))) return rc;
+        if (guess && (rc = make_kconst(family, hypp + (size_t)s * nhypp, nhypp, &kc[nsec + s]))) return rc;
     }
     if ((rc = need_device())) return rc;
     if (ntest == 0) return 0;
-    DevBuf x, y, al, xp, yp, alp, dk, q0, p0, dj, dm, dl;
+    DevBuf x, y, al, xp, yp, alp, dk, q0, p0, dj, dm, dl, di;
     hipStream_t st = nullptr;
-    const size_t ns = (size_t)nsec;
     static_assert(sizeof(KConst) % sizeof(double) == 0, "KConst is uploaded as doubles");
     if ((rc = upload(x, xtrain, ns * n0, st)) || (rc = upload(y, ytrain, ns * n0, st)) || (rc = upload(al, alpha, 2 * ns * n0, st)) ||
         (rc = upload(xp, xtrainp, ns * n0p, st)) || (rc = upload(yp, ytrainp, ns * n0p, st)) || (rc = upload(alp, alphap, ns * n0p, st)) ||
         (rc = upload(dk, reinterpret_cast<const double *>(kc.data()), kc.size() * (sizeof(KConst) / sizeof(double)), st)) ||
         (rc = upload(q0, Q0, ntest, st)) || (rc = upload(p0, P0, ntest, st)))
         return rc;
-    if (!tan)
-        return map_outputs(nm, ntest, qmap, pmap, pdiff, st, [&](double *qm, double *pm, double *pd) {
-            return applymap_sections(family, mode, nsec, first, nm, ntest, n0, x.as<double>(), y.as<double>(), al.as<double>(),
-                                     dk.as<KConst>(), n0p, xp.as<double>(), yp.as<double>(), alp.as<double>(), dk.as<KConst>() + nsec,
-                                     q0.as<double>(), p0.as<double>(), qm, pm, pd, st);
-        });
     const size_t mono_bytes = (size_t)ntest * 4 * sizeof(double), jac_bytes = (size_t)(nm - 1) * mono_bytes;
-    const size_t lyap_bytes = (size_t)ntest * 2 * sizeof(double);
-    if ((tan->jac && (rc = dj.alloc(jac_bytes))) || (tan->mono && (rc = dm.alloc(mono_bytes))) || (tan->lyap && (rc = dl.alloc(lyap_bytes))))
+    const size_t lyap_bytes = (size_t)ntest * 2 * sizeof(double), it_bytes = (size_t)(nm - 1) * ntest * sizeof(int);
+    const bool want_it = back && iters && it_bytes;
+    if ((want_it && (rc = di.alloc(it_bytes))) ||
+        (tan && ((tan->jac && (rc = dj.alloc(jac_bytes))) || (tan->mono && (rc = dm.alloc(mono_bytes))) || (tan->lyap && (rc = dl.alloc(lyap_bytes))))))
         return rc;
     rc = map_outputs(nm, ntest, qmap, pmap, pdiff, st, [&](double *qm, double *pm, double *pd) {
-        return applymap_sections_tangent(family, mode, nsec, first, nm, ntest, n0, x.as<double>(), y.as<double>(), al.as<double>(),
-                                         dk.as<KConst>(), n0p, xp.as<double>(), yp.as<double>(), alp.as<double>(),
-                                         dk.as<KConst>() + nsec, q0.as<double>(), p0.as<double>(), qm, pm, pd, dj.as<double>(),
-                                         dm.as<double>(), dl.as<double>(), st);
+        if (back)
+            return applymap_sections_inverse(family, mode, nsec, first, nm, ntest, n0, x.as<double>(), y.as<double>(), al.as<double>(),
+                                             dk.as<KConst>(), q0.as<double>(), p0.as<double>(), qm, pm, want_it ? di.as<int>() : nullptr, st);
+        return applymap_sections(family, mode, nsec, first, nm, ntest, n0, x.as<double>(), y.as<double>(), al.as<double>(),
+                                 dk.as<KConst>(), n0p, xp.as<double>(), yp.as<double>(), alp.as<double>(), dk.as<KConst>() + nsec,
+                                 q0.as<double>(), p0.as<double>(), qm, pm, pd, st, tan != nullptr, dj.as<double>(), dm.as<double>(),
+                                 dl.as<double>());
     });
-    if (rc) return rc;
-    if (tan->jac && jac_bytes) SGPR_HIP(hipMemcpyAsync(tan->jac, dj.p, jac_bytes, hipMemcpyDeviceToHost, st));
-    if (tan->mono) SGPR_HIP(hipMemcpyAsync(tan->mono, dm.p, mono_bytes, hipMemcpyDeviceToHost, st));
-    if (tan->lyap) SGPR_HIP(hipMemcpyAsync(tan->lyap, dl.p, lyap_bytes, hipMemcpyDeviceToHost, st));
+    if (rc || (!tan && !want_it)) return rc;
+    if (want_it) SGPR_HIP(hipMemcpyAsync(iters, di.p, it_bytes, hipMemcpyDeviceToHost, st));
+    if (tan && tan->jac && jac_bytes) SGPR_HIP(hipMemcpyAsync(tan->jac, dj.p, jac_bytes, hipMemcpyDeviceToHost, st));
+    if (tan && tan->mono) SGPR_HIP(hipMemcpyAsync(tan->mono, dm.p, mono_bytes, hipMemcpyDeviceToHost, st));
+    if (tan && tan->lyap) SGPR_HIP(hipMemcpyAsync(tan->lyap, dl.p, lyap_bytes, hipMemcpyDeviceToHost, st));
     SGPR_HIP(hipStreamSynchronize(st));
     return 0;
 }
@@ -583,7 +589,7 @@ int sgpr_applymap_sections_host(int family, int mode, int nsec, int first, int n
                                   hypp, nhypp, n0p, xtrainp, ytrainp, alphap, Q0, P0, qmap, pmap, pdiff, nullptr);
 }
 
-/* The same with the tangent map (mapsec_tan.h): the orbit outputs have the bits of sgpr_applymap_sections_host. */
+/* The same with the tangent map (mapsec_tan.h, tangent_core.h): the orbit outputs have the bits of sgpr_applymap_sections_host. */
 int sgpr_applymap_sections_tangent_host(int family, int mode, int nsec, int first, int nm, int ntest, const double *hyp, int nhyp,
                                         int n0, const double *xtrain, const double *ytrain, const double *alpha, const double *hypp,
                                         int nhypp, int n0p, const double *xtrainp, const double *ytrainp, const double *alphap,
@@ -601,37 +607,9 @@ int sgpr_applymap_sections_inverse_host(int family, int mode, int nsec, int firs
                                         int n0, const double *xtrain, const double *ytrain, const double *alpha, const double *Q0,
                                         const double *P0, double *qmap, double *pmap, int *iters)
 {
-    auto E = [&](const char *what) { set_error(std::string("applymap_sections_inverse_host: ") + what); return SGPR_E_ARG; };
-    if (mode & ~(SGPR_MAP_WRAP_Q | SGPR_MAP_WRAP_P | SGPR_MAP_EXPLICIT | SGPR_MAP_LOSS_NEGP)) return E("unknown mode bit");
-    if (mode & SGPR_MAP_WRAP_P) return E("SGPR_MAP_WRAP_P has no backward step (the two halves of a wrapped step sit at different P)");
-    if (mode & SGPR_MAP_EXPLICIT) return E("SGPR_MAP_EXPLICIT has no backward step (for the sum kernels the two maps coincide: use the implicit mode)");
-    if (nsec < 1) return E("nsec < 1");
-    if (first < 0 || first >= nsec) return E("first outside [0, nsec)");
-    if (nm < 1) return E("nm < 1");
-    if (ntest < 0 || n0 < 0) return E("negative ntest or n0");
-    if (!hyp || !Q0 || !P0 || !qmap || !pmap) return E("null hyp, Q0, P0, qmap or pmap");
-    if (n0 > 0 && (!xtrain || !ytrain || !alpha)) return E("null training points or alpha");
-    int rc;
-    std::vector<KConst> kc((size_t)nsec);
-    for (int s = 0; s < nsec; ++s)
-        if ((rc = make_kconst(family, hyp + (size_t)s * nhyp, nhyp, &kc[s]))) return rc;
-    if ((rc = need_device())) return rc;
-    if (ntest == 0) return 0;
-    DevBuf x, y, al, dk, q0, p0, di;
-    hipStream_t st = nullptr;
-    const size_t ns = (size_t)nsec, it_bytes = (size_t)(nm - 1) * ntest * sizeof(int);
-    const bool want_it = iters && it_bytes;
-    if ((rc = upload(x, xtrain, ns * n0, st)) || (rc = upload(y, ytrain, ns * n0, st)) || (rc = upload(al, alpha, 2 * ns * n0, st)) ||
-        (rc = upload(dk, reinterpret_cast<const double *>(kc.data()), kc.size() * (sizeof(KConst) / sizeof(double)), st)) ||
-        (rc = upload(q0, Q0, ntest, st)) || (rc = upload(p0, P0, ntest, st)) || (want_it && (rc = di.alloc(it_bytes))))
-        return rc;
-    return map_outputs(nm, ntest, qmap, pmap, nullptr, st, [&](double *qm, double *pm, double *) {
-        int r = applymap_sections_inverse(family, mode, nsec, first, nm, ntest, n0, x.as<double>(), y.as<double>(), al.as<double>(),
-                                          dk.as<KConst>(), q0.as<double>(), p0.as<double>(), qm, pm, want_it ? di.as<int>() : nullptr, st);
-        if (r) return r;
-        if (want_it) SGPR_HIP(hipMemcpyAsync(iters, di.p, it_bytes, hipMemcpyDeviceToHost, st));    // (map_outputs waits for the stream)
-        return 0;
-    });
+    return applymap_sections_host("applymap_sections_inverse_host", family, mode, nsec, first, nm, ntest, hyp, nhyp, n0, xtrain, ytrain,
+                                  alpha, nullptr, 0, 0, nullptr, nullptr, nullptr, Q0, P0, qmap, pmap, nullptr, nullptr, MAP_BACKWARD,
+                                  iters);
 }
 
 /* The d-pair map from caller-supplied training points and alpha (the counterpart of sgpr_applymap_host for d canonical pairs). */

@@ -100,12 +100,10 @@ unsigned applymap_last_calls();                 // K*-row evaluations (all orbit
 int applymap_sections(int family, int mode, int nsec, int first, int nm, int ntest, int n0, const double *xtr, const double *ytr,
                       const double *alpha, const KConst *kcs, int n0p, const double *xtrp, const double *ytrp,
                       const double *alphap, const KConst *kcps, const double *Q0, const double *P0, double *qmap, double *pmap,
-                      double *pdiff, hipStream_t st);
-// the same with the tangent map (mapsec_tan.h): jac [nm - 1][ntest][2][2], mono [ntest][2][2], lyap [ntest][2], each or null
-int applymap_sections_tangent(int family, int mode, int nsec, int first, int nm, int ntest, int n0, const double *xtr,
-                              const double *ytr, const double *alpha, const KConst *kcs, int n0p, const double *xtrp,
-                              const double *ytrp, const double *alphap, const KConst *kcps, const double *Q0, const double *P0,
-                              double *qmap, double *pmap, double *pdiff, double *jac, double *mono, double *lyap, hipStream_t st);
+                      double *pdiff, hipStream_t st, bool tan = false, double *jac = nullptr, double *mono = nullptr,
+                      double *lyap = nullptr);
+// `tan`: the same with the tangent map (mapsec_tan.h, tangent_core.h): jac [nm - 1][ntest][2][2], mono [ntest][2][2], lyap
+// [ntest][2], each or null
 // the sectioned map backwards: Q0 / P0 hold the images (Q, P), row i of qmap / pmap is the i-th preimage, step i undoes section
 // (first - i) mod nsec; no guess GPs; iters [nm - 1][ntest] or null
 int applymap_sections_inverse(int family, int mode, int nsec, int first, int nm, int ntest, int n0, const double *xtr,

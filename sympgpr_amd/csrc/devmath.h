@@ -145,4 +145,7 @@ SGPR_DEV double cos2h_sel(double h, double s2, double l2)
     return __builtin_fma(-2.0, s2, 1.0);
 }
 
+// the device code's one test for "a finite number": false for NaN too
+SGPR_DEV bool finite_d(double v) { return __builtin_fabs(v) <= 1.79769313486231570815e308; }
+
 }  // namespace sgpr

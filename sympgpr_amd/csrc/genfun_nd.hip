@@ -15,7 +15,7 @@ namespace sgpr {
 
 namespace {
 
-using namespace nd;         // all_coords, weights, is_sum, dispatch_nd (nd_eval.h); NT, NdArgs, fill_args, finite_d (nd_args.h)
+using namespace nd;         // all_coords, weights, is_sum, dispatch_nd (nd_eval.h); NT, NdArgs, fill_args (nd_args.h); finite_d (devmath.h)
 
 constexpr int GF_WAVES = NT / 64;   // test points per workgroup of the mean kernel: one wave each
 constexpr int GF_CT = 16;           // test points a thread of the cross kernel walks through (NTJ of the Gram kernel)

@@ -1,8 +1,10 @@
 // map.hip -- the symplectic map of a one-pair (d = 1) fit for gfx950 (MI355X): every time step of every orbit on the device,
 // for one GP pair (applymap_kernel) and for one GP pair per toroidal section (applymap_sections_kernel).  The two kernels
 // share one time step (map_step) and one copy of the per-thread sums (rows_part, guess_part).  The sectioned kernel has a TAN
-// instance (mapsec_tan.h): the step's Jacobian, the monodromy matrix and the finite-time Lyapunov exponents of every orbit.
+// instance: the step's Jacobian, the monodromy matrix and the finite-time Lyapunov exponents of every orbit -- mapsec_tan.h sums
+// the Hessian on this file's data layout, tangent_core.h (shared with map_nd.hip) has everything that follows from it.
 // applymap_sections_inverse_kernel iterates the sectioned map (one section: the one-pair map) backwards, with map_step_inverse.
+// The three sectioned kernels read their sections through one SecReader and are launched by one host helper.
 #include <atomic>
 #include <type_traits>
 #include "common.h"
@@ -282,6 +284,7 @@ __global__ __launch_bounds__(TT) void applymap_kernel(const MapArgs a)
 // applymap_kernel launch with S == 1 on that section's data.  One workgroup per orbit at every size: sections exist to keep
 // each fit small, and a kernel in which no workgroup waits for another has nothing that can hang.
 constexpr long MAPSEC_STAGE = 8960;   // doubles of LDS for the staged sections: the 70 KB applymap_kernel reserves (7 * MAP_STAGE * 256)
+// One argument block for the three sectioned kernels; the backward one has no guess GPs (n0p = 0, their pointers null) and no pdiff.
 struct MapSecArgs {
     int nm, ntest, n0, n0p, mode, maxiter;
     int nsec, first;
@@ -292,26 +295,31 @@ struct MapSecArgs {
     const double *Q0, *P0;
     double *qmap, *pmap, *pdiff;          // [nm][ntest], C order; pdiff may be null
 };
+struct MapSecInvArgs : MapSecArgs {
+    int *iters;                           // [nm - 1][ntest] or null
+};
 
-#include "mapsec_tan.h"   // the tangent map: what TAN = true adds to the kernel below
+#include "tangent_core.h"   // block_sum_n; the step matrix and the monodromy / Benettin step of the TAN instance
+#include "mapsec_tan.h"     // MapSecTanArgs; the Hessian sums of the TAN instance
 
-// TAN: after every accepted step (new p finite: block-uniform) one more pass over section m's points sums the Hessian of the
-// generating function at (q_old, P_new); the step's Jacobian M, the product of the M's and the Benettin sums follow from it.
-// The orbit itself makes the same rows / guess calls in the same order as without TAN and has the same bits.  A lost orbit's M
-// is NaN from that step on, and with it mono and the exponents.
-// kcs, kcps: the sections' constants (make_kconst) in device memory, nsec each; a step reads its pair with block-uniform loads
-// (__restrict__: nothing the kernel writes can alias them, so the compiler fetches them with scalar loads, into SGPRs, where
-// applymap_kernel has its kernel arguments)
-template <int FAM, int TT, bool TAN = false>
-__global__ __launch_bounds__(TT) void applymap_sections_kernel(const std::conditional_t<TAN, MapSecTanArgs, MapSecArgs> a,
-                                                               const KConst *__restrict__ kcs, const KConst *__restrict__ kcps)
-{
-    __shared__ double sh[2][(TAN ? 3 : 2) * (TT / 64)];
-    extern __shared__ double sec_st[];                  // [section]{x, y, alpha (two halves): n0 each; guess x, y, alpha: n0p each}
-    const int k = blockIdx.x, tid = threadIdx.x, n0 = a.n0, n0p = a.n0p;
-    const int per = 4 * n0 + 3 * n0p;                   // (staged only: nsec * per <= MAPSEC_STAGE)
-    const bool staged = a.staged != 0;
-    if (staged) {
+// The sections' points and weights as thread `tid` of an orbit's workgroup (TT threads) reads them: from dynamic LDS
+// ([section]{x, y, alpha (two halves): n0 each; guess x, y, alpha: n0p each}, `per` doubles a section) when all sections fit,
+// from memory otherwise.  The thread's points are j = tid, tid + TT, ... in that order, staged or not: the same bits.  Every
+// call keeps its staged / unstaged branch with one kind of pointer in each (see rows_part).  The sums over the workgroup stay
+// with the kernels.
+template <int TT>
+struct SecReader {
+    const MapSecArgs &a;
+    double *sec_st;
+    int per;                                            // (staged only: nsec * per <= MAPSEC_STAGE)
+    bool staged;
+    int n0, n0p, tid;
+    __device__ __forceinline__ SecReader(const MapSecArgs &args, double *lds)
+        : a(args), sec_st(lds), per(4 * args.n0 + 3 * args.n0p), staged(args.staged != 0), n0(args.n0), n0p(args.n0p), tid(threadIdx.x) {}
+
+    __device__ __forceinline__ void stage() const
+    {
+        if (!staged) return;
         for (int s = 0; s < a.nsec; ++s) {
             double *d = sec_st + s * per;
             const double *x = a.xtr + (size_t)s * n0, *y = a.ytr + (size_t)s * n0, *al = a.alpha + (size_t)s * 2 * n0;
@@ -326,6 +334,58 @@ __global__ __launch_bounds__(TT) void applymap_sections_kernel(const std::condit
         }
         // (every thread reads back what it wrote itself: no barrier needed)
     }
+    // this thread's share of section m's Kstar(1,:).alpha, Kstar(2,:).alpha at (q, P)
+    template <int FAM>
+    __device__ __forceinline__ void rows(int m, double q, double P, const KConst &kc, double &r1, double &r2) const
+    {
+        if (staged) {
+            const double *d = sec_st + m * per;
+            rows_part<FAM>(d, d + n0, d + 2 * n0, d + 3 * n0, tid, TT, tid, TT, n0, q, P, kc, r1, r2);
+        } else {
+            const double *al = a.alpha + (size_t)m * 2 * n0;
+            rows_part<FAM>(a.xtr + (size_t)m * n0, a.ytr + (size_t)m * n0, al, al + n0, tid, TT, tid, TT, n0, q, P, kc, r1, r2);
+        }
+    }
+    // ... of section m's regular GP's Kstar.alphap at (q, p)
+    template <int FAM>
+    __device__ __forceinline__ double guess(int m, double q, double p, const KConst &kcp) const
+    {
+        const double *d = sec_st + m * per + 4 * n0;
+        return staged ? guess_part<FAM>(d, d + n0p, d + 2 * n0p, tid, TT, tid, TT, n0p, q, p, kcp)
+                      : guess_part<FAM>(a.xtrp + (size_t)m * n0p, a.ytrp + (size_t)m * n0p, a.alphap + (size_t)m * n0p,
+                                        tid, TT, tid, TT, n0p, q, p, kcp);
+    }
+    // ... of section m's three Hessian sums at (q, P) (mapsec_tan.h)
+    template <int FAM>
+    __device__ __forceinline__ void hess(int m, double q, double P, const KConst &kc, double &hA, double &hB, double &hC) const
+    {
+        if (staged) {
+            const double *d = sec_st + m * per;
+            sec_hess_part<FAM>(d, d + n0, d + 2 * n0, d + 3 * n0, tid, TT, tid, TT, n0, q, P, kc, hA, hB, hC);
+        } else {
+            const double *al = a.alpha + (size_t)m * 2 * n0;
+            sec_hess_part<FAM>(a.xtr + (size_t)m * n0, a.ytr + (size_t)m * n0, al, al + n0, tid, TT, tid, TT, n0, q, P, kc, hA, hB, hC);
+        }
+    }
+};
+
+// TAN: after every accepted step (new p finite: block-uniform) one more pass over section m's points sums the Hessian of the
+// generating function at (q_old, P_new); the step's Jacobian M, the product of the M's and the Benettin sums follow from it
+// (tangent_core.h at D = 2, H = {A, B, C}).  The orbit itself makes the same rows / guess calls in the same order as without TAN
+// and has the same bits.  A lost orbit's M is NaN from that step on, and with it mono and the exponents.
+// kcs, kcps: the sections' constants (make_kconst) in device memory, nsec each; a step reads its pair with block-uniform loads
+// (__restrict__: nothing the kernel writes can alias them, so the compiler fetches them with scalar loads, into SGPRs, where
+// applymap_kernel has its kernel arguments)
+template <int FAM, int TT, bool TAN = false>
+__global__ __launch_bounds__(TT) void applymap_sections_kernel(const std::conditional_t<TAN, MapSecTanArgs, MapSecArgs> a,
+                                                               const KConst *__restrict__ kcs, const KConst *__restrict__ kcps)
+{
+    static_assert(TT / 64 <= 4, "block_sum_n<3, TT> gets no `res` half here");
+    __shared__ double sh[2][(TAN ? 3 : 2) * (TT / 64)];  // [wave][sum] of block_sum2 / block_sum_n<3>, two alternating halves
+    extern __shared__ double sec_st[];
+    const int k = blockIdx.x, tid = threadIdx.x;
+    const SecReader<TT> rd(a, sec_st);
+    rd.stage();
     unsigned seq = 0;
     auto sum2 = [&](double &x, double &y) {
         ++seq;
@@ -338,27 +398,18 @@ __global__ __launch_bounds__(TT) void applymap_sections_kernel(const std::condit
         if (a.pdiff) a.pdiff[k] = pd;
     }
     int m = a.first;
-    if constexpr (TAN) sec_tan_init();
+    if constexpr (TAN) maptan_init<2>();
     for (int i = 0; i + 1 < a.nm; ++i) {
         const KConst kc = kcs[m];
         const double q_old = q;
         auto rows = [&](double q, double P, double &r1, double &r2) {   // section m's Kstar(1,:).alpha, Kstar(2,:).alpha
-            if (staged) {
-                const double *d = sec_st + m * per;
-                rows_part<FAM>(d, d + n0, d + 2 * n0, d + 3 * n0, tid, TT, tid, TT, n0, q, P, kc, r1, r2);
-            } else {
-                const double *al = a.alpha + (size_t)m * 2 * n0;
-                rows_part<FAM>(a.xtr + (size_t)m * n0, a.ytr + (size_t)m * n0, al, al + n0, tid, TT, tid, TT, n0, q, P, kc, r1, r2);
-            }
+            rd.template rows<FAM>(m, q, P, kc, r1, r2);
             sum2(r1, r2);
         };
         auto guess = [&](double q, double p) {
             const KConst kcp = kcps[m];
-            const double *d = sec_st + m * per + 4 * n0;
             double z = 0.0;
-            double r = staged ? guess_part<FAM>(d, d + n0p, d + 2 * n0p, tid, TT, tid, TT, n0p, q, p, kcp)
-                              : guess_part<FAM>(a.xtrp + (size_t)m * n0p, a.ytrp + (size_t)m * n0p, a.alphap + (size_t)m * n0p,
-                                                tid, TT, tid, TT, n0p, q, p, kcp);
+            double r = rd.template guess<FAM>(m, q, p, kcp);
             sum2(r, z);
             return r;
         };
@@ -366,23 +417,16 @@ __global__ __launch_bounds__(TT) void applymap_sections_kernel(const std::condit
         if constexpr (TAN) {                                // section m's Hessian at (q_old, P_new) of the accepted step
             double M[4];
             bool tan_ok = false;
-            if (sec_finite(p)) {
-                double hA, hB, hC;
-                if (staged) {
-                    const double *d = sec_st + m * per;
-                    sec_hess_part<FAM>(d, d + n0, d + 2 * n0, d + 3 * n0, tid, TT, tid, TT, n0, q_old, p, kc, hA, hB, hC);
-                } else {
-                    const double *al = a.alpha + (size_t)m * 2 * n0;
-                    sec_hess_part<FAM>(a.xtr + (size_t)m * n0, a.ytr + (size_t)m * n0, al, al + n0, tid, TT, tid, TT, n0, q_old, p,
-                                       kc, hA, hB, hC);
-                }
+            if (finite_d(p)) {
+                double H[3];
+                rd.template hess<FAM>(m, q_old, p, kc, H[0], H[1], H[2]);
                 ++seq;
-                block_sum3<TT>(hA, hB, hC, sh[seq & 1u]);
-                tan_ok = sec_tan_matrix(hA, hB, hC, M);
+                block_sum_n<3, TT>(H, sh[seq & 1u], nullptr);
+                tan_ok = maptan_matrix<2>(H, M);
             }
             if (!tan_ok) M[0] = M[1] = M[2] = M[3] = __builtin_nan("");
-            sec_tan_publish(M, a.jac ? a.jac + ((size_t)i * a.ntest + k) * 4 : nullptr);
-            sec_tan_advance();
+            maptan_publish<2>(M, a.jac ? a.jac + ((size_t)i * a.ntest + k) * 4 : nullptr);
+            maptan_advance<2, true>();
         }
         if (++m == a.nsec) m = 0;
         if (tid == 0) {
@@ -391,7 +435,7 @@ __global__ __launch_bounds__(TT) void applymap_sections_kernel(const std::condit
             if (a.pdiff) a.pdiff[(size_t)(i + 1) * a.ntest + k] = pd;
         }
     }
-    if constexpr (TAN) sec_tan_finish(a, k);
+    if constexpr (TAN) maptan_finish<2>(a.mono, a.lyap, a.nm, k);
 }
 
 // ---- the sectioned map BACKWARDS.  The forward step passes through the point (q, P): it solves p = P + r1(q, P) for P and sets
@@ -411,7 +455,7 @@ __device__ __forceinline__ void map_step_inverse(int mode, int maxiter, double t
     const double Q = q, P = p;
     double qn = nan, pn = nan;
     int itn = -1;
-    if (sec_finite(Q) && sec_finite(P)) {              // NaN = lost orbit stays lost; an infinite start value is lost as well
+    if (finite_d(Q) && finite_d(P)) {              // NaN = lost orbit stays lost; an infinite start value is lost as well
         double r1, r2;
         double q0 = Q;
         rows(q0, P, r1, r2);
@@ -421,7 +465,7 @@ __device__ __forceinline__ void map_step_inverse(int mode, int maxiter, double t
         double f1 = q1 + r2 - Q;
         int it = 0;
         for (; it < maxiter; ++it) {                    // secant; every quantity is block-uniform
-            if (!(fabs(q1 - q0) > tol * fmax(1.0, fabs(q1))) || !sec_finite(f1)) break;
+            if (!(fabs(q1 - q0) > tol * fmax(1.0, fabs(q1))) || !finite_d(f1)) break;
             const double d = f1 - f0;
             if (d == 0.0) break;
             const double qs = q1 - f1 * (q1 - q0) / d;
@@ -429,11 +473,11 @@ __device__ __forceinline__ void map_step_inverse(int mode, int maxiter, double t
             rows(q1, P, r1, r2);
             f1 = q1 + r2 - Q;
         }
-        if (sec_finite(f1) && fabs(f1) <= 1e-8 * fmax(1.0, fabs(Q))) {   // the forward rule with the roles swapped
+        if (finite_d(f1) && fabs(f1) <= 1e-8 * fmax(1.0, fabs(Q))) {   // the forward rule with the roles swapped
             const double pp = P + r1;                   // r1 belongs to (q1, P)
             // the backward twin of the forward "new momentum < 0": the preimage has left the plasma
             const bool negp = (mode & SGPR_MAP_LOSS_NEGP) && pp < 0.0;
-            if (sec_finite(pp) && !negp) {
+            if (finite_d(pp) && !negp) {
                 pn = pp;
                 qn = q1;
                 if (mode & SGPR_MAP_WRAP_Q) qn -= twopi * floor(qn / twopi);
@@ -444,41 +488,18 @@ __device__ __forceinline__ void map_step_inverse(int mode, int maxiter, double t
     q = qn; p = pn; iters = itn;
 }
 
-struct MapSecInvArgs {
-    int nm, ntest, n0, mode, maxiter;
-    int nsec, first;
-    int staged;                           // all sections' points and weights (4 n0 doubles each) fit into MAPSEC_STAGE doubles of LDS
-    double tol;
-    const double *xtr, *ytr, *alpha;      // n0 x nsec, n0 x nsec, 2 n0 x nsec, column-major, tight
-    const double *Q0, *P0;                // the images (Q, P)
-    double *qmap, *pmap;                  // [nm][ntest], C order: row i the i-th preimage
-    int *iters;                           // [nm - 1][ntest] or null
-};
-
 // All nm - 1 backward steps of all orbits in one launch: step i (row i -> row i + 1) undoes section (first - i) mod nsec,
 // `first` the section whose forward step produced row 0.  applymap_sections_kernel's shape: one workgroup per orbit, the
-// sections staged in dynamic LDS when they fit (no guess GP: 4 n0 doubles per section), the same per-thread point order
-// (j = tid, tid + TT, ...) staged or not, rows_part + block_sum2 on alternating LDS halves, the sections' constants by
-// block-uniform scalar loads.  No workgroup waits for another.
+// sections through the same SecReader (no guess GP: n0p = 0, 4 n0 doubles per section), rows + block_sum2 on alternating LDS
+// halves, the sections' constants by block-uniform scalar loads.  No workgroup waits for another.
 template <int FAM, int TT>
 __global__ __launch_bounds__(TT) void applymap_sections_inverse_kernel(const MapSecInvArgs a, const KConst *__restrict__ kcs)
 {
     __shared__ double sh[2][2 * (TT / 64)];
-    extern __shared__ double sec_st[];                  // [section]{x, y, alpha (two halves): n0 each}
-    const int k = blockIdx.x, tid = threadIdx.x, n0 = a.n0;
-    const int per = 4 * n0;                             // (staged only: nsec * per <= MAPSEC_STAGE)
-    const bool staged = a.staged != 0;
-    if (staged) {
-        for (int s = 0; s < a.nsec; ++s) {
-            double *d = sec_st + s * per;
-            const double *x = a.xtr + (size_t)s * n0, *y = a.ytr + (size_t)s * n0, *al = a.alpha + (size_t)s * 2 * n0;
-            for (int j = tid; j < n0; j += TT) {
-                d[j] = x[j]; d[n0 + j] = y[j];
-                d[2 * n0 + j] = al[j]; d[3 * n0 + j] = al[n0 + j];
-            }
-        }
-        // (every thread reads back what it wrote itself: no barrier needed)
-    }
+    extern __shared__ double sec_st[];
+    const int k = blockIdx.x, tid = threadIdx.x;
+    const SecReader<TT> rd(a, sec_st);
+    rd.stage();
     unsigned seq = 0;
     auto sum2 = [&](double &x, double &y) {
         ++seq;
@@ -493,13 +514,7 @@ __global__ __launch_bounds__(TT) void applymap_sections_inverse_kernel(const Map
     for (int i = 0; i + 1 < a.nm; ++i) {
         const KConst kc = kcs[m];
         auto rows = [&](double q, double P, double &r1, double &r2) {   // section m's Kstar(1,:).alpha, Kstar(2,:).alpha
-            if (staged) {
-                const double *d = sec_st + m * per;
-                rows_part<FAM>(d, d + n0, d + 2 * n0, d + 3 * n0, tid, TT, tid, TT, n0, q, P, kc, r1, r2);
-            } else {
-                const double *al = a.alpha + (size_t)m * 2 * n0;
-                rows_part<FAM>(a.xtr + (size_t)m * n0, a.ytr + (size_t)m * n0, al, al + n0, tid, TT, tid, TT, n0, q, P, kc, r1, r2);
-            }
+            rd.template rows<FAM>(m, q, P, kc, r1, r2);
             sum2(r1, r2);
         };
         int it;
@@ -578,71 +593,58 @@ int applymap_status(const void *team_ws, int ntest, int n0)
     return 0;
 }
 
-// The sectioned map: one launch, one 256-thread workgroup per orbit.  Dynamic LDS: the drivers' size (4 sections of 70 points)
-// reserves 15.7 KB, not the 70 KB of the limit, so several orbits share a CU.
-template <bool TAN, typename Args>
-static int applymap_sections_launch(int family, const Args &a, size_t lds, const KConst *kcs, const KConst *kcps, hipStream_t st)
+// The sectioned maps: one launch, one 256-thread workgroup per orbit.  Dynamic LDS: exactly what is staged is reserved -- the
+// drivers' size (4 sections of 70 points) takes 15.7 KB, not the 70 KB of the limit, so several orbits share a CU.
+// The common arguments of the three kernels and, in `lds`, the bytes of dynamic LDS of the launch (0: nothing is staged).
+static MapSecArgs mapsec_args(int mode, int nsec, int first, int nm, int ntest, int n0, const double *xtr, const double *ytr,
+                              const double *alpha, int n0p, const double *xtrp, const double *ytrp, const double *alphap,
+                              const double *Q0, const double *P0, double *qmap, double *pmap, double *pdiff, size_t &lds)
 {
-    return dispatch_family(family, [&](auto fam) {
-        constexpr int F = decltype(fam)::value;
-        auto kern = applymap_sections_kernel<F, MAP_T, TAN>;
-        if (lds > 48 * 1024)
-            SGPR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(a.ntest), dim3(MAP_T), lds, st, a, kcs, kcps);
-        SGPR_CHECK_LAUNCH();
-        return 0;
-    });
+    const long need = (long)nsec * (4L * n0 + 3L * n0p);
+    const bool staged = need <= MAPSEC_STAGE;
+    lds = staged ? (size_t)need * sizeof(double) : 0;
+    return MapSecArgs{nm, ntest, n0, n0p, mode, 60, nsec, first, staged ? 1 : 0, 1e-13, xtr, ytr, alpha, xtrp, ytrp, alphap, Q0, P0,
+                      qmap, pmap, pdiff};
+}
+template <typename Kern, typename... Args>
+static int mapsec_launch(Kern kern, int ntest, size_t lds, hipStream_t st, const Args &...args)
+{
+    if (lds > 48 * 1024)
+        SGPR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kern, dim3(ntest), dim3(MAP_T), lds, st, args...);
+    SGPR_CHECK_LAUNCH();
+    return 0;
 }
 
+// Forwards.  jac [nm - 1][ntest][2][2], mono [ntest][2][2], lyap [ntest][2], each or null: with `tan` the launch is the TAN
+// instance (same staging rule, same LDS, same orbit bits) and fills those of the three that are given.
 int applymap_sections(int family, int mode, int nsec, int first, int nm, int ntest, int n0, const double *xtr, const double *ytr,
                       const double *alpha, const KConst *kcs, int n0p, const double *xtrp, const double *ytrp,
                       const double *alphap, const KConst *kcps, const double *Q0, const double *P0, double *qmap, double *pmap,
-                      double *pdiff, hipStream_t st)
+                      double *pdiff, hipStream_t st, bool tan, double *jac, double *mono, double *lyap)
 {
     if (nm <= 0 || ntest <= 0) return 0;
-    const long need = (long)nsec * (4L * n0 + 3L * n0p);
-    const bool staged = need <= MAPSEC_STAGE;
-    const size_t lds = staged ? (size_t)need * sizeof(double) : 0;
-    MapSecArgs a{nm, ntest, n0, n0p, mode, 60, nsec, first, staged ? 1 : 0, 1e-13, xtr, ytr, alpha, xtrp, ytrp, alphap, Q0, P0,
-                 qmap, pmap, pdiff};
-    return applymap_sections_launch<false>(family, a, lds, kcs, kcps, st);
+    size_t lds;
+    const MapSecTanArgs a{mapsec_args(mode, nsec, first, nm, ntest, n0, xtr, ytr, alpha, n0p, xtrp, ytrp, alphap, Q0, P0, qmap, pmap,
+                                      pdiff, lds), jac, mono, lyap};
+    return dispatch_family(family, [&](auto fam) {
+        constexpr int F = decltype(fam)::value;
+        if (tan) return mapsec_launch(applymap_sections_kernel<F, MAP_T, true>, ntest, lds, st, a, kcs, kcps);
+        return mapsec_launch(applymap_sections_kernel<F, MAP_T, false>, ntest, lds, st, static_cast<const MapSecArgs &>(a), kcs, kcps);
+    });
 }
 
-// The same with the tangent map (mapsec_tan.h): jac [nm - 1][ntest][2][2], mono [ntest][2][2], lyap [ntest][2], each or null.
-// Same staging rule, same LDS, same orbit bits.
-int applymap_sections_tangent(int family, int mode, int nsec, int first, int nm, int ntest, int n0, const double *xtr,
-                              const double *ytr, const double *alpha, const KConst *kcs, int n0p, const double *xtrp,
-                              const double *ytrp, const double *alphap, const KConst *kcps, const double *Q0, const double *P0,
-                              double *qmap, double *pmap, double *pdiff, double *jac, double *mono, double *lyap, hipStream_t st)
-{
-    if (nm <= 0 || ntest <= 0) return 0;
-    const long need = (long)nsec * (4L * n0 + 3L * n0p);
-    const bool staged = need <= MAPSEC_STAGE;
-    const size_t lds = staged ? (size_t)need * sizeof(double) : 0;
-    MapSecTanArgs a{{nm, ntest, n0, n0p, mode, 60, nsec, first, staged ? 1 : 0, 1e-13, xtr, ytr, alpha, xtrp, ytrp, alphap, Q0, P0,
-                     qmap, pmap, pdiff}, jac, mono, lyap};
-    return applymap_sections_launch<true>(family, a, lds, kcs, kcps, st);
-}
-
-// The sectioned map backwards: one launch, one 256-thread workgroup per orbit.  No guess GPs, so a section takes 4 n0 doubles of
-// the same MAPSEC_STAGE limit, and exactly what is staged is reserved.
+// Backwards.  No guess GPs, so a section takes 4 n0 doubles of the same MAPSEC_STAGE limit.
 int applymap_sections_inverse(int family, int mode, int nsec, int first, int nm, int ntest, int n0, const double *xtr,
                               const double *ytr, const double *alpha, const KConst *kcs, const double *Q0, const double *P0,
                               double *qmap, double *pmap, int *iters, hipStream_t st)
 {
     if (nm <= 0 || ntest <= 0) return 0;
-    const long need = (long)nsec * 4L * n0;
-    const bool staged = need <= MAPSEC_STAGE;
-    const size_t lds = staged ? (size_t)need * sizeof(double) : 0;
-    MapSecInvArgs a{nm, ntest, n0, mode, 60, nsec, first, staged ? 1 : 0, 1e-13, xtr, ytr, alpha, Q0, P0, qmap, pmap, iters};
+    size_t lds;
+    const MapSecInvArgs a{mapsec_args(mode, nsec, first, nm, ntest, n0, xtr, ytr, alpha, 0, nullptr, nullptr, nullptr, Q0, P0, qmap, pmap,
+                                      nullptr, lds), iters};
     return dispatch_family(family, [&](auto fam) {
-        constexpr int F = decltype(fam)::value;
-        auto kern = applymap_sections_inverse_kernel<F, MAP_T>;
-        if (lds > 48 * 1024)
-            SGPR_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(ntest), dim3(MAP_T), lds, st, a, kcs);
-        SGPR_CHECK_LAUNCH();
-        return 0;
+        return mapsec_launch(applymap_sections_inverse_kernel<decltype(fam)::value, MAP_T>, ntest, lds, st, a, kcs);
     });
 }
 

@@ -1,6 +1,6 @@
-// map_nd.hip -- the symplectic map of a fit with d canonical pairs per point, forwards (with or without its tangent map,
-// maptan.h) and backwards: every step of one orbit inside one workgroup.  gram_nd.hip has the kernel's derivation, nd_eval.h
-// its entry formulas.
+// map_nd.hip -- the symplectic map of a fit with d canonical pairs per point, forwards (with or without its tangent map:
+// maptan.h sums the Hessian, tangent_core.h, shared with map.hip, has what follows from it) and backwards: every step of one
+// orbit inside one workgroup.  gram_nd.hip has the kernel's derivation, nd_eval.h its entry formulas.
 //
 // x = (q_1..q_d, P_1..P_d), G(x) = K*(x) alpha as predict_nd_kernel forms it: G_q = dF/dq = p - P, G_P = dF/dP = Q - q.  One step
 // solves f(P) = G_q(q, P) - p + P = 0 for P in R^d by Newton from P = p, then Q = q + G_P(q, P).  The Jacobian is analytic:
@@ -19,7 +19,7 @@ namespace sgpr {
 
 namespace {
 
-using namespace nd;         // all_coords, weights, is_sum, dispatch_nd (nd_eval.h); NdArgs, fill_args, finite_d (nd_args.h)
+using namespace nd;         // all_coords, weights, is_sum, dispatch_nd (nd_eval.h); NdArgs, fill_args (nd_args.h); finite_d (devmath.h)
 
 constexpr int MAPND_T_SMALL = 256, MAPND_T_LARGE = 512;    // threads per orbit: n0 <= MAPND_STAGE_PTS / larger training sets
 constexpr int MAPND_STAGE_PTS = 4 * MAPND_T_SMALL;         // training points a 256-thread workgroup keeps in LDS (2 D doubles each: 96 KiB at D = 6)
@@ -34,42 +34,7 @@ struct MapNdArgs {
     int *iters;                        // [nm - 1][ntest], may be null
 };
 
-// v[s] := the sum over the workgroup of every thread's v[s], the same bits in every thread: wave shuffle, one row of NS sums
-// per wave in LDS, folded in wave order.  8 waves: lanes 0 .. NS-1 fold one sum each and publish it (NS instead of 8 NS
-// reads per thread).  `part` (W NS doubles) and `res` (NS) are the halves the call before did NOT use -- the callers alternate,
-// as block_sum2 of map.hip does: the barrier of call n + 1 lies between the reads of call n and the writes of call n + 2.
-template <int NS, int TT>
-__device__ __forceinline__ void block_sum_n(double (&v)[NS], double *part, double *res)
-{
-    constexpr int W = TT / 64;
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-        for (int o = 32; o > 0; o >>= 1) v[s] += __shfl_down(v[s], o, 64);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int s = 0; s < NS; ++s) part[(threadIdx.x >> 6) * NS + s] = v[s];
-    }
-    __syncthreads();
-    if constexpr (W <= 4) {
-#pragma unroll
-        for (int s = 0; s < NS; ++s) {
-            double x = 0.0;
-#pragma unroll
-            for (int w = 0; w < W; ++w) x += part[w * NS + s];
-            v[s] = x;
-        }
-    } else {
-        if (threadIdx.x < NS) {
-            double x = 0.0;
-#pragma unroll
-            for (int w = 0; w < W; ++w) x += part[w * NS + threadIdx.x];
-            res[threadIdx.x] = x;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int s = 0; s < NS; ++s) v[s] = res[s];
-    }
-}
+#include "tangent_core.h"   // block_sum_n; the step matrix and the monodromy / Benettin step of the TAN instances
 
 // G = K*(x) alpha (D sums) and, with JAC, J[c * d + e] = d G_c / d P_e (d^2 sums) over all n0 training points: thread t takes
 // the points t, t + TT, ...  `stg`: the staged points ([coordinate | alpha block][MAPND_STAGE_PTS]) or null (read from memory)
@@ -158,7 +123,7 @@ __device__ __forceinline__ bool newton_step(const double (&J)[d * d], const doub
     return ok;
 }
 
-#include "maptan.h"   // the tangent map: what TAN = true adds to the kernel below
+#include "maptan.h"   // the Hessian pass of the tangent map: with tangent_core.h what TAN = true adds to the kernel below
 
 // One workgroup per orbit runs all nm steps; nothing waits on another workgroup, and an orbit's bits depend on nothing but its
 // own start point (TT is chosen from n0 alone).  TT = 256: the training points and alpha are staged in LDS once when they fit
@@ -281,10 +246,10 @@ __global__ __launch_bounds__(TT) void applymap_nd_kernel(const std::conditional_
                 for (int s = 0; s < D * D; ++s) M[s] = nan;
             }
             maptan_publish<D>(M, a.jac ? a.jac + ((size_t)i * a.ntest + k) * (D * D) : nullptr);
-            maptan_advance<D>();
+            maptan_advance<D, false>();
         }
     }
-    if constexpr (TAN) maptan_finish<D>(a, k);
+    if constexpr (TAN) maptan_finish<D>(a.mono, a.lyap, a.nm, k);
 }
 
 // The backward step: rows qmap[0], pmap[0] hold (Q, P), and one step returns the (q, p) that the kernel above takes there.  The

@@ -1,5 +1,5 @@
 // nd_args.h -- what the single-problem d-pair units share beside the entry formulas (nd_eval.h): the argument block of one call
-// and two small helpers.  Included by gram_nd.hip (Gram build, prediction), map_nd.hip (the symplectic map) and genfun_nd.hip
+// and one small helper.  Included by gram_nd.hip (Gram build, prediction), map_nd.hip (the symplectic map) and genfun_nd.hip
 // (the generating function); the batched kernels (batch.hip) read one NdConst per problem instead and do not use it.
 #pragma once
 #include "nd_eval.h"
@@ -25,8 +25,6 @@ struct NdArgs {
 
 // the hyper-parameters of the call into the constants of its argument block (nd_eval.h)
 inline int fill_args(int family, int d, const double *hyp, int nhyp, NdArgs &a) { return fill_consts(family, d, hyp, nhyp, a.c); }
-
-__device__ __forceinline__ bool finite_d(double v) { return __builtin_fabs(v) <= 1.79769313486231570815e308; }   // false for NaN too
 
 }  // namespace nd
 }  // namespace sgpr

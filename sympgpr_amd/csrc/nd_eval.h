@@ -55,7 +55,7 @@ __device__ __forceinline__ void all_coords(const NdConst &a, const double *xa, c
 
 // E[m]: the factor that multiplies nh[m] on the diagonal blocks -- sig k for the product kernels (one exp
 // per pair), sig f_m for the sum kernel (one exp per coordinate)
-template <int FAM> constexpr bool is_sum() { return FAM == SGPR_FAM_B || (FAM == SGPR_FAM_USER && gen::user_is_sum); }
+using gen::is_sum;
 
 template <int FAM, int D>
 __device__ __forceinline__ void weights(const NdConst &a, const double (&arg)[D], double (&E)[D])

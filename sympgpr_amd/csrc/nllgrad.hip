@@ -47,7 +47,7 @@ struct GradArgs2 : GradArgs {  // the rank-2 weight of the LOO gradient (loograd
     const double *beta;        // n
 };
 
-template <int FAM> constexpr bool sum_kernel() { return FAM == SGPR_FAM_B || (FAM == SGPR_FAM_USER && gen::user_is_sum); }
+using nllg::sum_kernel;
 
 // the workgroup's NACC sums, wave by wave in a fixed order, to its slot of the partials
 template <int NACC>

@@ -15,7 +15,7 @@
 namespace sgpr {
 namespace nllg {
 
-template <int FAM> constexpr bool sum_kernel() { return FAM == SGPR_FAM_B || (FAM == SGPR_FAM_USER && gen::user_is_sum); }
+template <int FAM> constexpr bool sum_kernel() { return gen::is_sum<FAM>(); }
 
 // Pair fits, D = 2d output parts.  The row is part r of the point xi; w[c] weights the entry (row, c N + pj) of the column
 // point xj.  Accumulators: acc[0 .. D-1] the lengths, acc[D .. D+NP-1] the periods (HASP), acc[D+NP] sig -- all without

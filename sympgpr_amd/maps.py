@@ -107,31 +107,40 @@ def _sections_model(mode, nm, Ntest, hyp, xt, yt, alpha, first, family):
     return family, mode, nm, Ntest, first, nsec, N0, hyp, xt, yt, alpha
 
 
-def _sections_call(mode, nm, Ntest, hyp, xt, yt, alpha, Q0, P0, hypp, xp, yp, alphap, first, want_pdiff, family):
-    """What run_map_sections and run_map_sections_tangent share: the checked, laid-out arguments of the two C entries up to and
-    including pdiff, as a list, and the output arrays (qmap, pmap, pdiff or None).  Shape errors are ValueError."""
+def _sections_call(mode, nm, Ntest, hyp, xt, yt, alpha, Q0, P0, first, family, guess=None, want_pdiff=False):
+    """What the sectioned wrappers share: the checked, laid-out arguments of their C entries as a list, the arrays its pointers
+    point into, and the output arrays (qmap, pmap, pdiff or None).  guess = (hypp, xp, yp, alphap): the forward entries, whose
+    list runs up to and including pdiff; guess = None: the backward entry, whose list has neither the guess GPs nor pdiff and
+    ends with pmap.  Shape errors are ValueError."""
     family, mode, nm, Ntest, first, nsec, N0, hyp, xt, yt, alpha = _sections_model(mode, nm, Ntest, hyp, xt, yt, alpha, first, family)
-    if mode & EXPLICIT:
-        N0p, hp = 0, np.zeros((nsec, 0))
-        xp = yp = alphap = np.zeros((0, nsec), order="F")
-    else:
-        if hypp is None or xp is None or yp is None or alphap is None:
-            raise ValueError("the implicit map needs the guess GPs: hypp, xp, yp and alphap")
-        hp = np.asarray(hypp, dtype=np.float64)
-        if hp.ndim != 2 or hp.shape[0] != nsec:
-            raise ValueError("hypp must be (nsec = %d, nhyp)" % nsec)
-        xp = _section_columns("xp", xp, None, nsec)
-        N0p = xp.shape[0]
-        yp = _section_columns("yp", yp, N0p, nsec)
-        alphap = _section_columns("alphap", alphap, N0p, nsec)
-    hyp, hp = L.f64(hyp), L.f64(hp)                     # C order: section s at hyp + s * nhyp
+    hyp = L.f64(hyp)                                    # C order: section s at hyp + s * nhyp
+    keep, mid = [hyp, xt, yt, alpha], []
+    if guess is not None:
+        hypp, xp, yp, alphap = guess
+        if mode & EXPLICIT:
+            N0p, hp = 0, np.zeros((nsec, 0))
+            xp = yp = alphap = np.zeros((0, nsec), order="F")
+        else:
+            if hypp is None or xp is None or yp is None or alphap is None:
+                raise ValueError("the implicit map needs the guess GPs: hypp, xp, yp and alphap")
+            hp = np.asarray(hypp, dtype=np.float64)
+            if hp.ndim != 2 or hp.shape[0] != nsec:
+                raise ValueError("hypp must be (nsec = %d, nhyp)" % nsec)
+            xp = _section_columns("xp", xp, None, nsec)
+            N0p = xp.shape[0]
+            yp = _section_columns("yp", yp, N0p, nsec)
+            alphap = _section_columns("alphap", alphap, N0p, nsec)
+        hp = L.f64(hp)
+        keep += [hp, xp, yp, alphap]
+        mid = [L.dptr(hp), hp.shape[1], N0p, L.dptr(xp), L.dptr(yp), L.dptr(alphap)]
     Q0, P0 = L.f64(np.broadcast_to(Q0, (Ntest,))), L.f64(np.broadcast_to(P0, (Ntest,)))
     qmap, pmap = np.zeros([nm, Ntest]), np.zeros([nm, Ntest])
     pdiff = np.zeros([nm, Ntest]) if want_pdiff else None
-    keep = (hyp, hp, xt, yt, alpha, xp, yp, alphap, Q0, P0)        # the arrays the pointers below point into
+    keep += [Q0, P0]
     args = [L.family_id(family), mode, nsec, first, nm, Ntest, L.dptr(hyp), hyp.shape[1], N0, L.dptr(xt), L.dptr(yt), L.dptr(alpha),
-            L.dptr(hp), hp.shape[1], N0p, L.dptr(xp), L.dptr(yp), L.dptr(alphap), L.dptr(Q0), L.dptr(P0), L.dptr(qmap), L.dptr(pmap),
-            L.dptr(pdiff) if want_pdiff else None]
+            *mid, L.dptr(Q0), L.dptr(P0), L.dptr(qmap), L.dptr(pmap)]
+    if guess is not None:
+        args.append(L.dptr(pdiff) if want_pdiff else None)
     return args, keep, (qmap, pmap, pdiff)
 
 
@@ -147,8 +156,8 @@ def run_map_sections(mode, nm, Ntest, hyp, xt, yt, alpha, Q0, P0, hypp=None, xp=
     -> (qmap, pmap) or (qmap, pmap, pdiff), each [nm, Ntest]; NaN from the step at which an orbit is lost.  A map continued
     from row i with first = (first + i) mod nsec has the bits of the uninterrupted one.  Shape errors are ValueError before
     any device call."""
-    args, keep, (qmap, pmap, pdiff) = _sections_call(mode, nm, Ntest, hyp, xt, yt, alpha, Q0, P0, hypp, xp, yp, alphap, first,
-                                                     want_pdiff, family)
+    args, keep, (qmap, pmap, pdiff) = _sections_call(mode, nm, Ntest, hyp, xt, yt, alpha, Q0, P0, first, family,
+                                                     (hypp, xp, yp, alphap), want_pdiff)
     lib = L.load_library()
     L.check(lib.sgpr_applymap_sections_host(*args), "sgpr_applymap_sections_host")
     return (qmap, pmap, pdiff) if want_pdiff else (qmap, pmap)
@@ -168,8 +177,8 @@ def run_map_sections_tangent(mode, nm, Ntest, hyp, xt, yt, alpha, Q0, P0, hypp=N
     fam = get_family() if family is None else family
     if int(mode) & EXPLICIT and not L.family_id(fam) == L.family_id("B"):
         raise ValueError("EXPLICIT has a tangent map for the sum kernels only (family B)")
-    args, keep, (qmap, pmap, pdiff) = _sections_call(mode, nm, Ntest, hyp, xt, yt, alpha, Q0, P0, hypp, xp, yp, alphap, first,
-                                                     want_pdiff, family)
+    args, keep, (qmap, pmap, pdiff) = _sections_call(mode, nm, Ntest, hyp, xt, yt, alpha, Q0, P0, first, family,
+                                                     (hypp, xp, yp, alphap), want_pdiff)
     t = tangent_outputs_nd(int(nm), int(Ntest), 1, jac, mono, lyap)
     lib = L.load_library()
     L.check(lib.sgpr_applymap_sections_tangent_host(*args, _optr(t, "jac"), _optr(t, "mono"), _optr(t, "lyap")),
@@ -210,15 +219,10 @@ def run_map_sections_inverse(mode, nm, Ntest, hyp, xt, yt, alpha, Q0, P0, first=
     for a lost one.  NaN from the step at which an orbit is lost.  A run continued from row i with first = (first - i) mod nsec
     has the bits of the uninterrupted one.  Shape and mode errors are ValueError before any device call."""
     mode = map_mode_sections_inverse(mode)
-    family, mode, nm, Ntest, first, nsec, N0, hyp, xt, yt, alpha = _sections_model(mode, nm, Ntest, hyp, xt, yt, alpha, first, family)
-    hyp = L.f64(hyp)                                    # C order: section s at hyp + s * nhyp
-    Q0, P0 = L.f64(np.broadcast_to(Q0, (Ntest,))), L.f64(np.broadcast_to(P0, (Ntest,)))
-    qmap, pmap = np.zeros([nm, Ntest]), np.zeros([nm, Ntest])
-    iters = np.zeros((nm - 1, Ntest), dtype=np.int32)
+    args, keep, (qmap, pmap, _) = _sections_call(mode, nm, Ntest, hyp, xt, yt, alpha, Q0, P0, first, family)
+    iters = np.zeros((qmap.shape[0] - 1, qmap.shape[1]), dtype=np.int32)
     lib = L.load_library()
-    L.check(lib.sgpr_applymap_sections_inverse_host(L.family_id(family), mode, nsec, first, nm, Ntest, L.dptr(hyp), hyp.shape[1], N0,
-                                                    L.dptr(xt), L.dptr(yt), L.dptr(alpha), L.dptr(Q0), L.dptr(P0), L.dptr(qmap),
-                                                    L.dptr(pmap), iters.ctypes.data_as(C.POINTER(C.c_int))),
+    L.check(lib.sgpr_applymap_sections_inverse_host(*args, iters.ctypes.data_as(C.POINTER(C.c_int))),
             "sgpr_applymap_sections_inverse_host")
     return (qmap, pmap, iters) if return_iters else (qmap, pmap)
 

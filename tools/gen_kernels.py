@@ -171,6 +171,8 @@ template <int FAM, int Q> __device__ __forceinline__ double factor3(double dx, d
     body.append("// the user slot's shape: sum or product of its two factors; does its q-factor take the extra parameter p\n"
                 "// (then hyp = (lx, ly, p, sig) like family D, and (lq.., lP.., p_1..p_d, sig) for d > 1)\n"
                 "constexpr bool user_is_sum = %s;\nconstexpr bool user_has_p = %s;\n"
+                "// k is the sum of its factors, not their product (family B, or a user slot of that shape)\n"
+                "template <int FAM> constexpr bool is_sum() { return FAM == SGPR_FAM_B || (FAM == SGPR_FAM_USER && user_is_sum); }\n"
                 % ("true" if umode == "sum" else "false", "true" if p in kernel_of(ufq, ufP, umode).free_symbols else "false"))
     tail = "\n}  // namespace gen\n}  // namespace sgpr\n"
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
