@@ -143,11 +143,11 @@ typedef struct sgpr_fit *sgpr_fit_t;
  *   needs built:    factor;  get_matrix takes built or factored
  *   needs factored: solve, ldiag, solve_rhs, solve_rhs_dev, inverse, cond_estimate
  *   needs solved:   alpha, nll, predict_rows, predict_nd, predict_cov, predict_genfun, nll_grad, nll_grad_terms,
- *                   nll_grad_full, loo, applymap_nd, applymap_nd_tangent, applymap_nd_inverse
+ *                   nll_grad_full, loo, applymap_nd, applymap_nd_tangent, applymap_nd_inverse, periodic_nd
  *                   loo_grad (as nll_grad_full: SGPR_FIT_BLOCK_QQ / _PP fits refused; grows the fit's scratch block)
  * An entry called without what it needs returns SGPR_E_STATE.  So does one called on a kind of fit it is not defined for:
  *   SGPR_FIT_BLOCK_QQ / _PP fits: every "needs solved" entry except alpha and nll, and cond_estimate;
- *   SGPR_FIT_REG fits: predict_nd, applymap_nd, applymap_nd_tangent, applymap_nd_inverse (predict_genfun: SGPR_E_ARG, see there);
+ *   SGPR_FIT_REG fits: predict_nd, applymap_nd, applymap_nd_tangent, applymap_nd_inverse, periodic_nd (predict_genfun: SGPR_E_ARG, see there);
  *   create_nd fits with d > 1: predict_rows, nll_grad, nll_grad_terms.
  * Argument errors (SGPR_E_ARG) are reported first.  Every refusal happens before any device call and leaves the handle, the
  * device buffers and the scratch as they were; its message (sgpr_last_error) begins with the entry's name without "sgpr_"
@@ -770,6 +770,42 @@ int sgpr_fit_applymap_nd_inverse(sgpr_fit_t f, int mode, int nm, int ntest, cons
 int sgpr_applymap_nd_inverse_host(int family, int d, int mode, int nm, int ntest, const double *hyp, int nhyp, int n0,
                                   const double *X, size_t ldx, const double *alpha, const double *Q0, size_t ldq,
                                   const double *P0, size_t ldp, double *qmap, double *pmap, int *iters);
+/* PERIODIC ORBITS of the d-pair map: for each of ntest guesses z = (q, p) = row of (Q0, P0), a period n >= 1 and d integer
+ * winding numbers w, find z* with
+ *     r(z) = ( q_n - q_0 - 2 pi w,  p_n - p_0 ) = 0,      (q_n, p_n) the n-th image of z under the map of sgpr_fit_applymap_nd /
+ * sgpr_applymap_nd_host in lifted (unwrapped) coordinates, by plain Newton on the n-fold map, z <- z - (mono(z) - I)^-1 r(z) with
+ * mono = M_n ... M_1 from the tangent map (sgpr_*_applymap_nd_tangent); no damping, no line search.  One workgroup per guess
+ * runs ALL passes of that guess inside one launch: a pass is the n steps of the map -- the step of the map entries itself, not a
+ * copy -- with the Hessian pass and the monodromy product of the tangent entries, then the 2d x 2d solve by Gaussian elimination
+ * with partial pivoting.  A guess is CONVERGED when the pass that started from the current z has
+ * max|r| <= tol max(1, max|z|); that z is returned, so resid is the residual evaluated at the returned point.  A guess FAILS
+ * when maxit passes go by without convergence, when its orbit is lost (the map's NaN rule), when a step's I + B is singular, when
+ * mono - I is singular (a zero or non-finite pivot) or the update is not finite.  A failed guess, and one that starts non-finite,
+ * has NaN in every floating output and its = -1; the other guesses are not affected.
+ * mode: as the tangent entries -- SGPR_MAP_WRAP_Q, and SGPR_MAP_EXPLICIT for the sum kernels only.  With SGPR_MAP_WRAP_Q the turns
+ * the map takes out of every Q are counted and the q-residual is (Q_n - q_0) + 2 pi (turns - w); every updated q_0 is wrapped
+ * into [0, 2 pi) (a first guess that converges at once is returned as given).  Without it the residual is Q_n - q_0 - 2 pi w: a
+ * periodic family run unwrapped is a legitimate lifted map.  There is nothing for SGPR_MAP_WRAP_P.
+ * wind (may be NULL = all 0): ntest x d ints, column-major, leading dimension ntest.  Q0, P0: ntest x d column-major (ldq, ldp >=
+ * ntest).  z: [ntest][2d] = (q*, p*).  resid: [ntest] = max|r(z*)|.  its: [ntest], the passes run, the converged one included
+ * (1 = the guess was a periodic orbit already).  mono (may be NULL): [ntest][2d][2d], the monodromy of the returned orbit
+ * (rows (Q, P), columns (q, p)).  qorb, porb (both or neither NULL): [n][ntest][d], rows 0 .. n-1 of the returned orbit, row 0 =
+ * z; they have the bits sgpr_*_applymap_nd returns from z.  A guess's bits depend on nothing but its own inputs: not on ntest,
+ * its index, or a repeated call.  Threads per workgroup as the map entries (256 staged in LDS up to n0 = 1024, 512 beyond).
+ * HAZARD: far from the training data the GP returns its prior mean, the learned map is the identity, and every far point is a
+ * "fixed point" with mono = I to rounding; Newton can walk there from a poor guess and report convergence.  Discard results whose
+ * mono - I is negligible.
+ * Checked before any device call (SGPR_E_ARG): everything the map entries check (n in the place of nm), n < 1, maxit < 1, tol
+ * not positive or not finite, null z, resid or its, one of qorb / porb without the other, SGPR_MAP_EXPLICIT with a product
+ * family.  SGPR_E_STATE as sgpr_fit_applymap_nd_tangent: an unsolved fit, a SGPR_FIT_REG fit, a SGPR_FIT_BLOCK_* fit.
+ * ntest == 0 returns 0.  Added in ABI 5 (additional entry points). */
+int sgpr_fit_periodic_nd(sgpr_fit_t f, int mode, int n, int ntest, const int *wind, const double *Q0, size_t ldq,
+                         const double *P0, size_t ldp, double tol, int maxit, double *z, double *resid, int *its,
+                         double *mono, double *qorb, double *porb);
+int sgpr_periodic_nd_host(int family, int d, int mode, int n, int ntest, const double *hyp, int nhyp, int n0,
+                          const double *X, size_t ldx, const double *alpha, const int *wind, const double *Q0, size_t ldq,
+                          const double *P0, size_t ldp, double tol, int maxit, double *z, double *resid, int *its,
+                          double *mono, double *qorb, double *porb);
 /* alpha-solve on device with the factor and its leaf inverses: b (n) := L^-T L^-1 b */
 int sgpr_potrs_vec_dev(int n, const double *L, size_t ldl, void *work, double *b,
                        void *stream);

@@ -141,6 +141,11 @@ SIGNATURES = {
                                                C.POINTER(C.c_int)]),
     "sgpr_applymap_nd_inverse_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _dp,
                                                 C.c_size_t, _dp, _dp, C.c_size_t, _dp, C.c_size_t, _dp, _dp, C.POINTER(C.c_int)]),
+    "sgpr_fit_periodic_nd": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), _dp, C.c_size_t, _dp, C.c_size_t,
+                                       C.c_double, C.c_int, _dp, _dp, C.POINTER(C.c_int), _dp, _dp, _dp]),
+    "sgpr_periodic_nd_host": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_size_t,
+                                        _dp, C.POINTER(C.c_int), _dp, C.c_size_t, _dp, C.c_size_t, C.c_double, C.c_int, _dp, _dp,
+                                        C.POINTER(C.c_int), _dp, _dp, _dp]),
     "sgpr_potrs_vec_dev": (C.c_int, [C.c_int, _vp, C.c_size_t, _vp, _vp, _vp]),
     "sgpr_solve_status_dev": (C.c_int, [C.c_int, _vp, C.c_size_t, _vp, _vp]),
     "sgpr_fit_batch_max_order": (C.c_int, []),

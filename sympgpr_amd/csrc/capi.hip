@@ -640,6 +640,32 @@ int sgpr_applymap_nd_inverse_host(int family, int d, int mode, int nm, int ntest
                             qmap, pmap, iters, nullptr, MAP_BACKWARD);
 }
 
+/* Periodic orbits of the d-pair map from caller-supplied training points and alpha: every argument is checked before any device
+ * call, in the order of the map entries (the kernel's description, the shape of the call, the mode, the training set). */
+int sgpr_periodic_nd_host(int family, int d, int mode, int n, int ntest, const double *hyp, int nhyp, int n0, const double *X,
+                          size_t ldx, const double *alpha, const int *wind, const double *Q0, size_t ldq, const double *P0, size_t ldp,
+                          double tol, int maxit, double *z, double *resid, int *its, double *mono, double *qorb, double *porb)
+{
+    const char *me = "periodic_nd_host";
+    int rc = applymap_nd_kernel_check(me, family, d, hyp, nhyp);
+    if (rc || (rc = periodic_nd_call_check(me, mode, n, ntest, Q0, ldq, P0, ldp, tol, maxit, z, resid, its, qorb, porb)) ||
+        (rc = applymap_nd_tangent_check(me, family, mode, n + 1, nullptr)))
+        return rc;
+    if (n0 < 0 || (n0 > 0 && (!X || !alpha || ldx < (size_t)n0))) {
+        set_error(std::string(me) + ": n0 < 0, null X or alpha, or ldx < n0");
+        return SGPR_E_ARG;
+    }
+    if ((rc = need_device())) return rc;
+    if (ntest == 0) return 0;
+    DevBuf dX, dal;
+    hipStream_t st = nullptr;
+    const int D = 2 * d;
+    if ((rc = dX.alloc((size_t)n0 * D * sizeof(double))) || (rc = upload(dal, alpha, (size_t)D * n0, st))) return rc;
+    if (n0 > 0 && (rc = copy_in(dX.p, (size_t)n0, X, ldx, (size_t)n0, D, st))) return rc;
+    return periodic_nd_io(family, d, mode, n, ntest, n0, dX.as<double>(), (size_t)n0, hyp, nhyp, dal.as<double>(), wind, Q0, ldq, P0,
+                          ldp, tol, maxit, z, resid, its, mono, qorb, porb, st);
+}
+
 int sgpr_release_device_streams(int device)
 {
     return release_device_streams(device);      // (touches the device only if this library has streams on it)

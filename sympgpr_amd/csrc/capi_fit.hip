@@ -843,6 +843,27 @@ int sgpr_fit_applymap_nd_inverse(sgpr_fit_t f, int mode, int nm, int ntest, cons
     return check_solve(me, f);
 }
 
+/* Periodic orbits of the same map (periodic_nd.h: periodic_nd_kernel): Newton on the n-fold map from every guess, one launch. */
+int sgpr_fit_periodic_nd(sgpr_fit_t f, int mode, int n, int ntest, const int *wind, const double *Q0, size_t ldq, const double *P0,
+                         size_t ldp, double tol, int maxit, double *z, double *resid, int *its, double *mono, double *qorb,
+                         double *porb)
+{
+    const char *me = "fit_periodic_nd";
+    int rc = guard(me, f, true);
+    if (rc) return rc;
+    if ((rc = periodic_nd_call_check(me, mode, n, ntest, Q0, ldq, P0, ldp, tol, maxit, z, resid, its, qorb, porb))) return rc;
+    if ((rc = applymap_nd_tangent_check(me, f->family, mode, n + 1, nullptr))) return rc;
+    if ((rc = guard(me, f, true, NEED_SOLVED | NEED_ALL_BLOCKS | NEED_PAIR_KERNEL))) return rc;
+    if (ntest == 0) return 0;
+    double hyp1[4];
+    int nhyp;
+    const double *hyp = fit_hyp_nd(f, hyp1, &nhyp);
+    if ((rc = periodic_nd_io(f->family, f->d, mode, n, ntest, f->npts, f->dX, (size_t)f->npts, hyp, nhyp, f->dalpha, wind, Q0, ldq, P0,
+                             ldp, tol, maxit, z, resid, its, mono, qorb, porb, f->st)))
+        return rc;
+    return check_solve(me, f);
+}
+
 // cond_2(Ky) from below: lambda_max by power iteration on Ky v (the rows of K are re-evaluated from the training points by the
 // prediction kernel -- the matrix itself has been overwritten by its factor -- plus |sig2n| v), lambda_min by inverse iteration
 // with the cached factor (two strip solves per step).  Both are Rayleigh quotients of unit vectors, so lambda_max is a lower

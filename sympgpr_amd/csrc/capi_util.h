@@ -174,4 +174,54 @@ inline int applymap_nd_io(int family, int d, int mode, int nm, int ntest, int n0
     return 0;
 }
 
+// What sgpr_fit_periodic_nd and sgpr_periodic_nd_host share: the shape of the call -- applymap_nd_call_check with the period n
+// in the place of nm; the orbit is optional here, so z stands in for the two outputs that check requires -- and the search's own
+// arguments.  The family's part (SGPR_MAP_EXPLICIT) is applymap_nd_tangent_check's, which the entries call as the tangent ones do.
+inline int periodic_nd_call_check(const char *entry, int mode, int n, int ntest, const double *Q0, size_t ldq, const double *P0,
+                                  size_t ldp, double tol, int maxit, const double *z, const double *resid, const int *its,
+                                  const double *qorb, const double *porb)
+{
+    auto E = [&](const char *what) { set_error(std::string(entry) + ": " + what); return SGPR_E_ARG; };
+    if (n < 1) return E("n < 1");
+    if (maxit < 1) return E("maxit < 1");
+    if (!(tol > 0.0) || !std::isfinite(tol)) return E("tol must be positive and finite");
+    if (!z || !resid || !its) return E("null z, resid or its");
+    if (!qorb != !porb) return E("qorb and porb must both be given or both be null");
+    return applymap_nd_call_check(entry, mode, n, ntest, Q0, ldq, P0, ldp, z, z);
+}
+
+// uploads the guesses and the winding numbers (null: none), runs periodic_nd on device-resident training points and alpha,
+// brings the results back and waits.  Host arrays: wind ntest x d ints column-major; z [ntest][2d], resid [ntest], its [ntest];
+// mono [ntest][2d][2d] or null; qorb / porb [n][ntest][d] or both null.
+inline int periodic_nd_io(int family, int d, int mode, int n, int ntest, int n0, const double *dXtr, size_t ldxtr, const double *hyp,
+                          int nhyp, const double *dalpha, const int *wind, const double *Q0, size_t ldq, const double *P0, size_t ldp,
+                          double tol, int maxit, double *z, double *resid, int *its, double *mono, double *qorb, double *porb,
+                          hipStream_t st)
+{
+    int rc;
+    DevBuf q0, p0, dw, dz, dr, di, dm, dq, dp;
+    const size_t nt = (size_t)ntest, D = (size_t)2 * d, z_bytes = nt * D * sizeof(double), mono_bytes = nt * D * D * sizeof(double);
+    const size_t orb_bytes = (size_t)n * nt * d * sizeof(double), wind_bytes = nt * d * sizeof(int);
+    if ((rc = q0.alloc(nt * d * sizeof(double))) || (rc = p0.alloc(nt * d * sizeof(double))) || (rc = dz.alloc(z_bytes)) ||
+        (rc = dr.alloc(nt * sizeof(double))) || (rc = di.alloc(nt * sizeof(int))) || (wind && (rc = dw.alloc(wind_bytes))) ||
+        (mono && (rc = dm.alloc(mono_bytes))) || (qorb && ((rc = dq.alloc(orb_bytes)) || (rc = dp.alloc(orb_bytes)))))
+        return rc;
+    if ((rc = copy_in(q0.p, nt, Q0, ldq, nt, d, st)) || (rc = copy_in(p0.p, nt, P0, ldp, nt, d, st))) return rc;
+    if (wind) SGPR_HIP(hipMemcpyAsync(dw.p, wind, wind_bytes, hipMemcpyHostToDevice, st));
+    if ((rc = periodic_nd(family, d, mode, n, ntest, n0, dXtr, ldxtr, hyp, nhyp, dalpha, dw.as<int>(), q0.as<double>(), p0.as<double>(),
+                          tol, maxit, dz.as<double>(), dr.as<double>(), di.as<int>(), dm.as<double>(), dq.as<double>(),
+                          dp.as<double>(), st)))
+        return rc;
+    SGPR_HIP(hipMemcpyAsync(z, dz.p, z_bytes, hipMemcpyDeviceToHost, st));
+    SGPR_HIP(hipMemcpyAsync(resid, dr.p, nt * sizeof(double), hipMemcpyDeviceToHost, st));
+    SGPR_HIP(hipMemcpyAsync(its, di.p, nt * sizeof(int), hipMemcpyDeviceToHost, st));
+    if (mono) SGPR_HIP(hipMemcpyAsync(mono, dm.p, mono_bytes, hipMemcpyDeviceToHost, st));
+    if (qorb) {
+        SGPR_HIP(hipMemcpyAsync(qorb, dq.p, orb_bytes, hipMemcpyDeviceToHost, st));
+        SGPR_HIP(hipMemcpyAsync(porb, dp.p, orb_bytes, hipMemcpyDeviceToHost, st));
+    }
+    SGPR_HIP(hipStreamSynchronize(st));
+    return 0;
+}
+
 }  // namespace sgpr

@@ -120,7 +120,7 @@ int predict_nd(int family, int d, int m, const double *Xt, size_t ldxt, int n0, 
                const double *hyp, int nhyp, const double *alpha, double *out, hipStream_t st);
 bool family_is_sum(int family);   // k = sum of the factors (family B, or a USER sum kernel): the explicit maps
 
-// ---- map_nd.hip : the symplectic map of those fits, forwards, with its tangent map and backwards
+// ---- map_nd.hip : the symplectic map of those fits, forwards, with its tangent map and backwards, and its periodic orbits
 // nm steps of the d-pair symplectic map for ntest orbits, one workgroup per orbit (device buffers: Xtr n0 x 2d, alpha 2 d n0,
 // Q0 / P0 ntest x d with leading dimension ntest, qmap / pmap [nm][ntest][d], iters [nm - 1][ntest] or null)
 int applymap_nd(int family, int d, int mode, int nm, int ntest, int n0, const double *Xtr, size_t ldxtr, const double *hyp,
@@ -134,6 +134,12 @@ int applymap_nd_inverse(int family, int d, int mode, int nm, int ntest, int n0, 
 int applymap_nd_tangent(int family, int d, int mode, int nm, int ntest, int n0, const double *Xtr, size_t ldxtr, const double *hyp,
                         int nhyp, const double *alpha, const double *Q0, const double *P0, double *qmap, double *pmap, int *iters,
                         double *jac, double *mono, double *lyap, hipStream_t st);
+// periodic orbits of that map (periodic_nd.h): Newton on the n-fold map from the guesses Q0 / P0 with the winding numbers wind
+// (ntest x d ints, leading dimension ntest, or null), all passes in one launch; z [ntest][2d], resid [ntest], its [ntest], mono
+// [ntest][2d][2d] or null, qorb / porb [n][ntest][d] or both null
+int periodic_nd(int family, int d, int mode, int n, int ntest, int n0, const double *Xtr, size_t ldxtr, const double *hyp, int nhyp,
+                const double *alpha, const int *wind, const double *Q0, const double *P0, double tol, int maxit, double *z,
+                double *resid, int *its, double *mono, double *qorb, double *porb, hipStream_t st);
 
 // ---- genfun_nd.hip : the generating function of those fits
 // the generating function F itself at m device-resident test points (has_ref: row m of Xt is a reference point, F has m + 1

@@ -24,6 +24,11 @@ using namespace nd;         // all_coords, weights, is_sum, dispatch_nd (nd_eval
 constexpr int MAPND_T_SMALL = 256, MAPND_T_LARGE = 512;    // threads per orbit: n0 <= MAPND_STAGE_PTS / larger training sets
 constexpr int MAPND_STAGE_PTS = 4 * MAPND_T_SMALL;         // training points a 256-thread workgroup keeps in LDS (2 D doubles each: 96 KiB at D = 6)
 
+// The staged points, where a kernel has them: a pointer into LDS by its type.  As a generic pointer the compiler merged the
+// staged and the unstaged reads of a pass into flat loads through a pointer chosen per thread, and with the step in a function
+// of its own (mapnd_step) the backend failed on that cast ("illegal instruction": the LDS aperture moved into VCC).
+typedef const __attribute__((address_space(3))) double *stage_ptr;
+
 struct MapNdArgs {
     NdArgs k;                          // Xa = training points (mj = n0 of them), the hyper-parameters
     int nm, ntest, mode, maxiter;
@@ -39,7 +44,7 @@ struct MapNdArgs {
 // G = K*(x) alpha (D sums) and, with JAC, J[c * d + e] = d G_c / d P_e (d^2 sums) over all n0 training points: thread t takes
 // the points t, t + TT, ...  `stg`: the staged points ([coordinate | alpha block][MAPND_STAGE_PTS]) or null (read from memory)
 template <int FAM, int D, int TT, bool JAC>
-__device__ __forceinline__ void mapnd_pass(const MapNdArgs &a, const double (&x)[D], const double *stg, double (&G)[D],
+__device__ __forceinline__ void mapnd_pass(const MapNdArgs &a, const double (&x)[D], stage_ptr stg, double (&G)[D],
                                            double (&J)[(D / 2) * (D / 2)], double *part, double *res)
 {
     constexpr int d = D / 2;
@@ -125,6 +130,82 @@ __device__ __forceinline__ bool newton_step(const double (&J)[d * d], const doub
 
 #include "maptan.h"   // the Hessian pass of the tangent map: with tangent_core.h what TAN = true adds to the kernel below
 
+// One forward step from (q, p), the step of every kernel that runs the map forwards (applymap_nd_kernel, periodic_nd_kernel):
+// explicit or Newton in P, the closing pass, the acceptance rule and the wrap.  Block-uniform values, every thread alike.
+// -> whether the step is accepted; then P, Q (wrapped with SGPR_MAP_WRAP_Q) hold the image, x = (q, P) is the point of the
+// passes, turn[c] = floor(Q_c / 2 pi), the turns the wrap took out of Q_c (0 without the wrap), `its` the Newton iterations.
+// part / res: the two LDS halves of the workgroup sums, alternating with seq.
+template <int FAM, int D, int TT, int PH, int RH>
+__device__ __forceinline__ bool mapnd_step(const MapNdArgs &a, stage_ptr stg, const double (&q)[D / 2], const double (&p)[D / 2],
+                                           double (&x)[D], double (&Q)[D / 2], double (&P)[D / 2], double (&turn)[D / 2], int &its,
+                                           unsigned &seq, double (&part)[2][PH], double (&res)[2][RH])
+{
+    constexpr int d = D / 2;
+    const double nan = __builtin_nan("");
+    const double twopi = 6.283185307179586477;
+    bool good = true;
+#pragma unroll
+    for (int c = 0; c < d; ++c) good = good && finite_d(q[c]) && finite_d(p[c]);   // a lost (NaN) orbit stays lost
+    its = 0;
+    double G[D], J[d * d];
+#pragma unroll
+    for (int c = 0; c < d; ++c) { x[c] = q[c]; P[c] = p[c]; Q[c] = nan; turn[c] = 0.0; }
+    if (good && (a.mode & SGPR_MAP_EXPLICIT)) {         // P = p - G_q(q, p), no solve
+#pragma unroll
+        for (int c = 0; c < d; ++c) x[d + c] = p[c];
+        ++seq;
+        mapnd_pass<FAM, D, TT, false>(a, x, stg, G, J, part[seq & 1u], res[seq & 1u]);
+#pragma unroll
+        for (int c = 0; c < d; ++c) { P[c] = p[c] - G[c]; good = good && finite_d(P[c]); }
+    } else if (good) {                                  // Newton on f(P) = G_q(q, P) - p + P from P = p
+        for (int it = 0; it < a.maxiter; ++it) {
+#pragma unroll
+            for (int c = 0; c < d; ++c) x[d + c] = P[c];
+            ++seq;
+            mapnd_pass<FAM, D, TT, true>(a, x, stg, G, J, part[seq & 1u], res[seq & 1u]);
+            double f[d], dP[d], step = 0.0, size = 1.0;
+#pragma unroll
+            for (int c = 0; c < d; ++c) f[c] = G[c] - p[c] + P[c];
+            if (!newton_step<d>(J, f, dP)) { good = false; break; }
+#pragma unroll
+            for (int c = 0; c < d; ++c) {
+                P[c] += dP[c];
+                step = fmax(step, fabs(dP[c]));
+                size = fmax(size, fabs(P[c]));
+            }
+            ++its;
+            if (step <= a.tol * size) break;
+        }
+    }
+    if (good) {                                         // one pass without the Jacobian at the final P: the residual and G_P
+#pragma unroll
+        for (int c = 0; c < d; ++c) x[d + c] = P[c];
+        ++seq;
+        mapnd_pass<FAM, D, TT, false>(a, x, stg, G, J, part[seq & 1u], res[seq & 1u]);
+        if (!(a.mode & SGPR_MAP_EXPLICIT)) {
+            double r = 0.0, pmax = 1.0;
+#pragma unroll
+            for (int c = 0; c < d; ++c) {
+                const double fc = G[c] - p[c] + P[c];
+                good = good && finite_d(fc);
+                r = fmax(r, fabs(fc));
+                pmax = fmax(pmax, fabs(p[c]));
+            }
+            good = good && r <= 1e-8 * pmax;            // the d = 1 map's acceptance rule
+        }
+#pragma unroll
+        for (int c = 0; c < d; ++c) {
+            Q[c] = q[c] + G[d + c];
+            good = good && finite_d(Q[c]);
+            if (a.mode & SGPR_MAP_WRAP_Q) {
+                turn[c] = floor(Q[c] / twopi);
+                Q[c] -= twopi * turn[c];
+            }
+        }
+    }
+    return good;
+}
+
 // One workgroup per orbit runs all nm steps; nothing waits on another workgroup, and an orbit's bits depend on nothing but its
 // own start point (TT is chosen from n0 alone).  TT = 256: the training points and alpha are staged in LDS once when they fit
 // (every thread reads back what it wrote itself: no barrier); TT = 512 reads them from memory (L2) on every pass.  512, not 1024:
@@ -142,7 +223,7 @@ __global__ __launch_bounds__(TT) void applymap_nd_kernel(const std::conditional_
     __shared__ double res[2][NSMAX];
     __shared__ double stage[HAS_STAGE ? 2 * D * MAPND_STAGE_PTS : 1];
     const int k = blockIdx.x, n0 = a.k.mj;
-    const double *stg = nullptr;
+    stage_ptr stg = nullptr;
     if (HAS_STAGE && n0 <= MAPND_STAGE_PTS) {
         for (int j = threadIdx.x; j < n0; j += TT) {
 #pragma unroll
@@ -151,7 +232,7 @@ __global__ __launch_bounds__(TT) void applymap_nd_kernel(const std::conditional_
                 stage[(D + c) * MAPND_STAGE_PTS + j] = a.alpha[(size_t)c * n0 + j];
             }
         }
-        stg = stage;
+        stg = (stage_ptr)stage;
     }
     unsigned seq = 0;
     double q[d], p[d];
@@ -165,66 +246,11 @@ __global__ __launch_bounds__(TT) void applymap_nd_kernel(const std::conditional_
         for (int c = 0; c < d; ++c) { a.qmap[(size_t)k * d + c] = q[c]; a.pmap[(size_t)k * d + c] = p[c]; }
     }
     const double nan = __builtin_nan("");
-    const double twopi = 6.283185307179586477;
     if constexpr (TAN) maptan_init<D>();
     for (int i = 0; i + 1 < a.nm; ++i) {
-        bool good = true;                                   // block-uniform, like everything below
-#pragma unroll
-        for (int c = 0; c < d; ++c) good = good && finite_d(q[c]) && finite_d(p[c]);   // a lost (NaN) orbit stays lost
         int its = 0;
-        double x[D], G[D], J[d * d], P[d], Q[d];
-#pragma unroll
-        for (int c = 0; c < d; ++c) { x[c] = q[c]; P[c] = p[c]; Q[c] = nan; }
-        if (good && (a.mode & SGPR_MAP_EXPLICIT)) {         // P = p - G_q(q, p), no solve
-#pragma unroll
-            for (int c = 0; c < d; ++c) x[d + c] = p[c];
-            ++seq;
-            mapnd_pass<FAM, D, TT, false>(a, x, stg, G, J, part[seq & 1u], res[seq & 1u]);
-#pragma unroll
-            for (int c = 0; c < d; ++c) { P[c] = p[c] - G[c]; good = good && finite_d(P[c]); }
-        } else if (good) {                                  // Newton on f(P) = G_q(q, P) - p + P from P = p
-            for (int it = 0; it < a.maxiter; ++it) {
-#pragma unroll
-                for (int c = 0; c < d; ++c) x[d + c] = P[c];
-                ++seq;
-                mapnd_pass<FAM, D, TT, true>(a, x, stg, G, J, part[seq & 1u], res[seq & 1u]);
-                double f[d], dP[d], step = 0.0, size = 1.0;
-#pragma unroll
-                for (int c = 0; c < d; ++c) f[c] = G[c] - p[c] + P[c];
-                if (!newton_step<d>(J, f, dP)) { good = false; break; }
-#pragma unroll
-                for (int c = 0; c < d; ++c) {
-                    P[c] += dP[c];
-                    step = fmax(step, fabs(dP[c]));
-                    size = fmax(size, fabs(P[c]));
-                }
-                ++its;
-                if (step <= a.tol * size) break;
-            }
-        }
-        if (good) {                                         // one pass without the Jacobian at the final P: the residual and G_P
-#pragma unroll
-            for (int c = 0; c < d; ++c) x[d + c] = P[c];
-            ++seq;
-            mapnd_pass<FAM, D, TT, false>(a, x, stg, G, J, part[seq & 1u], res[seq & 1u]);
-            if (!(a.mode & SGPR_MAP_EXPLICIT)) {
-                double r = 0.0, pmax = 1.0;
-#pragma unroll
-                for (int c = 0; c < d; ++c) {
-                    const double fc = G[c] - p[c] + P[c];
-                    good = good && finite_d(fc);
-                    r = fmax(r, fabs(fc));
-                    pmax = fmax(pmax, fabs(p[c]));
-                }
-                good = good && r <= 1e-8 * pmax;            // the d = 1 map's acceptance rule
-            }
-#pragma unroll
-            for (int c = 0; c < d; ++c) {
-                Q[c] = q[c] + G[d + c];
-                good = good && finite_d(Q[c]);
-                if (a.mode & SGPR_MAP_WRAP_Q) Q[c] -= twopi * floor(Q[c] / twopi);
-            }
-        }
+        double x[D], P[d], Q[d], turn[d];                   // block-uniform, like everything below
+        const bool good = mapnd_step<FAM, D, TT>(a, stg, q, p, x, Q, P, turn, its, seq, part, res);
 #pragma unroll
         for (int c = 0; c < d; ++c) { q[c] = good ? Q[c] : nan; p[c] = good ? P[c] : nan; }
         if (threadIdx.x == 0) {
@@ -252,6 +278,8 @@ __global__ __launch_bounds__(TT) void applymap_nd_kernel(const std::conditional_
     if constexpr (TAN) maptan_finish<D>(a.mono, a.lyap, a.nm, k);
 }
 
+#include "periodic_nd.h"   // periodic_nd_kernel: Newton on the n-fold map around mapnd_step and the TAN pieces above
+
 // The backward step: rows qmap[0], pmap[0] hold (Q, P), and one step returns the (q, p) that the kernel above takes there.  The
 // point of the passes is the same x = (q, P); now P is known and q is not: Newton on f(q) = q + G_P(q, P) - Q = 0 from q = Q,
 // then p = P + G_q(q, P).  The Jacobian is I + dG_P/dq, and G is a gradient (of the generating function), so dG_P/dq is the
@@ -270,7 +298,7 @@ __global__ __launch_bounds__(TT) void applymap_nd_inverse_kernel(const MapNdArgs
     __shared__ double res[2][NSMAX];
     __shared__ double stage[HAS_STAGE ? 2 * D * MAPND_STAGE_PTS : 1];
     const int k = blockIdx.x, n0 = a.k.mj;
-    const double *stg = nullptr;
+    stage_ptr stg = nullptr;
     if (HAS_STAGE && n0 <= MAPND_STAGE_PTS) {               // as applymap_nd_kernel: every thread reads back what it wrote itself
         for (int j = threadIdx.x; j < n0; j += TT) {
 #pragma unroll
@@ -279,7 +307,7 @@ __global__ __launch_bounds__(TT) void applymap_nd_inverse_kernel(const MapNdArgs
                 stage[(D + c) * MAPND_STAGE_PTS + j] = a.alpha[(size_t)c * n0 + j];
             }
         }
-        stg = stage;
+        stg = (stage_ptr)stage;
     }
     unsigned seq = 0;
     double Q[d], P[d];                                      // the point the next step starts from: the image (Q, P)
@@ -426,5 +454,19 @@ int applymap_nd_tangent(int family, int d, int mode, int nm, int ntest, int n0, 
     return applymap_nd_launch(a, kernel, family, d, mode, nm, ntest, n0, Xtr, ldxtr, hyp, nhyp, alpha, Q0, P0, qmap, pmap, iters, st);
 }
 
-}  // namespace sgpr
+// Periodic orbits of the map of applymap_nd (periodic_nd.h): per guess (Q0, P0) Newton on the n-fold map with the winding
+// numbers wind (ntest x d, leading dimension ntest, or null), every pass inside the one launch.  Device buffers: z [ntest][2d],
+// resid [ntest], its [ntest]; mono [ntest][2d][2d] or null; qorb / porb [n][ntest][d] or both null.  mode as applymap_nd_tangent.
+int periodic_nd(int family, int d, int mode, int n, int ntest, int n0, const double *Xtr, size_t ldxtr, const double *hyp, int nhyp,
+                const double *alpha, const int *wind, const double *Q0, const double *P0, double tol, int maxit, double *z,
+                double *resid, int *its, double *mono, double *qorb, double *porb, hipStream_t st)
+{
+    PeriodicNdArgs a{};
+    a.wind = wind; a.ptol = tol; a.pmaxit = maxit; a.z = z; a.resid = resid; a.its = its; a.mono = mono;
+    auto kernel = [](auto fam, auto dd, auto tt) {
+        return periodic_nd_kernel<decltype(fam)::value, decltype(dd)::value, decltype(tt)::value>;
+    };
+    return applymap_nd_launch(a, kernel, family, d, mode, n, ntest, n0, Xtr, ldxtr, hyp, nhyp, alpha, Q0, P0, qorb, porb, nullptr, st);
+}
 
+}  // namespace sgpr

@@ -68,7 +68,7 @@ template <int FAM, int D, int TT> constexpr int maptan_groups() { return 1; }
 
 // H[LO .. HI) (product kernels) or the diagonal of H (sum kernels; the rest is set to 0) over all n0 training points at x
 template <int FAM, int D, int TT, int LO, int HI>
-__device__ __forceinline__ void maptan_hess_pass(const MapNdArgs &a, const double (&x)[D], const double *stg,
+__device__ __forceinline__ void maptan_hess_pass(const MapNdArgs &a, const double (&x)[D], stage_ptr stg,
                                                  double (&H)[D * (D + 1) / 2], double *part, double *res)
 {
     constexpr bool SUM = is_sum<FAM>();
@@ -128,7 +128,7 @@ __device__ __forceinline__ void maptan_hess_pass(const MapNdArgs &a, const doubl
 
 // all groups of the Hessian pass, one after the other; the two LDS halves keep alternating with seq
 template <int FAM, int D, int TT, int G = 0>
-__device__ __forceinline__ void maptan_hessian(const MapNdArgs &a, const double (&x)[D], const double *stg,
+__device__ __forceinline__ void maptan_hessian(const MapNdArgs &a, const double (&x)[D], stage_ptr stg,
                                                double (&H)[D * (D + 1) / 2], double *part0, double *res0, int part_half,
                                                int res_half, unsigned &seq)
 {

@@ -223,6 +223,29 @@ __device__ __forceinline__ void maptan_advance()
     }
 }
 
+// mono := M mono alone, for a caller that wants neither Qmat nor the sums (the periodic-orbit search): the owners' columns, the
+// FMA chain of maptan_advance in its order, so mono has the bits the TAN instances give it
+template <int D>
+__device__ __forceinline__ void maptan_advance_mono()
+{
+    if (threadIdx.x >= D) return;
+    double *st = maptan_state<D>();
+    const double *M = st + maptan_m_at<D>();
+    const int lane = threadIdx.x;
+    double mo[D], mn[D];
+#pragma unroll
+    for (int r = 0; r < D; ++r) mo[r] = st[r * D + lane];
+#pragma unroll
+    for (int r = 0; r < D; ++r) {
+        double v = 0.0;
+#pragma unroll
+        for (int s = 0; s < D; ++s) v = __builtin_fma(M[r * D + s], mo[s], v);
+        mn[r] = v;
+    }
+#pragma unroll
+    for (int r = 0; r < D; ++r) st[r * D + lane] = mn[r];
+}
+
 // orbit k's mono [ntest][D][D] (column by column) and exponents lyap [ntest][D] over nm - 1 steps, by their owners; each or null
 template <int D>
 __device__ __forceinline__ void maptan_finish(double *mono, double *lyap, int nm, int k)

@@ -179,6 +179,18 @@ class SympFit:
         qmap, pmap, iters, _ = maps._map_call_nd("sgpr_fit_applymap_nd_inverse", (self._h,), self.d, mode, nm, Q0, P0)
         return (qmap, pmap, iters) if return_iters else (qmap, pmap)
 
+    def periodic_orbits(self, n, Q0, P0, wind=None, wrap_q=False, explicit=False, tol=1e-12, maxit=30, mono=True, orbit=False):
+        """Periodic orbits of the fit's symplectic map (the map of applymap_pairs; d = 1 fits too): for every guess (Q0, P0)
+        (Ntest, d) -- for d = 1 also (Ntest,) -- Newton on the n-fold map with the winding numbers wind, all passes in one
+        device launch, one workgroup per guess.  -> dict with z, resid, its, converged and, as asked, mono, q, p: see
+        maps.run_periodic_nd, whose hazard applies here as well -- far from the training data the learned map is the identity,
+        every point there is a "fixed point" with mono = I, and results whose mono - I is negligible are to be discarded.
+        maps.multipliers and maps.greene_residue (d = 1) classify the orbits.  explicit: sum kernels only.
+        Needs a solved fit (run()); not defined for reg=True and block="qq" / "PP" fits."""
+        from . import maps
+        mode = (maps.WRAP_Q if wrap_q else 0) | (maps.EXPLICIT if explicit else 0)
+        return maps._periodic_call_nd("sgpr_fit_periodic_nd", (self._h,), self.d, mode, n, Q0, P0, wind, tol, maxit, mono, orbit)
+
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
             self._lib.sgpr_fit_destroy(self._h)

@@ -23,6 +23,8 @@ run_map_nd_tangent / SympFit.applymap_pairs_tangent return the same orbits with 
 finite-time Lyapunov exponents (sgpr_applymap_nd_tangent_host); symplectic_defect and greene_residue read them.
 run_map_nd_inverse / SympFit.applymap_pairs_inverse iterate the same map backwards (sgpr_applymap_nd_inverse_host): Newton on the
 d unknowns q with the transposed Jacobian; symplectic_inverse turns a forward step matrix into the backward step's.
+run_periodic_nd / SympFit.periodic_orbits find periodic orbits of that map: Newton on the n-fold map with winding numbers, every
+pass of every guess in one launch (sgpr_periodic_nd_host); multipliers reads the monodromy at any d.
 genfun_along evaluates the learned generating function itself along computed orbits (sgpr_fit_predict_genfun).
 
 alpha = Kyinv ztrain is formed once (the reference re-multiplies Kyinv inside every calcP / calcQ
@@ -396,6 +398,85 @@ def run_map_nd_inverse(family, d, mode, nm, hyp, X, alpha, Q0, P0, return_iters=
     qmap, pmap, iters, _ = _run_map_nd("sgpr_applymap_nd_inverse_host", family, d, map_mode_nd_inverse, mode, nm, hyp, X, alpha,
                                        Q0, P0)
     return (qmap, pmap, iters) if return_iters else (qmap, pmap)
+
+
+def _periodic_call_nd(entry_name, lead_args, d, mode, n, Q0, P0, wind, tol, maxit, mono, orbit, model_args=()):
+    """The one call behind run_periodic_nd and SympFit.periodic_orbits: the C entry `entry_name` with the arguments
+    (*lead_args, mode, n, Ntest, *model_args, wind, Q0, ldq, P0, ldp, tol, maxit, z, resid, its, mono, qorb, porb).  Shape errors
+    are ValueError before the library is loaded; n, tol and maxit are the library's to refuse (SympGPRError, SGPR_E_ARG)."""
+    Q0, P0 = start_points_nd(Q0, P0, d)
+    Ntest, D, n = Q0.shape[0], 2 * d, int(n)
+    wptr = None
+    if wind is not None:
+        w = np.asarray(wind)
+        if w.ndim <= 1 and w.size == d:
+            w = np.broadcast_to(w.reshape(1, d), (Ntest, d))                           # one winding vector for every guess
+        elif d == 1 and w.ndim == 1:
+            w = w.reshape(-1, 1)
+        if w.shape != (Ntest, d) or not np.array_equal(w, np.round(w)):
+            raise ValueError("wind must hold integers, (Ntest, %d) or (%d,)" % (d, d))
+        w = np.asfortranarray(w, dtype=np.int32)
+        wptr = w.ctypes.data_as(C.POINTER(C.c_int))
+    rows = max(n, 0)
+    out = {"z": np.zeros((Ntest, D)), "resid": np.zeros(Ntest), "its": np.zeros(Ntest, dtype=np.int32)}
+    if mono:
+        out["mono"] = np.zeros((Ntest, D, D))
+    if orbit:
+        out["q"], out["p"] = np.zeros((rows, Ntest, d)), np.zeros((rows, Ntest, d))
+    entry = getattr(L.load_library(), entry_name)
+    L.check(entry(*lead_args, mode, n, Ntest, *model_args, wptr, L.dptr(Q0), max(Ntest, 1), L.dptr(P0), max(Ntest, 1), float(tol),
+                  int(maxit), L.dptr(out["z"]), L.dptr(out["resid"]), out["its"].ctypes.data_as(C.POINTER(C.c_int)),
+                  _optr(out, "mono"), _optr(out, "q"), _optr(out, "p")), entry_name)
+    out["converged"] = out["its"] > 0
+    return out
+
+
+def run_periodic_nd(family, d, mode, n, hyp, X, alpha, Q0, P0, wind=None, tol=1e-12, maxit=30, mono=True, orbit=False):
+    """Periodic orbits of the map of run_map_nd (same family, d, hyp, X, alpha, mode = WRAP_Q | EXPLICIT bits, EXPLICIT for the
+    sum kernels only): for every guess z = (q, p) = row of Q0, P0 (Ntest, d) find z* with
+        r(z) = (q_n - q_0 - 2 pi w, p_n - p_0) = 0,      (q_n, p_n) the n-th image of z in lifted (unwrapped) coordinates,
+    for the period n >= 1 and the integer winding numbers wind ((Ntest, d), or (d,) for all guesses, default 0), by plain Newton
+    on the n-fold map, z <- z - (mono(z) - I)^-1 r(z): no damping, no line search.  Every pass of a guess -- n steps of the map
+    with its tangent map, the 2d x 2d solve -- runs on the device inside ONE launch, one workgroup per guess
+    (sgpr_periodic_nd_host).  A guess has converged when the pass that started from z has max|r| <= tol max(1, max|z|).
+    -> dict: z (Ntest, 2d) the points (q*, p*); resid (Ntest,) max|r| evaluated at z; its (Ntest,) int32, the passes run, the
+    converged one included; converged (Ntest,) bool; with mono=True mono (Ntest, 2d, 2d), the monodromy of the returned orbit
+    (multipliers and greene_residue read it); with orbit=True q, p (n, Ntest, d), the returned orbit, row 0 = z, bit for bit what
+    run_map_nd gives from z.  A guess that fails -- maxit passes without convergence, a lost orbit, a singular I + B or mono - I,
+    a non-finite update or start -- has its = -1 and NaN in z, resid, mono, q and p; the others keep their bits.  With WRAP_Q
+    the q of an updated guess is wrapped into [0, 2 pi).
+    HAZARD: far from the training data the GP returns its prior mean, the learned map is the identity, and EVERY far point is a
+    "fixed point" with mono = I to rounding.  Newton can walk there from a poor guess (on the CPU, family C at d = 3 went from
+    (0.1, ...) to such a point with |(mono - I)^-1| = 1e13) and report convergence: discard results whose mono - I is negligible."""
+    d, X, alpha, hyp = _nd_inputs(d, X, alpha, hyp)
+    N0 = X.shape[0]
+    model = (L.dptr(hyp), len(hyp), N0, L.dptr(X), max(N0, 1), L.dptr(alpha))
+    return _periodic_call_nd("sgpr_periodic_nd_host", (L.family_id(family), d), d, map_mode_nd(mode), n, Q0, P0, wind, tol, maxit,
+                             mono, orbit, model)
+
+
+def multipliers(mono):
+    """Floquet multipliers of symplectic monodromy matrices mono (..., D, D) as reciprocal pairs -> complex (..., D / 2, 2):
+    [..., i, 0] and [..., i, 1] are lambda_i and its partner closest to 1 / lambda_i, the pairs ordered by |lambda_i| descending
+    (|lambda| >= 1 first in each pair).  Classifies an orbit at any d (greene_residue is for d = 1): every pair on the unit circle
+    is elliptic, a real pair (lambda, 1 / lambda) hyperbolic, a quadruple off both is complex unstable.  NaN input gives NaN.
+    Mind the hazard named in run_periodic_nd: where the learned map is the identity every multiplier is 1 and means nothing."""
+    mono = np.asarray(mono, dtype=np.float64)
+    if mono.ndim < 2 or mono.shape[-1] != mono.shape[-2] or mono.shape[-1] % 2:
+        raise ValueError("mono must be (..., D, D) with D even")
+    D = mono.shape[-1]
+    flat = mono.reshape(-1, D, D)
+    out = np.full((flat.shape[0], D // 2, 2), np.nan + 0j)
+    for k, M in enumerate(flat):
+        if not np.isfinite(M).all():
+            continue
+        left = list(np.linalg.eigvals(M))
+        left.sort(key=lambda v: -abs(v))
+        for i in range(D // 2):
+            lam = left.pop(0)
+            j = int(np.argmin([abs(v - 1.0 / lam) for v in left]))
+            out[k, i] = lam, left.pop(j)
+    return out.reshape(mono.shape[:-2] + (D // 2, 2))
 
 
 def genfun_along(fit, qmap, pmap, ref=None):
