@@ -222,7 +222,7 @@ PROBE_SIGNATURES = {
     "sgpr_probe_gemm_strassen_top_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                                    C.c_double, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     "sgpr_probe_gemm_nt4_dev": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_double, C.c_int,
-                                          C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_double), C.c_void_p]),
+                                          C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_double), C.c_void_p]),
     "sgpr_probe_batch_layout": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.POINTER(C.c_ulonglong)]),
     "sgpr_probe_batch_layout_nd_loo": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]),

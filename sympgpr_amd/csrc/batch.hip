@@ -20,7 +20,8 @@
 // the phases (L1) - (L4) of the d = 1 loo gradient over those blocks (grad_problem_nd); above order 256 both layouts take the mid
 // path's loo gradient stage (sgpr_fit_batch_loo_grad_mid, sgpr_fit_batch_nd_loo_grad_mid: mid_loograd).
 // The device code is in batch_small.h (n <= 256) and batch_mid.h (256 < n <= 2048), included here and only here: one translation
-// unit.  This file holds the arena, its one layout function, the staging of a call and the two host drivers.
+// unit.  This file holds the arena, its one layout function, the staging of a call, the two host drivers and, last, the one
+// exported runner fit_batch_run, which takes a BatchCall (common.h) filled by the C entry (capi.hip) and chooses the driver.
 #include <cmath>
 #include <cstring>
 
@@ -77,18 +78,6 @@ struct Arena {
     }
 };
 thread_local Arena t_arena;
-
-// One batched call, as the drivers below take it.  The mode is the set of outputs asked for: grad (nbatch x (nhyp + 1)) the nll
-// gradient, loo (nbatch x 2) the {loo, press} rows, value (nbatch) beside grad the loo objective `which` and its gradient.
-struct BatchCall {
-    int family, d, reg, nbatch, npts, n, nhyp;      // d = 0: points as x | y; d > 0: d canonical pairs per point, x = X (nbatch x 2d x npts)
-    const double *x, *y, *z, *hyp, *sig2n;
-    double *alpha, *nll;                            // alpha may be null
-    int *info;
-    double *grad, *loo, *value;
-    int which;
-    int mode() const { return value ? MODE_LOOGRAD : grad ? MODE_GRAD : loo ? MODE_LOO : MODE_FIT; }
-};
 
 // the arena of the calling thread, cut by a layout: pinned input | output blocks, device input | output | scratch
 struct Blocks {
@@ -152,7 +141,6 @@ void finish_rows(const BatchCall &c, const BatchLayout &l, const Blocks &m, int 
     const KConst *kcs = at<const KConst>(m.hin, l.o_kc);
     const nd::NdConst *ncs = at<const nd::NdConst>(m.hin, l.o_kc);
     const size_t B = (size_t)nb, nacc = l.nacc, ngrad = (size_t)c.nhyp + 1;
-    const int nhyp = c.nhyp;
     if (c.grad) {
         for (size_t b = 0; b < B; ++b) {
             const size_t row = (size_t)b0 + b;
@@ -164,10 +152,7 @@ void finish_rows(const BatchCall &c, const BatchLayout &l, const Blocks &m, int 
                 for (size_t k = 0; k < ngrad; ++k) g[k] = std::nan("");
                 continue;
             }
-            const double sig = c.d ? ncs[b].sig : kcs[b].sig;
-            for (int k = 0; k < nhyp - 1; ++k) g[k] = 0.5 * sig * r[k];
-            g[nhyp - 1] = 0.5 * r[nhyp - 1];
-            g[nhyp] = (c.sig2n[row] < 0.0 ? -0.5 : 0.5) * r[nhyp];
+            scale_grad_sums(r, c.nhyp, c.d ? ncs[b].sig : kcs[b].sig, c.sig2n[row], g);
             if (c.value) c.value[row] = raw[b * nacc + (c.which == SGPR_LOO_PRESS ? 1 : 0)];
         }
     }
@@ -593,128 +578,9 @@ int fit_batch_mid(const BatchCall &c)
     return 0;
 }
 
-// the call of an entry that takes its points as x | y (include/sympgpr_hip.h: sgpr_fit_batch and the entries that follow it)
-BatchCall call_xy(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp, int nhyp,
-                  const double *sig2n, unsigned flags, double *alpha, double *nll, int *info)
-{
-    const int reg = (flags & SGPR_FIT_REG) ? 1 : 0;
-    return BatchCall{family, 0, reg, nbatch, npts, reg ? npts : 2 * npts, nhyp, x, y, z, hyp, sig2n, alpha, nll, info,
-                     nullptr, nullptr, nullptr, SGPR_LOO_LPD};
-}
-
 }  // namespace
 
-// host buffers in, host buffers out; see include/sympgpr_hip.h (sgpr_fit_batch)
-int fit_batch(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
-              int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, int *info)
-{
-    const BatchCall c = call_xy(family, nbatch, npts, x, y, z, hyp, nhyp, sig2n, flags, alpha, nll, info);
-    if (nbatch < 0 || npts <= 0 || c.n > potrf_batch_max_order() || !x || !y || !z || !hyp || !sig2n || !nll || !info ||
-        (flags & ~(unsigned)SGPR_FIT_REG)) {
-        set_error("fit_batch: bad arguments (order per problem at most 2048)");
-        return SGPR_E_ARG;
-    }
-    if (nbatch == 0) return 0;
-    if (family < SGPR_FAM_A || family > SGPR_FAM_USER) { set_error("fit_batch: unknown kernel family"); return SGPR_E_ARG; }
-    return c.n > BMAX ? fit_batch_mid(c) : fit_batch_small(c);
-}
-
-// The entries below: the arguments have been checked (capi.hip), nbatch > 0, and the order is in the entry's range.
-
-// sgpr_fit_batch_nd: n = 2 d npts <= fit_batch_max_order()
-int fit_batch_nd(int family, int d, int nbatch, int npts, const double *X, const double *z, const double *hyp, int nhyp,
-                 const double *sig2n, double *alpha, double *nll, int *info)
-{
-    const BatchCall c{family, d, 0, nbatch, npts, 2 * d * npts, nhyp, X, nullptr, z, hyp, sig2n, alpha, nll, info,
-                      nullptr, nullptr, nullptr, SGPR_LOO_LPD};
-    return c.n > BMAX ? fit_batch_mid(c) : fit_batch_small(c);
-}
-
-// sgpr_fit_batch_nd_grad: n = 2 d npts <= fit_batch_max_order()
-int fit_batch_nd_grad(int family, int d, int nbatch, int npts, const double *X, const double *z, const double *hyp, int nhyp,
-                      const double *sig2n, double *alpha, double *nll, double *grad, int *info)
-{
-    const BatchCall c{family, d, 0, nbatch, npts, 2 * d * npts, nhyp, X, nullptr, z, hyp, sig2n, alpha, nll, info,
-                      grad, nullptr, nullptr, SGPR_LOO_LPD};
-    return c.n > BMAX ? fit_batch_mid(c) : fit_batch_small(c);
-}
-
-// sgpr_fit_batch_nd_loo: n = 2 d npts <= fit_batch_max_order()
-int fit_batch_nd_loo(int family, int d, int nbatch, int npts, const double *X, const double *z, const double *hyp, int nhyp,
-                     const double *sig2n, double *alpha, double *nll, double *loo, int *info)
-{
-    const BatchCall c{family, d, 0, nbatch, npts, 2 * d * npts, nhyp, X, nullptr, z, hyp, sig2n, alpha, nll, info,
-                      nullptr, loo, nullptr, SGPR_LOO_LPD};
-    return c.n > BMAX ? fit_batch_mid(c) : fit_batch_small(c);
-}
-
-// sgpr_fit_batch_nd_loo_grad: n = 2 d npts <= BMAX
-int fit_batch_nd_loo_grad(int family, int d, int nbatch, int npts, const double *X, const double *z, const double *hyp, int nhyp,
-                          const double *sig2n, int which, double *alpha, double *nll, double *value, double *grad, int *info)
-{
-    const BatchCall c{family, d, 0, nbatch, npts, 2 * d * npts, nhyp, X, nullptr, z, hyp, sig2n, alpha, nll, info,
-                      grad, nullptr, value, which};
-    return fit_batch_small(c);
-}
-
-// sgpr_fit_batch_grad_mid: BMAX < n <= fit_batch_max_order()
-int fit_batch_grad_mid(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
-                       int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, double *grad, int *info)
-{
-    BatchCall c = call_xy(family, nbatch, npts, x, y, z, hyp, nhyp, sig2n, flags, alpha, nll, info);
-    c.grad = grad;
-    return fit_batch_mid(c);
-}
-
-// sgpr_fit_batch_grad: n <= BMAX
-int fit_batch_grad(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
-                   int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, double *grad, int *info)
-{
-    BatchCall c = call_xy(family, nbatch, npts, x, y, z, hyp, nhyp, sig2n, flags, alpha, nll, info);
-    c.grad = grad;
-    return fit_batch_small(c);
-}
-
-// sgpr_fit_batch_loo: n <= fit_batch_max_order()
-int fit_batch_loo(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
-                  int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, double *loo, int *info)
-{
-    BatchCall c = call_xy(family, nbatch, npts, x, y, z, hyp, nhyp, sig2n, flags, alpha, nll, info);
-    c.loo = loo;
-    return c.n > BMAX ? fit_batch_mid(c) : fit_batch_small(c);
-}
-
-// sgpr_fit_batch_loo_grad: n <= BMAX
-int fit_batch_loo_grad(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
-                       int nhyp, const double *sig2n, unsigned flags, int which, double *alpha, double *nll, double *value,
-                       double *grad, int *info)
-{
-    BatchCall c = call_xy(family, nbatch, npts, x, y, z, hyp, nhyp, sig2n, flags, alpha, nll, info);
-    c.grad = grad;
-    c.value = value;
-    c.which = which;
-    return fit_batch_small(c);
-}
-
-// sgpr_fit_batch_loo_grad_mid: BMAX < n <= fit_batch_max_order()
-int fit_batch_loo_grad_mid(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
-                           int nhyp, const double *sig2n, unsigned flags, int which, double *alpha, double *nll, double *value,
-                           double *grad, int *info)
-{
-    BatchCall c = call_xy(family, nbatch, npts, x, y, z, hyp, nhyp, sig2n, flags, alpha, nll, info);
-    c.grad = grad;
-    c.value = value;
-    c.which = which;
-    return fit_batch_mid(c);
-}
-
-// sgpr_fit_batch_nd_loo_grad_mid: BMAX < n = 2 d npts <= fit_batch_max_order()
-int fit_batch_nd_loo_grad_mid(int family, int d, int nbatch, int npts, const double *X, const double *z, const double *hyp, int nhyp,
-                              const double *sig2n, int which, double *alpha, double *nll, double *value, double *grad, int *info)
-{
-    const BatchCall c{family, d, 0, nbatch, npts, 2 * d * npts, nhyp, X, nullptr, z, hyp, sig2n, alpha, nll, info,
-                      grad, nullptr, value, which};
-    return fit_batch_mid(c);
-}
+// host buffers in, host buffers out (common.h); see include/sympgpr_hip.h, sgpr_fit_batch and the entries that follow it
+int fit_batch_run(const BatchCall &c) { return c.n > BMAX ? fit_batch_mid(c) : fit_batch_small(c); }
 
 }  // namespace sgpr

@@ -30,8 +30,6 @@ struct BatchArgs {
 template <int FAM> constexpr bool grad_has_p() { return FAM == SGPR_FAM_D || (FAM == SGPR_FAM_USER && gen::user_has_p); }
 template <int FAM> constexpr int grad_nacc() { return grad_has_p<FAM>() ? 5 : 4; }    // lx, ly, [p,] sig, sig2n
 
-enum { MODE_FIT = 0, MODE_GRAD = 1, MODE_LOO = 2, MODE_LOOGRAD = 3 };
-
 template <int FAM, int MODE>
 __device__ void grad_problem(const BatchArgs &a, int b, double *s, double *A, const double *inv, double *U, const double *al);
 

@@ -90,6 +90,26 @@ static int map_outputs(int nm, int ntest, double *qmap, double *pmap, double *pd
     return 0;
 }
 
+// The model of the d-pair *_host entries (capi_util.h: MapModel), behind their other checks: the check of the training set, the
+// device, the empty call, the upload of X and alpha; run(model) is the call itself
+template <typename Run>
+static int with_host_map_model(const char *me, int family, int d, int ntest, const double *hyp, int nhyp, int n0, const double *X,
+                               size_t ldx, const double *alpha, Run run)
+{
+    if (n0 < 0 || (n0 > 0 && (!X || !alpha || ldx < (size_t)n0))) {
+        set_error(std::string(me) + ": n0 < 0, null X or alpha, or ldx < n0");
+        return SGPR_E_ARG;
+    }
+    int rc = need_device();
+    if (rc || ntest == 0) return rc;
+    DevBuf dX, dal;
+    hipStream_t st = nullptr;
+    const int D = 2 * d;
+    if ((rc = dX.alloc((size_t)n0 * D * sizeof(double))) || (rc = upload(dal, alpha, (size_t)D * n0, st))) return rc;
+    if (n0 > 0 && (rc = copy_in(dX.p, (size_t)n0, X, ldx, (size_t)n0, D, st))) return rc;
+    return run(MapModel{family, d, n0, dX.as<double>(), (size_t)n0, hyp, nhyp, dal.as<double>(), st});
+}
+
 // sgpr_applymap_nd_host (tan null), sgpr_applymap_nd_tangent_host and sgpr_applymap_nd_inverse_host (MAP_BACKWARD, tan null):
 // every argument is checked before any device call
 static int applymap_nd_host(const char *me, int family, int d, int mode, int nm, int ntest, const double *hyp, int nhyp, int n0,
@@ -102,19 +122,9 @@ static int applymap_nd_host(const char *me, int family, int d, int mode, int nm,
         (tan && (rc = applymap_nd_tangent_check(me, family, mode, nm, tan->lyap))) ||
         (dir == MAP_BACKWARD && (rc = applymap_nd_inverse_check(me, mode))))
         return rc;
-    if (n0 < 0 || (n0 > 0 && (!X || !alpha || ldx < (size_t)n0))) {
-        set_error(std::string(me) + ": n0 < 0, null X or alpha, or ldx < n0");
-        return SGPR_E_ARG;
-    }
-    if ((rc = need_device())) return rc;
-    if (ntest == 0) return 0;
-    DevBuf dX, dal;
-    hipStream_t st = nullptr;
-    const int D = 2 * d;
-    if ((rc = dX.alloc((size_t)n0 * D * sizeof(double))) || (rc = upload(dal, alpha, (size_t)D * n0, st))) return rc;
-    if (n0 > 0 && (rc = copy_in(dX.p, (size_t)n0, X, ldx, (size_t)n0, D, st))) return rc;
-    return applymap_nd_io(family, d, mode, nm, ntest, n0, dX.as<double>(), (size_t)n0, hyp, nhyp, dal.as<double>(), Q0, ldq, P0, ldp,
-                          qmap, pmap, iters, st, tan, dir);
+    return with_host_map_model(me, family, d, ntest, hyp, nhyp, n0, X, ldx, alpha, [&](const MapModel &m) {
+        return applymap_nd_io(m, mode, nm, ntest, Q0, ldq, P0, ldp, qmap, pmap, iters, tan, dir);
+    });
 }
 
 // sgpr_applymap_sections_host (tan null), sgpr_applymap_sections_tangent_host and sgpr_applymap_sections_inverse_host (MAP_BACKWARD:
@@ -381,13 +391,41 @@ int sgpr_syev_host(int n, double *A, size_t lda, double *w)
 
 int sgpr_fit_batch_max_order(void) { return fit_batch_max_order(); }
 
+/* The BatchCall (common.h) of an entry that takes its points as x | y, and of one that takes d canonical pairs per point.  The
+ * mode of the call is the set of outputs the entry hands on: grad, loo, or value beside grad for the objective `which`. */
+struct BatchOuts {
+    double *grad = nullptr, *loo = nullptr, *value = nullptr;
+    int which = SGPR_LOO_LPD;
+};
+static BatchCall batch_call_xy(int family, int nbatch, int n_pts, const double *x, const double *y, const double *z, const double *hyp,
+                               int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, int *info, BatchOuts o = {})
+{
+    const int reg = (flags & SGPR_FIT_REG) ? 1 : 0;
+    return BatchCall{family, 0, reg, nbatch, n_pts, reg ? n_pts : 2 * n_pts, nhyp, x, y, z, hyp, sig2n, alpha, nll, info,
+                     o.grad, o.loo, o.value, o.which};
+}
+static BatchCall batch_call_nd(int family, int d, int nbatch, int n_pts, const double *X, const double *z, const double *hyp, int nhyp,
+                               const double *sig2n, double *alpha, double *nll, int *info, BatchOuts o = {})
+{
+    return BatchCall{family, d, 0, nbatch, n_pts, 2 * d * n_pts, nhyp, X, nullptr, z, hyp, sig2n, alpha, nll, info,
+                     o.grad, o.loo, o.value, o.which};
+}
+/* Unlike the entries below this one asks for a device first, and for the family only once an empty batch has returned. */
 int sgpr_fit_batch(int family, int nbatch, int n_pts, const double *x, const double *y, const double *z,
                    const double *hyp, int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll,
                    int *info)
 {
     int rc = need_device();
     if (rc) return rc;
-    return fit_batch(family, nbatch, n_pts, x, y, z, hyp, nhyp, sig2n, flags, alpha, nll, info);
+    const BatchCall c = batch_call_xy(family, nbatch, n_pts, x, y, z, hyp, nhyp, sig2n, flags, alpha, nll, info);
+    if (nbatch < 0 || n_pts <= 0 || c.n > fit_batch_max_order() || !x || !y || !z || !hyp || !sig2n || !nll || !info ||
+        (flags & ~(unsigned)SGPR_FIT_REG)) {
+        set_error("fit_batch: bad arguments (order per problem at most 2048)");
+        return SGPR_E_ARG;
+    }
+    if (nbatch == 0) return 0;
+    if (family < SGPR_FAM_A || family > SGPR_FAM_USER) { set_error("fit_batch: unknown kernel family"); return SGPR_E_ARG; }
+    return fit_batch_run(c);
 }
 
 /* The argument check of the batched entries below, before any device call: an argument error is SGPR_E_ARG on any machine, and
@@ -423,9 +461,8 @@ int sgpr_fit_batch_nd(int family, int d, int nbatch, int n_pts, const double *X,
 {
     int rc = check_batch_args("fit_batch_nd", family, &d, nhyp, flags, nullptr, nbatch, n_pts, 0, fit_batch_max_order(), "nll or info",
                               nll && info, X && z && hyp && sig2n);
-    if (rc || nbatch == 0) return rc;
-    if ((rc = need_device())) return rc;
-    return fit_batch_nd(family, d, nbatch, n_pts, X, z, hyp, nhyp, sig2n, alpha, nll, info);
+    if (rc || nbatch == 0 || (rc = need_device())) return rc;
+    return fit_batch_run(batch_call_nd(family, d, nbatch, n_pts, X, z, hyp, nhyp, sig2n, alpha, nll, info));
 }
 
 /* sgpr_fit_batch_nd plus the gradient of every problem's nll, every order up to the maximum (batch.hip: the gradient mode of
@@ -435,9 +472,8 @@ int sgpr_fit_batch_nd_grad(int family, int d, int nbatch, int n_pts, const doubl
 {
     int rc = check_batch_args("fit_batch_nd_grad", family, &d, nhyp, flags, nullptr, nbatch, n_pts, 0, fit_batch_max_order(),
                               "nll, grad or info", nll && grad && info, X && z && hyp && sig2n);
-    if (rc || nbatch == 0) return rc;
-    if ((rc = need_device())) return rc;
-    return fit_batch_nd_grad(family, d, nbatch, n_pts, X, z, hyp, nhyp, sig2n, alpha, nll, grad, info);
+    if (rc || nbatch == 0 || (rc = need_device())) return rc;
+    return fit_batch_run(batch_call_nd(family, d, nbatch, n_pts, X, z, hyp, nhyp, sig2n, alpha, nll, info, {grad}));
 }
 
 /* sgpr_fit_batch_nd plus leave-one-point-out cross-validation per problem over 2d x 2d point blocks, every order up to the maximum
@@ -447,9 +483,8 @@ int sgpr_fit_batch_nd_loo(int family, int d, int nbatch, int n_pts, const double
 {
     int rc = check_batch_args("fit_batch_nd_loo", family, &d, nhyp, flags, nullptr, nbatch, n_pts, 0, fit_batch_max_order(),
                               "nll, loo or info", nll && loo && info, X && z && hyp && sig2n);
-    if (rc || nbatch == 0) return rc;
-    if ((rc = need_device())) return rc;
-    return fit_batch_nd_loo(family, d, nbatch, n_pts, X, z, hyp, nhyp, sig2n, alpha, nll, loo, info);
+    if (rc || nbatch == 0 || (rc = need_device())) return rc;
+    return fit_batch_run(batch_call_nd(family, d, nbatch, n_pts, X, z, hyp, nhyp, sig2n, alpha, nll, info, {nullptr, loo}));
 }
 
 /* sgpr_fit_batch_nd plus one leave-one-point-out objective and its gradient per problem, orders up to 256 (batch.hip: the loograd
@@ -460,9 +495,8 @@ int sgpr_fit_batch_nd_loo_grad(int family, int d, int nbatch, int n_pts, const d
 {
     int rc = check_batch_args("fit_batch_nd_loo_grad", family, &d, nhyp, flags, &which, nbatch, n_pts, 0, fit_batch_grad_max_order(),
                               "nll, value, grad or info", nll && value && grad && info, X && z && hyp && sig2n);
-    if (rc || nbatch == 0) return rc;
-    if ((rc = need_device())) return rc;
-    return fit_batch_nd_loo_grad(family, d, nbatch, n_pts, X, z, hyp, nhyp, sig2n, which, alpha, nll, value, grad, info);
+    if (rc || nbatch == 0 || (rc = need_device())) return rc;
+    return fit_batch_run(batch_call_nd(family, d, nbatch, n_pts, X, z, hyp, nhyp, sig2n, alpha, nll, info, {grad, nullptr, value, which}));
 }
 
 /* sgpr_fit_batch plus the gradient of every problem's nll (batch.hip: the gradient mode of fit_batch_kernel). */
@@ -472,9 +506,8 @@ int sgpr_fit_batch_grad(int family, int nbatch, int n_pts, const double *x, cons
 {
     int rc = check_batch_args("fit_batch_grad", family, nullptr, nhyp, flags, nullptr, nbatch, n_pts, 0, fit_batch_grad_max_order(),
                               "nll, grad or info", nll && grad && info, x && y && z && hyp && sig2n);
-    if (rc || nbatch == 0) return rc;
-    if ((rc = need_device())) return rc;
-    return fit_batch_grad(family, nbatch, n_pts, x, y, z, hyp, nhyp, sig2n, flags, alpha, nll, grad, info);
+    if (rc || nbatch == 0 || (rc = need_device())) return rc;
+    return fit_batch_run(batch_call_xy(family, nbatch, n_pts, x, y, z, hyp, nhyp, sig2n, flags, alpha, nll, info, {grad}));
 }
 
 /* The same above order 256, up to sgpr_fit_batch_max_order() (batch.hip: the mid path with its gradient phase). */
@@ -484,9 +517,8 @@ int sgpr_fit_batch_grad_mid(int family, int nbatch, int n_pts, const double *x, 
 {
     int rc = check_batch_args("fit_batch_grad_mid", family, nullptr, nhyp, flags, nullptr, nbatch, n_pts, fit_batch_grad_max_order(),
                               fit_batch_max_order(), "nll, grad or info", nll && grad && info, x && y && z && hyp && sig2n);
-    if (rc || nbatch == 0) return rc;
-    if ((rc = need_device())) return rc;
-    return fit_batch_grad_mid(family, nbatch, n_pts, x, y, z, hyp, nhyp, sig2n, flags, alpha, nll, grad, info);
+    if (rc || nbatch == 0 || (rc = need_device())) return rc;
+    return fit_batch_run(batch_call_xy(family, nbatch, n_pts, x, y, z, hyp, nhyp, sig2n, flags, alpha, nll, info, {grad}));
 }
 
 /* sgpr_fit_batch plus leave-one-point-out cross-validation per problem, every order up to sgpr_fit_batch_max_order() (batch.hip:
@@ -497,9 +529,8 @@ int sgpr_fit_batch_loo(int family, int nbatch, int n_pts, const double *x, const
 {
     int rc = check_batch_args("fit_batch_loo", family, nullptr, nhyp, flags, nullptr, nbatch, n_pts, 0, fit_batch_max_order(),
                               "nll, loo or info", nll && loo && info, x && y && z && hyp && sig2n);
-    if (rc || nbatch == 0) return rc;
-    if ((rc = need_device())) return rc;
-    return fit_batch_loo(family, nbatch, n_pts, x, y, z, hyp, nhyp, sig2n, flags, alpha, nll, loo, info);
+    if (rc || nbatch == 0 || (rc = need_device())) return rc;
+    return fit_batch_run(batch_call_xy(family, nbatch, n_pts, x, y, z, hyp, nhyp, sig2n, flags, alpha, nll, info, {nullptr, loo}));
 }
 
 /* sgpr_fit_batch plus one leave-one-point-out objective and its gradient per problem, orders up to 256 (batch.hip: the loograd
@@ -510,9 +541,8 @@ int sgpr_fit_batch_loo_grad(int family, int nbatch, int n_pts, const double *x, 
 {
     int rc = check_batch_args("fit_batch_loo_grad", family, nullptr, nhyp, flags, &which, nbatch, n_pts, 0, fit_batch_grad_max_order(),
                               "nll, value, grad or info", nll && value && grad && info, x && y && z && hyp && sig2n);
-    if (rc || nbatch == 0) return rc;
-    if ((rc = need_device())) return rc;
-    return fit_batch_loo_grad(family, nbatch, n_pts, x, y, z, hyp, nhyp, sig2n, flags, which, alpha, nll, value, grad, info);
+    if (rc || nbatch == 0 || (rc = need_device())) return rc;
+    return fit_batch_run(batch_call_xy(family, nbatch, n_pts, x, y, z, hyp, nhyp, sig2n, flags, alpha, nll, info, {grad, nullptr, value, which}));
 }
 
 /* The same above order 256, up to sgpr_fit_batch_max_order() (batch.hip: the mid path with its loo gradient stage). */
@@ -522,9 +552,8 @@ int sgpr_fit_batch_loo_grad_mid(int family, int nbatch, int n_pts, const double 
 {
     int rc = check_batch_args("fit_batch_loo_grad_mid", family, nullptr, nhyp, flags, &which, nbatch, n_pts, fit_batch_grad_max_order(),
                               fit_batch_max_order(), "nll, value, grad or info", nll && value && grad && info, x && y && z && hyp && sig2n);
-    if (rc || nbatch == 0) return rc;
-    if ((rc = need_device())) return rc;
-    return fit_batch_loo_grad_mid(family, nbatch, n_pts, x, y, z, hyp, nhyp, sig2n, flags, which, alpha, nll, value, grad, info);
+    if (rc || nbatch == 0 || (rc = need_device())) return rc;
+    return fit_batch_run(batch_call_xy(family, nbatch, n_pts, x, y, z, hyp, nhyp, sig2n, flags, alpha, nll, info, {grad, nullptr, value, which}));
 }
 
 /* sgpr_fit_batch_nd_loo_grad above order 256, up to sgpr_fit_batch_max_order() (batch.hip: the same stage over 2d x 2d point blocks). */
@@ -534,9 +563,8 @@ int sgpr_fit_batch_nd_loo_grad_mid(int family, int d, int nbatch, int n_pts, con
 {
     int rc = check_batch_args("fit_batch_nd_loo_grad_mid", family, &d, nhyp, flags, &which, nbatch, n_pts, fit_batch_grad_max_order(),
                               fit_batch_max_order(), "nll, value, grad or info", nll && value && grad && info, X && z && hyp && sig2n);
-    if (rc || nbatch == 0) return rc;
-    if ((rc = need_device())) return rc;
-    return fit_batch_nd_loo_grad_mid(family, d, nbatch, n_pts, X, z, hyp, nhyp, sig2n, which, alpha, nll, value, grad, info);
+    if (rc || nbatch == 0 || (rc = need_device())) return rc;
+    return fit_batch_run(batch_call_nd(family, d, nbatch, n_pts, X, z, hyp, nhyp, sig2n, alpha, nll, info, {grad, nullptr, value, which}));
 }
 
 /* applymap / applymap_henon (functions/func.py:216-260) and the per-example variants for all Ntest
@@ -651,19 +679,9 @@ int sgpr_periodic_nd_host(int family, int d, int mode, int n, int ntest, const d
     if (rc || (rc = periodic_nd_call_check(me, mode, n, ntest, Q0, ldq, P0, ldp, tol, maxit, z, resid, its, qorb, porb)) ||
         (rc = applymap_nd_tangent_check(me, family, mode, n + 1, nullptr)))
         return rc;
-    if (n0 < 0 || (n0 > 0 && (!X || !alpha || ldx < (size_t)n0))) {
-        set_error(std::string(me) + ": n0 < 0, null X or alpha, or ldx < n0");
-        return SGPR_E_ARG;
-    }
-    if ((rc = need_device())) return rc;
-    if (ntest == 0) return 0;
-    DevBuf dX, dal;
-    hipStream_t st = nullptr;
-    const int D = 2 * d;
-    if ((rc = dX.alloc((size_t)n0 * D * sizeof(double))) || (rc = upload(dal, alpha, (size_t)D * n0, st))) return rc;
-    if (n0 > 0 && (rc = copy_in(dX.p, (size_t)n0, X, ldx, (size_t)n0, D, st))) return rc;
-    return periodic_nd_io(family, d, mode, n, ntest, n0, dX.as<double>(), (size_t)n0, hyp, nhyp, dal.as<double>(), wind, Q0, ldq, P0,
-                          ldp, tol, maxit, z, resid, its, mono, qorb, porb, st);
+    return with_host_map_model(me, family, d, ntest, hyp, nhyp, n0, X, ldx, alpha, [&](const MapModel &m) {
+        return periodic_nd_io(m, mode, n, ntest, wind, Q0, ldq, P0, ldp, tol, maxit, z, resid, its, mono, qorb, porb);
+    });
 }
 
 int sgpr_release_device_streams(int device)

@@ -1,4 +1,8 @@
-// capi_fit.hip -- the fit handle of libsympgpr_hip.so: struct sgpr_fit and every sgpr_fit_* entry that takes one
+// capi_fit.hip -- the fit handle of libsympgpr_hip.so: struct sgpr_fit and every sgpr_fit_* entry that takes one.  In front of the
+// entries, what several of them share, once each: guard (the state an entry needs), fit_gram / fit_predict (the fit's layout to a
+// kernel), fit_hyp (its hyperparameters), fit_scratch / rhs_scratch / cov_scratch (its scratch block), wait_results / check_solve
+// (the wait for the results and the strip solves' give-up words); fit_map_model, the model of the d-pair map entries, stands in
+// front of them.  The batched fits are in capi.hip, the map entries' checks and device traffic in capi_util.h.
 #include <cmath>
 #include <new>
 #include <vector>
@@ -82,14 +86,29 @@ static int fit_predict(const sgpr_fit *f, Points t, const double *alpha, double 
     return predict_nd(f->family, f->d, m, t.p, t.ld, N, f->dX, (size_t)N, f->hyp_nd, f->nhyp_nd, alpha, out, f->st);
 }
 
-// the fit's hyperparameters as the d-pair kernels take them: (lq.., lP.., [p..,] sig); d = 1 assembles them in buf
-static const double *fit_hyp_nd(const sgpr_fit *f, double buf[4], int *nhyp)
+// One view of the fit's hyperparameters: the lengths l, the periods pp (zeros in a family without; d = 1 carries kc.p as it is) and
+// sig as the gradient kernels take them, and vec[nhyp] = (lq.., lP.., [p..,] sig) as the d-pair kernels do, for d = 1 fits too
+struct FitHyp {
+    int nhyp;
+    double l[6], pp[3], sig, vec[12];
+};
+static FitHyp fit_hyp(const sgpr_fit *f)
 {
-    if (f->d > 1) { *nhyp = f->nhyp_nd; return f->hyp_nd; }
+    FitHyp h{};
     const bool hasp = family_has_p(f->family);
-    buf[0] = f->kc.lx; buf[1] = f->kc.ly; buf[2] = hasp ? f->kc.p : f->kc.sig; buf[3] = hasp ? f->kc.sig : 0.0;
-    *nhyp = hasp ? 4 : 3;
-    return buf;
+    if (f->d > 1) {
+        const int nl = 2 * f->d;
+        h.nhyp = f->nhyp_nd;
+        for (int m = 0; m < h.nhyp; ++m) h.vec[m] = f->hyp_nd[m];
+        for (int m = 0; m < nl; ++m) h.l[m] = f->hyp_nd[m];
+        for (int m = 0; m < f->d && hasp; ++m) h.pp[m] = f->hyp_nd[nl + m];
+        h.sig = f->hyp_nd[h.nhyp - 1];
+    } else {
+        h.nhyp = hasp ? 4 : 3;
+        h.l[0] = h.vec[0] = f->kc.lx; h.l[1] = h.vec[1] = f->kc.ly; h.pp[0] = f->kc.p; h.sig = f->kc.sig;
+        h.vec[2] = hasp ? f->kc.p : f->kc.sig; h.vec[3] = hasp ? f->kc.sig : 0.0;
+    }
+    return h;
 }
 
 // scratch for a solve with nrhs right-hand sides: the fit's own block, grown when a call needs more.  (Allocating and freeing
@@ -133,14 +152,42 @@ static int strip_give_up(const char *entry, const int h[8])
     return 0;
 }
 
-// ... a give-up is reported at the first call that waits for the solve
-static int check_solve(const char *entry, sgpr_fit_t f)
+// The wait of an entry whose result copies are enqueued on the fit's stream: the strip solves' state words come back in the same
+// synchronisation, so a give-up is reported at the first call that waits for the solve
+static int wait_results(const char *entry, sgpr_fit_t f)
 {
-    if (!trsv_uses_strips(f->n, f->dA, (size_t)f->n)) return 0;
     int h[8] = {};
-    SGPR_HIP(hipMemcpyAsync(h, trsv_state(f->n, f->work), sizeof(h), hipMemcpyDeviceToHost, f->st));
+    if (trsv_uses_strips(f->n, f->dA, (size_t)f->n))
+        SGPR_HIP(hipMemcpyAsync(h, trsv_state(f->n, f->work), sizeof(h), hipMemcpyDeviceToHost, f->st));
     SGPR_HIP(hipStreamSynchronize(f->st));
     return strip_give_up(entry, h);
+}
+// ... the same for an entry that has waited already: nothing to do unless the solve used strips
+static int check_solve(const char *entry, sgpr_fit_t f)
+{
+    return trsv_uses_strips(f->n, f->dA, (size_t)f->n) ? wait_results(entry, f) : 0;
+}
+
+// The fit's scratch for a covariance in chunks of mc points of D outputs each, ncols = D mc right-hand-side columns: [solve scratch
+// | V (n x ncols) | K** (ncols x ncols) | postcov's stage-1 partial sums], each part on a 256-byte boundary.  The solve's part is
+// sized for a full chunk: a chunk of fewer columns takes the same path or, with one column, the transposed fallback, whose n
+// doubles the strip scratch covers.
+struct CovScratch { double *S, *V, *Kss, *part; };
+static int cov_scratch(sgpr_fit_t f, int D, int mc, CovScratch *o)
+{
+    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
+    const int ncols = D * mc;
+    const size_t n = (size_t)f->n, nc = (size_t)ncols;
+    const size_t solve_raw = potrs_mat_scratch(f->n, ncols, f->dA, n), solve_b = up(solve_raw);
+    const size_t v_b = up(n * nc * sizeof(double)), k_b = up(nc * nc * sizeof(double));
+    const size_t p_b = up(postcov_partial_doubles(f->n, D, mc) * sizeof(double));
+    const int rc = rhs_scratch(f, ncols, &o->S, solve_b - solve_raw + v_b + k_b + p_b);
+    if (rc) return rc;
+    char *base = reinterpret_cast<char *>(o->S);
+    o->V = reinterpret_cast<double *>(base + solve_b);
+    o->Kss = reinterpret_cast<double *>(base + solve_b + v_b);
+    o->part = reinterpret_cast<double *>(base + solve_b + v_b + k_b);
+    return 0;
 }
 
 // W (n x n, leading dimension n) = I: zeros, then one strided copy of ones onto the diagonal
@@ -367,8 +414,7 @@ int sgpr_fit_alpha(sgpr_fit_t f, double *alpha_out)
     int rc = guard("fit_alpha", f, alpha_out, NEED_SOLVED);
     if (rc) return rc;
     SGPR_HIP(hipMemcpyAsync(alpha_out, f->dalpha, (size_t)f->n * sizeof(double), hipMemcpyDeviceToHost, f->st));
-    SGPR_HIP(hipStreamSynchronize(f->st));
-    return check_solve("fit_alpha", f);
+    return wait_results("fit_alpha", f);
 }
 
 int sgpr_fit_nll(sgpr_fit_t f, double *nll_out)
@@ -376,8 +422,7 @@ int sgpr_fit_nll(sgpr_fit_t f, double *nll_out)
     int rc = guard("fit_nll", f, nll_out, NEED_SOLVED);
     if (rc) return rc;
     SGPR_HIP(hipMemcpyAsync(nll_out, f->dscal, sizeof(double), hipMemcpyDeviceToHost, f->st));
-    SGPR_HIP(hipStreamSynchronize(f->st));
-    return check_solve("fit_nll", f);
+    return wait_results("fit_nll", f);
 }
 
 int sgpr_fit_ldiag(sgpr_fit_t f, double *diag_out)
@@ -535,35 +580,19 @@ int sgpr_fit_nll_grad_full(sgpr_fit_t f, double *grad, int ngrad)
 {
     int rc = guard("fit_nll_grad_full", f, grad);
     if (rc) return rc;
-    const bool reg = f->flags & SGPR_FIT_REG, hasp = family_has_p(f->family);
-    const int nhyp = f->d > 1 ? f->nhyp_nd : (hasp ? 4 : 3);
+    const FitHyp hy = fit_hyp(f);
+    const int nhyp = hy.nhyp, nacc = nhyp + 1;
     if (ngrad != nhyp + 1) { set_error("fit_nll_grad_full: ngrad must be nhyp + 1 = " + std::to_string(nhyp + 1)); return SGPR_E_ARG; }
     if ((rc = guard("fit_nll_grad_full", f, true, NEED_SOLVED | NEED_ALL_BLOCKS))) return rc;
-    const int d = f->d, nl = reg ? 2 : 2 * d;
-    double l[6], pp[3] = {0.0, 0.0, 0.0}, sig;
-    if (d > 1) {
-        for (int m = 0; m < nl; ++m) l[m] = f->hyp_nd[m];
-        for (int m = 0; m < d && hasp; ++m) pp[m] = f->hyp_nd[nl + m];
-        sig = f->hyp_nd[nhyp - 1];
-    } else {
-        l[0] = f->kc.lx; l[1] = f->kc.ly; pp[0] = f->kc.p; sig = f->kc.sig;
-    }
-    const int nacc = nhyp + 1;
     DevBuf S, O;
     if ((rc = S.alloc(nll_grad_full_scratch(f->n, f->npts, nacc))) || (rc = O.alloc(nacc * sizeof(double)))) return rc;
-    if ((rc = nll_grad_full(f->family, d, reg, f->npts, f->n, f->dA, (size_t)f->n, f->work, f->dX, f->dalpha, l, pp, nacc,
-                            S.as<double>(), O.as<double>(), f->st)))
+    if ((rc = nll_grad_full(f->family, f->d, f->flags & SGPR_FIT_REG, f->npts, f->n, f->dA, (size_t)f->n, f->work, f->dX, f->dalpha,
+                            hy.l, hy.pp, nacc, S.as<double>(), O.as<double>(), f->st)))
         return rc;
     double raw[12];
-    int h[8] = {};   // the strip solves' state words, fetched in the results' synchronisation
     SGPR_HIP(hipMemcpyAsync(raw, O.p, nacc * sizeof(double), hipMemcpyDeviceToHost, f->st));
-    if (trsv_uses_strips(f->n, f->dA, (size_t)f->n))
-        SGPR_HIP(hipMemcpyAsync(h, trsv_state(f->n, f->work), sizeof(h), hipMemcpyDeviceToHost, f->st));
-    SGPR_HIP(hipStreamSynchronize(f->st));
-    if ((rc = strip_give_up("fit_nll_grad_full", h))) return rc;
-    for (int k = 0; k < nhyp - 1; ++k) grad[k] = 0.5 * sig * raw[k];
-    grad[nhyp - 1] = 0.5 * raw[nhyp - 1];
-    grad[nhyp] = (f->sig2n < 0.0 ? -0.5 : 0.5) * raw[nhyp];
+    if ((rc = wait_results("fit_nll_grad_full", f))) return rc;
+    scale_grad_sums(raw, nhyp, hy.sig, f->sig2n, grad);
     return 0;
 }
 
@@ -579,15 +608,11 @@ int sgpr_fit_loo(sgpr_fit_t f, double *loo2, double *resid, double *cov, double 
     double *S;
     if ((rc = fit_scratch(f, o.total * sizeof(double), &S))) return rc;
     if ((rc = fit_loo(D, N, f->n, f->dA, (size_t)f->n, f->work, f->dalpha, S, f->st))) return rc;
-    int h[8] = {};   // the strip solves' state words, fetched in the results' synchronisation
     SGPR_HIP(hipMemcpyAsync(loo2, S + o.sums, 2 * sizeof(double), hipMemcpyDeviceToHost, f->st));
     if (resid) SGPR_HIP(hipMemcpyAsync(resid, S + o.resid, (size_t)f->n * sizeof(double), hipMemcpyDeviceToHost, f->st));
     if (cov) SGPR_HIP(hipMemcpyAsync(cov, S + o.cov, (size_t)N * D * D * sizeof(double), hipMemcpyDeviceToHost, f->st));
     if (lpd) SGPR_HIP(hipMemcpyAsync(lpd, S + o.lpd, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, f->st));
-    if (trsv_uses_strips(f->n, f->dA, (size_t)f->n))
-        SGPR_HIP(hipMemcpyAsync(h, trsv_state(f->n, f->work), sizeof(h), hipMemcpyDeviceToHost, f->st));
-    SGPR_HIP(hipStreamSynchronize(f->st));
-    return strip_give_up("fit_loo", h);
+    return wait_results("fit_loo", f);
 }
 
 /* The gradient of loo or press in every hyperparameter and sig2n (loograd.hip): the dense Ky^-1, one weight matrix
@@ -598,21 +623,13 @@ int sgpr_fit_loo_grad(sgpr_fit_t f, int which, double *value, double *grad, int 
 {
     int rc = guard("fit_loo_grad", f, value && grad);
     if (rc) return rc;
-    const bool reg = f->flags & SGPR_FIT_REG, hasp = family_has_p(f->family);
-    const int nhyp = f->d > 1 ? f->nhyp_nd : (hasp ? 4 : 3);
+    const FitHyp hy = fit_hyp(f);
+    const int nhyp = hy.nhyp, nacc = nhyp + 1;
     if (ngrad != nhyp + 1) { set_error("fit_loo_grad: ngrad must be nhyp + 1 = " + std::to_string(nhyp + 1)); return SGPR_E_ARG; }
     if (which != SGPR_LOO_LPD && which != SGPR_LOO_PRESS) { set_error("fit_loo_grad: which must be SGPR_LOO_LPD or SGPR_LOO_PRESS"); return SGPR_E_ARG; }
     if ((rc = guard("fit_loo_grad", f, true, NEED_SOLVED | NEED_ALL_BLOCKS))) return rc;
-    const int d = f->d, nl = reg ? 2 : 2 * d, D = reg ? 1 : 2 * d;
-    double l[6], pp[3] = {0.0, 0.0, 0.0}, sig;
-    if (d > 1) {
-        for (int m = 0; m < nl; ++m) l[m] = f->hyp_nd[m];
-        for (int m = 0; m < d && hasp; ++m) pp[m] = f->hyp_nd[nl + m];
-        sig = f->hyp_nd[nhyp - 1];
-    } else {
-        l[0] = f->kc.lx; l[1] = f->kc.ly; pp[0] = f->kc.p; sig = f->kc.sig;
-    }
-    const int nacc = nhyp + 1;
+    const bool reg = f->flags & SGPR_FIT_REG;
+    const int d = f->d, D = reg ? 1 : 2 * d;
     const LooGradLayout o = loo_grad_layout(f->n, f->npts, D, nacc);
     const size_t need = o.total * sizeof(double);
     if (need > f->rhs_scratch_bytes) {
@@ -627,20 +644,14 @@ int sgpr_fit_loo_grad(sgpr_fit_t f, int which, double *value, double *grad, int 
         f->rhs_scratch_bytes = need;
     }
     double *S = static_cast<double *>(f->rhs_scratch);
-    if ((rc = fit_loo_grad(f->family, d, reg, which, f->npts, f->n, f->dA, (size_t)f->n, f->work, f->dX, f->dalpha, l, pp, nacc, S,
-                           f->st)))
+    if ((rc = fit_loo_grad(f->family, d, reg, which, f->npts, f->n, f->dA, (size_t)f->n, f->work, f->dX, f->dalpha, hy.l, hy.pp, nacc,
+                           S, f->st)))
         return rc;
     double raw[13];
-    int h[8] = {};   // the strip solves' state words, fetched in the results' synchronisation
     SGPR_HIP(hipMemcpyAsync(raw, S + o.sums, (nacc + 1) * sizeof(double), hipMemcpyDeviceToHost, f->st));
-    if (trsv_uses_strips(f->n, f->dA, (size_t)f->n))
-        SGPR_HIP(hipMemcpyAsync(h, trsv_state(f->n, f->work), sizeof(h), hipMemcpyDeviceToHost, f->st));
-    SGPR_HIP(hipStreamSynchronize(f->st));
-    if ((rc = strip_give_up("fit_loo_grad", h))) return rc;
+    if ((rc = wait_results("fit_loo_grad", f))) return rc;
     *value = which == SGPR_LOO_LPD ? -raw[nacc] : raw[nacc];
-    for (int k = 0; k < nhyp - 1; ++k) grad[k] = 0.5 * sig * raw[k];
-    grad[nhyp - 1] = 0.5 * raw[nhyp - 1];
-    grad[nhyp] = (f->sig2n < 0.0 ? -0.5 : 0.5) * raw[nhyp];
+    scale_grad_sums(raw, nhyp, hy.sig, f->sig2n, grad);
     if (std::isnan(*value))   // a point without a positive definite block: its NaN reaches every sum through M; made explicit
         for (int k = 0; k <= nhyp; ++k) grad[k] = *value;
     return 0;
@@ -658,10 +669,8 @@ int sgpr_fit_predict_nd(sgpr_fit_t f, int m, const double *Xt, size_t ldxt, doub
     DevBuf dT, dO;
     if ((rc = dT.alloc((size_t)m * D * sizeof(double))) || (rc = dO.alloc((size_t)m * D * sizeof(double)))) return rc;
     if ((rc = copy_in(dT.p, (size_t)m, Xt, ldxt, (size_t)m, D, f->st))) return rc;
-    double hyp1[4];
-    int nhyp;
-    const double *hyp = fit_hyp_nd(f, hyp1, &nhyp);   // the d-pair kernel whatever the fit's layout: d = 1 too
-    if ((rc = predict_nd(f->family, f->d, m, dT.as<double>(), (size_t)m, f->npts, f->dX, (size_t)f->npts, hyp, nhyp, f->dalpha,
+    const FitHyp hy = fit_hyp(f);   // the d-pair kernel whatever the fit's layout: d = 1 too
+    if ((rc = predict_nd(f->family, f->d, m, dT.as<double>(), (size_t)m, f->npts, f->dX, (size_t)f->npts, hy.vec, hy.nhyp, f->dalpha,
                          dO.as<double>(), f->st)))
         return rc;
     SGPR_HIP(hipMemcpyAsync(out, dO.p, (size_t)m * D * sizeof(double), hipMemcpyDeviceToHost, f->st));
@@ -690,17 +699,9 @@ int sgpr_fit_predict_cov(sgpr_fit_t f, int m, const double *Xt, size_t ldxt, dou
     double *T = dT.as<double>(), *M = dM.as<double>(), *C = dC.as<double>();
     if ((rc = copy_in(T, (size_t)m, Xt, ldxt, (size_t)m, nx, f->st))) return rc;
     if ((rc = fit_predict(f, {T, (size_t)m, m}, f->dalpha, M))) return rc;
-    // scratch: the solve's for D mc columns (a chunk of fewer columns takes the same path or, with one column, the transposed
-    // fallback, whose n doubles the strip scratch covers), then V, K** and the partial sums, each on a 256-byte boundary
-    auto up = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t solve_raw = potrs_mat_scratch(f->n, D * mc, f->dA, n), solve_b = up(solve_raw);
-    const size_t v_b = up(n * D * mc * sizeof(double)), k_b = up((size_t)D * mc * D * mc * sizeof(double));
-    const size_t p_b = up(postcov_partial_doubles(f->n, D, mc) * sizeof(double));
-    double *S;
-    if ((rc = rhs_scratch(f, D * mc, &S, solve_b - solve_raw + v_b + k_b + p_b))) return rc;
-    char *base = reinterpret_cast<char *>(S);
-    double *V = reinterpret_cast<double *>(base + solve_b), *Kss = reinterpret_cast<double *>(base + solve_b + v_b);
-    double *part = reinterpret_cast<double *>(base + solve_b + v_b + k_b);
+    CovScratch cs;
+    if ((rc = cov_scratch(f, D, mc, &cs))) return rc;
+    double *S = cs.S, *V = cs.V, *Kss = cs.Kss, *part = cs.part;
     for (int c0 = 0; c0 < m; c0 += mc) {
         const int cnt = m - c0 < mc ? m - c0 : mc, ncols = D * cnt;
         const Points chunk = {T + c0, (size_t)m, cnt};
@@ -745,21 +746,15 @@ int sgpr_fit_predict_genfun(sgpr_fit_t f, int m, const double *Xt, size_t ldxt, 
     if ((rc = copy_in(T, M1, Xt, ldxt, (size_t)m, D, f->st))) return rc;
     if (ref && (rc = copy_in(T + m, M1, ref, 1, 1, D, f->st))) return rc;
     const double *x0 = ref ? T + m : nullptr;
-    double hyp1[4];
-    int nhyp;
-    const double *hyp = fit_hyp_nd(f, hyp1, &nhyp);   // the d-pair kernels whatever the fit's layout: d = 1 too
+    const FitHyp hy = fit_hyp(f);   // the d-pair kernels whatever the fit's layout: d = 1 too
+    const double *hyp = hy.vec;
+    const int nhyp = hy.nhyp;
     if ((rc = genfun_nd(f->family, f->d, m, T, M1, ref != nullptr, f->npts, f->dX, (size_t)f->npts, hyp, nhyp, f->dalpha, Fd, f->st)))
         return rc;
     if (var) {
-        auto up = [](size_t b) { return (b + 255) / 256 * 256; };   // the layout of sgpr_fit_predict_cov with D mc = 256 columns
-        const size_t solve_raw = potrs_mat_scratch(f->n, mc, f->dA, n), solve_b = up(solve_raw);
-        const size_t v_b = up(n * mc * sizeof(double)), k_b = up((size_t)mc * mc * sizeof(double));
-        const size_t p_b = up(postcov_partial_doubles(f->n, 1, mc) * sizeof(double));
-        double *S;
-        if ((rc = rhs_scratch(f, mc, &S, solve_b - solve_raw + v_b + k_b + p_b))) return rc;
-        char *base = reinterpret_cast<char *>(S);
-        double *V = reinterpret_cast<double *>(base + solve_b), *Kss = reinterpret_cast<double *>(base + solve_b + v_b);
-        double *part = reinterpret_cast<double *>(base + solve_b + v_b + k_b);
+        CovScratch cs;   // D = 1: 256 columns, the priors on the diagonal of K**
+        if ((rc = cov_scratch(f, 1, mc, &cs))) return rc;
+        double *S = cs.S, *V = cs.V, *Kss = cs.Kss, *part = cs.part;
         for (int c0 = 0; c0 < m; c0 += mc) {
             const int cnt = m - c0 < mc ? m - c0 : mc;
             if ((rc = genfun_cross_nd(f->family, f->d, cnt, T + c0, M1, x0, M1, f->npts, f->dX, (size_t)f->npts, hyp, nhyp, V, n, Kss,
@@ -783,23 +778,31 @@ int sgpr_fit_predict_genfun(sgpr_fit_t f, int m, const double *Xt, size_t ldxt, 
     return 0;
 }
 
-/* nm steps of the fit's symplectic map (map_nd.hip: applymap_nd_kernel) for ntest orbits, with the fit's own device-resident
- * training points and alpha; d = 1 fits run the D = 2 instance of the d-pair kernel. */
+/* The last check of a d-pair map entry, the state of its handle, and the model (capi_util.h: MapModel) its launch takes: the fit's
+ * own device-resident training points and alpha on its stream, the hyperparameters of `hy`; d = 1 fits run the D = 2 instance of
+ * the d-pair kernels. */
+static int fit_map_model(const char *me, const sgpr_fit *f, FitHyp &hy, MapModel *m)
+{
+    const int rc = guard(me, f, true, NEED_SOLVED | NEED_ALL_BLOCKS | NEED_PAIR_KERNEL);
+    if (rc) return rc;
+    hy = fit_hyp(f);
+    *m = MapModel{f->family, f->d, f->npts, f->dX, (size_t)f->npts, hy.vec, hy.nhyp, f->dalpha, f->st};
+    return 0;
+}
+
+/* nm steps of the fit's symplectic map (map_nd.hip: applymap_nd_kernel) for ntest orbits.  alpha is the strip solves' result: a
+ * give-up there is reported by the first call that waits (as sgpr_fit_alpha), so every map entry ends on check_solve. */
 int sgpr_fit_applymap_nd(sgpr_fit_t f, int mode, int nm, int ntest, const double *Q0, size_t ldq, const double *P0, size_t ldp,
                          double *qmap, double *pmap, int *iters)
 {
-    int rc = guard("fit_applymap_nd", f, true);
-    if (rc) return rc;
-    if ((rc = applymap_nd_call_check("fit_applymap_nd", mode, nm, ntest, Q0, ldq, P0, ldp, qmap, pmap))) return rc;
-    if ((rc = guard("fit_applymap_nd", f, true, NEED_SOLVED | NEED_ALL_BLOCKS | NEED_PAIR_KERNEL))) return rc;
-    if (ntest == 0) return 0;
-    double hyp1[4];
-    int nhyp;
-    const double *hyp = fit_hyp_nd(f, hyp1, &nhyp);
-    if ((rc = applymap_nd_io(f->family, f->d, mode, nm, ntest, f->npts, f->dX, (size_t)f->npts, hyp, nhyp, f->dalpha, Q0, ldq, P0,
-                             ldp, qmap, pmap, iters, f->st)))
+    const char *me = "fit_applymap_nd";
+    FitHyp hy;
+    MapModel m;
+    int rc = guard(me, f, true);
+    if (rc || (rc = applymap_nd_call_check(me, mode, nm, ntest, Q0, ldq, P0, ldp, qmap, pmap)) || (rc = fit_map_model(me, f, hy, &m)) ||
+        ntest == 0 || (rc = applymap_nd_io(m, mode, nm, ntest, Q0, ldq, P0, ldp, qmap, pmap, iters)))
         return rc;
-    return check_solve("fit_applymap_nd", f);   // alpha is the strip solves' result: a give-up there is reported by the first call that waits (as sgpr_fit_alpha)
+    return check_solve(me, f);
 }
 
 /* The same with the tangent map (maptan.h): the orbit outputs have the bits of sgpr_fit_applymap_nd. */
@@ -807,18 +810,13 @@ int sgpr_fit_applymap_nd_tangent(sgpr_fit_t f, int mode, int nm, int ntest, cons
                                  size_t ldp, double *qmap, double *pmap, int *iters, double *jac, double *mono, double *lyap)
 {
     const char *me = "fit_applymap_nd_tangent";
-    int rc = guard(me, f, true);
-    if (rc) return rc;
-    if ((rc = applymap_nd_call_check(me, mode, nm, ntest, Q0, ldq, P0, ldp, qmap, pmap))) return rc;
-    if ((rc = applymap_nd_tangent_check(me, f->family, mode, nm, lyap))) return rc;
-    if ((rc = guard(me, f, true, NEED_SOLVED | NEED_ALL_BLOCKS | NEED_PAIR_KERNEL))) return rc;
-    if (ntest == 0) return 0;
-    double hyp1[4];
-    int nhyp;
-    const double *hyp = fit_hyp_nd(f, hyp1, &nhyp);
     const MapTangentOut tan = {jac, mono, lyap};
-    if ((rc = applymap_nd_io(f->family, f->d, mode, nm, ntest, f->npts, f->dX, (size_t)f->npts, hyp, nhyp, f->dalpha, Q0, ldq, P0,
-                             ldp, qmap, pmap, iters, f->st, &tan)))
+    FitHyp hy;
+    MapModel m;
+    int rc = guard(me, f, true);
+    if (rc || (rc = applymap_nd_call_check(me, mode, nm, ntest, Q0, ldq, P0, ldp, qmap, pmap)) ||
+        (rc = applymap_nd_tangent_check(me, f->family, mode, nm, lyap)) || (rc = fit_map_model(me, f, hy, &m)) || ntest == 0 ||
+        (rc = applymap_nd_io(m, mode, nm, ntest, Q0, ldq, P0, ldp, qmap, pmap, iters, &tan)))
         return rc;
     return check_solve(me, f);
 }
@@ -828,17 +826,12 @@ int sgpr_fit_applymap_nd_inverse(sgpr_fit_t f, int mode, int nm, int ntest, cons
                                  size_t ldp, double *qmap, double *pmap, int *iters)
 {
     const char *me = "fit_applymap_nd_inverse";
+    FitHyp hy;
+    MapModel m;
     int rc = guard(me, f, true);
-    if (rc) return rc;
-    if ((rc = applymap_nd_call_check(me, mode, nm, ntest, Q0, ldq, P0, ldp, qmap, pmap))) return rc;
-    if ((rc = applymap_nd_inverse_check(me, mode))) return rc;
-    if ((rc = guard(me, f, true, NEED_SOLVED | NEED_ALL_BLOCKS | NEED_PAIR_KERNEL))) return rc;
-    if (ntest == 0) return 0;
-    double hyp1[4];
-    int nhyp;
-    const double *hyp = fit_hyp_nd(f, hyp1, &nhyp);
-    if ((rc = applymap_nd_io(f->family, f->d, mode, nm, ntest, f->npts, f->dX, (size_t)f->npts, hyp, nhyp, f->dalpha, Q0, ldq, P0,
-                             ldp, qmap, pmap, iters, f->st, nullptr, MAP_BACKWARD)))
+    if (rc || (rc = applymap_nd_call_check(me, mode, nm, ntest, Q0, ldq, P0, ldp, qmap, pmap)) ||
+        (rc = applymap_nd_inverse_check(me, mode)) || (rc = fit_map_model(me, f, hy, &m)) || ntest == 0 ||
+        (rc = applymap_nd_io(m, mode, nm, ntest, Q0, ldq, P0, ldp, qmap, pmap, iters, nullptr, MAP_BACKWARD)))
         return rc;
     return check_solve(me, f);
 }
@@ -849,17 +842,12 @@ int sgpr_fit_periodic_nd(sgpr_fit_t f, int mode, int n, int ntest, const int *wi
                          double *porb)
 {
     const char *me = "fit_periodic_nd";
+    FitHyp hy;
+    MapModel m;
     int rc = guard(me, f, true);
-    if (rc) return rc;
-    if ((rc = periodic_nd_call_check(me, mode, n, ntest, Q0, ldq, P0, ldp, tol, maxit, z, resid, its, qorb, porb))) return rc;
-    if ((rc = applymap_nd_tangent_check(me, f->family, mode, n + 1, nullptr))) return rc;
-    if ((rc = guard(me, f, true, NEED_SOLVED | NEED_ALL_BLOCKS | NEED_PAIR_KERNEL))) return rc;
-    if (ntest == 0) return 0;
-    double hyp1[4];
-    int nhyp;
-    const double *hyp = fit_hyp_nd(f, hyp1, &nhyp);
-    if ((rc = periodic_nd_io(f->family, f->d, mode, n, ntest, f->npts, f->dX, (size_t)f->npts, hyp, nhyp, f->dalpha, wind, Q0, ldq, P0,
-                             ldp, tol, maxit, z, resid, its, mono, qorb, porb, f->st)))
+    if (rc || (rc = periodic_nd_call_check(me, mode, n, ntest, Q0, ldq, P0, ldp, tol, maxit, z, resid, its, qorb, porb)) ||
+        (rc = applymap_nd_tangent_check(me, f->family, mode, n + 1, nullptr)) || (rc = fit_map_model(me, f, hy, &m)) || ntest == 0 ||
+        (rc = periodic_nd_io(m, mode, n, ntest, wind, Q0, ldq, P0, ldp, tol, maxit, z, resid, its, mono, qorb, porb)))
         return rc;
     return check_solve(me, f);
 }

@@ -1,4 +1,7 @@
-// capi_util.h -- what more than one of the C API units (capi.hip, capi_fit.hip, capi_dev.hip) needs: host code only
+// capi_util.h -- what more than one of the C API units (capi.hip, capi_fit.hip, capi_dev.hip) needs: host code only.  Device
+// buffers and copies (DevBuf, upload, copy_2d); the factorisation's one retry; the choice of a solve path (potrs_blocked,
+// potrs_dispatch); and the d-pair map entries of a fit handle and of the _host calls: their argument checks, their model
+// (MapModel) and the device traffic of one call (applymap_nd_io, periodic_nd_io).
 #pragma once
 #include "common.h"
 
@@ -131,14 +134,27 @@ struct MapTangentOut {
     double *jac, *mono, *lyap;
 };
 
-// uploads the start points, runs applymap_nd on device-resident training points and alpha, brings the orbits back and waits;
-// with `tan` the launch is applymap_nd_tangent and its outputs come back too; MAP_BACKWARD runs applymap_nd_inverse (no tangent)
+// The model of a d-pair map as map_nd.hip takes it: the kernel (hyp = (lq.., lP.., [p..,] sig) on the host), the device-resident
+// training points X (n0 x 2d, leading dimension ldx) and alpha, and the stream of the call.  A fit handle's comes from
+// fit_map_model (capi_fit.hip), a *_host entry's from with_host_map_model (capi.hip).
+struct MapModel {
+    int family, d, n0;
+    const double *X;
+    size_t ldx;
+    const double *hyp;
+    int nhyp;
+    const double *alpha;
+    hipStream_t stream;
+};
+
+// uploads the start points, runs applymap_nd on the model, brings the orbits back and waits; with `tan` the launch is
+// applymap_nd_tangent and its outputs come back too; MAP_BACKWARD runs applymap_nd_inverse (no tangent)
 enum MapDirection { MAP_FORWARD, MAP_BACKWARD };
-inline int applymap_nd_io(int family, int d, int mode, int nm, int ntest, int n0, const double *dXtr, size_t ldxtr,
-                          const double *hyp, int nhyp, const double *dalpha, const double *Q0, size_t ldq, const double *P0,
-                          size_t ldp, double *qmap, double *pmap, int *iters, hipStream_t st, const MapTangentOut *tan = nullptr,
-                          MapDirection dir = MAP_FORWARD)
+inline int applymap_nd_io(const MapModel &m, int mode, int nm, int ntest, const double *Q0, size_t ldq, const double *P0, size_t ldp,
+                          double *qmap, double *pmap, int *iters, const MapTangentOut *tan = nullptr, MapDirection dir = MAP_FORWARD)
 {
+    const int d = m.d;
+    hipStream_t st = m.stream;
     int rc;
     DevBuf q0, p0, qm, pm, it, dj, dm, dl;
     const size_t nt = (size_t)ntest, out_bytes = (size_t)nm * nt * d * sizeof(double), it_bytes = (size_t)(nm - 1) * nt * sizeof(int);
@@ -151,16 +167,15 @@ inline int applymap_nd_io(int family, int d, int mode, int nm, int ntest, int n0
                 (tan->lyap && (rc = dl.alloc(lyap_bytes)))))
         return rc;
     if ((rc = copy_in(q0.p, nt, Q0, ldq, nt, d, st)) || (rc = copy_in(p0.p, nt, P0, ldp, nt, d, st))) return rc;
+    double *q = q0.as<double>(), *p = p0.as<double>(), *dq = qm.as<double>(), *dp = pm.as<double>();
+    int *dit = iters ? it.as<int>() : nullptr;
     if (dir == MAP_BACKWARD)
-        rc = applymap_nd_inverse(family, d, mode, nm, ntest, n0, dXtr, ldxtr, hyp, nhyp, dalpha, q0.as<double>(), p0.as<double>(),
-                                 qm.as<double>(), pm.as<double>(), iters ? it.as<int>() : nullptr, st);
+        rc = applymap_nd_inverse(m.family, d, mode, nm, ntest, m.n0, m.X, m.ldx, m.hyp, m.nhyp, m.alpha, q, p, dq, dp, dit, st);
     else if (!tan)
-        rc = applymap_nd(family, d, mode, nm, ntest, n0, dXtr, ldxtr, hyp, nhyp, dalpha, q0.as<double>(), p0.as<double>(),
-                         qm.as<double>(), pm.as<double>(), iters ? it.as<int>() : nullptr, st);
+        rc = applymap_nd(m.family, d, mode, nm, ntest, m.n0, m.X, m.ldx, m.hyp, m.nhyp, m.alpha, q, p, dq, dp, dit, st);
     else
-        rc = applymap_nd_tangent(family, d, mode, nm, ntest, n0, dXtr, ldxtr, hyp, nhyp, dalpha, q0.as<double>(), p0.as<double>(),
-                                 qm.as<double>(), pm.as<double>(), iters ? it.as<int>() : nullptr, dj.as<double>(),
-                                 dm.as<double>(), dl.as<double>(), st);
+        rc = applymap_nd_tangent(m.family, d, mode, nm, ntest, m.n0, m.X, m.ldx, m.hyp, m.nhyp, m.alpha, q, p, dq, dp, dit,
+                                 dj.as<double>(), dm.as<double>(), dl.as<double>(), st);
     if (rc) return rc;
     SGPR_HIP(hipMemcpyAsync(qmap, qm.p, out_bytes, hipMemcpyDeviceToHost, st));
     SGPR_HIP(hipMemcpyAsync(pmap, pm.p, out_bytes, hipMemcpyDeviceToHost, st));
@@ -190,14 +205,15 @@ inline int periodic_nd_call_check(const char *entry, int mode, int n, int ntest,
     return applymap_nd_call_check(entry, mode, n, ntest, Q0, ldq, P0, ldp, z, z);
 }
 
-// uploads the guesses and the winding numbers (null: none), runs periodic_nd on device-resident training points and alpha,
-// brings the results back and waits.  Host arrays: wind ntest x d ints column-major; z [ntest][2d], resid [ntest], its [ntest];
-// mono [ntest][2d][2d] or null; qorb / porb [n][ntest][d] or both null.
-inline int periodic_nd_io(int family, int d, int mode, int n, int ntest, int n0, const double *dXtr, size_t ldxtr, const double *hyp,
-                          int nhyp, const double *dalpha, const int *wind, const double *Q0, size_t ldq, const double *P0, size_t ldp,
-                          double tol, int maxit, double *z, double *resid, int *its, double *mono, double *qorb, double *porb,
-                          hipStream_t st)
+// uploads the guesses and the winding numbers (null: none), runs periodic_nd on the model, brings the results back and waits.
+// Host arrays: wind ntest x d ints column-major; z [ntest][2d], resid [ntest], its [ntest]; mono [ntest][2d][2d] or null; qorb /
+// porb [n][ntest][d] or both null.
+inline int periodic_nd_io(const MapModel &m, int mode, int n, int ntest, const int *wind, const double *Q0, size_t ldq, const double *P0,
+                          size_t ldp, double tol, int maxit, double *z, double *resid, int *its, double *mono, double *qorb,
+                          double *porb)
 {
+    const int d = m.d;
+    hipStream_t st = m.stream;
     int rc;
     DevBuf q0, p0, dw, dz, dr, di, dm, dq, dp;
     const size_t nt = (size_t)ntest, D = (size_t)2 * d, z_bytes = nt * D * sizeof(double), mono_bytes = nt * D * D * sizeof(double);
@@ -208,8 +224,8 @@ inline int periodic_nd_io(int family, int d, int mode, int n, int ntest, int n0,
         return rc;
     if ((rc = copy_in(q0.p, nt, Q0, ldq, nt, d, st)) || (rc = copy_in(p0.p, nt, P0, ldp, nt, d, st))) return rc;
     if (wind) SGPR_HIP(hipMemcpyAsync(dw.p, wind, wind_bytes, hipMemcpyHostToDevice, st));
-    if ((rc = periodic_nd(family, d, mode, n, ntest, n0, dXtr, ldxtr, hyp, nhyp, dalpha, dw.as<int>(), q0.as<double>(), p0.as<double>(),
-                          tol, maxit, dz.as<double>(), dr.as<double>(), di.as<int>(), dm.as<double>(), dq.as<double>(),
+    if ((rc = periodic_nd(m.family, d, mode, n, ntest, m.n0, m.X, m.ldx, m.hyp, m.nhyp, m.alpha, dw.as<int>(), q0.as<double>(),
+                          p0.as<double>(), tol, maxit, dz.as<double>(), dr.as<double>(), di.as<int>(), dm.as<double>(), dq.as<double>(),
                           dp.as<double>(), st)))
         return rc;
     SGPR_HIP(hipMemcpyAsync(z, dz.p, z_bytes, hipMemcpyDeviceToHost, st));

@@ -306,45 +306,35 @@ struct BatchLayout {
     size_t o_lpart, o_wt, o_v, o_beta, o_zero;       // mid path's loo gradient: the point pass's partials, W~, v, beta, zeros (behind o_part)
 };
 BatchLayout batch_layout(int mid, int mode, int d, int reg, int nbatch, int npts, int nhyp);
-int fit_batch(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
-              int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, int *info);
-// the fit for problems with d canonical pairs per point (X: nbatch x 2d x npts), n = 2 d npts <= fit_batch_max_order(); the
-// arguments have been checked (capi.hip), nbatch > 0
-int fit_batch_nd(int family, int d, int nbatch, int npts, const double *X, const double *z, const double *hyp, int nhyp,
-                 const double *sig2n, double *alpha, double *nll, int *info);
-// the same plus the gradient of every problem's nll: grad is nbatch x (nhyp + 1), rows in sgpr_fit_nll_grad_full's order for a
-// d-pair fit; both paths (the one-launch kernel in its gradient mode, the mid path with mid_grad_nd_kernel)
-int fit_batch_nd_grad(int family, int d, int nbatch, int npts, const double *X, const double *z, const double *hyp, int nhyp,
-                      const double *sig2n, double *alpha, double *nll, double *grad, int *info);
-// the same plus leave-one-point-out cross-validation over 2d x 2d point blocks: loo is nbatch x 2, row b = {loo, press}; both paths
-int fit_batch_nd_loo(int family, int d, int nbatch, int npts, const double *X, const double *z, const double *hyp, int nhyp,
-                     const double *sig2n, double *alpha, double *nll, double *loo, int *info);
-// one of the two objectives (which: SGPR_LOO_LPD / SGPR_LOO_PRESS) and its gradient, n = 2 d npts <= fit_batch_grad_max_order(): value
-// is nbatch doubles, grad nbatch x (nhyp + 1) in fit_batch_nd_grad's order
-int fit_batch_nd_loo_grad(int family, int d, int nbatch, int npts, const double *X, const double *z, const double *hyp, int nhyp,
-                          const double *sig2n, int which, double *alpha, double *nll, double *value, double *grad, int *info);
+
+// One batched call, as the C entries (capi.hip) describe it and the drivers take it.  The mode is the set of outputs asked for: grad
+// (nbatch x (nhyp + 1)) the nll gradient, loo (nbatch x 2) the {loo, press} rows, value (nbatch) beside grad the loo objective
+// `which` (SGPR_LOO_LPD / SGPR_LOO_PRESS) and its gradient, rows in sgpr_fit_nll_grad_full's order.
+enum { MODE_FIT = 0, MODE_GRAD = 1, MODE_LOO = 2, MODE_LOOGRAD = 3 };
+struct BatchCall {
+    int family, d, reg, nbatch, npts, n, nhyp;      // d = 0: points as x | y; d > 0: d canonical pairs per point, x = X (nbatch x 2d x npts)
+    const double *x, *y, *z, *hyp, *sig2n;
+    double *alpha, *nll;                            // alpha may be null
+    int *info;
+    double *grad, *loo, *value;
+    int which;
+    int mode() const { return value ? MODE_LOOGRAD : grad ? MODE_GRAD : loo ? MODE_LOO : MODE_FIT; }
+};
+// The one driver: the one-launch path up to fit_batch_grad_max_order(), the mid path above.  The arguments have been checked and
+// nbatch > 0.  The order decides alone because check_batch_args (capi.hip) has held every entry to its own range before the call
+// -- above fit_batch_grad_max_order() for the _mid entries, at most that for the one-launch gradients, up to fit_batch_max_order()
+// for the rest -- so this choice is the one each entry used to make for itself.
+int fit_batch_run(const BatchCall &c);
 int fit_batch_grad_max_order();                  // 256: one workgroup holds the whole problem
-int fit_batch_grad(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
-                   int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, double *grad, int *info);
-// the same for 256 < order <= fit_batch_max_order(): the mid path's factor and solves, then Ky^-1 per problem on the matrix cores
-int fit_batch_grad_mid(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
-                       int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, double *grad, int *info);
-// the batched fits with leave-one-point-out cross-validation, every order up to fit_batch_max_order(): loo is nbatch x 2,
-// row b = {loo, press}; the arguments have been checked (capi.hip), nbatch > 0
-int fit_batch_loo(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
-                  int nhyp, const double *sig2n, unsigned flags, double *alpha, double *nll, double *loo, int *info);
-// one of the two objectives (which: SGPR_LOO_LPD / SGPR_LOO_PRESS) and its gradient, order <= fit_batch_grad_max_order(): value is
-// nbatch doubles, grad nbatch x (nhyp + 1); the arguments have been checked (capi.hip), nbatch > 0
-int fit_batch_loo_grad(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
-                       int nhyp, const double *sig2n, unsigned flags, int which, double *alpha, double *nll, double *value,
-                       double *grad, int *info);
-// the same for 256 < order <= fit_batch_max_order(), x | y points and d canonical pairs per point: the mid path with its Ky^-1 phase,
-// then M = Ky^-1 W~ Ky^-1 per problem on the matrix cores in a third image (batch_mid.h)
-int fit_batch_loo_grad_mid(int family, int nbatch, int npts, const double *x, const double *y, const double *z, const double *hyp,
-                           int nhyp, const double *sig2n, unsigned flags, int which, double *alpha, double *nll, double *value,
-                           double *grad, int *info);
-int fit_batch_nd_loo_grad_mid(int family, int d, int nbatch, int npts, const double *X, const double *z, const double *hyp, int nhyp,
-                              const double *sig2n, int which, double *alpha, double *nll, double *value, double *grad, int *info);
+
+// the raw sums of a gradient (nll_grad_full's layout: lengths, periods, sig, sig2n) into the gradient: the lengths and periods by
+// sig / 2 (the kernels differentiate k without sig), sig by 1/2, sig2n by sign(sig2n) / 2
+inline void scale_grad_sums(const double *raw, int nhyp, double sig, double sig2n, double *grad)
+{
+    for (int k = 0; k < nhyp - 1; ++k) grad[k] = 0.5 * sig * raw[k];
+    grad[nhyp - 1] = 0.5 * raw[nhyp - 1];
+    grad[nhyp] = (sig2n < 0.0 ? -0.5 : 0.5) * raw[nhyp];
+}
 
 // ---- blas_small.hip
 int zero_strict_upper(int n, double *A, size_t lda, hipStream_t st);

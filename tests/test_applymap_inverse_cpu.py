@@ -3,7 +3,6 @@ exported and bound alike; every argument error answered with SGPR_E_ARG before a
 every family; the Python wrappers and maps.symplectic_inverse; and the NumPy restatement tests/ref_inverse.py -- the CPU reference
 of tests/test_gpu_applymap_inverse.py -- held against central differences and against the forward step it undoes."""
 import ctypes as C
-import fnmatch
 import os
 import re
 import subprocess
@@ -16,6 +15,8 @@ from tests import ref_tangent as RT
 from tests.test_applymap_nd_cpu import HOST_BAD as FORWARD_HOST_BAD
 from tests.test_gpu_applymap_nd import _hyp, _starts, _training
 
+from tests import c_header
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _ip = C.POINTER(C.c_int)
 NAMES = (("sgpr_fit_applymap_nd_inverse", 11), ("sgpr_applymap_nd_inverse_host", 18))
@@ -23,23 +24,11 @@ NAMES = (("sgpr_fit_applymap_nd_inverse", 11), ("sgpr_applymap_nd_inverse_host",
 
 def test_header_exports_map_ctypes_table_and_library_agree():
     from sympgpr_amd import _lib as L
-    hdr = open(os.path.join(ROOT, "include", "sympgpr_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     lib = L.load_library()
-    exports = open(os.path.join(ROOT, "sympgpr_amd", "csrc", "exports.map")).read()
-    globs = re.findall(r"^\s*([A-Za-z_*]+);", exports.split("local:")[0], flags=re.M)
     dyn = subprocess.run(["nm", "-D", "--defined-only", L.lib_path()], capture_output=True, text=True, check=True).stdout
     for name, nargs in NAMES:
-        m = re.search(r"\bint\s+%s\s*\(([^)]*)\)" % name, code)
-        assert m, name + " is not declared"
-        params = [p.strip() for p in m.group(1).split(",")]
-        res, args = L.SIGNATURES[name]
-        assert res is C.c_int and len(params) == len(args) == nargs
-        for p, a in zip(params, args):      # int / size_t / pointer in the same places
-            want = C.c_size_t if p.startswith("size_t") else (C.c_int if p.startswith("int ") and "*" not in p else None)
-            assert (a is want) if want else (a not in (C.c_int, C.c_size_t)), (name, p)
-        assert getattr(lib, name).argtypes == args
-        assert any(fnmatch.fnmatchcase(name, g) for g in globs), name + " is not covered by exports.map"
+        c_header.assert_bound_as_declared(name, nargs)
+        assert c_header.in_exports_map(name), name + " is not covered by exports.map"
         assert re.search(r" T %s$" % name, dyn, flags=re.M), name + " is not exported"
     # the same argument list as the forward pair, position by position
     for inv, fwd in (("sgpr_fit_applymap_nd_inverse", "sgpr_fit_applymap_nd"), ("sgpr_applymap_nd_inverse_host", "sgpr_applymap_nd_host")):

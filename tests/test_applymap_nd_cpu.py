@@ -3,10 +3,11 @@ every argument error answered with SGPR_E_ARG before any device call, and the Py
 are checked on the GPU (tests/test_gpu_applymap_nd.py)."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
+
+from tests import c_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _ip = C.POINTER(C.c_int)
@@ -14,20 +15,9 @@ _ip = C.POINTER(C.c_int)
 
 def test_header_ctypes_table_and_library_agree():
     from sympgpr_amd import _lib as L
-    hdr = open(os.path.join(ROOT, "include", "sympgpr_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    lib = L.load_library()
     for name, nargs in (("sgpr_fit_applymap_nd", 11), ("sgpr_applymap_nd_host", 18)):
-        m = re.search(r"\bint\s+%s\s*\(([^)]*)\)" % name, code)
-        assert m, name + " is not declared"
-        params = [p.strip() for p in m.group(1).split(",")]
-        res, args = L.SIGNATURES[name]
-        assert res is C.c_int and len(params) == len(args) == nargs
-        for p, a in zip(params, args):      # int / size_t / pointer in the same places
-            want = C.c_size_t if p.startswith("size_t") else (C.c_int if p.startswith("int ") and "*" not in p else None)
-            assert (a is want) if want else (a not in (C.c_int, C.c_size_t)), (name, p)
-        assert getattr(lib, name).argtypes == args
-    assert lib.sgpr_abi_version() == 5
+        c_header.assert_bound_as_declared(name, nargs)
+    assert L.load_library().sgpr_abi_version() == 5
 
 
 def _host_args(**over):

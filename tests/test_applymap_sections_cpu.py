@@ -2,12 +2,12 @@
 declared, exported and bound alike, every argument error is answered with SGPR_E_ARG before any device call, the Python
 wrapper validates shapes, and the chunk-and-callback bookkeeping of applymap_tok is checked against the reference's
 step-by-step double loop with a NumPy stepper.  The numbers are checked on the GPU (tests/test_gpu_applymap_sections.py)."""
-import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
+
+from tests import c_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "sgpr_applymap_sections_host"
@@ -15,18 +15,8 @@ NAME = "sgpr_applymap_sections_host"
 
 def test_header_ctypes_table_and_library_agree():
     from sympgpr_amd import _lib as L
-    hdr = open(os.path.join(ROOT, "include", "sympgpr_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    lib = L.load_library()
-    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)" % NAME, code)
-    assert m, NAME + " is not declared"
-    params = [p.strip() for p in m.group(1).split(",")]
-    res, args = L.SIGNATURES[NAME]
-    assert res is C.c_int and len(params) == len(args) == 23
-    for p, a in zip(params, args):          # int / pointer in the same places
-        assert (a is C.c_int) == (p.startswith("int ") and "*" not in p), p
-    assert getattr(lib, NAME).argtypes == args
-    assert lib.sgpr_abi_version() == 5
+    c_header.assert_bound_as_declared(NAME, 23)
+    assert L.load_library().sgpr_abi_version() == 5
 
 
 def _args(**over):

@@ -5,7 +5,6 @@ NumPy stepper; and the NumPy restatement tests/ref_sections_inverse.py -- the CP
 tests/test_gpu_applymap_sections_inverse.py -- held against the MINPACK forward orbit it undoes and against MINPACK on its own
 equation.  The device's numbers are checked on the GPU."""
 import ctypes as C
-import fnmatch
 import inspect
 import os
 import re
@@ -18,6 +17,8 @@ from tests import ref_inverse as RI
 from tests import ref_sections_inverse as RS
 from tests.test_gpu_applymap_sections import _sections, _starts
 
+from tests import c_header
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "sgpr_applymap_sections_inverse_host"
 _ip = C.POINTER(C.c_int)
@@ -25,22 +26,11 @@ _ip = C.POINTER(C.c_int)
 
 def test_header_exports_map_ctypes_table_and_library_agree():
     from sympgpr_amd import _lib as L
-    hdr = open(os.path.join(ROOT, "include", "sympgpr_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     lib = L.load_library()
-    exports = open(os.path.join(ROOT, "sympgpr_amd", "csrc", "exports.map")).read()
-    globs = re.findall(r"^\s*([A-Za-z_*]+);", exports.split("local:")[0], flags=re.M)
     dyn = subprocess.run(["nm", "-D", "--defined-only", L.lib_path()], capture_output=True, text=True, check=True).stdout
-    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)" % NAME, code)
-    assert m, NAME + " is not declared"
-    params = [p.strip() for p in m.group(1).split(",")]
-    res, args = L.SIGNATURES[NAME]
-    assert res is C.c_int and len(params) == len(args) == 17
-    for p, a in zip(params, args):          # int / pointer in the same places
-        assert (a is C.c_int) == (p.startswith("int ") and "*" not in p), p
+    params, args = c_header.assert_bound_as_declared(NAME, 17), L.SIGNATURES[NAME][1]
     assert args[-1] == _ip and params[-1].startswith("int *")
-    assert getattr(lib, NAME).argtypes == args
-    assert any(fnmatch.fnmatchcase(NAME, g) for g in globs), NAME + " is not covered by exports.map"
+    assert c_header.in_exports_map(NAME), NAME + " is not covered by exports.map"
     assert re.search(r" T %s$" % NAME, dyn, flags=re.M), NAME + " is not exported"
     # sgpr_applymap_sections_host without the guess GPs and pdiff, with iters: the same leading arguments, position by position
     fwd = L.SIGNATURES["sgpr_applymap_sections_host"][1]

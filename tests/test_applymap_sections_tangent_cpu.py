@@ -3,8 +3,6 @@ maps.tangent_from_jac, examples/tokamak_split.applymap_tok_tangent): declared, e
 answered with SGPR_E_ARG before any device call; the Python wrapper's ValueErrors; the host Benettin / monodromy helper against
 tests/ref_tangent.py; the chunk bookkeeping's jac rows; and the d = 1 Hessian of tests/ref_tangent.py -- the reference of
 tests/test_gpu_applymap_sections_tangent.py -- against central differences of the CPU oracle's rows."""
-import ctypes as C
-import fnmatch
 import os
 import re
 import subprocess
@@ -13,6 +11,7 @@ import numpy as np
 import pytest
 
 from tests import ref_tangent as RT
+from tests import c_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "sgpr_applymap_sections_tangent_host"
@@ -20,23 +19,11 @@ NAME = "sgpr_applymap_sections_tangent_host"
 
 def test_header_exports_map_ctypes_table_and_library_agree():
     from sympgpr_amd import _lib as L
-    hdr = open(os.path.join(ROOT, "include", "sympgpr_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     lib = L.load_library()
-    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)" % NAME, code)
-    assert m, NAME + " is not declared"
-    params = [p.strip() for p in m.group(1).split(",")]
-    plain = [p.strip() for p in re.search(r"\bint\s+sgpr_applymap_sections_host\s*\(([^)]*)\)", code).group(1).split(",")]
+    params, plain = c_header.assert_bound_as_declared(NAME, 26), c_header.assert_bound_as_declared("sgpr_applymap_sections_host")
     assert params[:23] == plain and params[23:] == ["double *jac", "double *mono", "double *lyap"]
-    res, args = L.SIGNATURES[NAME]
-    assert res is C.c_int and len(params) == len(args) == 26
-    for p, a in zip(params, args):          # int / pointer in the same places
-        assert (a is C.c_int) == (p.startswith("int ") and "*" not in p), p
-    assert args[:23] == L.SIGNATURES["sgpr_applymap_sections_host"][1]
-    assert getattr(lib, NAME).argtypes == args
-    exports = open(os.path.join(ROOT, "sympgpr_amd", "csrc", "exports.map")).read()
-    globs = re.findall(r"^\s*([A-Za-z_*]+);", exports.split("local:")[0], flags=re.M)
-    assert any(fnmatch.fnmatchcase(NAME, g) for g in globs), NAME + " is not covered by exports.map"
+    assert L.SIGNATURES[NAME][1][:23] == L.SIGNATURES["sgpr_applymap_sections_host"][1]
+    assert c_header.in_exports_map(NAME), NAME + " is not covered by exports.map"
     dyn = subprocess.run(["nm", "-D", "--defined-only", L.lib_path()], capture_output=True, text=True, check=True).stdout
     assert re.search(r" T %s$" % NAME, dyn, flags=re.M), NAME + " is not exported"
     assert lib.sgpr_abi_version() == 5

@@ -3,7 +3,6 @@ exported and bound alike; every argument error answered with SGPR_E_ARG before a
 and the NumPy restatement tests/ref_tangent.py -- the CPU reference of tests/test_gpu_applymap_tangent.py -- held against
 sympy's own derivatives of the kernels tools/gen_kernels.py defines and against central differences of a CPU step."""
 import ctypes as C
-import fnmatch
 import importlib.util
 import os
 import re
@@ -13,6 +12,7 @@ import numpy as np
 import pytest
 
 from tests import ref_tangent as RT
+from tests import c_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _ip = C.POINTER(C.c_int)
@@ -21,23 +21,11 @@ NAMES = (("sgpr_fit_applymap_nd_tangent", 14), ("sgpr_applymap_nd_tangent_host",
 
 def test_header_exports_map_ctypes_table_and_library_agree():
     from sympgpr_amd import _lib as L
-    hdr = open(os.path.join(ROOT, "include", "sympgpr_hip.h")).read()
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     lib = L.load_library()
-    exports = open(os.path.join(ROOT, "sympgpr_amd", "csrc", "exports.map")).read()
-    globs = re.findall(r"^\s*([A-Za-z_*]+);", exports.split("local:")[0], flags=re.M)
     dyn = subprocess.run(["nm", "-D", "--defined-only", L.lib_path()], capture_output=True, text=True, check=True).stdout
     for name, nargs in NAMES:
-        m = re.search(r"\bint\s+%s\s*\(([^)]*)\)" % name, code)
-        assert m, name + " is not declared"
-        params = [p.strip() for p in m.group(1).split(",")]
-        res, args = L.SIGNATURES[name]
-        assert res is C.c_int and len(params) == len(args) == nargs
-        for p, a in zip(params, args):      # int / size_t / pointer in the same places
-            want = C.c_size_t if p.startswith("size_t") else (C.c_int if p.startswith("int ") and "*" not in p else None)
-            assert (a is want) if want else (a not in (C.c_int, C.c_size_t)), (name, p)
-        assert getattr(lib, name).argtypes == args
-        assert any(fnmatch.fnmatchcase(name, g) for g in globs), name + " is not covered by exports.map"
+        c_header.assert_bound_as_declared(name, nargs)
+        assert c_header.in_exports_map(name), name + " is not covered by exports.map"
         assert re.search(r" T %s$" % name, dyn, flags=re.M), name + " is not exported"
     assert lib.sgpr_abi_version() == 5
 

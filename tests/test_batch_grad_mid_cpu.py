@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from tests import ref_batch_inv as R
+from tests import c_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "sgpr_fit_batch_grad_mid"
@@ -23,26 +24,17 @@ def _lib():
 
 def test_symbol_in_header_dynamic_table_and_signatures():
     L, lib = _lib()
-    hdr = open(os.path.join(ROOT, "include", "sympgpr_hip.h")).read()
-    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % NAME, hdr)
-    assert m, "not declared in include/sympgpr_hip.h"
-    ctype = {"int": C.c_int, "unsigned": C.c_uint, "double *": C.POINTER(C.c_double), "int *": C.POINTER(C.c_int)}
-    kinds = []
-    for p in (p.strip() for p in m.group(1).split(",")):
-        base = re.sub(r"\s*\b\w+$", "", p).replace("const ", "").strip()
-        kinds.append(ctype[re.sub(r"\s*\*\s*", " *", base).strip()])
-    assert kinds == L.SIGNATURES[NAME][1] == L.SIGNATURES["sgpr_fit_batch_grad"][1]
-    assert L.SIGNATURES[NAME][0] is C.c_int
-    fn = getattr(lib, NAME)
-    assert fn.argtypes == L.SIGNATURES[NAME][1]
+    c_header.assert_bound_as_declared(NAME)
+    assert L.SIGNATURES[NAME][1] == L.SIGNATURES["sgpr_fit_batch_grad"][1]
     nm = subprocess.run(["nm", "-D", "--defined-only", L.lib_path()], capture_output=True, text=True, check=True).stdout
     assert re.search(r"\bT %s$" % NAME, nm, re.M)
     assert lib.sgpr_abi_version() == 5
     # the header documents the layout, the range, the scratch and who gives it back, next to the declaration
-    doc = " ".join(hdr[:m.start()].rsplit("*/", 1)[0].rsplit("/*", 1)[1].split())
+    doc = c_header.comment_above(NAME)
     for word in ("nhyp + 1", "sign(sig2n[b])", "<= 256", "sgpr_fit_batch_max_order()", "NaN", "scratch", "sgpr_trim"):
         assert word in doc, word
     # sgpr_fit_batch_grad keeps its limit and its text
+    hdr = open(c_header.HEADER).read()
     old = re.search(r"\bint\s+sgpr_fit_batch_grad\s*\(", hdr)
     assert "n_pts with SGPR_FIT_REG) <= 256." in hdr[:old.start()].rsplit("/*", 1)[1]
 

@@ -10,6 +10,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import c_header
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "sgpr_fit_batch_loo_grad"
 
@@ -21,25 +23,13 @@ def _lib():
 
 def test_symbol_in_header_dynamic_table_and_signatures():
     L, lib = _lib()
-    hdr = open(os.path.join(ROOT, "include", "sympgpr_hip.h")).read()
-    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % NAME, hdr)
-    assert m, "not declared in include/sympgpr_hip.h"
-    ctype = {"int": C.c_int, "unsigned": C.c_uint, "double *": C.POINTER(C.c_double), "int *": C.POINTER(C.c_int)}
-    kinds = []
-    for p in (p.strip() for p in m.group(1).split(",")):
-        base = re.sub(r"\s*\b\w+$", "", p).replace("const ", "").strip()
-        kinds.append(ctype[re.sub(r"\s*\*\s*", " *", base).strip()])
-    assert len(kinds) == 16
-    assert kinds == L.SIGNATURES[NAME][1]
-    assert L.SIGNATURES[NAME][0] is C.c_int
-    fn = getattr(lib, NAME)
-    assert fn.argtypes == L.SIGNATURES[NAME][1]
+    c_header.assert_bound_as_declared(NAME, 16)
     nm = subprocess.run(["nm", "-D", "--defined-only", L.lib_path()], capture_output=True, text=True, check=True).stdout
     assert re.search(r"\bT %s$" % NAME, nm, re.M)
     assert lib.sgpr_abi_version() == 5
     assert (L.LOO_LPD, L.LOO_PRESS) == (0, 1)
     # the header documents the layout, the guarantees and the scratch next to the declaration
-    doc = " ".join(hdr[:m.start()].rsplit("*/", 1)[0].rsplit("/*", 1)[1].split())
+    doc = c_header.comment_above(NAME)
     for word in ("nhyp + 1", "sign(sig2n[b])", "<= 256", "NaN", "sgpr_fit_loo_grad", "bit-identical", "1.8 MiB"):
         assert word in doc, word
 

@@ -5,12 +5,12 @@ SGPR_E_ARG before a device is asked for, the symbols are exported under ABI 5, t
 (sgpr_probe_batch_layout_loograd_mid) equals the formulas restated here, and the Python wrappers make exactly one call of the new
 entry under mid="device", keep their slow path under mid=None and apply the siblings' sign and NaN conventions."""
 import ctypes as C
-import fnmatch
 import os
-import re
 
 import numpy as np
 import pytest
+
+from tests import c_header
 
 LEAF = 128
 GT, GCJ, GPART, GPART_ND = 256, 64, 8, 16      # contraction: rows and column points per workgroup, doubles per partial
@@ -109,20 +109,12 @@ def test_the_existing_entries_keep_refusing_orders_above_256():
 def test_abi_and_exports():
     L, lib = _lib()
     assert lib.sgpr_abi_version() == 5 and L.ABI_VERSION == 5
-    with open(os.path.join(ROOT, "include", "sympgpr_hip.h")) as f:
-        header = f.read()
-    with open(os.path.join(ROOT, "include", "sympgpr_probe.h")) as f:
-        probe_header = f.read()
-    with open(os.path.join(ROOT, "sympgpr_amd", "csrc", "exports.map")) as f:
-        globs = re.findall(r"^\s*(sgpr_[\w*]*);", f.read(), re.M)
     for entry in (XY, ND):
-        assert hasattr(lib, entry) and entry in L.SIGNATURES
-        assert re.search(r"\bint %s\(" % entry, header)
-        assert any(fnmatch.fnmatchcase(entry, g) for g in globs), globs
+        c_header.assert_bound_as_declared(entry)
+        assert c_header.in_exports_map(entry), entry
     assert len(L.SIGNATURES[XY][1]) == len(L.SIGNATURES["sgpr_fit_batch_loo_grad"][1])
     assert len(L.SIGNATURES[ND][1]) == len(L.SIGNATURES["sgpr_fit_batch_nd_loo_grad"][1])
-    assert "sgpr_probe_batch_layout_loograd_mid" in L.PROBE_SIGNATURES
-    assert re.search(r"\bint sgpr_probe_batch_layout_loograd_mid\(", probe_header)
+    c_header.assert_bound_as_declared("sgpr_probe_batch_layout_loograd_mid", probe=True)
 
 
 # ---- the arena layout of the mode, against formulas restated here

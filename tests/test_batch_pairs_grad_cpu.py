@@ -4,10 +4,11 @@ under ABI 5, the arena layout of its two paths equals the formulas restated here
 wrappers hand the library the documented layout and apply the documented signs and NaN / +inf rows."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
+
+from tests import c_header
 
 LEAF, BMAX, PER_WG = 128, 256, 98816          # leaf order, largest one-launch order, scratch doubles per workgroup of a plain fit
 GT, GCJ, GPART_ND = 256, 64, 16                # mid gradient: rows / column points per workgroup, doubles per d-pair partial
@@ -62,13 +63,8 @@ def test_an_order_check_names_the_limit_and_an_empty_batch_returns_zero():
 def test_abi_and_export():
     L, lib = _lib()
     assert lib.sgpr_abi_version() == 5
-    assert hasattr(lib, "sgpr_fit_batch_nd_grad") and "sgpr_fit_batch_nd_grad" in L.SIGNATURES
-    with open(os.path.join(ROOT, "include", "sympgpr_hip.h")) as f:
-        assert re.search(r"\bint sgpr_fit_batch_nd_grad\(", f.read())
-    with open(os.path.join(ROOT, "sympgpr_amd", "csrc", "exports.map")) as f:
-        globs = re.findall(r"^\s*(sgpr_[\w*]*);", f.read(), re.M)
-    import fnmatch
-    assert any(fnmatch.fnmatchcase("sgpr_fit_batch_nd_grad", g) for g in globs), globs
+    c_header.assert_bound_as_declared("sgpr_fit_batch_nd_grad")
+    assert c_header.in_exports_map("sgpr_fit_batch_nd_grad")
 
 
 # ---- the arena layout for mode = GRAD with d > 0, against the formulas restated here

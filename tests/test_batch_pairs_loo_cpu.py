@@ -5,12 +5,12 @@ of their modes (sgpr_probe_batch_layout_nd_loo) equals the formulas restated her
 Python wrappers hand the library the documented layout, apply the documented signs and NaN / LinAlgError conventions and switch to their slow paths above orders 256
 and 2048."""
 import ctypes as C
-import fnmatch
 import os
-import re
 
 import numpy as np
 import pytest
+
+from tests import c_header
 
 LEAF, BMAX, PER_WG = 128, 256, 98816          # leaf order, largest one-launch order, scratch doubles per workgroup of a plain fit
 GT = 256                                       # mid loo: points per workgroup
@@ -85,14 +85,9 @@ def test_the_order_checks_name_their_limits_and_an_empty_batch_returns_zero():
 def test_abi_and_exports():
     L, lib = _lib()
     assert lib.sgpr_abi_version() == 5
-    with open(os.path.join(ROOT, "include", "sympgpr_hip.h")) as f:
-        header = f.read()
-    with open(os.path.join(ROOT, "sympgpr_amd", "csrc", "exports.map")) as f:
-        globs = re.findall(r"^\s*(sgpr_[\w*]*);", f.read(), re.M)
     for entry in ENTRIES:
-        assert hasattr(lib, entry) and entry in L.SIGNATURES
-        assert re.search(r"\bint %s\(" % entry, header)
-        assert any(fnmatch.fnmatchcase(entry, g) for g in globs), globs
+        c_header.assert_bound_as_declared(entry)
+        assert c_header.in_exports_map(entry), entry
 
 
 # ---- the arena layout for d > 0 in the loo modes, against the formulas of tests/test_batch_layout_cpu.py restated here

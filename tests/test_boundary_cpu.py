@@ -8,20 +8,16 @@ import re
 import numpy as np
 import pytest
 
+from tests import c_header
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _header_symbols():
-    txt = open(os.path.join(ROOT, "include", "sympgpr_hip.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(sgpr_[a-z0-9_]+)\s*\(", txt)))
 
 
 def test_library_exports_every_declared_symbol():
     import ctypes
     from sympgpr_amd import _lib
     lib = ctypes.CDLL(_lib.lib_path())
-    syms = _header_symbols()
+    syms = sorted(c_header.prototypes())
     assert len(syms) >= 40
     for s in syms:
         assert hasattr(lib, s), "libsympgpr_hip.so does not export " + s
@@ -35,7 +31,7 @@ def test_library_exports_nothing_but_the_c_abi_and_the_probe_hooks():
     out = subprocess.run(["nm", "-D", "--defined-only", _lib.lib_path()], capture_output=True, text=True, check=True).stdout
     names = [ln.split()[-1] for ln in out.splitlines() if " T " in ln or " W " in ln or " B " in ln or " D " in ln]
     c_abi = sorted(n for n in names if n.startswith("sgpr_"))
-    assert c_abi == _header_symbols()
+    assert c_abi == sorted(c_header.prototypes())
     rest = [n for n in names if not n.startswith("sgpr_")]
     hooks = open(os.path.join(ROOT, "sympgpr_amd", "csrc", "exports.map")).read()
     stems = re.findall(r"sgpr::([A-Za-z_:]+)\*;", hooks)
@@ -47,9 +43,29 @@ def test_library_exports_nothing_but_the_c_abi_and_the_probe_hooks():
 
 def test_ctypes_table_matches_header():
     from sympgpr_amd import _lib
-    assert sorted(_lib.SIGNATURES) == _header_symbols()
+    assert sorted(_lib.SIGNATURES) == sorted(c_header.prototypes())
     lib = _lib.load_library()
     assert lib.sgpr_abi_version() == 5
+
+
+# entries excused from test_every_signature_is_bound_as_its_header_declares by name: none, and meant to stay so
+SIGNATURE_EXCEPTIONS = ()
+
+
+def test_every_signature_is_bound_as_its_header_declares():
+    """Both headers against both ctypes tables: the same names; every restype and every argtype is the header's (a c_int where
+    the header says size_t shifts the stack silently); the function of the loaded library carries exactly its row.  The one
+    exception is c_header.binding_errors': a pointer of a *_dev entry may be bound as c_void_p."""
+    from sympgpr_amd import _lib
+    errs = []
+    for path, table, lib in ((c_header.HEADER, _lib.SIGNATURES, _lib.load_library()),
+                             (c_header.PROBE_HEADER, _lib.PROBE_SIGNATURES, _lib.load_probe_library())):
+        protos = c_header.prototypes(path)
+        assert len(protos) >= 30 and sorted(protos) == sorted(table)
+        for name in sorted(protos):
+            if name not in SIGNATURE_EXCEPTIONS:
+                errs += c_header.binding_errors(name, protos[name], table[name], getattr(lib, name))
+    assert not errs, "\n".join(errs)
 
 
 def test_mirror_has_reference_call_surface():
@@ -148,23 +164,17 @@ int main(){ std::mt19937_64 g(1); std::uniform_real_distribution<double> ux(-745
     assert me < 4e-16 and ms < 1.5e-16 and mc < 1.5e-16
 
 
-def _probe_header_symbols():
-    txt = open(os.path.join(ROOT, "include", "sympgpr_probe.h")).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(sgpr_[a-z0-9_]+)\s*\(", txt)))
-
-
 def test_probe_library_is_separate_and_complete():
     """measurement aids live in libsympgpr_probe.so / include/sympgpr_probe.h: every declared symbol is
     exported there, bound in _lib.PROBE_SIGNATURES, and NOT part of the product header"""
     import ctypes
     from sympgpr_amd import _lib
     probe = ctypes.CDLL(os.path.join(os.path.dirname(_lib.lib_path()), "libsympgpr_probe.so"))
-    syms = _probe_header_symbols()
+    syms = sorted(c_header.prototypes(c_header.PROBE_HEADER))
     assert syms and sorted(_lib.PROBE_SIGNATURES) == syms
     for s in syms:
         assert hasattr(probe, s), "libsympgpr_probe.so does not export " + s
-    assert not any(s.startswith("sgpr_probe") for s in _header_symbols())
+    assert not any(s.startswith("sgpr_probe") for s in sorted(c_header.prototypes()))
 
 
 def test_generated_kernels_are_up_to_date(tmp_path, monkeypatch):

@@ -5,12 +5,12 @@ what predict_rows / build_K_nd . alpha return.  Tolerance 1e-6 max(1, max|rows|)
 h = 1e-5 l."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 
 from tests import ref_genfun as RG
+from tests import c_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EPS = np.finfo(np.float64).eps
@@ -40,10 +40,7 @@ def nd_case(N, d, fam, m=37, seed=0):
 
 def test_symbol_is_exported_and_bound_with_the_header_signature():
     from sympgpr_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "sympgpr_hip.h")).read()
-    m = re.search(r"^int sgpr_fit_predict_genfun\(([^)]*)\);", hdr, flags=re.M)
-    assert m, "include/sympgpr_hip.h does not declare sgpr_fit_predict_genfun"
-    params = [" ".join(p.split()) for p in m.group(1).split(",")]
+    params = c_header.assert_bound_as_declared("sgpr_fit_predict_genfun")
     assert params == ["sgpr_fit_t f", "int m", "const double *Xt", "size_t ldxt", "const double *ref", "double *F", "double *var"]
     dp = C.POINTER(C.c_double)
     assert _lib.SIGNATURES["sgpr_fit_predict_genfun"] == (C.c_int, [C.c_void_p, C.c_int, dp, C.c_size_t, dp, dp, dp])

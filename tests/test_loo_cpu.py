@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from tests import ref_loo as R
+from tests import c_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -40,24 +41,13 @@ def _lib():
 @pytest.mark.parametrize("name,like", [("sgpr_fit_loo", None), ("sgpr_fit_batch_loo", "sgpr_fit_batch_grad")])
 def test_symbols_in_header_dynamic_table_and_signatures(name, like):
     L, lib = _lib()
-    hdr = open(os.path.join(ROOT, "include", "sympgpr_hip.h")).read()
-    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, hdr)
-    assert m, "not declared in include/sympgpr_hip.h"
-    ctype = {"int": C.c_int, "unsigned": C.c_uint, "double *": C.POINTER(C.c_double), "int *": C.POINTER(C.c_int),
-             "sgpr_fit_t": C.c_void_p}
-    kinds = []
-    for p in (p.strip() for p in m.group(1).split(",")):
-        base = re.sub(r"\s*\b\w+$", "", p).replace("const ", "").strip()
-        kinds.append(ctype[re.sub(r"\s*\*\s*", " *", base).strip()])
-    assert kinds == L.SIGNATURES[name][1]
+    c_header.assert_bound_as_declared(name)
     if like:
-        assert kinds == L.SIGNATURES[like][1]
-    assert L.SIGNATURES[name][0] is C.c_int
-    assert getattr(lib, name).argtypes == L.SIGNATURES[name][1]
+        assert L.SIGNATURES[name][1] == L.SIGNATURES[like][1]
     nm = subprocess.run(["nm", "-D", "--defined-only", L.lib_path()], capture_output=True, text=True, check=True).stdout
     assert re.search(r"\bT %s$" % name, nm, re.M)
     assert lib.sgpr_abi_version() == 5
-    doc = " ".join(hdr[:m.start()].rsplit("*/", 1)[0].rsplit("/*", 1)[1].split())
+    doc = c_header.comment_above(name)
     for word in ("press", "NaN", "scratch", "ABI 5 (an additional entry point)"):
         assert word in doc, word
 

@@ -8,7 +8,6 @@
     that the reference's own error cannot decide a device comparison.  SGPR_RECORD=1 writes the ratios to
     profiles/loograd/reference_margin.txt.
 (c) the boundary: the symbol declared, bound and exported; argument errors answered before any device is touched."""
-import ctypes as C
 import os
 import re
 import subprocess
@@ -18,6 +17,7 @@ import pytest
 
 from tests import ref_loo as R
 from tests import ref_loograd as G
+from tests import c_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -109,20 +109,11 @@ def _lib():
 def test_symbol_in_header_dynamic_table_and_signatures():
     L, lib = _lib()
     name = "sgpr_fit_loo_grad"
-    assert name in L.SIGNATURES
-    hdr = open(os.path.join(ROOT, "include", "sympgpr_hip.h")).read()
-    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, hdr)
-    assert m, "not declared in include/sympgpr_hip.h"
-    ctype = {"int": C.c_int, "double *": C.POINTER(C.c_double), "sgpr_fit_t": C.c_void_p}
-    kinds = []
-    for par in (par.strip() for par in m.group(1).split(",")):
-        base = re.sub(r"\s*\b\w+$", "", par).replace("const ", "").strip()
-        kinds.append(ctype[re.sub(r"\s*\*\s*", " *", base).strip()])
-    assert kinds == L.SIGNATURES[name][1] and L.SIGNATURES[name][0] is C.c_int
-    assert getattr(lib, name).argtypes == L.SIGNATURES[name][1]
+    c_header.assert_bound_as_declared(name, 5)
     nm = subprocess.run(["nm", "-D", "--defined-only", L.lib_path()], capture_output=True, text=True, check=True).stdout
     assert re.search(r"\bT %s$" % name, nm, re.M)
     assert lib.sgpr_abi_version() == 5
+    hdr = open(c_header.HEADER).read()
     assert re.search(r"enum\s*\{\s*SGPR_LOO_LPD\s*=\s*0\s*,\s*SGPR_LOO_PRESS\s*=\s*1\s*\}", hdr)
     assert (L.LOO_LPD, L.LOO_PRESS) == (0, 1)
     assert re.search(r"needs solved:.*?loo_grad", hdr, re.S), "no row in the header's state table"

@@ -1,11 +1,11 @@
 """CPU checks of the full NLL gradient entry point (sgpr_fit_nll_grad_full): exported, bound with its SIGNATURES argtypes,
 argument errors answered before any device is touched, the header and the binding agree, and SympFit.nll_grad_full
 documents its layout.  The numbers are checked on the GPU (tests/test_gpu_nll_grad_full.py)."""
-import ctypes as C
 import os
-import re
 
 import numpy as np
+
+from tests import c_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -35,21 +35,9 @@ def test_nll_grad_full_argument_errors():
 
 def test_header_and_signature_agree():
     from sympgpr_amd import _lib as L
-    hdr = open(os.path.join(ROOT, "include", "sympgpr_hip.h")).read()
-    m = re.search(r"\bint\s+sgpr_fit_nll_grad_full\s*\(([^)]*)\)\s*;", hdr)
-    assert m, "sgpr_fit_nll_grad_full is not declared in include/sympgpr_hip.h"
-    params = [p.strip() for p in m.group(1).split(",")]
-    ctype = {"sgpr_fit_t": C.c_void_p, "double *": C.POINTER(C.c_double), "int": C.c_int}
-    kinds = []
-    for p in params:
-        base = re.sub(r"\s*\b\w+$", "", p).replace("const ", "").strip()
-        base = re.sub(r"\s*\*\s*", " *", base).strip()
-        kinds.append(ctype[base])
-    assert kinds == L.SIGNATURES["sgpr_fit_nll_grad_full"][1]
-    assert L.SIGNATURES["sgpr_fit_nll_grad_full"][0] is C.c_int
+    c_header.assert_bound_as_declared("sgpr_fit_nll_grad_full", 3)
     # the header documents the layout next to the declaration
-    block = hdr[:m.start()].rsplit("*/", 1)[0].rsplit("/*", 1)[1]
-    doc = " ".join(block.split())
+    doc = c_header.comment_above("sgpr_fit_nll_grad_full")
     assert "nhyp + 1" in doc and "sign(sig2n)" in doc and "SGPR_E_STATE" in doc and "scratch" in doc
 
 

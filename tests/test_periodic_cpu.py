@@ -16,13 +16,14 @@ Two training sets: the data of tests/test_gpu_applymap_nd.py (sig2n 1e-8; fixed 
 a twist map defined here (twist_training; true periods with non-zero winding numbers)."""
 import ctypes as C
 import os
-import re
 
 import numpy as np
 import pytest
 
 from tests import ref_periodic as RP
 from tests.test_gpu_applymap_nd import _hyp, _ref_map_nd, _training
+
+from tests import c_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PI, TWO_PI = np.pi, 2.0 * np.pi
@@ -96,12 +97,9 @@ def model(oracle, c):
 
 def test_header_declares_and_library_exports_both_entries():
     from sympgpr_amd import _lib
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "sympgpr_hip.h")).read(), flags=re.S)
     lib = C.CDLL(_lib.lib_path())
     for name, nargs in zip(ENTRIES, (17, 24)):
-        m = re.search(r"\bint\s+%s\s*\(([^;]*)\)\s*;" % name, txt)
-        assert m, name + " is not declared"
-        assert len(m.group(1).split(",")) == nargs
+        c_header.assert_bound_as_declared(name, nargs)
         assert hasattr(lib, name), "libsympgpr_hip.so does not export " + name           # exports.map: sgpr_*
         restype, argtypes = _lib.SIGNATURES[name]
         assert restype is C.c_int and len(argtypes) == nargs
